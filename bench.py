@@ -24,6 +24,10 @@ Default workload = BASELINE.json configs[1] (synthetic chr22-sized contig, 50 Mb
     SURVEY.md 8d names FP64 VALU as the close second bound; for every kernel but bsc_call_kernel it is the one that binds.
   * cpu_baseline (rank 0, N = 1): the CPU oracle's libm flavour (= the reference's arithmetic; "port") on this host's
     cores over a bounded sample of the same contig: SURVEY.md 8d's three timings, medians of repetitions of >= 1 s.
+  A plain run prints the step's line with its `roofline` (the events of the timed launches); everything after it —
+  roofline.stream_probe, roofline_chain, roofline_accumulate, roofline_reads, roofline_bcf, roofline_prep, raw_to_bcf,
+  cpu_baseline and the parity checks of the legs — runs with --full.  --dump-outputs DIR writes a seeded sample of the
+  last timed step's output as DIR/<name>.npy.
 
 --config 3 = BASELINE.json configs[2]: a human-scale genome (24 contigs, 3.1 G positions, 30x, 1 % N-runs), contigs
   assigned to ranks by longest-processing-time (the reference is run one process per contig: README.md:73-76), each
@@ -77,7 +81,14 @@ def main():
     ap.add_argument("--dbsnp", action="store_true", help="config 3 -> BASELINE.json configs[4]: a synthetic dbSNP index (1 site / 300 bp, "
                     "10 %% fq_mask) is written, read back through the library's reader and its flags drive the chain")
     ap.add_argument("--genome-scale", type=float, default=1.0, help="config 3: scale every contig length (rehearsals)")
+    ap.add_argument("--full", action="store_true", help="config 2: after the headline, the legs that take runs of their own (roofline_chain, "
+                    "roofline_accumulate, roofline_reads, roofline_bcf, roofline_prep, raw_to_bcf, roofline.stream_probe) and the CPU baseline "
+                    "with its parity checks; without it a run sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="config 2: after the timed steps, write a fixed, seeded sample of the "
+                    "last step's output (gt_meth fields and skip flags) and the per-step counters as DIR/<name>.npy (float64)")
     args = ap.parse_args()
+    if args.dump_outputs and args.config != 2:
+        ap.error("--dump-outputs is implemented for --config 2")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` on its own: this process never touches a GPU; it starts one rank per GPU as a fresh
@@ -211,6 +222,8 @@ def run_config2(args, env):
     covered = int(stats[1])
     assert total_sites == n * world * args.steps, (total_sites, n, world, args.steps)
     value = total_sites / dt
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, d_out, d_skip, n, stats // args.steps)
     res = None
     if rank == 0:
         k_ms = float(np.mean(kernel_ms))
@@ -257,6 +270,9 @@ def run_config2(args, env):
                 "positions_per_s_kernel_only": n / (k_ms * 1e-3),
             },
         }
+    if not args.full:
+        caller.close()
+        return res
     if world == 1 and not args.no_chain:
         res["roofline_chain"] = chain_roofline(args, caller, d_cts, d_ref, n, first_site)
     if world == 1 and not args.no_reads:
@@ -280,6 +296,31 @@ def run_config2(args, env):
             }
     caller.close()
     return res
+
+
+DUMP_SITES = 1 << 17  # --dump-outputs: positions sampled, one in each stretch of n / DUMP_SITES (32 float64 per position: 34 MB)
+
+
+def dump_outputs(path, d_out, d_skip, n, counters):
+    """What the timed path hands its caller, from its last step: the gt_meth records (bs_call.h:152-160) and skip flags of a fixed,
+    seeded sample of the contig's positions, field by field as float64 (every integer field is exact in it), and the 13 counters of
+    one step.  The inputs depend on the arguments alone (SEED), so two builds run with the same arguments compare array by array."""
+    import numpy as np
+    import torch
+
+    import bs_call_amd as B
+
+    k = min(n, DUMP_SITES)
+    stride = n // k
+    idx = np.arange(k, dtype=np.int64) * stride + np.random.default_rng(SEED).integers(0, stride, k)
+    t = torch.from_numpy(idx).to(d_out.device)
+    rec = d_out.view(n, 200)[t].cpu().numpy().reshape(-1).view(B.GT_METH)
+    arrays = {"position": idx, "skip": d_skip[t].cpu().numpy(), "counters": counters}
+    for f in ("counts", "qual", "gt_prob", "fisher_strand", "mq", "aq", "max_gt"):
+        arrays["gt_meth_" + f] = rec[f]
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
 
 
 WARM_MS = 40.0  # device time of untimed launches in front of the legs below: after an idle stretch (host-side set-up) the first

@@ -57,3 +57,43 @@ def test_under_a_launcher_bench_does_not_launch_again(monkeypatch):
         raise AssertionError("expected the torch import to be reached")
     except ImportError:
         pass
+
+
+def test_dump_outputs_writes_a_fixed_float64_sample(tmp_path):
+    """--dump-outputs: the same seeded sample of positions every run, every array float64, the whole dump within 64 MB."""
+    import numpy as np
+    import torch
+
+    b = _bench()
+    n = 3_000_000
+    g = torch.Generator().manual_seed(1)
+    d_out = torch.randint(0, 256, (n * 200,), dtype=torch.uint8, generator=g)
+    d_skip = torch.randint(0, 2, (n,), dtype=torch.uint8, generator=g)
+    counters = np.arange(13, dtype=np.int64)
+    for d in ("a", "b"):
+        b.dump_outputs(str(tmp_path / d), d_out, d_skip, n, counters)
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == sorted(os.listdir(tmp_path / "b")) and "position.npy" in names and "gt_meth_gt_prob.npy" in names
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in names) <= 64 << 20
+    for f in names:
+        x, y = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert x.dtype == np.float64 and x.tobytes() == y.tobytes(), f
+    pos = np.load(tmp_path / "a" / "position.npy").astype(np.int64)
+    assert len(pos) == b.DUMP_SITES and pos.max() < n and (np.diff(pos) > 0).all()
+    import bs_call_amd as B
+
+    rec = d_out.view(n, 200)[torch.from_numpy(pos)].numpy().reshape(-1).view(B.GT_METH)
+    assert (np.load(tmp_path / "a" / "gt_meth_counts.npy") == rec["counts"].astype(np.float64)).all()
+    assert (np.load(tmp_path / "a" / "skip.npy") == d_skip.numpy()[pos]).all()
+    assert (np.load(tmp_path / "a" / "counters.npy") == counters).all()
+
+
+def test_dump_outputs_is_refused_for_config3(monkeypatch, capsys):
+    b = _bench()
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--config", "3", "--dump-outputs", "x"])
+    try:
+        b.main()
+        raise AssertionError("expected a usage error")
+    except SystemExit as e:
+        assert e.code == 2
+    assert "--dump-outputs" in capsys.readouterr().err

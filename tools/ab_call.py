@@ -18,7 +18,7 @@ for sites in sizes.split(","):
     for rep in range(2):
         for n, f in libs:
             env = dict(os.environ, BSCALL_AMD_LIB=f)
-            p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--no-cpu-baseline", "--sites", sites, "--coverage", cov, "--steps", "20",
+            p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--no-cpu-baseline", "--sites", sites, "--coverage", cov, "--steps", "20",
                                 "--no-reads", "--no-chain"], env=env, capture_output=True, text=True)
             try:
                 d = json.loads(p.stdout.strip().splitlines()[-1])

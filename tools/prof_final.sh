@@ -20,8 +20,8 @@ bash tools/pmc_sq.sh $TAG > gpurun_out/sq_$TAG.txt 2>&1 || { tail -20 gpurun_out
 bash tools/pmc_chain.sh $TAG > gpurun_out/sqc_$TAG.txt 2>&1 || { tail -20 gpurun_out/sqc_$TAG.txt; exit 1; }
 find $OUT/chain_trace -name "*kernel_stats.csv" | xargs cat | cut -c1-200 > gpurun_out/chain_stats_$TAG.csv
 cat $OUT/chain_bench.json
-timeout -k 10 500 python3 bench.py > gpurun_out/bench_$TAG.json 2> gpurun_out/bench_$TAG.err || { tail -5 gpurun_out/bench_$TAG.err; exit 1; }
-cat gpurun_out/bench_$TAG.json
+timeout -k 10 500 python3 bench.py --full > $OUT/bench.json 2> $OUT/bench.err || { tail -5 $OUT/bench.err; exit 1; }
+cat $OUT/bench.json
 timeout -k 10 300 python3 bench.py --config 3 --rank-of 8 --steps 3 --warmup 1 > gpurun_out/cfg3_$TAG.json 2> gpurun_out/cfg3_$TAG.err
 timeout -k 10 300 python3 bench.py --config 3 --rank-of 8 --steps 3 --warmup 1 --window 16711680 > gpurun_out/cfg3w16_$TAG.json 2>> gpurun_out/cfg3_$TAG.err
 timeout -k 10 300 python3 bench.py --config 3 --rank-of 8 --steps 3 --warmup 1 --dbsnp > gpurun_out/cfg5_$TAG.json 2>> gpurun_out/cfg3_$TAG.err

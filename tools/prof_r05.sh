@@ -73,9 +73,9 @@ timeout -k 10 600 python3 tools/bench_small_blocks.py > $O/small_blocks.json 2> 
 # 6b file to file: BAM + FASTA -> BCF + report (pre-processing on the device, and on the host as in round 4)
 timeout -k 10 900 python3 tools/bench_bam2bcf.py 2000000 > $O/bam2bcf.json 2> $O/bam2bcf.err || { tail -5 $O/bam2bcf.err; exit 1; }
 # 7
-timeout -k 10 600 python3 bench.py > $O/bench.json 2> $O/bench.err || { tail -5 $O/bench.err; exit 1; }
-timeout -k 10 300 python3 bench.py --sites 10000000 --coverage 200 --no-cpu-baseline --warmup 40 > $O/bench_cfg4_10Mb_200x.json 2>> $O/bench.err
-timeout -k 10 300 python3 bench.py --sites 1000000 --coverage 10 --no-cpu-baseline --warmup 200 > $O/bench_cfg1_1Mb_10x.json 2>> $O/bench.err
+timeout -k 10 600 python3 bench.py --full > $O/bench.json 2> $O/bench.err || { tail -5 $O/bench.err; exit 1; }
+timeout -k 10 300 python3 bench.py --full --sites 10000000 --coverage 200 --no-cpu-baseline --warmup 40 > $O/bench_cfg4_10Mb_200x.json 2>> $O/bench.err
+timeout -k 10 300 python3 bench.py --full --sites 1000000 --coverage 10 --no-cpu-baseline --warmup 200 > $O/bench_cfg1_1Mb_10x.json 2>> $O/bench.err
 timeout -k 10 300 python3 bench.py --config 3 --rank-of 8 --steps 3 --warmup 1 > $O/cfg3_rank0of8.json 2> $O/cfg3.err
 timeout -k 10 300 python3 bench.py --config 3 --rank-of 8 --steps 3 --warmup 1 --dbsnp > $O/cfg5_rank0of8.json 2>> $O/cfg3.err
 python3 - <<PY

@@ -60,5 +60,5 @@ grep "^device_reader" $O/bam2bcf_50Mb_8contigs.log | cut -c1-330
 # 5
 tools/r06_glue.sh > $O/glue_demo.txt 2>&1 || { tail -5 $O/glue_demo.txt; exit 1; }
 grep "end to end" $O/glue_demo.txt
-timeout -k 10 600 python3 bench.py > $O/bench.json 2> $O/bench.err || { tail -5 $O/bench.err; exit 1; }
+timeout -k 10 600 python3 bench.py --full > $O/bench.json 2> $O/bench.err || { tail -5 $O/bench.err; exit 1; }
 echo part c done

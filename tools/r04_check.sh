@@ -12,8 +12,8 @@ mkdir -p $O
 timeout -k 10 300 python3 tools/bench_chain.py --no-unfused --steps 20 --warm 8 > $O/chain.json 2> $O/chain.err || { tail -5 $O/chain.err; exit 1; }
 timeout -k 10 300 python3 tools/bench_reads.py --steps 10 --warm 10 --no-check > $O/reads.json 2> $O/reads.err || { tail -5 $O/reads.err; exit 1; }
 timeout -k 10 300 python3 tools/bench_reads.py --one-kernel --steps 10 --warm 10 --no-check > $O/reads1.json 2>> $O/reads.err || { tail -5 $O/reads.err; exit 1; }
-timeout -k 10 400 python3 bench.py --no-cpu-baseline > $O/bench.json 2> $O/bench.err || { tail -5 $O/bench.err; exit 1; }
-timeout -k 10 400 python3 bench.py --no-cpu-baseline --no-chain > $O/bench_nochain.json 2>> $O/bench.err || { tail -5 $O/bench.err; exit 1; }
+timeout -k 10 400 python3 bench.py --full --no-cpu-baseline > $O/bench.json 2> $O/bench.err || { tail -5 $O/bench.err; exit 1; }
+timeout -k 10 400 python3 bench.py --full --no-cpu-baseline --no-chain > $O/bench_nochain.json 2>> $O/bench.err || { tail -5 $O/bench.err; exit 1; }
 python3 - <<PY
 import json
 ch = json.loads(open("$O/chain.json").read().strip().splitlines()[-1])

@@ -22,6 +22,6 @@ python3 tools/make_r06_json.py $O | tee $O/r06_json.txt | tail -4
 bash tools/pmc_bcf.sh $TAG/pmc_bcf > $O/pmc_bcf.log 2>&1 || { tail -5 $O/pmc_bcf.log; exit 1; }
 tail -4 $O/pmc_bcf.log
 cp profiles/traffic.json $O/traffic.json
-timeout -k 10 600 python3 bench.py > $O/bench.json 2> $O/bench.err || { tail -5 $O/bench.err; exit 1; }
+timeout -k 10 600 python3 bench.py --full > $O/bench.json 2> $O/bench.err || { tail -5 $O/bench.err; exit 1; }
 cut -c1-400 $O/bench.json
 echo final done
