@@ -11,7 +11,7 @@ LIBDIR = bs_call_amd/lib
 HIPFLAGS = -O3 --offload-arch=$(ARCH) -fPIC -ffp-contract=off -fno-fast-math -std=c++17 -Wall -Wno-unused-function -Wno-inline-asm
 CFLAGS = -O2 -fPIC -Wall -ffp-contract=off -std=gnu11 -I$(ROCM)/include -D__HIP_PLATFORM_AMD__
 
-all: $(LIBDIR)/libbscall_amd.so oracle demo
+all: $(LIBDIR)/libbscall_amd.so oracle demo devmath-probe
 
 $(LIBDIR)/kernels.o: $(CSRC)/kernels.hip $(CSRC)/callmath.h $(CSRC)/call_body.inc $(CSRC)/call_summary.inc $(CSRC)/bsmath.h $(CSRC)/bsmath_tables.h $(CSRC)/devtables.h $(CSRC)/synth.h
 	@mkdir -p $(LIBDIR)
@@ -108,6 +108,16 @@ $(LIBDIR)/libbscall_amd.so: $(LIBDIR)/kernels.o $(LIBDIR)/fused.o $(LIBDIR)/accu
 oracle:
 	$(MAKE) -C oracle liboracle.so
 
+# TEST ONLY: the device numeric primitives (callmath.h, bsmath.h, sitestats_dev.h) one call per lane, for
+# tests/test_gpu_devmath.py.  The product's own headers and exactly the product's $(HIPFLAGS) (-ffp-contract=off is part of
+# what is tested); nothing of it goes into libbscall_amd.so.  DEVMATH_INC: where the headers are taken from (a mutated copy,
+# to see that the tests catch a change); DEVMATH_SO: where the library goes.
+DEVMATH_INC ?= $(CSRC)
+DEVMATH_SO ?= tests/devmath/libdevmath_probe.so
+devmath-probe: $(DEVMATH_SO)
+$(DEVMATH_SO): tests/devmath/devmath_probe.hip $(CSRC)/callmath.h $(CSRC)/bsmath.h $(CSRC)/bsmath_tables.h $(CSRC)/sitestats_dev.h $(CSRC)/devtables.h include/bscall_amd.h
+	$(HIPCC) $(HIPFLAGS) -I$(DEVMATH_INC) -shared -o $@ $<
+
 # The library with its HOST C files under AddressSanitizer + UndefinedBehaviorSanitizer (gcc's runtimes; the device objects
 # are the ordinary ones): what tests/test_host_sanitizers.py and tools/fuzz_host_inputs.py run the readers and the host
 # logic under, on the CPU.  Load it with LD_PRELOAD=<libasan.so>:<libubsan.so> BSCALL_AMD_LIB=$(LIBDIR)/san/libbscall_amd_san.so.
@@ -147,7 +157,7 @@ asm: $(CSRC)/kernels.hip
 	$(HIPCC) $(HIPFLAGS) -S --cuda-device-only -Rpass-analysis=kernel-resource-usage $< -o $(LIBDIR)/kernels.s
 
 clean:
-	rm -rf $(LIBDIR)/san; rm -f $(LIBDIR)/*.o $(LIBDIR)/*.so $(LIBDIR)/*.s $(LIBDIR)/demo_block $(LIBDIR)/bam2bcf
+	rm -rf $(LIBDIR)/san; rm -f tests/devmath/libdevmath_probe.so $(LIBDIR)/*.o $(LIBDIR)/*.so $(LIBDIR)/*.s $(LIBDIR)/demo_block $(LIBDIR)/bam2bcf
 	$(MAKE) -C oracle clean
 
-.PHONY: all oracle demo asm clean glue-check san
+.PHONY: all oracle demo asm clean glue-check san devmath-probe

@@ -178,6 +178,23 @@ double orc_fisher(int *c, const orc_tables *tb, int flavour) {
   return flavour ? orc_fisher_bsm(c, tb->lfact_store) : orc_fisher_libm(c, tb->lfact_store);
 }
 
+/* array forms of the flavoured lfact2 / fisher / get_Z: many cases without a foreign call per case (the device probe of
+ * tests/test_gpu_devmath.py).  c is n x 4 ints, each row mutated as the reference mutates it; in is n x 6 doubles
+ * {x1, x2, k1, k2, l, t}, Z is n x 3. */
+void orc_lfact_array(const int *x, double *y, uint64_t n, const orc_tables *tb, int flavour) {
+  for (uint64_t i = 0; i < n; i++) y[i] = orc_lfact(x[i], tb, flavour);
+}
+void orc_fisher_array(int *c, double *p, uint64_t n, const orc_tables *tb, int flavour) {
+  for (uint64_t i = 0; i < n; i++) p[i] = orc_fisher(c + 4 * i, tb, flavour);
+}
+void orc_get_Z_array(const double *in, double *Z, uint64_t n, int flavour) {
+  for (uint64_t i = 0; i < n; i++) {
+    const double *a = in + 6 * i;
+    if (flavour) orc_get_Z_bsm(a[0], a[1], a[2], a[3], a[4], a[5], Z + 3 * i);
+    else orc_get_Z_libm(a[0], a[1], a[2], a[3], a[4], a[5], Z + 3 * i);
+  }
+}
+
 /* ---- HOT LOOP A: src/call_genotypes.c:178-226 ------------------------------------------------ */
 /* counts[] has y-x+1 entries and is zeroed here (:178).  Returns 0, or -1 where the reference asserts
  * (:158 y>=x, :186 x1>=x, :188 ori<2). */

@@ -63,6 +63,12 @@ def lib():
         for f in ("orc_log_array", "orc_exp_array"):
             getattr(L, f).restype = None
             getattr(L, f).argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int]
+        L.orc_lfact_array.restype = None
+        L.orc_lfact_array.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_int]
+        L.orc_fisher_array.restype = None
+        L.orc_fisher_array.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_int]
+        L.orc_get_Z_array.restype = None
+        L.orc_get_Z_array.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int]
         assert L.orc_sizeof_tables() == TABLES_BYTES, (L.orc_sizeof_tables(), TABLES_BYTES)
         _lib = L
     return _lib
@@ -148,6 +154,30 @@ def exp_array(x, flavour):
     y = np.empty_like(x)
     lib().orc_exp_array(_ptr(x), _ptr(y), x.size, flavour)
     return y
+
+
+def lfact_array(x, tables, flavour):
+    """lfact2 (include/bs_call.h:335) of every int in x: lfact_store below 256, lgamma(x + 1) (libm or bsmath.h) above."""
+    x = np.ascontiguousarray(x, dtype=np.int32)
+    y = np.empty(x.shape, dtype=np.float64)
+    lib().orc_lfact_array(_ptr(x), _ptr(y), x.size, tables.ptr, flavour)
+    return y
+
+
+def fisher_array(c, tables, flavour):
+    """fisher() (src/stats_utils.c:25-91) of every row of c (n x 4 ints) -> float64[n]; c itself is not changed."""
+    c = np.array(c, dtype=np.int32, order="C").reshape(-1, 4)
+    p = np.empty(len(c), dtype=np.float64)
+    lib().orc_fisher_array(_ptr(c), _ptr(p), len(c), tables.ptr, flavour)
+    return p
+
+
+def get_Z_array(a, flavour):
+    """get_Z (src/genotype_model.c:23-42) of every row {x1, x2, k1, k2, l, t} of a (n x 6) -> Z (n x 3)."""
+    a = np.ascontiguousarray(a, dtype=np.float64).reshape(-1, 6)
+    z = np.empty((len(a), 3), dtype=np.float64)
+    lib().orc_get_Z_array(_ptr(a), _ptr(z), len(a), flavour)
+    return z
 
 
 _libm_exact = None
