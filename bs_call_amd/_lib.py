@@ -107,6 +107,11 @@ EXPORTS = (
     "bsc_detached_read",
     "bsc_detached_wait",
     "bsc_detached_free",
+    "bsc_bgzf_open",
+    "bsc_bgzf_write",
+    "bsc_bgzf_write_device",
+    "bsc_bgzf_take",
+    "bsc_bgzf_close",
     "bsc_debug_fail_summary_alloc",
     "bsc_last_kernel_ms",
     "bsc_kernel_ms_history",
@@ -475,6 +480,16 @@ def load():
     L.bsc_detached_wait.argtypes = [vp]
     L.bsc_detached_free.restype = i32
     L.bsc_detached_free.argtypes = [vp, vp]
+    L.bsc_bgzf_open.restype = i32
+    L.bsc_bgzf_open.argtypes = [vp, C.POINTER(vp)]
+    L.bsc_bgzf_write.restype = i32
+    L.bsc_bgzf_write.argtypes = [vp, vp, u64]
+    L.bsc_bgzf_write_device.restype = i32
+    L.bsc_bgzf_write_device.argtypes = [vp, vp, u64]
+    L.bsc_bgzf_take.restype = i32
+    L.bsc_bgzf_take.argtypes = [vp, C.POINTER(vp), C.POINTER(u64)]
+    L.bsc_bgzf_close.restype = i32
+    L.bsc_bgzf_close.argtypes = [vp, C.POINTER(vp), C.POINTER(u64)]
     L.bsc_block_bcf_again.restype = i32
     L.bsc_block_bcf_again.argtypes = [vp, vp, u64, C.POINTER(u64), C.POINTER(u64)]
     L.bsc_debug_fail_summary_alloc.restype = i32

@@ -48,6 +48,49 @@ def _check_dest(name, a, nbytes):
         raise ValueError("%s has %d bytes, the call writes %d" % (name, a.nbytes, nbytes))
 
 
+class DeviceBgzf:
+    """BGZF on the device (bsc_bgzf_*): write host bytes (bytes-like) or device bytes (a pointer and a length), take the members
+    completed so far, close for the last member and the end-of-file marker.  take() / close() return bytes."""
+
+    def __init__(self, caller):
+        self._c = caller
+        self._L = caller._L
+        h = C.c_void_p()
+        _check(self._L.bsc_bgzf_open(caller._h, C.byref(h)))
+        self._h = h
+
+    def write(self, data):
+        a = np.frombuffer(memoryview(data).cast("B"), dtype=np.uint8) if len(data) else np.zeros(1, np.uint8)
+        _check(self._L.bsc_bgzf_write(self._h, _ptr(a), len(data)))
+
+    def write_device(self, d_ptr, n):
+        _check(self._L.bsc_bgzf_write_device(self._h, C.c_void_p(int(d_ptr)), int(n)))
+
+    def _hand_over(self, fn, h):
+        """bsc_bgzf_take / _close: the device buffer read out (bsc_detached_read) and given back to the context's pool."""
+        d, n = C.c_void_p(), C.c_uint64()
+        _check(fn(h, C.byref(d), C.byref(n)))
+        if not d.value:
+            return b""
+        out = np.empty(n.value, np.uint8)
+        try:
+            _check(self._L.bsc_detached_read(self._c._h, d, 0, n.value, _ptr(out)))
+            _check(self._L.bsc_detached_wait(self._c._h))
+        finally:
+            _check(self._L.bsc_detached_free(self._c._h, d))
+        return out.tobytes()
+
+    def take(self):
+        return self._hand_over(self._L.bsc_bgzf_take, self._h)
+
+    def close(self):
+        """The last member and the end-of-file marker; the writer is gone afterwards (a second close returns b"")."""
+        if self._h is None:
+            return b""
+        h, self._h = self._h, None
+        return self._hand_over(self._L.bsc_bgzf_close, h)
+
+
 class SiteCaller:
     def __init__(self, under_conv=0.01, over_conv=0.05, ref_bias=2.0, min_qual=20, device=-1):
         self._L = _lib.load()
@@ -75,6 +118,27 @@ class SiteCaller:
             self.close()
         except Exception:
             pass
+
+    # -- BGZF on the device ---------------------------------------------------------------------------
+    def bgzf(self):
+        """A DeviceBgzf writer on this context (close it before the context)."""
+        return DeviceBgzf(self)
+
+    def bgzf_compress(self, data, pieces=None):
+        """BGZF bytes of `data` (bytes-like), written whole or in the given piece lengths, with the end-of-file marker."""
+        z = self.bgzf()
+        parts = []
+        if pieces is None:
+            pieces = [len(data)]
+        at = 0
+        for k in pieces:
+            z.write(data[at : at + k])
+            at += k
+            parts.append(z.take())
+        if at < len(data):
+            z.write(data[at:])
+        parts.append(z.close())
+        return b"".join(parts)
 
     # -- tables -----------------------------------------------------------------------------------
     def tables(self):

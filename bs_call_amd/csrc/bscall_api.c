@@ -80,6 +80,9 @@ int bsc_dev_launch_ref_pad(const void *packed, const void *d_blk, uint32_t n_blk
 int bsc_dev_launch_bin_reads_multi(const void *tpl, uint32_t nr, const void *seq, uint64_t seq_bytes, const void *d_blk, uint32_t n_blk,
                                    uint32_t n_bins, void *tflag, void *bin_cnt, void *bin_off, void *bin_cur, void *scan_tmp,
                                    size_t scan_tmp_bytes, void *rd, void *counters, void *stream);
+int bsc_dev_launch_bgzf(const void *src, uint64_t n, uint32_t n_members, void *slots, void *sizes, void *offs, void *scratch, uint32_t grid,
+                        void *stream); /* bgzfdev.hip */
+int bsc_dev_launch_bgzf_gather(const void *slots, const void *offs, const void *sizes, uint32_t n_members, void *out, void *stream);
 #define BSC_PREP_CNT_SLOTS 64u                               /* csrc/prepdev.hip: PREP_CNT_SLOTS */
 #define BSC_PREP_CNT_ALL (8u + 8u * BSC_PREP_CNT_SLOTS)     /* the eight shared words and the slots behind them */
 #define BSC_LN10 (2.30258509299404568402) /* the reference's LOG10 literal (include/bs_call.h:36) */
@@ -3140,4 +3143,277 @@ int bsc_synth_pileup_host(uint64_t seed, uint64_t first_site, uint64_t n, uint32
     ref[i] = (uint8_t)rf;
   }
   return BSC_OK;
+}
+
+/* ---- BGZF on the device (bgzfdev.hip): a writer that cuts the logical stream into 0xFF00-byte members whatever the pieces it is given --
+ * The carry (the bytes of the member not yet complete) stays in HBM; complete members are compressed as soon as they are there, in launches
+ * of at most BGZF_BATCH members (their 64 KiB slots, their sizes, a sum of the sizes, then the slots packed behind the members already
+ * pending).  The pending members change hands at bsc_bgzf_take / _close like a detached BCF stream: booked in the context's pool, read with
+ * bsc_detached_read, given back with bsc_detached_free — and the next pending buffer is taken from what came back. */
+#define BGZF_MEMBER 0xFF00u
+#define BGZF_SLOT 65536u
+#define BGZF_BATCH 4096u
+#define BGZF_HOST_PIECE ((size_t)64 << 20)
+struct bsc_bgzf {
+  bsc_context *ctx;
+  void *d_carry;
+  uint32_t carry_n;
+  void *d_stage; /* host bytes on their way up */
+  size_t cap_stage;
+  void *d_slots, *d_sizes, *d_offs, *d_scratch;
+  uint32_t cap_members, cap_grid;
+  void *d_pend;
+  size_t cap_pend;
+  uint64_t n_pend;
+  struct bsc_bgzf *next_open;
+};
+static const uint8_t bsc_bgzf_eof[28] = {0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 0x42, 0x43, 2, 0, 0x1b, 0, 3, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+/* the writers that are open: a call on anything else (NULL, a closed writer) is refused instead of touching freed memory */
+static pthread_mutex_t bsc_bgzf_mu = PTHREAD_MUTEX_INITIALIZER;
+static struct bsc_bgzf *bsc_bgzf_open_list;
+static int bsc_bgzf_is_open(const bsc_bgzf *z) {
+  int found = 0;
+  pthread_mutex_lock(&bsc_bgzf_mu);
+  for (const struct bsc_bgzf *q = bsc_bgzf_open_list; q && !found; q = q->next_open) found = q == z;
+  pthread_mutex_unlock(&bsc_bgzf_mu);
+  return found;
+}
+
+static void bsc_pool_init(bsc_context *ctx) {
+  if (!ctx->pool_mu_made) {
+    pthread_mutex_init(&ctx->pool_mu, NULL);
+    ctx->pool_mu_made = 1;
+  }
+}
+/* the smallest buffer in the pool that holds `need` bytes, or NULL */
+static void *bsc_pool_get(bsc_context *ctx, size_t need, size_t *cap) {
+  void *p = NULL;
+  pthread_mutex_lock(&ctx->pool_mu);
+  int best = -1;
+  for (int k = 0; k < 4; k++)
+    if (ctx->bcf_pool.p[k] && ctx->bcf_pool.cap[k] >= need && (best < 0 || ctx->bcf_pool.cap[k] < ctx->bcf_pool.cap[best])) best = k;
+  if (best >= 0) {
+    p = ctx->bcf_pool.p[best];
+    *cap = ctx->bcf_pool.cap[best];
+    ctx->bcf_pool.p[best] = NULL;
+    ctx->bcf_pool.cap[best] = 0;
+  }
+  pthread_mutex_unlock(&ctx->pool_mu);
+  return p;
+}
+/* a buffer handed to the caller: booked like a detached stream, so that bsc_detached_free puts it back in the pool */
+static void bsc_pool_book(bsc_context *ctx, void *p, size_t cap) {
+  pthread_mutex_lock(&ctx->pool_mu);
+  for (int k = 0; k < 4; k++)
+    if (!ctx->bcf_pool.p[k] && !ctx->bcf_pool.cap[k]) {
+      ctx->bcf_pool.cap[k] = cap | ((size_t)1 << 63);
+      ctx->det_ptr[k] = p;
+      break;
+    }
+  pthread_mutex_unlock(&ctx->pool_mu);
+}
+
+static int bsc_bgzf_reserve(bsc_bgzf *z, size_t need) { /* room for `need` pending bytes */
+  if (need <= z->cap_pend) return BSC_OK;
+  size_t cap = z->cap_pend * 2 > need ? z->cap_pend * 2 : need;
+  if (cap < ((size_t)1 << 20)) cap = (size_t)1 << 20;
+  size_t got = 0;
+  void *p = bsc_pool_get(z->ctx, cap, &got);
+  if (!p) {
+    HIP_TRY(hipMalloc(&p, cap));
+    got = cap;
+  }
+  if (z->n_pend) {
+    const hipError_t e = hipMemcpyAsync(p, z->d_pend, (size_t)z->n_pend, hipMemcpyDeviceToDevice, z->ctx->stream);
+    if (e == hipSuccess) (void)hipStreamSynchronize(z->ctx->stream);
+    if (e != hipSuccess) {
+      hipFree(p);
+      return bsc_fail(BSC_ERR_HIP, "bsc_bgzf: copying the pending members failed: %s", hipGetErrorString(e));
+    }
+  }
+  if (z->d_pend) hipFree(z->d_pend);
+  z->d_pend = p;
+  z->cap_pend = got;
+  return BSC_OK;
+}
+
+/* members of src[0, n) (a whole number of them but the last), queued on the context's stream, behind the pending ones */
+static int bsc_bgzf_compress(bsc_bgzf *z, const uint8_t *src, uint64_t n) {
+  bsc_context *ctx = z->ctx;
+  const uint64_t nm = (n + BGZF_MEMBER - 1) / BGZF_MEMBER;
+  for (uint64_t m0 = 0; m0 < nm; m0 += BGZF_BATCH) {
+    const uint32_t nb = (uint32_t)(nm - m0 < BGZF_BATCH ? nm - m0 : BGZF_BATCH);
+    const uint64_t at = m0 * BGZF_MEMBER, bytes = n - at < (uint64_t)nb * BGZF_MEMBER ? n - at : (uint64_t)nb * BGZF_MEMBER;
+    uint32_t grid = (uint32_t)ctx->num_cus;
+    if (grid > nb) grid = nb;
+    if (nb > z->cap_members) {
+      hipFree(z->d_slots);
+      hipFree(z->d_sizes);
+      hipFree(z->d_offs);
+      z->d_slots = z->d_sizes = z->d_offs = NULL;
+      z->cap_members = 0;
+      HIP_TRY(hipMalloc(&z->d_slots, (size_t)nb * BGZF_SLOT));
+      HIP_TRY(hipMalloc(&z->d_sizes, (size_t)nb * 8));
+      HIP_TRY(hipMalloc(&z->d_offs, ((size_t)nb + 1) * 8));
+      z->cap_members = nb;
+    }
+    if (grid > z->cap_grid) {
+      hipFree(z->d_scratch);
+      z->d_scratch = NULL;
+      z->cap_grid = 0;
+      HIP_TRY(hipMalloc(&z->d_scratch, (size_t)grid * BGZF_MEMBER * 4));
+      z->cap_grid = grid;
+    }
+    HIP_TRY((hipError_t)bsc_dev_launch_bgzf(src + at, bytes, nb, z->d_slots, z->d_sizes, z->d_offs, z->d_scratch, grid, ctx->stream));
+    uint64_t total = 0;
+    HIP_TRY(hipMemcpyAsync(&total, (uint64_t *)z->d_offs + nb, 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    if (total > (uint64_t)nb * BGZF_SLOT) return bsc_fail(BSC_ERR_HIP, "bsc_bgzf: the compressor reported %llu bytes for %u members", (unsigned long long)total, nb);
+    const int rc = bsc_bgzf_reserve(z, (size_t)(z->n_pend + total));
+    if (rc) return rc;
+    HIP_TRY((hipError_t)bsc_dev_launch_bgzf_gather(z->d_slots, z->d_offs, z->d_sizes, nb, (uint8_t *)z->d_pend + z->n_pend, ctx->stream));
+    z->n_pend += total;
+  }
+  return BSC_OK;
+}
+
+static int bsc_bgzf_feed(bsc_bgzf *z, const uint8_t *src, uint64_t n) { /* device bytes into the logical stream */
+  bsc_context *ctx = z->ctx;
+  if (z->carry_n) {
+    const uint64_t k = n < BGZF_MEMBER - z->carry_n ? n : BGZF_MEMBER - z->carry_n;
+    if (k) HIP_TRY(hipMemcpyAsync((uint8_t *)z->d_carry + z->carry_n, src, (size_t)k, hipMemcpyDeviceToDevice, ctx->stream));
+    z->carry_n += (uint32_t)k;
+    src += k;
+    n -= k;
+    if (z->carry_n < BGZF_MEMBER) {
+      HIP_TRY(hipStreamSynchronize(ctx->stream));
+      return BSC_OK;
+    }
+    const int rc = bsc_bgzf_compress(z, (const uint8_t *)z->d_carry, BGZF_MEMBER);
+    if (rc) return rc;
+    z->carry_n = 0;
+  }
+  const uint64_t full = n / BGZF_MEMBER * BGZF_MEMBER;
+  if (full) {
+    const int rc = bsc_bgzf_compress(z, src, full);
+    if (rc) return rc;
+  }
+  if (n > full) {
+    HIP_TRY(hipMemcpyAsync(z->d_carry, src + full, (size_t)(n - full), hipMemcpyDeviceToDevice, ctx->stream));
+    z->carry_n = (uint32_t)(n - full);
+  }
+  HIP_TRY(hipStreamSynchronize(ctx->stream)); /* the caller may reuse its bytes */
+  return BSC_OK;
+}
+
+int bsc_bgzf_open(bsc_context *ctx, bsc_bgzf **out) {
+  if (!out) return bsc_fail(BSC_ERR_ARG, "bsc_bgzf_open: out is NULL");
+  *out = NULL;
+  if (!ctx) return bsc_fail(BSC_ERR_ARG, "bsc_bgzf_open: ctx is NULL");
+  BSC_ENTER(ctx);
+  bsc_bgzf *z = calloc(1, sizeof *z);
+  if (!z) return bsc_fail(BSC_ERR_NOMEM, "bsc_bgzf_open: out of host memory");
+  z->ctx = ctx;
+  hipError_t e = hipMalloc(&z->d_carry, BGZF_MEMBER + 16);
+  if (e == hipSuccess && !ctx->s_det) e = hipStreamCreateWithFlags(&ctx->s_det, hipStreamNonBlocking);
+  if (e != hipSuccess) {
+    hipFree(z->d_carry);
+    free(z);
+    return bsc_fail(BSC_ERR_HIP, "bsc_bgzf_open: %s", hipGetErrorString(e));
+  }
+  bsc_pool_init(ctx);
+  pthread_mutex_lock(&bsc_bgzf_mu);
+  z->next_open = bsc_bgzf_open_list;
+  bsc_bgzf_open_list = z;
+  pthread_mutex_unlock(&bsc_bgzf_mu);
+  *out = z;
+  return BSC_OK;
+}
+
+int bsc_bgzf_write_device(bsc_bgzf *z, const void *d_src, uint64_t n) {
+  if (!bsc_bgzf_is_open(z)) return bsc_fail(BSC_ERR_ARG, "bsc_bgzf_write_device: not an open BGZF writer (NULL, or closed)");
+  if (!d_src && n) return bsc_fail(BSC_ERR_ARG, "bsc_bgzf_write_device: d_src is NULL");
+  if (!n) return BSC_OK;
+  BSC_ENTER(z->ctx);
+  return bsc_bgzf_feed(z, (const uint8_t *)d_src, n);
+}
+
+int bsc_bgzf_write(bsc_bgzf *z, const void *src, uint64_t n) {
+  if (!bsc_bgzf_is_open(z)) return bsc_fail(BSC_ERR_ARG, "bsc_bgzf_write: not an open BGZF writer (NULL, or closed)");
+  if (!src && n) return bsc_fail(BSC_ERR_ARG, "bsc_bgzf_write: src is NULL");
+  if (!n) return BSC_OK;
+  BSC_ENTER(z->ctx);
+  for (uint64_t off = 0; off < n;) {
+    const size_t k = n - off < BGZF_HOST_PIECE ? (size_t)(n - off) : BGZF_HOST_PIECE;
+    if (k > z->cap_stage) {
+      hipFree(z->d_stage);
+      z->d_stage = NULL;
+      z->cap_stage = 0;
+      const size_t cap = k < ((size_t)1 << 20) ? ((size_t)1 << 20) : k;
+      HIP_TRY(hipMalloc(&z->d_stage, cap));
+      z->cap_stage = cap;
+    }
+    HIP_TRY(hipMemcpyAsync(z->d_stage, (const uint8_t *)src + off, k, hipMemcpyHostToDevice, z->ctx->stream));
+    const int rc = bsc_bgzf_feed(z, (const uint8_t *)z->d_stage, k);
+    if (rc) return rc;
+    off += k;
+  }
+  return BSC_OK;
+}
+
+static int bsc_bgzf_hand_over(bsc_bgzf *z, void **d_out, uint64_t *n_bytes) {
+  HIP_TRY(hipStreamSynchronize(z->ctx->stream));
+  if (!z->n_pend) return BSC_OK;
+  bsc_pool_book(z->ctx, z->d_pend, z->cap_pend);
+  *d_out = z->d_pend;
+  *n_bytes = z->n_pend;
+  z->d_pend = NULL;
+  z->cap_pend = 0;
+  z->n_pend = 0;
+  return BSC_OK;
+}
+
+int bsc_bgzf_take(bsc_bgzf *z, void **d_out, uint64_t *n_bytes) {
+  if (!bsc_bgzf_is_open(z)) return bsc_fail(BSC_ERR_ARG, "bsc_bgzf_take: not an open BGZF writer (NULL, or closed)");
+  if (!d_out || !n_bytes) return bsc_fail(BSC_ERR_ARG, "bsc_bgzf_take: NULL argument");
+  *d_out = NULL;
+  *n_bytes = 0;
+  BSC_ENTER(z->ctx);
+  return bsc_bgzf_hand_over(z, d_out, n_bytes);
+}
+
+int bsc_bgzf_close(bsc_bgzf *z, void **d_out, uint64_t *n_bytes) {
+  if (!bsc_bgzf_is_open(z)) return bsc_fail(BSC_ERR_ARG, "bsc_bgzf_close: not an open BGZF writer (NULL, or closed)");
+  if (!d_out || !n_bytes) return bsc_fail(BSC_ERR_ARG, "bsc_bgzf_close: NULL argument");
+  *d_out = NULL;
+  *n_bytes = 0;
+  BSC_ENTER(z->ctx);
+  int rc = z->carry_n ? bsc_bgzf_compress(z, (const uint8_t *)z->d_carry, z->carry_n) : BSC_OK;
+  if (!rc) {
+    z->carry_n = 0;
+    rc = bsc_bgzf_reserve(z, (size_t)z->n_pend + sizeof bsc_bgzf_eof);
+  }
+  if (!rc) {
+    const hipError_t e = hipMemcpyAsync((uint8_t *)z->d_pend + z->n_pend, bsc_bgzf_eof, sizeof bsc_bgzf_eof, hipMemcpyHostToDevice, z->ctx->stream);
+    if (e != hipSuccess) rc = bsc_fail(BSC_ERR_HIP, "bsc_bgzf_close: %s", hipGetErrorString(e));
+    else z->n_pend += sizeof bsc_bgzf_eof;
+  }
+  if (!rc) rc = bsc_bgzf_hand_over(z, d_out, n_bytes);
+  pthread_mutex_lock(&bsc_bgzf_mu);
+  for (struct bsc_bgzf **q = &bsc_bgzf_open_list; *q; q = &(*q)->next_open)
+    if (*q == z) {
+      *q = z->next_open;
+      break;
+    }
+  pthread_mutex_unlock(&bsc_bgzf_mu);
+  (void)hipStreamSynchronize(z->ctx->stream);
+  hipFree(z->d_carry);
+  hipFree(z->d_stage);
+  hipFree(z->d_slots);
+  hipFree(z->d_sizes);
+  hipFree(z->d_offs);
+  hipFree(z->d_scratch);
+  hipFree(z->d_pend);
+  free(z);
+  return rc;
 }

@@ -934,6 +934,25 @@ int bsc_block_bcf_rawdev(bsc_context *ctx, const void *d_raw, uint32_t nr, const
                          uint64_t ins_pad, const bsc_prep_params *prep, uint32_t x, uint32_t y, const uint8_t *ref, const uint8_t *dbsnp,
                          const bsc_vcf_params *params, int with_stats, int32_t rid, const bsc_bcf_ids *ids, const bsc_bcf_names *names, uint8_t *out,
                          uint64_t out_cap, uint64_t *n_bytes, uint64_t *n_records, bsc_prep_stats *prep_stats, bsc_read_profile *profile);
+/* BGZF on the device (csrc/bgzfdev.hip; SAM specification section 4.1): a writer that turns a byte stream — the BCF magic and header from the
+ * host, then the blocks' streams as they are on the device — into BGZF members.  Member k holds exactly bytes [k 0xFF00, (k + 1) 0xFF00) of
+ * the LOGICAL stream (only the last is shorter), whatever the pieces the writes came in; each is one final DEFLATE block with dynamic
+ * Huffman codes, or a stored block where that would not be smaller than the input.  The bytes depend on the logical stream alone.
+ *   bsc_bgzf_open          a writer on the context (close it before the context is destroyed)
+ *   bsc_bgzf_write         n host bytes;  bsc_bgzf_write_device: n bytes in HBM (ready when the call is made: work the context queued
+ *                          is ordered before; a detached BCF stream may be freed when the call returns).  The bytes short of a member
+ *                          wait in HBM for the next write.
+ *   bsc_bgzf_take          the members completed so far (NULL and 0 when there are none), handed over like bsc_bcf_stream_detach:
+ *                          bsc_detached_read / _wait, then bsc_detached_free (they count against the four pooled buffers out)
+ *   bsc_bgzf_close         the last, short member and the 28-byte end-of-file marker (an empty stream is the marker alone), handed
+ *                          over the same way; frees the writer whatever it returns
+ * A NULL or closed writer, or a NULL pointer with bytes behind it: BSC_ERR_ARG. */
+typedef struct bsc_bgzf bsc_bgzf;
+int bsc_bgzf_open(bsc_context *ctx, bsc_bgzf **out);
+int bsc_bgzf_write(bsc_bgzf *z, const void *src, uint64_t n);
+int bsc_bgzf_write_device(bsc_bgzf *z, const void *d_src, uint64_t n);
+int bsc_bgzf_take(bsc_bgzf *z, void **d_out, uint64_t *n_bytes);
+int bsc_bgzf_close(bsc_bgzf *z, void **d_out, uint64_t *n_bytes);
 /* bsc_block_bcf_rawdev with the stream left on the device (room: dev_cap bytes; BSC_ERR_ARG and the length needed in *n_bytes when it does
  * not fit), and bytes [off, off + n) of that stream -> dst, queued on the context's stream (bsc_synchronize before dst is read): a contig-sized
  * block's stream is gigabytes — read in pieces through a small page-locked buffer it costs no page-locking of its own */

@@ -15,14 +15,16 @@
  *                                                   (BAM2BCF_HOST_BCF: bsc_block_records_raw, then bsc_bcf_block on this thread;
  *                                                   BAM2BCF_HOST_PREP: also the pre-processing on this thread,
  *                                                   bsc_prepare_templates_profile + bsc_block_records, as in round 4)
- *   output            fwrite                        bcf_write's write
+ *   output            fwrite                        bcf_write's write (-O u)
+ *     + BGZF          bsc_bgzf_write[_device]       -O b: hts_open(..., "wb")'s BGZF layer, ON THE DEVICE (csrc/bgzfdev.hip): the header and
+ *                     bsc_bgzf_take / _close        every block's kept stream go in, the completed members come out to the output thread
  *   at the end        bsc_report_json               output_stats
  *
- * Not a replacement of the bs_call executable (no option parsing, regions, contig lists, dbSNP, compression): a worked
+ * Not a replacement of the bs_call executable (no option parsing beyond -O, regions, contig lists, dbSNP, compressed VCF): a worked
  * example of the calls in order, and the C twin of bs_call_amd/pipeline.py — tests/test_gpu_pipeline.py checks that both
  * write the same bytes.
  *
- *   make bam2bcf && bs_call_amd/lib/bam2bcf in.bam ref.fa out.bcf report.json [sample]
+ *   make bam2bcf && bs_call_amd/lib/bam2bcf [-O u|b] in.bam ref.fa out.bcf report.json [sample]
  *
  * A sharded run over ONE file (SURVEY.md 8e on real input; the reference's unit of parallelism is a process per contig set, README.md): rank r of n
  *   bam2bcf --rank r --world n in.bam ref.fa out.bcf report.json [sample]
@@ -33,6 +35,12 @@
  * writes the header, the shards behind it in the header's contig order, and the report from the ranks' sums — the bytes of the single run
  * (tests/test_gpu_shard_bam.py).  tools/bam2bcf_sharded.sh starts the ranks, one per GPU, and merges.
  * The header's date lines are left out (the reference's --benchmark-mode) so that the output is reproducible.
+ *
+ * Output type (the reference's -O): -O u (the default) writes uncompressed BCF; -O b writes compressed BCF, BGZF on the device
+ * (bsc_bgzf_*, csrc/bgzfdev.hip): the header goes in through bsc_bgzf_write, every block's kept stream through bsc_bgzf_write_device, and
+ * the members bsc_bgzf_take hands over go to the output thread, which writes them at the running compressed offset; bsc_bgzf_close gives
+ * the last member and the end-of-file marker.  Decompressed, the file is byte for byte the -O u file.  -O b needs the device reader and
+ * encoder and a single run (a shard compressed on its own would cut its members elsewhere than the single run does).
  */
 #include <pthread.h>
 #include <stdio.h>
@@ -394,8 +402,21 @@ static int merge_main(int world, char **argv, const char *sample) {
 }
 
 int main(int argc, char **argv) {
-  int rank = -1, world = 1, merge = 0;
-  while (argc > 2 && argv[1][0] == '-' && argv[1][1] == '-') { /* --rank r --world n | --merge n */
+  int rank = -1, world = 1, merge = 0, bgzf = 0;
+  while (argc > 2 && argv[1][0] == '-' && (argv[1][1] == '-' || argv[1][1] == 'O')) { /* --rank r --world n | --merge n | -O u|b */
+    if (argv[1][1] == 'O') { /* -O b, -Ob */
+      const char *v = argv[1][2] ? argv[1] + 2 : argv[2];
+      if (strcmp(v, "b") && strcmp(v, "u")) {
+        fprintf(stderr, "%s: -O takes b (compressed BCF) or u (uncompressed BCF), not '%s'\n", argv[0], v);
+        return 2;
+      }
+      bgzf = v[0] == 'b';
+      const int k = argv[1][2] ? 1 : 2;
+      argv[k] = argv[0];
+      argv += k;
+      argc -= k;
+      continue;
+    }
     if (!strcmp(argv[1], "--rank")) rank = atoi(argv[2]);
     else if (!strcmp(argv[1], "--world")) world = atoi(argv[2]);
     else if (!strcmp(argv[1], "--merge")) merge = atoi(argv[2]);
@@ -405,7 +426,11 @@ int main(int argc, char **argv) {
     argc -= 2;
   }
   if (argc < 5 || world < 1 || (rank >= 0 && rank >= world)) {
-    fprintf(stderr, "usage: %s [--rank r --world n | --merge n] in.bam ref.fa out.bcf report.json [sample]\n", argv[0]);
+    fprintf(stderr, "usage: %s [-O u|b] [--rank r --world n | --merge n] in.bam ref.fa out.bcf report.json [sample]\n", argv[0]);
+    return 2;
+  }
+  if (bgzf && (rank >= 0 || merge > 0)) {
+    fprintf(stderr, "%s: -O b writes a single run's file; a sharded run (--rank / --merge) writes uncompressed BCF (-O u)\n", argv[0]);
     return 2;
   }
   const char *sample = argc > 5 ? argv[5] : "SAMPLE";
@@ -416,6 +441,10 @@ int main(int argc, char **argv) {
   const int host_reader = host_bcf || getenv("BAM2BCF_HOST_READER") != NULL;
   if (sharded && host_reader) {
     fprintf(stderr, "bam2bcf: a sharded run reads through the device reader (its contig selection)\n");
+    return 2;
+  }
+  if (bgzf && host_reader) {
+    fprintf(stderr, "bam2bcf: -O b compresses the device encoder's streams: not with BAM2BCF_HOST_READER / _HOST_BCF / _HOST_PREP\n");
     return 2;
   }
   const double t_start = now();
@@ -455,6 +484,7 @@ int main(int argc, char **argv) {
     return 1;
   }
   const int n_ref = N_REFS();
+  bsc_bgzf *zw = NULL;
   if (!sharded) {
     const char **names = calloc((size_t)n_ref + 1, sizeof *names);
     uint32_t *lens = calloc((size_t)n_ref + 1, sizeof *lens);
@@ -462,7 +492,23 @@ int main(int argc, char **argv) {
       names[i] = REF_NAME(i);
       lens[i] = REF_LEN(i);
     }
-    write_header(out, n_ref, names, lens, sample);
+    if (bgzf) { /* the header into the compressor: its members come out with the first block's */
+      char *hb = NULL;
+      size_t hn = 0;
+      FILE *hm = open_memstream(&hb, &hn);
+      if (!hm) {
+        perror("open_memstream");
+        return 1;
+      }
+      write_header(hm, n_ref, names, lens, sample);
+      if (fclose(hm)) {
+        perror("open_memstream");
+        return 1;
+      }
+      CHECK(bsc_bgzf_open(ctx, &zw));
+      CHECK(bsc_bgzf_write(zw, hb, hn));
+      free(hb);
+    } else write_header(out, n_ref, names, lens, sample);
     free(names);
     free(lens);
   }
@@ -595,8 +641,22 @@ int main(int argc, char **argv) {
         void *d_stream = NULL;
         uint64_t n_det = 0;
         CHECK(bsc_bcf_stream_detach(ctx, &d_stream, &n_det));
-        const out_job j = {d_stream, n_det, file_at, out_fd, 0};
-        writer_push(&W, j);
+        if (zw) { /* compressed on the device; the members completed so far go to the output thread */
+          CHECK(bsc_bgzf_write_device(zw, d_stream, n_det));
+          CHECK(bsc_detached_free(ctx, d_stream));
+          void *d_z = NULL;
+          uint64_t n_z = 0;
+          CHECK(bsc_bgzf_take(zw, &d_z, &n_z));
+          if (n_z) {
+            const out_job j = {d_z, n_z, file_at, out_fd, 0};
+            writer_push(&W, j);
+          }
+          file_at += n_z;
+          n_bytes = 0;
+        } else {
+          const out_job j = {d_stream, n_det, file_at, out_fd, 0};
+          writer_push(&W, j);
+        }
       }
       file_at += n_bytes;
       n_bytes = 0; /* written by the output thread */
@@ -665,6 +725,17 @@ int main(int argc, char **argv) {
     t0 = t1;
   }
   CHECK(r);
+  if (zw) { /* the last member and the end-of-file marker */
+    void *d_z = NULL;
+    uint64_t n_z = 0;
+    CHECK(bsc_bgzf_close(zw, &d_z, &n_z));
+    zw = NULL;
+    if (n_z) {
+      const out_job j = {d_z, n_z, file_at, out_fd, 0};
+      writer_push(&W, j);
+    }
+    file_at += n_z;
+  }
   if (W.started) { /* the output thread writes what it still holds, then goes */
     pthread_mutex_lock(&W.mu);
     W.quit = 1;
@@ -684,8 +755,10 @@ int main(int argc, char **argv) {
     uint64_t *d = ctot[cur_tid].snps;
     for (int i = 0; i < 14; i++) d[i] += after[i] - before[i];
   }
-  if (out) fclose(out);
-  else if (out_fd >= 0) close(out_fd);
+  if (out && fclose(out) && bgzf) {
+    perror(argv[3]);
+    return 1;
+  } else if (!out && out_fd >= 0) close(out_fd);
 
   /* the report */
   static bsc_site_stats total;
