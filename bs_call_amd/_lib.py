@@ -148,6 +148,11 @@ EXPORTS = (
     "bsc_block_records_rawdev",
     "bsc_block_bcf_rawdev",
     "bsc_block_bcf_rawdev_keep",
+    "bsc_vcf_text_block_device",
+    "bsc_vcf_text_sites_device",
+    "bsc_fmt_g",
+    "bsc_fmt_g_device",
+    "bsc_block_vcf_rawdev_keep",
     "bsc_bcf_stream_read",
     "bsc_inflate_raw",
     "bsc_crc32",
@@ -600,6 +605,17 @@ def load():
                                        C.POINTER(u64), C.POINTER(u64), vp, vp]
     L.bsc_block_bcf_rawdev_keep.restype = i32
     L.bsc_block_bcf_rawdev_keep.argtypes = [vp, vp, u32, vp, u64, vp, u64, u64, vp, u32, u32, vp, vp, vp, i32, i32, C.POINTER(BcfIds), vp, u64,
+                                            C.POINTER(u64), C.POINTER(u64), vp, vp]
+    L.bsc_vcf_text_block_device.restype = i32
+    L.bsc_vcf_text_block_device.argtypes = [vp, vp, vp, u64, C.c_char_p, vp, vp, u64, vp, vp]
+    L.bsc_vcf_text_sites_device.restype = i32
+    L.bsc_vcf_text_sites_device.argtypes = [vp, vp, vp, u32, C.c_char_p, vp, vp, u64, vp, vp]
+    L.bsc_fmt_g.restype = i32
+    L.bsc_fmt_g.argtypes = [vp, u64, vp]
+    L.bsc_fmt_g_device.restype = i32
+    L.bsc_fmt_g_device.argtypes = [vp, vp, u64, vp, vp]
+    L.bsc_block_vcf_rawdev_keep.restype = i32
+    L.bsc_block_vcf_rawdev_keep.argtypes = [vp, vp, u32, vp, u64, vp, u64, u64, vp, u32, u32, vp, vp, vp, i32, C.c_char_p, vp, u64,
                                             C.POINTER(u64), C.POINTER(u64), vp, vp]
     L.bsc_reads_chain_len_device.restype = i32
     L.bsc_reads_chain_len_device.argtypes = [vp, vp, u32, vp, u64, u32, u32, vp, vp, C.POINTER(VcfParams), i32, vp, vp, vp, vp]

@@ -655,6 +655,75 @@ class SiteCaller:
                                             d_totals, stream))
         del keep
 
+    # -- VCF text on the device (csrc/vcftextdev.hip) ---------------------------------------------------
+    @staticmethod
+    def _contig_bytes(contig):
+        return contig if isinstance(contig, (bytes, bytearray)) else str(contig).encode()
+
+    def fmt_g_device(self, d_v, n, d_out16, stream=None):
+        """bsc_fmt_g_device: n floats in HBM -> 16-byte slots in HBM (the characters of "%g", zero padding, the length in byte 15)."""
+        _check(self._L.bsc_fmt_g_device(self._h, d_v, n, d_out16, stream))
+
+    def fmt_g(self, values):
+        """bsc_fmt_g: the host checker of fmt_g_device (the C library's snprintf), float32[n] -> uint8[n, 16]."""
+        v = np.ascontiguousarray(values, dtype=np.float32)
+        out = np.zeros((len(v), 16), dtype=np.uint8)
+        _check(self._L.bsc_fmt_g(_ptr(v), len(v), _ptr(out)))
+        return out
+
+    def vcf_text_block_device(self, d_recs, d_n_recs, max_recs, contig, d_out, out_cap, d_totals, names=None, stream=None):
+        """bsc_vcf_text_block_device: packed records in HBM -> their VCF lines in HBM (asynchronous on `stream`)."""
+        nm, keep = self._bcf_names(names)
+        _check(self._L.bsc_vcf_text_block_device(self._h, d_recs, d_n_recs, max_recs, self._contig_bytes(contig), None if nm is None else C.addressof(nm),
+                                                 d_out, out_cap, d_totals, stream))
+        del keep
+
+    def vcf_text_sites_device(self, d_core, d_aux, n, contig, d_out, out_cap, d_totals, names=None, stream=None):
+        """bsc_vcf_text_sites_device: the per-position arrays of reads_chain_device (d_core, d_aux) -> the VCF lines, no packing pass."""
+        nm, keep = self._bcf_names(names)
+        _check(self._L.bsc_vcf_text_sites_device(self._h, d_core, d_aux, n, self._contig_bytes(contig), None if nm is None else C.addressof(nm), d_out,
+                                                 out_cap, d_totals, stream))
+        del keep
+
+    def block_vcf_rawdev(self, blk, ref, contig, names=None, left_trim=(0, 0), right_trim=(0, 0), min_qual=20, all_positions=False, reg_start=1,
+                         reg_stop=0xFFFFFFFF, dbsnp=None, with_stats=False, cap=None, profile=None):
+        """bsc_block_vcf_rawdev_keep + bsc_bcf_stream_read: a block of the DEVICE reader -> the block's VCF lines (bytes), encoded on the
+        device.  Returns (bytes, n_records, PREP_STATS record).  cap: the room on the device (default: sized from the block; a stream
+        that does not fit is encoded once more into the room it needs, bsc_block_bcf_again)."""
+        from .abi import PREP_PARAMS, PREP_STATS
+
+        x, y = int(blk.x), int(blk.y)
+        ref = np.ascontiguousarray(ref, dtype=np.uint8)
+        n = y - x + 1
+        if len(ref) != n + 2:
+            raise ValueError("ref must have y - x + 3 entries (x .. y + 2)")
+        db = None if dbsnp is None else np.ascontiguousarray(dbsnp, dtype=np.uint8)
+        nm, keep = self._bcf_names(names)
+        cap_given = cap
+        cap = 64 + 160 * n if cap is None else int(cap)
+        par = np.zeros(1, dtype=PREP_PARAMS)
+        par["left_trim"][0], par["right_trim"][0], par["min_qual"][0] = left_trim, right_trim, min_qual
+        p = _lib.VcfParams(1 if all_positions else 0, reg_start, reg_stop)
+        nb, nr = C.c_uint64(0), C.c_uint64(0)
+        st = np.zeros(1, dtype=PREP_STATS)
+        pf = None if profile is None else _lib.ReadProfile(None, 0, 0, profile.counts.ctypes.data, profile.counts.shape[0], profile.used)
+        rc = self._L.bsc_block_vcf_rawdev_keep(self._h, blk.d_tpl, blk.nr, blk.d_seq, blk.seq_bytes, blk.d_misms, blk.n_misms, blk.ins_pad, _ptr(par), x, y,
+                                               _ptr(ref), None if db is None else _ptr(db), C.byref(p), 1 if with_stats else 0,
+                                               self._contig_bytes(contig), None if nm is None else C.addressof(nm), cap, C.byref(nb), C.byref(nr),
+                                               _ptr(st), None if pf is None else C.byref(pf))
+        if rc == -1 and nb.value > cap and cap_given is None:
+            cap = int(nb.value)
+            rc = self._L.bsc_block_bcf_again(self._h, None, cap, C.byref(nb), C.byref(nr))
+        _check(rc)
+        del keep
+        if pf is not None:
+            profile.used = int(pf.used)
+        out = np.empty(max(int(nb.value), 1), dtype=np.uint8)
+        if nb.value:
+            _check(self._L.bsc_bcf_stream_read(self._h, 0, nb.value, _ptr(out)))
+            self.synchronize()
+        return out[: nb.value].tobytes(), nr.value, st[0]
+
     def blocks_records(self, blocks, ref, out=None, all_positions=False, reg_start=1, reg_stop=0xFFFFFFFF, dbsnp=None, with_stats=False,
                        submit_only=False):
         """Several blocks in one launch sequence (bsc_blocks_records): blocks = [(templates, seq, x, y), ...] in genome order;

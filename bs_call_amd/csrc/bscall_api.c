@@ -76,6 +76,11 @@ int bsc_dev_launch_bcf(const void *recs, const void *core, const void *aux, cons
                        const bsc_bcf_ids *ids, const void *name_pos, const void *name_off, const void *name_bytes, uint32_t n_names,
                        void *tile_bytes, void *tile_off, void *scan_tmp, size_t scan_tmp_bytes, void *out, uint64_t out_cap, void *totals,
                        int num_cus, void *stream, const void *emit_len); /* bcfdev.hip */
+int bsc_dev_launch_vcf_text(const void *recs, const void *core, const void *aux, const void *n_recs, uint64_t max_recs, const char *contig,
+                            uint32_t contig_len, const void *name_pos, const void *name_off, const void *name_bytes, uint32_t n_names,
+                            void *tile_bytes, void *tile_off, void *line_len, void *scan_tmp, size_t scan_tmp_bytes, void *out, uint64_t out_cap,
+                            void *totals, int num_cus, void *stream); /* vcftextdev.hip */
+int bsc_dev_launch_fmt_g(const void *v, uint64_t n, void *out16, int num_cus, void *stream);
 int bsc_dev_launch_ref_pad(const void *packed, const void *d_blk, uint32_t n_blk, void *padded, uint32_t n_pos, int num_cus, void *stream);
 int bsc_dev_launch_bin_reads_multi(const void *tpl, uint32_t nr, const void *seq, uint64_t seq_bytes, const void *d_blk, uint32_t n_blk,
                                    uint32_t n_bins, void *tflag, void *bin_cnt, void *bin_off, void *bin_cur, void *scan_tmp,
@@ -154,6 +159,8 @@ struct bsc_context {
    * many bytes went ahead of the length, the bytes per position the next copy is sized from */
   void *d_btb, *d_bto, *d_bscn, *d_bnm, *d_bcf, *d_btot;
   size_t cap_btb, cap_bto, cap_bscn, cap_bnm, cap_bcf, cap_btot;
+  void *d_vtl; /* the text encoder (vcftextdev.hip): a line's length per record / position, between its two passes */
+  size_t cap_vtl;
   struct { /* streams handed to the caller (bsc_bcf_stream_detach) come back here (bsc_detached_free) and are taken again by the next block:
             * no hipMalloc / hipFree — a device-wide wait — in the steady state of a run that writes behind the calling */
     void *p[4];
@@ -177,6 +184,8 @@ struct bsc_context {
     bsc_bcf_ids ids;
     const void *emit;
     bsc_bcf_names names;
+    int text;         /* the block was a text block (bsc_block_vcf_rawdev_keep): the text encoder runs again */
+    char contig[256]; /* and its contig name */
   } again;
   int no_h2d_turns; /* BSC_NO_H2D_TURNS in the environment when the context was made (the A/B of tools/bench_two_contexts.py) */
   void *d_emit; /* the chain's emit flags, a byte per position, for the block entries' packing / encoding passes (bsc_records_queue) */
@@ -522,6 +531,7 @@ int bsc_destroy(bsc_context *ctx) {
   if (ctx->pool_mu_made) pthread_mutex_destroy(&ctx->pool_mu);
   hipFree(ctx->d_bcf);
   hipFree(ctx->d_btot);
+  hipFree(ctx->d_vtl);
   hipFree(ctx->d_emit);
   for (int i = 0; i < 2; i++)
     if (ctx->ev_raw[i]) hipEventDestroy(ctx->ev_raw[i]);
@@ -1906,6 +1916,104 @@ int bsc_bcf_sites_len_device(bsc_context *ctx, const void *d_core, const void *d
   return rc;
 }
 
+/* ---- the same records as VCF text (vcftextdev.hip): the line bsc_vcf_format_rec writes and '\n', per written record ---------------- */
+static int bsc_contig_check(const char *who, const char *contig, uint32_t *len) {
+  *len = 0;
+  if (!contig) return bsc_fail(BSC_ERR_ARG, "%s: NULL argument", who);
+  const size_t l = strnlen(contig, 256);
+  if (l == 0 || l > 255) return bsc_fail(BSC_ERR_ARG, "%s: the contig name must have 1 .. 255 bytes", who);
+  for (size_t i = 0; i < l; i++)
+    if (contig[i] == '\t' || contig[i] == '\n') return bsc_fail(BSC_ERR_ARG, "%s: the contig name holds a tab or a newline", who);
+  *len = (uint32_t)l;
+  return BSC_OK;
+}
+
+static int bsc_vcf_text_encode(bsc_context *ctx, const char *who, const void *d_recs, const void *d_core, const void *d_aux, const void *d_n_recs,
+                               uint64_t max_recs, const char *contig, const bsc_bcf_names *names, void *d_out, uint64_t out_cap, void *d_totals,
+                               void *stream) {
+  if (!ctx || !d_totals || (out_cap && !d_out)) return bsc_fail(BSC_ERR_ARG, "%s: NULL argument", who);
+  if (d_recs ? !d_n_recs : (max_recs && (!d_core || !d_aux))) return bsc_fail(BSC_ERR_ARG, "%s: NULL argument", who);
+  if (((uintptr_t)d_recs & 15u) || ((uintptr_t)d_core & 15u) || ((uintptr_t)d_aux & 15u) || ((uintptr_t)d_n_recs & 7u) || ((uintptr_t)d_totals & 7u))
+    return bsc_fail(BSC_ERR_ARG, "%s: the records must be 16-byte, the count and the totals 8-byte aligned", who);
+  if ((uintptr_t)d_out & 15u) /* the write kernel owns whole 16-byte pieces of the stream, counted from its start */
+    return bsc_fail(BSC_ERR_ARG, "%s: d_out must be 16-byte aligned (append blocks at multiples of 16, or encode into a buffer of its own)", who);
+  if (max_recs > 0x1fffffffc0ull) return bsc_fail(BSC_ERR_ARG, "%s: more than 2^37 records", who);
+  uint32_t contig_len = 0;
+  int rc;
+  if ((rc = bsc_contig_check(who, contig, &contig_len))) return rc;
+  uint32_t n_names = 0;
+  uint64_t name_bytes = 0;
+  const int names_up = names && ctx->names_up == names; /* a block entry: checked and uploaded with the block's other inputs */
+  if (names_up) {
+    n_names = ctx->names_up_n;
+    name_bytes = ctx->names_up_bytes;
+  } else if ((rc = bsc_names_check(who, names, &n_names, &name_bytes)))
+    return rc;
+  BSC_ENTER(ctx);
+  hipStream_t s = (hipStream_t)stream;
+  const uint32_t n_tiles = (uint32_t)((max_recs + 63u) / 64u);
+  size_t scan_bytes = 0;
+  if (bsc_dev_scan_tmp_bytes_u64(n_tiles + 1u, &scan_bytes)) return bsc_fail(BSC_ERR_HIP, "%s: scan size query failed", who);
+  if ((rc = bsc_reserve(&ctx->d_btb, &ctx->cap_btb, ((size_t)n_tiles + 1u) * 8u))) return rc;
+  if ((rc = bsc_reserve(&ctx->d_bto, &ctx->cap_bto, ((size_t)n_tiles + 1u) * 8u))) return rc;
+  if ((rc = bsc_reserve(&ctx->d_bscn, &ctx->cap_bscn, scan_bytes ? scan_bytes : 1))) return rc;
+  if ((rc = bsc_reserve(&ctx->d_vtl, &ctx->cap_vtl, ((size_t)n_tiles + 1u) * 128u))) return rc;
+  const void *d_pos = NULL, *d_off = NULL, *d_nb = NULL;
+  if (n_names) { /* positions | offsets | bytes in one workspace, as the BCF encoder */
+    const size_t o_off = (size_t)n_names * 4u, o_by = o_off + ((size_t)n_names + 1u) * 4u;
+    if (!names_up) {
+      if ((rc = bsc_reserve(&ctx->d_bnm, &ctx->cap_bnm, o_by + (size_t)name_bytes + 1u))) return rc;
+      HIP_TRY(hipMemcpyAsync(ctx->d_bnm, names->pos, (size_t)n_names * 4u, hipMemcpyHostToDevice, s));
+      HIP_TRY(hipMemcpyAsync((char *)ctx->d_bnm + o_off, names->off, ((size_t)n_names + 1u) * 4u, hipMemcpyHostToDevice, s));
+      if (name_bytes) HIP_TRY(hipMemcpyAsync((char *)ctx->d_bnm + o_by, names->bytes, (size_t)name_bytes, hipMemcpyHostToDevice, s));
+    }
+    d_pos = ctx->d_bnm;
+    d_off = (char *)ctx->d_bnm + o_off;
+    d_nb = (char *)ctx->d_bnm + o_by;
+  }
+  HIP_TRY(hipMemsetAsync(d_totals, 0, 3 * sizeof(unsigned long long), s));
+  const int e = bsc_dev_launch_vcf_text(d_recs, d_core, d_aux, d_n_recs, max_recs, contig, contig_len, d_pos, d_off, d_nb, n_names, ctx->d_btb, ctx->d_bto,
+                                        ctx->d_vtl, ctx->d_bscn, scan_bytes, d_out, out_cap, d_totals, ctx->num_cus, stream);
+  if (e) return bsc_fail(BSC_ERR_HIP, "VCF text encoder launch failed: %s", hipGetErrorString((hipError_t)e));
+  return BSC_OK;
+}
+
+int bsc_vcf_text_block_device(bsc_context *ctx, const void *d_recs, const void *d_n_recs, uint64_t max_recs, const char *contig,
+                              const bsc_bcf_names *names, void *d_out, uint64_t out_cap, void *d_totals, void *stream) {
+  if (!d_n_recs || (max_recs && !d_recs)) return bsc_fail(BSC_ERR_ARG, "bsc_vcf_text_block_device: NULL argument");
+  /* (no records at all: the per-position form over zero positions — nothing is read) */
+  return bsc_vcf_text_encode(ctx, "bsc_vcf_text_block_device", d_recs, NULL, NULL, d_recs ? d_n_recs : NULL, max_recs, contig, names, d_out, out_cap,
+                             d_totals, stream);
+}
+
+int bsc_vcf_text_sites_device(bsc_context *ctx, const void *d_core, const void *d_aux, uint32_t n, const char *contig, const bsc_bcf_names *names,
+                              void *d_out, uint64_t out_cap, void *d_totals, void *stream) {
+  return bsc_vcf_text_encode(ctx, "bsc_vcf_text_sites_device", NULL, d_core, d_aux, NULL, n, contig, names, d_out, out_cap, d_totals, stream);
+}
+
+/* the number formatter alone: 16 bytes per value — the characters, zero padding, the length in byte 15.  Host: the C library. */
+int bsc_fmt_g(const float *v, uint64_t n, uint8_t *out16) {
+  if (n && (!v || !out16)) return bsc_fail(BSC_ERR_ARG, "bsc_fmt_g: NULL argument");
+  for (uint64_t i = 0; i < n; i++) {
+    char buf[32];
+    const int l = snprintf(buf, sizeof buf, "%g", (double)v[i]);
+    if (l < 0 || l > 15) return bsc_fail(BSC_ERR_RANGE, "bsc_fmt_g: a value printed in %d characters", l);
+    memset(out16 + 16u * i, 0, 16);
+    memcpy(out16 + 16u * i, buf, (size_t)l);
+    out16[16u * i + 15u] = (uint8_t)l;
+  }
+  return BSC_OK;
+}
+
+int bsc_fmt_g_device(bsc_context *ctx, const void *d_v, uint64_t n, void *d_out16, void *stream) {
+  if (!ctx || (n && (!d_v || !d_out16))) return bsc_fail(BSC_ERR_ARG, "bsc_fmt_g_device: NULL argument");
+  if (((uintptr_t)d_v & 3u) || ((uintptr_t)d_out16 & 15u)) return bsc_fail(BSC_ERR_ARG, "bsc_fmt_g_device: the values must be 4-byte, the slots 16-byte aligned");
+  BSC_ENTER(ctx);
+  const int e = bsc_dev_launch_fmt_g(d_v, n, d_out16, ctx->num_cus, stream);
+  if (e) return bsc_fail(BSC_ERR_HIP, "bsc_fmt_g_device: launch failed: %s", hipGetErrorString((hipError_t)e));
+  return BSC_OK;
+}
+
 static void bsc_bcf_pool_take(bsc_context *ctx, size_t need);
 /* what bsc_block_bcf asks of bsc_records_queue: the encoder behind the packing, its stream instead of the records on the way back */
 typedef struct {
@@ -1914,6 +2022,8 @@ typedef struct {
   const bsc_bcf_names *names;
   uint8_t *out;
   uint64_t out_cap;
+  int text;           /* 0: BCF2 records (bcfdev.hip; ids is read).  1: VCF text lines (vcftextdev.hip; contig is read, ids and rid are not) */
+  const char *contig; /* text: the contig's name, checked by the entry */
 } bsc_bcf_req;
 
 /*
@@ -2075,13 +2185,19 @@ static int bsc_records_queue(bsc_context *ctx, const bsc_template *tpl, uint32_t
     ctx->emit_hint = d_emit;
     ctx->again.sz = sz;
     ctx->again.rid = bcf->rid;
-    ctx->again.ids = *bcf->ids;
+    ctx->again.text = bcf->text;
+    if (bcf->text) {
+      strncpy(ctx->again.contig, bcf->contig, sizeof ctx->again.contig - 1);
+      ctx->again.contig[sizeof ctx->again.contig - 1] = 0;
+    } else
+      ctx->again.ids = *bcf->ids;
     ctx->again.emit = d_emit;
     ctx->again.have_names = names_ready != NULL;
     ctx->again.n_names = ctx->names_up_n;
     ctx->again.name_bytes = ctx->names_up_bytes;
     ctx->names_up = names_ready;
-    rc = bsc_bcf_sites_device(ctx, ctx->d_vout, ctx->d_out, sz, bcf->rid, bcf->ids, bcf->names, ctx->d_bcf, bcf->out_cap, ctx->d_btot, s);
+    rc = bcf->text ? bsc_vcf_text_sites_device(ctx, ctx->d_vout, ctx->d_out, sz, bcf->contig, bcf->names, ctx->d_bcf, bcf->out_cap, ctx->d_btot, s)
+                   : bsc_bcf_sites_device(ctx, ctx->d_vout, ctx->d_out, sz, bcf->rid, bcf->ids, bcf->names, ctx->d_bcf, bcf->out_cap, ctx->d_btot, s);
     ctx->emit_hint = NULL;
     ctx->names_up = NULL;
     if (rc) return rc;
@@ -2111,11 +2227,13 @@ static int bsc_bcf_finish(bsc_context *ctx, uint8_t *out, int inexact) {
   const unsigned long long bytes = ctx->h_cnt[4], bad = ctx->h_cnt[5];
   ctx->bcf_bytes = bytes;
   ctx->bcf_copied = ctx->bcf_copied < bytes ? ctx->bcf_copied : bytes;
-  if (bad) return bsc_fail(BSC_ERR_ARG, "bsc_block_bcf: %llu records with a genotype beyond 9 or more than 6 likelihoods", bad);
+  const char *const who = ctx->again.text ? "bsc_block_vcf" : "bsc_block_bcf"; /* (again.* describe the block in flight since bsc_records_queue) */
+  /* the chain never forms such a record; a block entry refuses them for both formats (the device-level text entries write them clamped) */
+  if (bad) return bsc_fail(BSC_ERR_ARG, "%s: %llu records with a genotype beyond 9 or more than 6 likelihoods", who, bad);
   if (bytes > ctx->bcf_cap) {
     ctx->again.valid = 1; /* bsc_block_bcf_again: the encoder alone, into the room it asks for */
     ctx->again.inexact = inexact;
-    return bsc_fail(BSC_ERR_ARG, "bsc_block_bcf: the block's stream has %llu bytes, out_cap is %llu", bytes, (unsigned long long)ctx->bcf_cap);
+    return bsc_fail(BSC_ERR_ARG, "%s: the block's stream has %llu bytes, out_cap is %llu", who, bytes, (unsigned long long)ctx->bcf_cap);
   }
   if (ctx->bcf_keep) return bsc_inexact_status(inexact);
   if (bytes > ctx->bcf_copied) { /* first block, or more bytes than the share so far suggested: the rest in a second copy */
@@ -2141,7 +2259,9 @@ int bsc_block_bcf_again(bsc_context *ctx, uint8_t *out, uint64_t out_cap, uint64
   ctx->names_up_n = ctx->again.n_names;
   ctx->names_up_bytes = ctx->again.name_bytes;
   ctx->emit_hint = ctx->again.emit;
-  rc = bsc_bcf_sites_device(ctx, ctx->d_vout, ctx->d_out, ctx->again.sz, ctx->again.rid, &ctx->again.ids, ctx->names_up, ctx->d_bcf, out_cap, ctx->d_btot, s);
+  rc = ctx->again.text
+           ? bsc_vcf_text_sites_device(ctx, ctx->d_vout, ctx->d_out, ctx->again.sz, ctx->again.contig, ctx->names_up, ctx->d_bcf, out_cap, ctx->d_btot, s)
+           : bsc_bcf_sites_device(ctx, ctx->d_vout, ctx->d_out, ctx->again.sz, ctx->again.rid, &ctx->again.ids, ctx->names_up, ctx->d_bcf, out_cap, ctx->d_btot, s);
   ctx->emit_hint = NULL;
   ctx->names_up = NULL;
   if (rc) return rc;
@@ -2150,7 +2270,9 @@ int bsc_block_bcf_again(bsc_context *ctx, uint8_t *out, uint64_t out_cap, uint64
   const unsigned long long bytes = ctx->h_cnt[4];
   *n_bytes = ctx->bcf_bytes = bytes;
   *n_records = ctx->h_cnt[6];
-  if (bytes > out_cap) return bsc_fail(BSC_ERR_ARG, "bsc_block_bcf: the block's stream has %llu bytes, out_cap is %llu", bytes, (unsigned long long)out_cap);
+  if (bytes > out_cap)
+    return bsc_fail(BSC_ERR_ARG, "%s: the block's stream has %llu bytes, out_cap is %llu", ctx->again.text ? "bsc_block_vcf" : "bsc_block_bcf", bytes,
+                    (unsigned long long)out_cap);
   if (out && bytes) {
     HIP_TRY(hipMemcpyAsync(out, ctx->d_bcf, (size_t)bytes, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
@@ -2439,6 +2561,33 @@ int bsc_block_bcf_rawdev_keep(bsc_context *ctx, const void *d_raw, uint32_t nr, 
   if ((rc = bsc_block_rawdev_check(ctx, d_raw, nr, d_seq, seq_bytes, d_misms, n_misms, prep, x, y, ref, params, n_records, NULL, 0))) return rc;
   if (prep_stats) memset(prep_stats, 0, sizeof *prep_stats);
   const bsc_bcf_req req = {rid, ids, names, NULL, dev_cap};
+  ctx->bcf_bytes = 0;
+  if (!nr) rc = bsc_block_records_(ctx, NULL, 0, NULL, 0, x, y, ref, dbsnp, params, with_stats, NULL, 0, n_records, &req);
+  else {
+    BSC_ENTER(ctx);
+    rc = bsc_block_records_rawdev_(ctx, d_raw, nr, d_seq, seq_bytes, d_misms, n_misms, seq_bytes + ins_pad + 16, prep, x, y, ref, dbsnp, params, with_stats,
+                                   NULL, 0, n_records, prep_stats, profile, &req);
+  }
+  *n_bytes = ctx->bcf_bytes;
+  return rc;
+}
+
+/* The text twin of bsc_block_bcf_rawdev_keep: the same call with the text encoder named in the request; the stream (lines, not BCF2 records)
+ * is handed over and read with the same bsc_bcf_stream_* / bsc_detached_* entries, and a dev_cap too small is answered the same way
+ * (bsc_block_bcf_again then runs the TEXT encoder once more). */
+int bsc_block_vcf_rawdev_keep(bsc_context *ctx, const void *d_raw, uint32_t nr, const void *d_seq, uint64_t seq_bytes, const void *d_misms, uint64_t n_misms,
+                              uint64_t ins_pad, const bsc_prep_params *prep, uint32_t x, uint32_t y, const uint8_t *ref, const uint8_t *dbsnp,
+                              const bsc_vcf_params *params, int with_stats, const char *contig, const bsc_bcf_names *names, uint64_t dev_cap,
+                              uint64_t *n_bytes, uint64_t *n_records, bsc_prep_stats *prep_stats, bsc_read_profile *profile) {
+  if (!n_bytes || !n_records) return bsc_fail(BSC_ERR_ARG, "bsc_block_vcf_rawdev_keep: NULL argument");
+  *n_bytes = 0;
+  *n_records = 0;
+  int rc;
+  uint32_t contig_len;
+  if ((rc = bsc_contig_check("bsc_block_vcf_rawdev_keep", contig, &contig_len))) return rc;
+  if ((rc = bsc_block_rawdev_check(ctx, d_raw, nr, d_seq, seq_bytes, d_misms, n_misms, prep, x, y, ref, params, n_records, NULL, 0))) return rc;
+  if (prep_stats) memset(prep_stats, 0, sizeof *prep_stats);
+  const bsc_bcf_req req = {0, NULL, names, NULL, dev_cap, 1, contig};
   ctx->bcf_bytes = 0;
   if (!nr) rc = bsc_block_records_(ctx, NULL, 0, NULL, 0, x, y, ref, dbsnp, params, with_stats, NULL, 0, n_records, &req);
   else {
@@ -2776,6 +2925,7 @@ static int bsc_blocks_queue(bsc_context *ctx, const bsc_block_desc *blocks, uint
     ctx->emit_hint = d_emit;
     ctx->again.sz = P;
     ctx->again.rid = bcf->rid;
+    ctx->again.text = 0;
     ctx->again.ids = *bcf->ids;
     ctx->again.emit = d_emit;
     ctx->again.have_names = names_ready != NULL;

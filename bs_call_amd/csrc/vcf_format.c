@@ -3,6 +3,9 @@
  * htslib's VCF writer gives the fields the reference encodes in _print_vcf_entry (src/print_vcf.c:160-380).  No
  * computation: every number comes from the device records.  Integer fields are exact by construction; the text form of
  * the GL floats ("%g", six significant digits, as htslib prints floats) is not pinned against htslib here.
+ *
+ * This is the CHECKER of the device's text encoder (csrc/vcftextdev.hip, vcftext_emit.h, fmtg_dev.h): the device writes, for any 128 bytes
+ * of record, exactly the line this file writes (and '\n') — change one and the other has to follow; tests/test_gpu_vcf_text.py compares them.
  */
 #include <stdio.h>
 #include <string.h>

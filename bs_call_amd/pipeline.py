@@ -17,7 +17,7 @@ def run(bam_path: str, reference: Dict[str, np.ndarray], bcf_path: str, sample: 
         caller: Optional[SiteCaller] = None, dbsnp=None, compressed: bool = True, date=None, left_trim=(0, 0), right_trim=(0, 0),
         min_qual: Optional[int] = None, benchmark_mode: bool = False, under_conv: Optional[float] = None, over_conv: Optional[float] = None,
         host_prep: bool = False, host_bcf: bool = False, device_reader: bool = False, shard_rank: Optional[int] = None, shard_world: int = 1,
-        reduce_device=None, **reader_kw) -> dict:
+        reduce_device=None, text: bool = False, **reader_kw) -> dict:
     """reference: contig name -> uint8 reference codes (0 = N, 1..4 = ACGT; position 1 first).  Returns a summary dict.
     under_conv / over_conv / min_qual (defaults 0.01 / 0.05 / 20, src/init_param.c:26-31) are the MODEL's parameters: without
     `caller` the run builds its SiteCaller from them; with one, they are taken from it and a differing explicit value is an error
@@ -31,7 +31,12 @@ def run(bam_path: str, reference: Dict[str, np.ndarray], bcf_path: str, sample: 
     shard.assign_contigs (longest first), every rank reads the stretches of the file that hold ITS contigs (the device reader's contig
     selection: no index file), writes each contig's records to a shard beside bcf_path, and at the end the ranks all-reduce what the report
     sums (torch.distributed's default group: RCCL between GPUs, gloo in the rehearsal; reduce_device = the tensors' device) and rank 0
-    concatenates the shards in contig order behind the header — the bytes of the single run."""
+    concatenates the shards in contig order behind the header — the bytes of the single run.
+    text: the output file is VCF TEXT (the reference's -O v; with `compressed`, BGZF members cut every 0xFF00 bytes: its -O z) — the header
+    text, then every block's lines as the device's text encoder writes them (SiteCaller.block_vcf_rawdev: bsc_block_vcf_rawdev_keep).  Needs
+    device_reader; a sharded text run is refused."""
+    if text and (shard_rank is not None or not device_reader or host_prep or host_bcf):
+        raise ValueError("text=True is a single run on the device reader (device_reader=True, no shard_rank, no host_prep / host_bcf)")
     own = caller is None
     if own:
         under_conv = 0.01 if under_conv is None else under_conv
@@ -111,8 +116,12 @@ def run(bam_path: str, reference: Dict[str, np.ndarray], bcf_path: str, sample: 
                     flags = None if dbsnp is None else dbsnp.flags(x, y - x + 1)
                     if device_reader:  # the block is in HBM already: pre-processing, calling, encoding behind it
                         names = None if dbsnp is None else dbsnp.names(x, y - x + 1)
-                        blob, n_rec, st = c.block_bcf_rawdev(dblk, ref, tid, names=names, left_trim=left_trim, right_trim=right_trim, min_qual=min_qual,
-                                                             reg_stop=len(codes), dbsnp=flags, with_stats=True, profile=prof)
+                        if text:
+                            blob, n_rec, st = c.block_vcf_rawdev(dblk, ref, name, names=names, left_trim=left_trim, right_trim=right_trim, min_qual=min_qual,
+                                                                 reg_stop=len(codes), dbsnp=flags, with_stats=True, profile=prof)
+                        else:
+                            blob, n_rec, st = c.block_bcf_rawdev(dblk, ref, tid, names=names, left_trim=left_trim, right_trim=right_trim, min_qual=min_qual,
+                                                                 reg_stop=len(codes), dbsnp=flags, with_stats=True, profile=prof)
                         recs = None
                     elif host_prep:  # round 4's split: the process thread's per-template work here, then the block
                         tpl, pseq, st = prepare_templates(raw, seq, ms, left_trim, right_trim, min_qual, profile=prof, x=x, ref=ref)
@@ -145,6 +154,8 @@ def run(bam_path: str, reference: Dict[str, np.ndarray], bcf_path: str, sample: 
                     pass
                 for f_ in shard_files.values():
                     f_.close()
+            elif text:
+                vcf.write_vcf_blobs(bcf_path, header, block_blobs(), compressed)
             else:
                 vcf.write_bcf(bcf_path, header, block_blobs(), compressed)  # blocks go to the writer as they are formed
             cts, bases = rd.filter_counts()
@@ -189,7 +200,7 @@ def run(bam_path: str, reference: Dict[str, np.ndarray], bcf_path: str, sample: 
             per_contig = [(names[i], tab[i].reshape(7, 2)) for i in range(len(refs)) if seen[i]]
             if dist.is_available() and dist.is_initialized():
                 dist.barrier()  # every shard is on disk
-        text = report.render_json(site_stats, gc=gc, min_qual=min_qual, date=date, have_dbsnp=dbsnp is not None, filter_cts=cts, filter_bases=bases,
+        report_text = report.render_json(site_stats, gc=gc, min_qual=min_qual, date=date, have_dbsnp=dbsnp is not None, filter_cts=cts, filter_bases=bases,
                                   base_filter=np.asarray(base_filter).tolist(), read_profile=prof_rows, contigs=per_contig)
         if sharded and shard_rank == 0:  # the header, then the contigs' shards in the header's order
             import os
@@ -209,8 +220,8 @@ def run(bam_path: str, reference: Dict[str, np.ndarray], bcf_path: str, sample: 
             vcf.write_bcf(bcf_path, header, shards(), compressed)
         if report_path and (not sharded or shard_rank == 0):
             with open(report_path, "w") as f:
-                f.write(text)
-        return {"blocks": n_blocks, "records": n_records, "report": text, "filter_cts": cts, "contigs": [n for n, _ in per_contig]}
+                f.write(report_text)
+        return {"blocks": n_blocks, "records": n_records, "report": report_text, "filter_cts": cts, "contigs": [n for n, _ in per_contig]}
     finally:
         if own:
             c.close()

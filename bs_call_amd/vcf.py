@@ -1,5 +1,7 @@
-"""Host-side text rendering of bsc_vcf_core records (+ their gt_meth) as VCF data lines — through the library's ONE
-formatter, bsc_vcf_format / bsc_vcf_format_rec (host C, csrc/vcf_format.c).
+"""Host-side text rendering of bsc_vcf_core records (+ their gt_meth) as VCF data lines — through the library's ONE host
+formatter, bsc_vcf_format / bsc_vcf_format_rec (host C, csrc/vcf_format.c).  The device writes the same lines at speed
+(csrc/vcftextdev.hip: SiteCaller.vcf_text_*_device, block_vcf_rawdev); the host formatter is that encoder's CHECKER, and the
+contract between them is bytes: whatever bsc_vcf_format_rec writes for a record, the device writes.
 
 The reference hands each record to htslib (bcf_write, src/print_vcf.c:160-380); htslib is not part of this
 repository, so the lines are the layout htslib's VCF text writer gives those fields.  Integer fields are exact by
@@ -191,6 +193,26 @@ def write_vcf(path, header: str, line_blocks, bgzip=False):
         pend = bytearray()
         for c in chunks():
             pend += c
+            while len(pend) >= 0xFF00:
+                f.write(_bgzf_block(bytes(pend[:0xFF00])))
+                del pend[:0xFF00]
+        if pend:
+            f.write(_bgzf_block(bytes(pend)))
+        f.write(BGZF_EOF)
+
+
+def write_vcf_blobs(path, header: str, blobs, compressed=False):
+    """write_vcf for blocks that are already bytes (the device text encoder's streams: SiteCaller.block_vcf_rawdev): the header,
+    then the blobs; compressed=True writes BGZF members cut every 0xFF00 bytes of the stream, as write_bcf does."""
+    with open(path, "wb") as f:
+        if not compressed:
+            f.write(header.encode())
+            for b in blobs:
+                f.write(b)
+            return
+        pend = bytearray(header.encode())
+        for b in blobs:
+            pend += b
             while len(pend) >= 0xFF00:
                 f.write(_bgzf_block(bytes(pend[:0xFF00])))
                 del pend[:0xFF00]

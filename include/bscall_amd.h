@@ -961,6 +961,43 @@ int bsc_block_bcf_rawdev_keep(bsc_context *ctx, const void *d_raw, uint32_t nr, 
                               const bsc_vcf_params *params, int with_stats, int32_t rid, const bsc_bcf_ids *ids, const bsc_bcf_names *names, uint64_t dev_cap,
                               uint64_t *n_bytes, uint64_t *n_records, bsc_prep_stats *prep_stats, bsc_read_profile *profile);
 int bsc_bcf_stream_read(bsc_context *ctx, uint64_t off, uint64_t n, void *dst);
+
+/*
+ * VCF TEXT on the device (csrc/vcftextdev.hip): for every record with emit != 0, in position order, the line bsc_vcf_format_rec writes
+ * for it and '\n' — the data lines of the reference's -O v; through a bsc_bgzf writer, its -O z.  The host formatter is the checker: the
+ * bytes are the same for ANY record contents (gt > 9 prints as genotype 0, at most six GL values, "%.5s" of the context strings stops at
+ * a NUL; FORMAT GL is printf's "%g" of each float, in integer arithmetic: csrc/fmtg_dev.h).
+ *   contig               CHROM: 1 .. 255 bytes without a tab or a newline (BSC_ERR_ARG otherwise).  The longest line is the contig's name
+ *                        + 410 bytes (at most 665).
+ *   names                the table the BCF encoder takes (bsc_bcf_names above) and its rule: the ID of a record whose rs_found flag is
+ *                        set and whose position the table lists, at most 63 bytes of it (up to a NUL, as "%s" prints); "." otherwise
+ *   bsc_vcf_text_block_device   d_recs[<= max_recs] packed records in HBM, *d_n_recs of them (a device u64) -> d_out[<= out_cap] bytes
+ *                        (16-byte aligned, as the BCF encoder's); d_totals = three device u64 {length of the stream, records written
+ *                        with a clamped gt / n_gl, records written}; a stream longer than out_cap is cut at a 64-record boundary, its
+ *                        full length still in d_totals[0].  Asynchronous on `stream`.
+ *   bsc_vcf_text_sites_device   the same from the per-position arrays bsc_reads_chain_device leaves (d_core[n], d_aux[n]); a position
+ *                        without a record costs the 16 bytes that hold its emit flag (the chain's length byte is not used: it holds BCF
+ *                        lengths)
+ *   bsc_fmt_g[_device]   the number formatter alone, 16 bytes per value: the characters, zero padding, the length in byte 15.  The host
+ *                        form is the C library's snprintf("%g"); the device form gives the same bytes for every one of the 2^32 patterns.
+ *   bsc_block_vcf_rawdev_keep   bsc_block_bcf_rawdev_keep with the text encoder in the BCF encoder's place: the block's lines stay on the
+ *                        device and are handed over with bsc_bcf_stream_detach / bsc_detached_* / bsc_bcf_stream_read; dev_cap too small:
+ *                        BSC_ERR_ARG with *n_bytes = the room needed, and bsc_block_bcf_again then runs the TEXT encoder once more.
+ *                        Like the BCF block entries, it REFUSES (BSC_ERR_ARG) a block with a record whose gt > 9 or n_gl > 6 — records the
+ *                        chain never forms — although the device-level entries above write such records clamped and count them.
+ * The other bsc_block_bcf* / bsc_blocks_bcf* entries have no text twin yet: inside, the request that names the encoder (a format tag and
+ * the contig's name) is the only difference, so each can be added on the same field.
+ */
+int bsc_vcf_text_block_device(bsc_context *ctx, const void *d_recs, const void *d_n_recs, uint64_t max_recs, const char *contig,
+                              const bsc_bcf_names *names, void *d_out, uint64_t out_cap, void *d_totals, void *stream);
+int bsc_vcf_text_sites_device(bsc_context *ctx, const void *d_core, const void *d_aux, uint32_t n, const char *contig, const bsc_bcf_names *names,
+                              void *d_out, uint64_t out_cap, void *d_totals, void *stream);
+int bsc_fmt_g(const float *v, uint64_t n, uint8_t *out16);
+int bsc_fmt_g_device(bsc_context *ctx, const void *d_v, uint64_t n, void *d_out16, void *stream);
+int bsc_block_vcf_rawdev_keep(bsc_context *ctx, const void *d_raw, uint32_t nr, const void *d_seq, uint64_t seq_bytes, const void *d_misms, uint64_t n_misms,
+                              uint64_t ins_pad, const bsc_prep_params *prep, uint32_t x, uint32_t y, const uint8_t *ref, const uint8_t *dbsnp,
+                              const bsc_vcf_params *params, int with_stats, const char *contig, const bsc_bcf_names *names, uint64_t dev_cap,
+                              uint64_t *n_bytes, uint64_t *n_records, bsc_prep_stats *prep_stats, bsc_read_profile *profile);
 /* with bsc_set_profiling: device time (HIP events on the context's stream) of the most recent raw block — bsc_block_records_raw[dev],
  * bsc_block_bcf_raw[dev][_keep] — from its first pre-processing launch to the last launch it queued, the host's wait for the prepared size included */
 int bsc_last_raw_block_ms(bsc_context *ctx, float *ms);

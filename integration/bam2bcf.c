@@ -24,7 +24,7 @@
  * example of the calls in order, and the C twin of bs_call_amd/pipeline.py — tests/test_gpu_pipeline.py checks that both
  * write the same bytes.
  *
- *   make bam2bcf && bs_call_amd/lib/bam2bcf [-O u|b] in.bam ref.fa out.bcf report.json [sample]
+ *   make bam2bcf && bs_call_amd/lib/bam2bcf [-O u|b] [--format bcf|vcf] in.bam ref.fa out.bcf report.json [sample]
  *
  * A sharded run over ONE file (SURVEY.md 8e on real input; the reference's unit of parallelism is a process per contig set, README.md): rank r of n
  *   bam2bcf --rank r --world n in.bam ref.fa out.bcf report.json [sample]
@@ -39,7 +39,10 @@
  * Output type (the reference's -O): -O u (the default) writes uncompressed BCF; -O b writes compressed BCF, BGZF on the device
  * (bsc_bgzf_*, csrc/bgzfdev.hip): the header goes in through bsc_bgzf_write, every block's kept stream through bsc_bgzf_write_device, and
  * the members bsc_bgzf_take hands over go to the output thread, which writes them at the running compressed offset; bsc_bgzf_close gives
- * the last member and the end-of-file marker.  Decompressed, the file is byte for byte the -O u file.  -O b needs the device reader and
+ * the last member and the end-of-file marker.  Decompressed, the file is byte for byte the -O u file.
+ * Format: --format bcf (the default) writes BCF2 records; --format vcf writes VCF TEXT — the same header text without the BCF magic, length
+ * and terminator, then every block's lines, encoded on the device too (bsc_block_vcf_rawdev_keep, csrc/vcftextdev.hip): with -O u the
+ * reference's -O v, with -O b (the same BGZF path) its -O z.  A single run on the device reader only (no --rank / --merge, no BAM2BCF_HOST_*).  -O b needs the device reader and
  * encoder and a single run (a shard compressed on its own would cut its members elsewhere than the single run does).
  */
 #include <pthread.h>
@@ -203,7 +206,7 @@ static void ref_start(ref_job *j, const char *fasta, const char *name, uint64_t 
 }
 
 /* the header print_vcf_header assembles in --benchmark-mode (src/print_vcf.c:621-745) */
-static void write_header(FILE *f, int n_refs, const char *const *names, const uint32_t *lens, const char *sample) {
+static void write_header(FILE *f, int n_refs, const char *const *names, const uint32_t *lens, const char *sample, int text) {
   static const char *const defs[] = {
       "##INFO=<ID=CX,Number=1,Type=String,Description=\"5 base sequence context (from position -2 to +2 on the positive strand) determined from the reference\">",
       "##FILTER=<ID=fail,Description=\"No sample passed filters\">",
@@ -244,6 +247,11 @@ static void write_header(FILE *f, int n_refs, const char *const *names, const ui
   for (size_t i = 0; i < sizeof defs / sizeof defs[0]; i++) ADD("%s\n", defs[i]);
   ADD("#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\tFORMAT\t%s\n", sample);
 #undef ADD
+  if (text) { /* --format vcf: the header text as it is — no magic, no length, no terminator */
+    fwrite(t, 1, len, f);
+    free(t);
+    return;
+  }
   const uint32_t l_text = (uint32_t)len + 1; /* the terminator is part of the BCF header text */
   fwrite("BCF\2\2", 1, 5, f);
   fwrite(&l_text, 4, 1, f); /* little-endian hosts only, like the rest of this example */
@@ -301,7 +309,7 @@ static void header_of(const char *bam_path, int *n_ref, const char ***names, uin
   *keep = h; /* (the names live in it) */
 }
 
-static void write_header(FILE *f, int n_refs, const char *const *names, const uint32_t *lens, const char *sample);
+static void write_header(FILE *f, int n_refs, const char *const *names, const uint32_t *lens, const char *sample, int text);
 
 static int merge_main(int world, char **argv, const char *sample) {
   int n_ref;
@@ -314,7 +322,7 @@ static int merge_main(int world, char **argv, const char *sample) {
     perror(argv[3]);
     return 1;
   }
-  write_header(out, n_ref, names, lens, sample);
+  write_header(out, n_ref, names, lens, sample, 0);
   char *path = malloc(strlen(argv[3]) + 64), *buf = malloc(1 << 24);
   for (int t = 0; t < n_ref; t++) { /* the contigs' shards in the header's order */
     sprintf(path, "%s.shard%05d", argv[3], t);
@@ -402,7 +410,7 @@ static int merge_main(int world, char **argv, const char *sample) {
 }
 
 int main(int argc, char **argv) {
-  int rank = -1, world = 1, merge = 0, bgzf = 0;
+  int rank = -1, world = 1, merge = 0, bgzf = 0, text = 0;
   while (argc > 2 && argv[1][0] == '-' && (argv[1][1] == '-' || argv[1][1] == 'O')) { /* --rank r --world n | --merge n | -O u|b */
     if (argv[1][1] == 'O') { /* -O b, -Ob */
       const char *v = argv[1][2] ? argv[1] + 2 : argv[2];
@@ -420,13 +428,28 @@ int main(int argc, char **argv) {
     if (!strcmp(argv[1], "--rank")) rank = atoi(argv[2]);
     else if (!strcmp(argv[1], "--world")) world = atoi(argv[2]);
     else if (!strcmp(argv[1], "--merge")) merge = atoi(argv[2]);
+    else if (!strcmp(argv[1], "--format")) { /* bcf: BCF2 records (the default).  vcf: text lines, encoded on the device as well */
+      if (strcmp(argv[2], "bcf") && strcmp(argv[2], "vcf")) {
+        fprintf(stderr, "%s: --format takes bcf or vcf, not '%s'\n", argv[0], argv[2]);
+        return 2;
+      }
+      text = argv[2][0] == 'v';
+    }
     else break;
     argv[2] = argv[0];
     argv += 2;
     argc -= 2;
   }
   if (argc < 5 || world < 1 || (rank >= 0 && rank >= world)) {
-    fprintf(stderr, "usage: %s [-O u|b] [--rank r --world n | --merge n] in.bam ref.fa out.bcf report.json [sample]\n", argv[0]);
+    fprintf(stderr, "usage: %s [-O u|b] [--format bcf|vcf] [--rank r --world n | --merge n] in.bam ref.fa out.bcf report.json [sample]\n", argv[0]);
+    return 2;
+  }
+  if (text && (rank >= 0 || merge > 0)) {
+    fprintf(stderr, "%s: --format vcf writes a single run's file; a sharded run (--rank / --merge) writes BCF\n", argv[0]);
+    return 2;
+  }
+  if (text && (getenv("BAM2BCF_HOST_PREP") || getenv("BAM2BCF_HOST_BCF") || getenv("BAM2BCF_HOST_READER"))) {
+    fprintf(stderr, "%s: --format vcf is the device encoder's text: not with BAM2BCF_HOST_READER / _HOST_BCF / _HOST_PREP\n", argv[0]);
     return 2;
   }
   if (bgzf && (rank >= 0 || merge > 0)) {
@@ -500,7 +523,7 @@ int main(int argc, char **argv) {
         perror("open_memstream");
         return 1;
       }
-      write_header(hm, n_ref, names, lens, sample);
+      write_header(hm, n_ref, names, lens, sample, text);
       if (fclose(hm)) {
         perror("open_memstream");
         return 1;
@@ -508,7 +531,7 @@ int main(int argc, char **argv) {
       CHECK(bsc_bgzf_open(ctx, &zw));
       CHECK(bsc_bgzf_write(zw, hb, hn));
       free(hb);
-    } else write_header(out, n_ref, names, lens, sample);
+    } else write_header(out, n_ref, names, lens, sample, text);
     free(names);
     free(lens);
   }
@@ -627,9 +650,13 @@ int main(int argc, char **argv) {
     const bsc_vcf_params vp = {0, 1, (uint32_t)codes_len};
     uint64_t n_out = 0, n_bytes = 0;
     if (!host_reader) { /* the block is in HBM already; its stream stays there too and comes over in pieces, the output thread writing behind */
-      uint64_t dev_cap = (uint64_t)n * 96 + 4096;
-      int rc = bsc_block_bcf_rawdev_keep(ctx, dblk.d_tpl, dblk.nr, dblk.d_seq, dblk.seq_bytes, dblk.d_misms, dblk.n_misms, dblk.ins_pad, &ppar, x, y, ref, NULL,
-                                         &vp, 1, dblk.tid, &ids, NULL, dev_cap, &n_bytes, &n_out, &st, &prof);
+      /* room for the kept stream: a BCF record is ~113 bytes, a text line ~143 (contig name included), about half the positions of WGBS data
+       * write one; a denser block is encoded once more into the room it asks for (bsc_block_bcf_again) */
+      uint64_t dev_cap = (uint64_t)n * (text ? 160 : 96) + 4096;
+      int rc = text ? bsc_block_vcf_rawdev_keep(ctx, dblk.d_tpl, dblk.nr, dblk.d_seq, dblk.seq_bytes, dblk.d_misms, dblk.n_misms, dblk.ins_pad, &ppar, x, y, ref,
+                                                NULL, &vp, 1, REF_NAME(dblk.tid), NULL, dev_cap, &n_bytes, &n_out, &st, &prof)
+                    : bsc_block_bcf_rawdev_keep(ctx, dblk.d_tpl, dblk.nr, dblk.d_seq, dblk.seq_bytes, dblk.d_misms, dblk.n_misms, dblk.ins_pad, &ppar, x, y, ref,
+                                                NULL, &vp, 1, dblk.tid, &ids, NULL, dev_cap, &n_bytes, &n_out, &st, &prof);
       if (rc == BSC_ERR_ARG && n_bytes > dev_cap) { /* a block of long records: the encoder alone once more, with the room it asks for */
         dev_cap = n_bytes + 4096;
         rc = bsc_block_bcf_again(ctx, NULL, dev_cap, &n_bytes, &n_out);
@@ -844,7 +871,7 @@ int main(int argc, char **argv) {
             "\"device_reader\": {\"passes\": %llu, \"replay_passes\": %llu, \"records\": %llu, \"inflated_bytes\": %llu, \"waiting_for_inflate_s\": %.3f, "
             "\"device_passes_s\": %.3f}, \"output_thread\": {\"waiting_for_a_block_s\": %.3f, \"waiting_for_copies_s\": %.3f, \"pwrite_s\": %.3f}}\n",
             host_reader ? "host (csrc/bamio.c)" : "device (csrc/bamstream.c + csrc/bamdev.hip)", t_ctx, t_read, t_ref, t_prep,
-            host_prep ? "bsc_block_records" : (host_bcf ? "bsc_block_records_raw" : (host_reader ? "bsc_block_bcf_raw" : "bsc_block_bcf_rawdev")), t_gpu, t_enc,
+            host_prep ? "bsc_block_records" : (host_bcf ? "bsc_block_records_raw" : (host_reader ? "bsc_block_bcf_raw" : (text ? "bsc_block_vcf_rawdev" : "bsc_block_bcf_rawdev"))), t_gpu, t_enc,
             now() - t_loop_end, now() - t_start, now() - t_start - t_ctx, (unsigned long long)rc4[0], (unsigned long long)rc4[1], (unsigned long long)rc4[2],
             (unsigned long long)rc4[3], rs[0], rs[1], W.t_idle, W.t_wait, W.t_write);
   }
