@@ -46,11 +46,11 @@ $(LIBDIR)/prepdev.o: $(CSRC)/prepdev.hip include/bscall_amd.h
 	@mkdir -p $(LIBDIR)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
-$(LIBDIR)/bcfdev.o: $(CSRC)/bcfdev.hip include/bscall_amd.h
+$(LIBDIR)/bcfdev.o: $(CSRC)/bcfdev.hip $(CSRC)/recstream_dev.h include/bscall_amd.h
 	@mkdir -p $(LIBDIR)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
-$(LIBDIR)/vcftextdev.o: $(CSRC)/vcftextdev.hip $(CSRC)/vcftext_emit.h $(CSRC)/fmtg_dev.h include/bscall_amd.h
+$(LIBDIR)/vcftextdev.o: $(CSRC)/vcftextdev.hip $(CSRC)/vcftext_emit.h $(CSRC)/fmtg_dev.h $(CSRC)/recstream_dev.h include/bscall_amd.h
 	@mkdir -p $(LIBDIR)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 

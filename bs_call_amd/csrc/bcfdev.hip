@@ -11,10 +11,11 @@
  *   (exclusive scan of the tile sums, rocPRIM u64: sort.hip; one more entry behind the last tile = the stream's length)
  *   bsc_bcf_write_kernel_t one wave per tile: lane offsets from a wave prefix sum, every lane writes its record into the wave's LDS
  *                          image of the tile's span of the stream — field by field, a key and its value composed as one word in
- *                          registers (see "sinks" below); the image starts at the span's phase within 16 bytes — then the wave copies
- *                          the image out: whole 16-byte chunks as one dwordx4 store per lane, the ragged head and tail byte by byte
- *                          (the neighbouring tiles own the other bytes of those chunks).  A tile whose span does not fit the image
- *                          (8 KB: long IDs, wide dictionary indices, deep counts) goes out in 2, 4 or 8 parts.
+ *                          registers (see "sinks" below) — then the wave copies the image out.  A tile whose span does not fit the
+ *                          image (8 KB: long IDs, wide dictionary indices, deep counts) goes out in 2, 4 or 8 parts.
+ * The placement — record loader, name lookup, wave prefix sum, the parts, the image's copy-out — is recstream_dev.h's, shared with
+ * the VCF text encoder (vcftextdev.hip).  Here: the sinks, the emitter, the size pass over the chain's length bytes, and the barrier
+ * between the records' bodies and their fixed fields.
  *
  * Two sources: packed records (bsc_vcf_compact_device's output; bsc_bcf_block_device), or the per-position arrays the reads-in chain leaves
  * (bsc_vcf_core + the 64-byte aux array that is the packed record's second half; bsc_bcf_sites_device, and what bsc_block_bcf runs): the
@@ -30,20 +31,17 @@
  */
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <stdlib.h>
 
 #include "../../include/bscall_amd.h"
+#include "recstream_dev.h"
 
 static_assert(sizeof(bsc_vcf_rec) == 128, "bsc_vcf_rec is 128 bytes");
 
 enum { BT_INT8 = 1, BT_INT16 = 2, BT_INT32 = 3, BT_FLOAT = 5, BT_CHAR = 7 };
 #define BCF_ID_MAX 63u        /* bsc_bcf_block's rs[64] */
 #define BCF_REC_MAX 336u      /* 32 + shared (3 + 63 + 2 + 4 + 5 + 5 + 6) + per-sample (13 keys x 5 + 136): an upper bound of one record */
-#define BCF_IMG_BYTES 10752u  /* the one-pass kernel's image per wave: 32 records of the longest kind (10 752 = 32 x 336), or 64 ordinary ones */
 #define BCF_WAVES 4u
-static_assert(BCF_IMG_BYTES >= 32u * BCF_REC_MAX, "half a tile of the longest records must fit the wave's image");
-#define BCF_ONEPASS_WAVES_PER_EU 3
-/* The write kernel's image per wave and the waves a SIMD is to hold, by form (tools/r06_ab_bcf_words.sh: the A/B of these).  A tile of the
+/* The write kernel's image per wave and the waves a SIMD is to hold, by form (profiles/r06_ab_bcf_words.txt: the A/B of these).  A tile of the
  * per-position form carries ~32 records of ~113 bytes at WGBS densities (3.6 KB; every position written: 7.2 KB, two parts); a tile of
  * packed records 64 of them. */
 #ifndef BCF_IMG_SITES
@@ -59,17 +57,10 @@ static_assert(BCF_IMG_BYTES >= 32u * BCF_REC_MAX, "half a tile of the longest re
 #define BCF_WPE_PACKED 4
 #endif
 
-struct bcf_args {
-  const uint8_t *recs;                /* bsc_vcf_rec[] — or NULL: the records are taken where the chain left them, */
-  const uint8_t *core, *aux;          /* bsc_vcf_core[] and the chain's aux array (64 B per position: the second half of a bsc_vcf_rec) */
-  const unsigned long long *n_recs;   /* device: how many records / positions (NULL: max_recs of them) */
-  uint64_t max_recs;                  /* never more than this (the arrays' size) */
+struct bcf_args { /* (rid and ids in front: with src first the compiler gives three of the kernels three more registers, profiles/recstream_resources.txt) */
   int32_t rid;
   bsc_bcf_ids ids;
-  const uint32_t *name_pos;           /* n_names sorted 1-based positions, or NULL */
-  const uint32_t *name_off;           /* n_names + 1 offsets into name_bytes */
-  const uint8_t *name_bytes;
-  uint32_t n_names;
+  rs_src src;
   const uint8_t *gate;                /* per-position form: the chain's byte per position (0 = no record) or NULL — a position without a record
                                        * then costs that byte, not the 64-byte sector around its first 16 bytes; with one-byte dictionary
                                        * indices a byte of 1 .. 254 is the record's length (fused.hip: ebyte) */
@@ -189,16 +180,10 @@ __device__ __forceinline__ void put_descriptor(S &s, uint32_t n, int type) {
     s.u8(n << 4 | (unsigned)type);
 }
 
-/* the record's fields as the emitter reads them: one 128-byte record in eight 16-byte loads */
-struct rec_regs {
-  uint32_t w[32];
-  __device__ __forceinline__ uint8_t byte(unsigned o) const { return (uint8_t)(w[o >> 2] >> (8u * (o & 3u))); }
-};
-
 /* Everything behind the 32 fixed bytes, in the reference's order; returns l_shared (the per-sample block follows it in the sink).
  * id / id_len: the record's name (global memory).  bad: set for a record bsc_bcf_record refuses (gt > 9, n_gl > 6). */
 template <bool SHORT, class S>
-__device__ __forceinline__ unsigned bcf_emit_body(S &s, const rec_regs &r, const bcf_args &a, const uint8_t *id, unsigned id_len, bool &bad) {
+__device__ __forceinline__ unsigned bcf_emit_body(S &s, const rs_rec &r, const bcf_args &a, const uint8_t *id, unsigned id_len, bool &bad) {
   const unsigned gt_raw = r.byte(5), n_gl_raw = r.byte(10);
   bad = gt_raw > 9u || n_gl_raw > 6u;
   const unsigned gt = gt_raw > 9u ? 9u : gt_raw, n_gl = n_gl_raw > 6u ? 6u : n_gl_raw;
@@ -335,7 +320,7 @@ __device__ __forceinline__ unsigned bcf_emit_body(S &s, const rec_regs &r, const
 }
 
 /* the 32 fixed bytes bcf_write puts in front */
-__device__ __forceinline__ void bcf_emit_fixed(uint8_t *p, const rec_regs &r, const bcf_args &a, unsigned l_shared, unsigned l_indiv) {
+__device__ __forceinline__ void bcf_emit_fixed(uint8_t *p, const rs_rec &r, const bcf_args &a, unsigned l_shared, unsigned l_indiv) {
   const unsigned gt = r.byte(5) > 9u ? 9u : r.byte(5);
   const unsigned alt0 = r.byte(12), alt1 = r.byte(13);
   const uint32_t n_allele = 1u + (alt0 ? 1u : 0u) + (alt0 && alt1 ? 1u : 0u);
@@ -355,64 +340,19 @@ __device__ __forceinline__ void bcf_emit_fixed(uint8_t *p, const rec_regs &r, co
   f.put_w(n_fmt << 24 | 1u);    /* one sample */
 }
 
-/* record / position i into registers; false: nothing is written for it (emit == 0).  Without the chain's byte (gate < 0) the flag is in
- * the record's first 16 bytes: a position that writes no record costs those (their 64-byte sector), and a record's other loads wait for
- * them.  With it (gate: the byte) a position without a record costs nothing more, and a record's eight loads leave together. */
-__device__ __forceinline__ bool load_rec(rec_regs &r, const bcf_args &a, uint64_t i, int gate = -1) {
-  if (gate == 0) return false;
-  const uint4 *lo = reinterpret_cast<const uint4 *>(a.recs ? a.recs + i * 128u : a.core + i * 64u);
-  const uint4 v0 = lo[0];
-  r.w[0] = v0.x; r.w[1] = v0.y; r.w[2] = v0.z; r.w[3] = v0.w;
-  if (gate < 0 && !(v0.y & 0xffu)) return false; /* bsc_vcf_core.emit */
-  const uint4 *hi = a.recs ? lo + 4 : reinterpret_cast<const uint4 *>(a.aux + i * 64u);
-#pragma unroll
-  for (int k = 1; k < 4; k++) {
-    const uint4 v = lo[k];
-    r.w[4 * k] = v.x; r.w[4 * k + 1] = v.y; r.w[4 * k + 2] = v.z; r.w[4 * k + 3] = v.w;
-  }
-#pragma unroll
-  for (int k = 0; k < 4; k++) {
-    const uint4 v = hi[k];
-    r.w[16 + 4 * k] = v.x; r.w[17 + 4 * k] = v.y; r.w[18 + 4 * k] = v.z; r.w[19 + 4 * k] = v.w;
-  }
-  return true;
-}
-
-/* the name of a flagged record: binary search of its position in the block's table */
-__device__ __forceinline__ unsigned find_name(const bcf_args &a, const rec_regs &r, const uint8_t *&id) {
-  id = nullptr;
-  if (!a.n_names || !r.byte(113)) return 0u;
-  const uint32_t pos = r.w[0];
-  uint32_t lo = 0, hi = a.n_names;
-  while (lo < hi) {
-    const uint32_t mid = (lo + hi) >> 1;
-    if (a.name_pos[mid] < pos) lo = mid + 1u; else hi = mid;
-  }
-  if (lo >= a.n_names || a.name_pos[lo] != pos) return 0u;
-  const uint32_t o0 = a.name_off[lo], o1 = a.name_off[lo + 1u];
-  id = a.name_bytes + o0;
-  const uint32_t l = o1 - o0;
-  return l > BCF_ID_MAX ? BCF_ID_MAX : l;
-}
-
-__device__ __forceinline__ uint64_t clamp_n(const bcf_args &a) {
-  if (!a.n_recs) return a.max_recs;
-  const unsigned long long n = *a.n_recs;
-  return n < a.max_recs ? n : a.max_recs;
-}
-
 /* length of record i (0 beyond n, 0 for a record that is not written).  gate: the chain's byte of the position, or -1; len_known: a byte
  * of 1 .. 254 IS the length (SHORT indices, and the chain gives 255 to every record with a name or one the encoder refuses) */
 template <bool SHORT>
-__device__ __forceinline__ unsigned rec_len(const bcf_args &a, uint64_t i, uint64_t n, rec_regs &r, const uint8_t *&id, unsigned &id_len, bool &bad,
+__device__ __forceinline__ unsigned rec_len(const bcf_args &a, uint64_t i, uint64_t n, rs_rec &r, const uint8_t *&id, unsigned &id_len, bool &bad,
                                             int gate = -1, bool len_known = false) {
   bad = false;
   id_len = 0;
   id = nullptr;
   if (i >= n) return 0u;
-  if (!load_rec(r, a, i, gate)) return 0u;
+  if (!rs_load(r, a.src, i, gate)) return 0u;
   if (len_known && gate > 0 && gate != 255) return (unsigned)gate;
-  id_len = find_name(a, r, id);
+  id_len = rs_find_name(a.src, r, id);
+  id_len = id_len > BCF_ID_MAX ? BCF_ID_MAX : id_len;
   count_sink c = {0u};
   (void)bcf_emit_body<SHORT>(c, r, a, id, id_len, bad);
   return 32u + c.len;
@@ -423,11 +363,11 @@ __device__ __forceinline__ unsigned rec_len(const bcf_args &a, uint64_t i, uint6
 extern "C" __global__ __launch_bounds__(256) void bsc_bcf_size_kernel(bcf_args a, uint32_t n_tiles, unsigned long long *__restrict__ tile_bytes,
                                                                       unsigned long long *__restrict__ err) {
   const unsigned lane = threadIdx.x & 63u;
-  const uint64_t n = clamp_n(a);
+  const uint64_t n = rs_clamp_n(a.src);
   if (blockIdx.x == 0 && threadIdx.x == 0) tile_bytes[n_tiles] = 0ull;
   unsigned n_written = 0; /* wave-uniform */
   for (uint32_t tile = blockIdx.x * BCF_WAVES + (threadIdx.x >> 6); tile < n_tiles; tile += gridDim.x * BCF_WAVES) {
-    rec_regs r;
+    rs_rec r;
     const uint8_t *id;
     unsigned id_len;
     bool bad;
@@ -438,13 +378,8 @@ extern "C" __global__ __launch_bounds__(256) void bsc_bcf_size_kernel(bcf_args a
     for (int d = 1; d < 64; d <<= 1) len += __shfl_xor(len, d);
     if (lane == 0) tile_bytes[tile] = len;
   }
-  /* totals[2]: once per workgroup (n_written is wave-uniform) — atomics on one word are served one after the other, 23 ns each */
-  __shared__ unsigned s_written;
-  if (threadIdx.x == 0) s_written = 0;
-  __syncthreads();
-  if (lane == 0 && n_written) atomicAdd(&s_written, n_written);
-  __syncthreads();
-  if (threadIdx.x == 0 && s_written) atomicAdd(err + 1, (unsigned long long)s_written);
+  const unsigned cnt[1] = {n_written};
+  rs_flush_counts(cnt, err + 1); /* totals[2] */
 }
 
 /* The same sums from the chain kernel's byte per position (csrc/fused.hip, emit_out): 0 = no record, 1 .. 254 = the record's length with
@@ -454,7 +389,7 @@ extern "C" __global__ __launch_bounds__(256) void bsc_bcf_size_bytes_kernel(bcf_
                                                                             unsigned long long *__restrict__ tile_bytes, unsigned long long *__restrict__ err) {
   /* a THREAD per tile (round 6, second form; the first was a wave per tile, a byte per lane and six shuffles): the tile's 64 bytes are four
    * 16-byte loads of a lane, summed four at a time (v_sad_u8), 4 KB a wave instruction: 30 us per 50 M positions */
-  const uint64_t n = clamp_n(a);
+  const uint64_t n = rs_clamp_n(a.src);
   if (blockIdx.x == 0 && threadIdx.x == 0) tile_bytes[n_tiles] = 0ull;
   unsigned n_written = 0;
   for (uint64_t tile = (uint64_t)blockIdx.x * 256u + threadIdx.x; tile < n_tiles; tile += (uint64_t)gridDim.x * 256u) {
@@ -485,7 +420,7 @@ extern "C" __global__ __launch_bounds__(256) void bsc_bcf_size_bytes_kernel(bcf_
       for (int q = 0; q < 16; q++)
         for (int t = 0; t < 4; t++)
           if (((w[q] >> (8 * t)) & 0xffu) == 0xffu) {
-            rec_regs r;
+            rs_rec r;
             const uint8_t *id;
             unsigned id_len;
             bool bad;
@@ -497,16 +432,10 @@ extern "C" __global__ __launch_bounds__(256) void bsc_bcf_size_bytes_kernel(bcf_
     }
     tile_bytes[tile] = len;
   }
-  /* totals[2]: once per WORKGROUP, and few workgroups — atomics on one word are served one after the other, 23 ns each: one per wave of
-   * 12 288 waves was the whole 0.25 ms of the first form of this kernel */
-  __shared__ unsigned s_written;
-  if (threadIdx.x == 0) s_written = 0;
-  __syncthreads();
 #pragma unroll
   for (int d = 1; d < 64; d <<= 1) n_written += __shfl_xor(n_written, d);
-  if ((threadIdx.x & 63u) == 0 && n_written) atomicAdd(&s_written, n_written);
-  __syncthreads();
-  if (threadIdx.x == 0 && s_written) atomicAdd(err + 1, (unsigned long long)s_written);
+  const unsigned cnt[1] = {n_written};
+  rs_flush_counts(cnt, err + 1); /* totals[2]; and few workgroups */
 }
 
 /* SHORT: every dictionary index is 0 .. 127 (bcf_emit_body); IMG: the wave's image of its part of the stream, bytes.  A tile whose span
@@ -519,7 +448,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE, WPE)))
   __shared__ __attribute__((aligned(16))) uint8_t s_img[BCF_WAVES][IMG + 32u]; /* 15 bytes of phase in front, 7 of a last field's excess behind */
   const unsigned lane = threadIdx.x & 63u, wid = threadIdx.x >> 6;
   uint8_t *const img = s_img[wid];
-  const uint64_t n = clamp_n(a);
+  const uint64_t n = rs_clamp_n(a.src);
   if (blockIdx.x == 0 && threadIdx.x == 0) *total = tile_off[n_tiles];
   /* the chain's byte of a position (0: no record; with SHORT indices 1 .. 254: the record's length) is fetched a tile ahead: the record
    * loads then wait for nothing but themselves, and all eight leave together */
@@ -534,41 +463,20 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE, WPE)))
       gate_next = -1;
       if (a.gate && nt < n_tiles && nt * 64u + lane < n) gate_next = a.gate[nt * 64u + lane];
     }
-    rec_regs r;
+    rs_rec r;
     const uint8_t *id;
     unsigned id_len;
     bool bad;
     const unsigned len = rec_len<SHORT>(a, (uint64_t)tile * 64u + lane, n, r, id, id_len, bad, gate, SHORT);
-    /* exclusive prefix of the lengths over the wave */
-    unsigned inc = len;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const unsigned v = __shfl_up(inc, d);
-      if (lane >= (unsigned)d) inc += v;
-    }
-    const unsigned excl = inc - len;
-    const unsigned t_all = (unsigned)__builtin_amdgcn_readlane((int)inc, 63);
+    unsigned excl, t_all;
+    const unsigned inc = rs_wave_excl_scan(len, excl, t_all);
     const uint64_t g_tile = tile_off[tile];
     if (g_tile + t_all > out_cap) continue; /* the host reports the overflow from *total */
-    /* one part when the tile's span fits the image (the usual case), else the fewest parts of equal lane counts that do */
-    unsigned parts = 1u;
-    if (t_all > IMG) {
-      for (parts = 2u; parts < 8u; parts <<= 1) {
-        const unsigned step = 64u / parts;
-        bool fits = true;
-        unsigned prev = 0u;
-        for (unsigned q = 0; q < parts; q++) {
-          const unsigned e = (unsigned)__builtin_amdgcn_readlane((int)inc, (int)(step * (q + 1u) - 1u));
-          fits = fits && e - prev <= IMG;
-          prev = e;
-        }
-        if (fits) break;
-      }
-    }
+    const unsigned parts = rs_pick_parts<IMG, 8u>(inc);
     const unsigned step = 64u / parts;
     unsigned b0 = 0u; /* the part's first byte within the tile */
     for (unsigned ps = 0; ps < parts; ps++) {
-      const unsigned b1 = (unsigned)__builtin_amdgcn_readlane((int)inc, (int)(step * (ps + 1u) - 1u)); /* one past its last */
+      const unsigned b1 = rs_lane(inc, step * (ps + 1u) - 1u); /* one past its last */
       const bool mine = len && excl >= b0 && excl < b1;
       const uint64_t g0 = g_tile + b0;
       const unsigned ph = (unsigned)(g0 & 15u);
@@ -583,164 +491,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE, WPE)))
          * and this emitter are two statements of one rule) */
         if (32u + w.len != len) atomicAdd(total + 1, 1ull);
       }
-      /* every body before any of the fixed fields: a body's last store may reach into the next record's first bytes */
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+      rs_wave_sync(); /* every body before any of the fixed fields: a body's last store may reach into the next record's first bytes */
       if (mine) bcf_emit_fixed(p, r, a, l_shared, w.len - l_shared);
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-      /* the image [ph, ph + t) -> out[g0, g0 + t) */
-      const unsigned t = b1 - b0, end = ph + t;
-      uint8_t *const dst = out + (g0 - ph);
-      const unsigned head_end = ph ? (end < 16u ? end : 16u) : 0u; /* bytes [ph, head_end) singly */
-      if (lane >= ph && lane < head_end) dst[lane] = img[lane];
-      const unsigned body0 = ph ? 16u : 0u, body1 = end & ~15u;
-      for (unsigned o = body0 + 16u * lane; o < body1; o += 1024u) *reinterpret_cast<uint4 *>(dst + o) = *reinterpret_cast<const uint4 *>(img + o);
-      const unsigned tail0 = body1 > head_end ? body1 : head_end;
-      if (tail0 + lane < end) dst[tail0 + lane] = img[tail0 + lane];
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+      rs_wave_sync();
+      rs_copy_out(img, out + (g0 - ph), lane, rs_copy_ranges(ph, b1 - b0)); /* the image [ph, ph + t) -> out[g0, g0 + t) */
+      rs_wave_sync();
       b0 = b1;
     }
-  }
-}
-
-/*
- * Round 6: the two kernels above read every record twice (sizes, then bytes: 2 x (64 B per position + 64 B per written record) for the
- * per-position form).  ONE kernel with a decoupled look-back (Merrill & Garland's single-pass scan): a wave takes the next tile from a
- * counter (tiles are therefore started in order: a wave never waits for a tile nobody runs), sums its lanes' record lengths, publishes the
- * sum, and finds its place in the stream by walking back over its predecessors' published words — a tile's own sum (flag 1) is added and
- * the walk goes on, a tile's inclusive prefix (flag 2) ends it — then publishes its own inclusive prefix and writes its records as the
- * write kernel does.  A word = flag << 62 | bytes: one 8-byte store publishes both.  The records are read once.
- * The words are published and polled with RELAXED atomic stores and loads at agent scope (they bypass the XCD's L2, nothing else): a word
- * carries everything it has to say — nothing else is ordered by it.  (First form: release stores and acquire loads at agent scope —
- * 31 ms against the two kernels' 0.87 per 10 M records: every publish wrote the XCD's L2 back, every poll invalidated it.)
- */
-#define BCF_FLAG_SUM (1ull << 62)
-#define BCF_FLAG_PREFIX (2ull << 62)
-#define BCF_VAL_MASK ((1ull << 62) - 1ull)
-extern "C" __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(BCF_ONEPASS_WAVES_PER_EU, BCF_ONEPASS_WAVES_PER_EU))) void bsc_bcf_onepass_kernel(
-    bcf_args a, uint32_t n_tiles, unsigned long long *__restrict__ state /* [n_tiles], zeroed */, unsigned int *__restrict__ next_tile /* zeroed */,
-    uint8_t *__restrict__ out, uint64_t out_cap, unsigned long long *__restrict__ totals /* [0] length, [1] += refused, [2] += written */) {
-  __shared__ __attribute__((aligned(16))) uint8_t s_img[BCF_WAVES][BCF_IMG_BYTES + 32u]; /* 15 bytes of phase in front, 7 of a last field's excess behind */
-  const unsigned lane = threadIdx.x & 63u, wid = threadIdx.x >> 6;
-  uint8_t *const img = s_img[wid];
-  const uint64_t n = clamp_n(a);
-  unsigned n_written = 0, n_bad = 0;
-  /* Tiles are dealt round-robin over the launch's waves, every wave taking its tiles in rising order: the launch is sized so that all its
-   * waves are resident at once, so the tile a wave waits for is in the hands of a running wave.  (Tried: one atomic counter handing out
-   * single tiles in order — 157 k claims on one word took 23 ns each, the kernel's whole time; the counter handing out chunks of 32 tiles
-   * to a workgroup — a chunk's first tile then waits for ALL of the chunk before it: 318 ms.)  A wave that polls a word far longer than
-   * any launch lasts gives up and says so (next_tile[0] = 1: the host runs the two kernels instead) — a launch that was NOT all resident
-   * (the device shared with another process) must still drain. */
-  bool gave_up = false;
-  for (uint32_t tile = blockIdx.x * BCF_WAVES + wid; tile < n_tiles && !gave_up; tile += gridDim.x * BCF_WAVES) {
-    rec_regs r;
-    const uint8_t *id;
-    unsigned id_len;
-    bool bad;
-    const unsigned len = rec_len<false>(a, (uint64_t)tile * 64u + lane, n, r, id, id_len, bad);
-    n_bad += (unsigned)__popcll(__ballot(bad));
-    n_written += (unsigned)__popcll(__ballot(len != 0u));
-    unsigned inc = len;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const unsigned v = __shfl_up(inc, d);
-      if (lane >= (unsigned)d) inc += v;
-    }
-    const unsigned excl = inc - len;
-    const unsigned t_all = __shfl(inc, 63);
-    /* the tile's place: its predecessors' bytes */
-    unsigned long long before = 0ull;
-    if (tile == 0u) {
-      if (lane == 0) __hip_atomic_store(&state[0], BCF_FLAG_PREFIX | (unsigned long long)t_all, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    } else {
-      if (lane == 0) __hip_atomic_store(&state[tile], BCF_FLAG_SUM | (unsigned long long)t_all, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      /* 64 predecessors at a time, lane l looking at tile - 1 - l (- 64 per round): the nearest inclusive prefix ends the walk */
-      int64_t base = (int64_t)tile - 1;
-      for (;;) {
-        const int64_t j = base - (int64_t)lane;
-        unsigned long long w = BCF_FLAG_PREFIX; /* before tile 0: a prefix of nothing */
-        if (j >= 0) {
-          for (unsigned polls = 0;; polls++) {
-            w = __hip_atomic_load(&state[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if ((w >> 62) != 0ull) break;
-            if (polls > (1u << 22)) { /* ~ a second */
-              w = BCF_FLAG_PREFIX;
-              gave_up = true;
-              break;
-            }
-            __builtin_amdgcn_s_sleep(2);
-          }
-        }
-        if (__ballot(gave_up)) {
-          gave_up = true;
-          if (lane == 0) {
-            atomicExch(next_tile, 1u);
-            atomicMax(totals, ~0ull); /* a length no buffer holds: the host's check of totals[0] fails the call */
-          }
-          break;
-        }
-        const unsigned long long is_prefix = __ballot((w >> 62) == 2ull);
-        const unsigned first = (unsigned)__builtin_ctzll(is_prefix ? is_prefix : 1ull); /* the nearest prefix among these 64 */
-        unsigned long long v = (is_prefix == 0ull || lane <= first) ? (w & BCF_VAL_MASK) : 0ull;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) v += __shfl_xor(v, d);
-        before += v;
-        if (is_prefix) break;
-        base -= 64;
-      }
-      if (lane == 0) __hip_atomic_store(&state[tile], BCF_FLAG_PREFIX | (before + (unsigned long long)t_all), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    if (gave_up) {
-      if (lane == 0) __hip_atomic_store(&state[tile], BCF_FLAG_PREFIX, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); /* nobody waits for this one in vain */
-      break;
-    }
-    if (tile == n_tiles - 1u && lane == 0) atomicMax(totals, before + (unsigned long long)t_all);
-    const uint64_t g_tile = before;
-    if ((uint64_t)tile * 64u >= n || g_tile + t_all > out_cap) continue; /* nothing to write / the host reports the overflow from totals[0] */
-    const unsigned t_half = __shfl(inc, 31);
-    const unsigned passes = t_all <= BCF_IMG_BYTES ? 1u : 2u;
-    for (unsigned ps = 0; ps < passes; ps++) {
-      const unsigned b0 = ps ? t_half : 0u;
-      const unsigned b1 = passes == 1u ? t_all : (ps ? t_all : t_half);
-      const bool mine = len && excl >= b0 && excl < b1;
-      const uint64_t g0 = g_tile + b0;
-      const unsigned ph = (unsigned)(g0 & 15u);
-      uint8_t *const p = img + ph + (excl - b0);
-      lds_sink w = {p + 32u, 0u};
-      unsigned l_shared = 0u;
-      if (mine) {
-        bool bad2;
-        l_shared = bcf_emit_body<false>(w, r, a, id, id_len, bad2);
-      }
-      /* every body before any of the fixed fields: a body's last store may reach into the next record's first bytes */
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-      if (mine) bcf_emit_fixed(p, r, a, l_shared, w.len - l_shared);
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-      const unsigned t = b1 - b0, end = ph + t;
-      uint8_t *const dst = out + (g0 - ph);
-      const unsigned head_end = ph ? (end < 16u ? end : 16u) : 0u;
-      if (lane >= ph && lane < head_end) dst[lane] = img[lane];
-      const unsigned body0 = ph ? 16u : 0u, body1 = end & ~15u;
-      for (unsigned o = body0 + 16u * lane; o < body1; o += 1024u) *reinterpret_cast<uint4 *>(dst + o) = *reinterpret_cast<const uint4 *>(img + o);
-      const unsigned tail0 = body1 > head_end ? body1 : head_end;
-      if (tail0 + lane < end) dst[tail0 + lane] = img[tail0 + lane];
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    }
-  }
-  if (lane == 0) {
-    if (n_bad) atomicAdd(totals + 1, (unsigned long long)n_bad);
-    if (n_written) atomicAdd(totals + 2, (unsigned long long)n_written);
   }
 }
 
@@ -758,17 +515,9 @@ extern "C" int bsc_dev_launch_bcf(const void *recs, const void *core, const void
                                   int num_cus, void *stream, const void *emit_len) {
   hipStream_t s = (hipStream_t)stream;
   bcf_args a;
-  a.recs = (const uint8_t *)recs;
-  a.core = (const uint8_t *)core;
-  a.aux = (const uint8_t *)aux;
-  a.n_recs = (const unsigned long long *)n_recs;
-  a.max_recs = max_recs;
+  a.src = rs_make_src(recs, core, aux, n_recs, max_recs, name_pos, name_off, name_bytes, n_names);
   a.rid = rid;
   a.ids = *ids;
-  a.name_pos = (const uint32_t *)name_pos;
-  a.name_off = (const uint32_t *)name_off;
-  a.name_bytes = (const uint8_t *)name_bytes;
-  a.n_names = name_pos ? n_names : 0u;
   a.gate = nullptr;
   const uint64_t nt64 = (max_recs + 63u) / 64u;
   if (nt64 > 0x7fffffffull) return (int)hipErrorInvalidValue;
@@ -776,53 +525,25 @@ extern "C" int bsc_dev_launch_bcf(const void *recs, const void *core, const void
   unsigned grid = (n_tiles + BCF_WAVES - 1u) / BCF_WAVES;
   if (grid > (unsigned)num_cus * 12u) grid = (unsigned)num_cus * 12u;
   if (grid == 0) grid = 1;
-  static int one_pass = -1; /* BSC_BCF_ONE_PASS in the environment: the look-back kernel (the A/B of tools/bench_bcf.py; slower, see there) */
-  if (one_pass < 0) one_pass = getenv("BSC_BCF_ONE_PASS") != nullptr;
-  if (one_pass) {
-    if (n_tiles == 0) return (int)hipMemsetAsync(totals, 0, sizeof(unsigned long long), s);
-    hipError_t e1 = hipMemsetAsync(tile_off, 0, (size_t)n_tiles * 8u, s);
-    if (e1 == hipSuccess) e1 = hipMemsetAsync(tile_bytes, 0, 8, s);
-    if (e1 != hipSuccess) return (int)e1;
-    /* as many workgroups as are resident at once (the look-back's guarantee of progress) */
-    static int per_cu = 0;
-    if (!per_cu) {
-      int nb = 0;
-      const hipError_t eo = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, bsc_bcf_onepass_kernel, 256, 0);
-      per_cu = (eo == hipSuccess && nb > 0) ? nb : 1;
-      (void)hipGetLastError();
-    }
-    unsigned g1 = (n_tiles + BCF_WAVES - 1u) / BCF_WAVES;
-    const unsigned cap1 = (unsigned)num_cus * (unsigned)per_cu;
-    if (g1 > cap1) g1 = cap1;
-    hipLaunchKernelGGL(bsc_bcf_onepass_kernel, dim3(g1), dim3(256), 0, s, a, n_tiles, (unsigned long long *)tile_off, (unsigned int *)tile_bytes, (uint8_t *)out, out_cap,
-                       (unsigned long long *)totals);
-    return (int)hipGetLastError();
-  }
   /* the sizes from the chain's length bytes when they can be trusted: per-position form, no names, every dictionary index in one byte */
   bool short_ids = true;
   {
     const int32_t *iv = &ids->pass;
     for (size_t k = 0; k < sizeof(bsc_bcf_ids) / sizeof(int32_t); k++) short_ids = short_ids && iv[k] >= 0 && iv[k] <= 127;
   }
-  static int no_len = -1; /* BSC_BCF_NO_LEN_BYTES: the size pass over the records, as in round 5 (A/B) */
-  if (no_len < 0) no_len = getenv("BSC_BCF_NO_LEN_BYTES") != nullptr;
-  if (emit_len && !recs && short_ids && !a.n_names && !no_len)
-  {
+  if (emit_len && !recs && short_ids && !a.src.n_names) {
     unsigned gb = (n_tiles + 255u) / 256u; /* a thread per tile */
     if (gb > (unsigned)num_cus * 2u) gb = (unsigned)num_cus * 2u; /* (few: each ends in an atomic on one word) */
     if (gb == 0) gb = 1;
     hipLaunchKernelGGL(bsc_bcf_size_bytes_kernel, dim3(gb), dim3(256), 0, s, a, (const uint8_t *)emit_len, n_tiles, (unsigned long long *)tile_bytes,
                        (unsigned long long *)totals + 1);
-  }
-  else
+  } else
     hipLaunchKernelGGL(bsc_bcf_size_kernel, dim3(grid), dim3(256), 0, s, a, n_tiles, (unsigned long long *)tile_bytes, (unsigned long long *)totals + 1);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return (int)e;
   const int rc = bsc_dev_scan_u64(tile_bytes, tile_off, n_tiles + 1u, scan_tmp, scan_tmp_bytes, stream);
   if (rc) return rc;
-  static int no_gate = -1; /* BSC_BCF_NO_GATE: the write kernel finds a position's flag in its record, as before the gate (A/B) */
-  if (no_gate < 0) no_gate = getenv("BSC_BCF_NO_GATE") != nullptr;
-  if (emit_len && !recs && !no_len && !no_gate) a.gate = (const uint8_t *)emit_len; /* not 0 <=> bsc_vcf_core.emit (fused.hip: ebyte) */
+  if (emit_len && !recs) a.gate = (const uint8_t *)emit_len; /* not 0 <=> bsc_vcf_core.emit (fused.hip: ebyte) */
 #define BCF_LAUNCH_WRITE(SH, IMG, WPE)                                                                                                      \
   hipLaunchKernelGGL((bsc_bcf_write_kernel_t<SH, IMG, WPE>), dim3(grid), dim3(256), 0, s, a, n_tiles, (const unsigned long long *)tile_off, \
                      (uint8_t *)out, out_cap, (unsigned long long *)totals)

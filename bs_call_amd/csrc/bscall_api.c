@@ -263,15 +263,18 @@ typedef struct {
 static void bsc_devguard_exit(bsc_devguard *g) {
   if (g->prev >= 0) (void)hipSetDevice(g->prev);
 }
-#define BSC_ENTER(ctx)                                                               \
-  bsc_devguard guard_ __attribute__((cleanup(bsc_devguard_exit), unused)) = {-1};    \
+#define BSC_GUARD(g) bsc_devguard g __attribute__((cleanup(bsc_devguard_exit), unused)) = {-1}
+#define BSC_ENTER_GUARD(ctx, g) /* g: a BSC_GUARD of the caller's — what a helper enters on its caller's behalf */ \
   do {                                                                               \
     int cur_ = -1;                                                                   \
     if (hipGetDevice(&cur_) != hipSuccess || cur_ != (ctx)->device) {                \
       HIP_TRY(hipSetDevice((ctx)->device));                                          \
-      guard_.prev = cur_;                                                            \
+      (g).prev = cur_;                                                               \
     }                                                                                \
   } while (0)
+#define BSC_ENTER(ctx) \
+  BSC_GUARD(guard_);   \
+  BSC_ENTER_GUARD(ctx, guard_)
 
 /* the same channel for the other C files of the library (dbsnp.c, prep.c) */
 int bsc_set_error(int code, const char *fmt, ...) {
@@ -1843,27 +1846,48 @@ static int bsc_names_upload(bsc_context *ctx, const char *who, const bsc_bcf_nam
   return BSC_OK;
 }
 
-/* d_recs != NULL: packed records, *d_n_recs of them; else d_core / d_aux: the per-position arrays of the reads-in chain, max_recs positions */
-static int bsc_bcf_encode(bsc_context *ctx, const char *who, const void *d_recs, const void *d_core, const void *d_aux, const void *d_n_recs,
-                          uint64_t max_recs, int32_t rid, const bsc_bcf_ids *ids, const bsc_bcf_names *names, void *d_out, uint64_t out_cap,
-                          void *d_totals, void *stream) {
-  if (!ctx || !ids || !d_totals || (out_cap && !d_out)) return bsc_fail(BSC_ERR_ARG, "%s: NULL argument", who);
+/*
+ * The host half the two stream encoders (bcfdev.hip, vcftextdev.hip) share.  d_recs != NULL: packed records, *d_n_recs of them; else
+ * d_core / d_aux: the per-position arrays of the reads-in chain, max_recs positions.
+ */
+static int bsc_stream_args_check(const bsc_context *ctx, const char *who, const void *d_recs, const void *d_core, const void *d_aux, const void *d_n_recs,
+                                 uint64_t max_recs, const void *d_out, uint64_t out_cap, const void *d_totals) {
+  if (!ctx || !d_totals || (out_cap && !d_out)) return bsc_fail(BSC_ERR_ARG, "%s: NULL argument", who);
   if (d_recs ? !d_n_recs : (max_recs && (!d_core || !d_aux))) return bsc_fail(BSC_ERR_ARG, "%s: NULL argument", who);
   if (((uintptr_t)d_recs & 15u) || ((uintptr_t)d_core & 15u) || ((uintptr_t)d_aux & 15u) || ((uintptr_t)d_n_recs & 7u) || ((uintptr_t)d_totals & 7u))
     return bsc_fail(BSC_ERR_ARG, "%s: the records must be 16-byte, the count and the totals 8-byte aligned", who);
   if ((uintptr_t)d_out & 15u) /* the write kernel owns whole 16-byte pieces of the stream, counted from its start */
     return bsc_fail(BSC_ERR_ARG, "%s: d_out must be 16-byte aligned (append blocks at multiples of 16, or encode into a buffer of its own)", who);
   if (max_recs > 0x1fffffffc0ull) return bsc_fail(BSC_ERR_ARG, "%s: more than 2^37 records", who);
+  return BSC_OK;
+}
+
+typedef struct {
+  bsc_devguard guard; /* the context's device stays current while the plan lives (BSC_STREAM_PLAN): the launch follows */
+  uint32_t n_tiles;
+  size_t scan_bytes;
+  const void *d_pos, *d_off, *d_nb; /* the names table on the device: positions | offsets | bytes in one workspace */
+  uint32_t n_names;
+} bsc_stream_plan;
+static void bsc_stream_plan_exit(bsc_stream_plan *p) { bsc_devguard_exit(&p->guard); }
+#define BSC_STREAM_PLAN(p) bsc_stream_plan p __attribute__((cleanup(bsc_stream_plan_exit))) = {.guard = {-1}}
+
+/* the checks, the names table (checked here, or adopted from the block's uploads), the context's device, the workspaces of the size pass and
+ * the scan (ctx->d_btb, d_bto, d_bscn), the table's copies and the zeroed totals — everything up to the launch */
+static int bsc_stream_encode_begin(bsc_context *ctx, const char *who, const void *d_recs, const void *d_core, const void *d_aux, const void *d_n_recs,
+                                   uint64_t max_recs, const bsc_bcf_names *names, void *d_out, uint64_t out_cap, void *d_totals, void *stream,
+                                   bsc_stream_plan *plan) {
+  int rc;
+  if ((rc = bsc_stream_args_check(ctx, who, d_recs, d_core, d_aux, d_n_recs, max_recs, d_out, out_cap, d_totals))) return rc;
   uint32_t n_names = 0;
   uint64_t name_bytes = 0;
   const int names_up = names && ctx->names_up == names; /* a block entry: checked and uploaded with the block's other inputs (bsc_names_upload) */
-  int rc;
   if (names_up) {
     n_names = ctx->names_up_n;
     name_bytes = ctx->names_up_bytes;
   } else if ((rc = bsc_names_check(who, names, &n_names, &name_bytes)))
     return rc;
-  BSC_ENTER(ctx);
+  BSC_ENTER_GUARD(ctx, plan->guard);
   hipStream_t s = (hipStream_t)stream;
   const uint32_t n_tiles = (uint32_t)((max_recs + 63u) / 64u);
   size_t scan_bytes = 0;
@@ -1871,8 +1895,8 @@ static int bsc_bcf_encode(bsc_context *ctx, const char *who, const void *d_recs,
   if ((rc = bsc_reserve(&ctx->d_btb, &ctx->cap_btb, ((size_t)n_tiles + 1u) * 8u))) return rc;
   if ((rc = bsc_reserve(&ctx->d_bto, &ctx->cap_bto, ((size_t)n_tiles + 1u) * 8u))) return rc;
   if ((rc = bsc_reserve(&ctx->d_bscn, &ctx->cap_bscn, scan_bytes ? scan_bytes : 1))) return rc;
-  const void *d_pos = NULL, *d_off = NULL, *d_nb = NULL;
-  if (n_names) { /* positions | offsets | bytes in one workspace */
+  plan->d_pos = plan->d_off = plan->d_nb = NULL;
+  if (n_names) {
     const size_t o_off = (size_t)n_names * 4u, o_by = o_off + ((size_t)n_names + 1u) * 4u;
     if (!names_up) { /* the device-level entries: the caller's arrays, on the caller's stream (page-locked arrays make it a true DMA) */
       if ((rc = bsc_reserve(&ctx->d_bnm, &ctx->cap_bnm, o_by + (size_t)name_bytes + 1u))) return rc;
@@ -1880,14 +1904,27 @@ static int bsc_bcf_encode(bsc_context *ctx, const char *who, const void *d_recs,
       HIP_TRY(hipMemcpyAsync((char *)ctx->d_bnm + o_off, names->off, ((size_t)n_names + 1u) * 4u, hipMemcpyHostToDevice, s));
       if (name_bytes) HIP_TRY(hipMemcpyAsync((char *)ctx->d_bnm + o_by, names->bytes, (size_t)name_bytes, hipMemcpyHostToDevice, s));
     }
-    d_pos = ctx->d_bnm;
-    d_off = (char *)ctx->d_bnm + o_off;
-    d_nb = (char *)ctx->d_bnm + o_by;
+    plan->d_pos = ctx->d_bnm;
+    plan->d_off = (char *)ctx->d_bnm + o_off;
+    plan->d_nb = (char *)ctx->d_bnm + o_by;
   }
   HIP_TRY(hipMemsetAsync(d_totals, 0, 3 * sizeof(unsigned long long), s));
+  plan->n_tiles = n_tiles;
+  plan->scan_bytes = scan_bytes;
+  plan->n_names = n_names;
+  return BSC_OK;
+}
+
+static int bsc_bcf_encode(bsc_context *ctx, const char *who, const void *d_recs, const void *d_core, const void *d_aux, const void *d_n_recs,
+                          uint64_t max_recs, int32_t rid, const bsc_bcf_ids *ids, const bsc_bcf_names *names, void *d_out, uint64_t out_cap,
+                          void *d_totals, void *stream) {
+  if (!ids) return bsc_fail(BSC_ERR_ARG, "%s: NULL argument", who);
+  BSC_STREAM_PLAN(plan);
+  int rc;
+  if ((rc = bsc_stream_encode_begin(ctx, who, d_recs, d_core, d_aux, d_n_recs, max_recs, names, d_out, out_cap, d_totals, stream, &plan))) return rc;
   /* (the per-position form behind the chain: the chain's byte per position holds every record's length, ctx->emit_hint) */
-  const int e = bsc_dev_launch_bcf(d_recs, d_core, d_aux, d_n_recs, max_recs, rid, ids, d_pos, d_off, d_nb, n_names, ctx->d_btb, ctx->d_bto, ctx->d_bscn,
-                                   scan_bytes, d_out, out_cap, d_totals, ctx->num_cus, stream, d_recs ? NULL : ctx->emit_hint);
+  const int e = bsc_dev_launch_bcf(d_recs, d_core, d_aux, d_n_recs, max_recs, rid, ids, plan.d_pos, plan.d_off, plan.d_nb, plan.n_names, ctx->d_btb,
+                                   ctx->d_bto, ctx->d_bscn, plan.scan_bytes, d_out, out_cap, d_totals, ctx->num_cus, stream, d_recs ? NULL : ctx->emit_hint);
   if (e) return bsc_fail(BSC_ERR_HIP, "BCF encoder launch failed: %s", hipGetErrorString((hipError_t)e));
   return BSC_OK;
 }
@@ -1931,49 +1968,15 @@ static int bsc_contig_check(const char *who, const char *contig, uint32_t *len) 
 static int bsc_vcf_text_encode(bsc_context *ctx, const char *who, const void *d_recs, const void *d_core, const void *d_aux, const void *d_n_recs,
                                uint64_t max_recs, const char *contig, const bsc_bcf_names *names, void *d_out, uint64_t out_cap, void *d_totals,
                                void *stream) {
-  if (!ctx || !d_totals || (out_cap && !d_out)) return bsc_fail(BSC_ERR_ARG, "%s: NULL argument", who);
-  if (d_recs ? !d_n_recs : (max_recs && (!d_core || !d_aux))) return bsc_fail(BSC_ERR_ARG, "%s: NULL argument", who);
-  if (((uintptr_t)d_recs & 15u) || ((uintptr_t)d_core & 15u) || ((uintptr_t)d_aux & 15u) || ((uintptr_t)d_n_recs & 7u) || ((uintptr_t)d_totals & 7u))
-    return bsc_fail(BSC_ERR_ARG, "%s: the records must be 16-byte, the count and the totals 8-byte aligned", who);
-  if ((uintptr_t)d_out & 15u) /* the write kernel owns whole 16-byte pieces of the stream, counted from its start */
-    return bsc_fail(BSC_ERR_ARG, "%s: d_out must be 16-byte aligned (append blocks at multiples of 16, or encode into a buffer of its own)", who);
-  if (max_recs > 0x1fffffffc0ull) return bsc_fail(BSC_ERR_ARG, "%s: more than 2^37 records", who);
   uint32_t contig_len = 0;
-  int rc;
+  int rc; /* (the contig between the argument checks and the names table's: a bad call's first error stays what it was) */
+  if ((rc = bsc_stream_args_check(ctx, who, d_recs, d_core, d_aux, d_n_recs, max_recs, d_out, out_cap, d_totals))) return rc;
   if ((rc = bsc_contig_check(who, contig, &contig_len))) return rc;
-  uint32_t n_names = 0;
-  uint64_t name_bytes = 0;
-  const int names_up = names && ctx->names_up == names; /* a block entry: checked and uploaded with the block's other inputs */
-  if (names_up) {
-    n_names = ctx->names_up_n;
-    name_bytes = ctx->names_up_bytes;
-  } else if ((rc = bsc_names_check(who, names, &n_names, &name_bytes)))
-    return rc;
-  BSC_ENTER(ctx);
-  hipStream_t s = (hipStream_t)stream;
-  const uint32_t n_tiles = (uint32_t)((max_recs + 63u) / 64u);
-  size_t scan_bytes = 0;
-  if (bsc_dev_scan_tmp_bytes_u64(n_tiles + 1u, &scan_bytes)) return bsc_fail(BSC_ERR_HIP, "%s: scan size query failed", who);
-  if ((rc = bsc_reserve(&ctx->d_btb, &ctx->cap_btb, ((size_t)n_tiles + 1u) * 8u))) return rc;
-  if ((rc = bsc_reserve(&ctx->d_bto, &ctx->cap_bto, ((size_t)n_tiles + 1u) * 8u))) return rc;
-  if ((rc = bsc_reserve(&ctx->d_bscn, &ctx->cap_bscn, scan_bytes ? scan_bytes : 1))) return rc;
-  if ((rc = bsc_reserve(&ctx->d_vtl, &ctx->cap_vtl, ((size_t)n_tiles + 1u) * 128u))) return rc;
-  const void *d_pos = NULL, *d_off = NULL, *d_nb = NULL;
-  if (n_names) { /* positions | offsets | bytes in one workspace, as the BCF encoder */
-    const size_t o_off = (size_t)n_names * 4u, o_by = o_off + ((size_t)n_names + 1u) * 4u;
-    if (!names_up) {
-      if ((rc = bsc_reserve(&ctx->d_bnm, &ctx->cap_bnm, o_by + (size_t)name_bytes + 1u))) return rc;
-      HIP_TRY(hipMemcpyAsync(ctx->d_bnm, names->pos, (size_t)n_names * 4u, hipMemcpyHostToDevice, s));
-      HIP_TRY(hipMemcpyAsync((char *)ctx->d_bnm + o_off, names->off, ((size_t)n_names + 1u) * 4u, hipMemcpyHostToDevice, s));
-      if (name_bytes) HIP_TRY(hipMemcpyAsync((char *)ctx->d_bnm + o_by, names->bytes, (size_t)name_bytes, hipMemcpyHostToDevice, s));
-    }
-    d_pos = ctx->d_bnm;
-    d_off = (char *)ctx->d_bnm + o_off;
-    d_nb = (char *)ctx->d_bnm + o_by;
-  }
-  HIP_TRY(hipMemsetAsync(d_totals, 0, 3 * sizeof(unsigned long long), s));
-  const int e = bsc_dev_launch_vcf_text(d_recs, d_core, d_aux, d_n_recs, max_recs, contig, contig_len, d_pos, d_off, d_nb, n_names, ctx->d_btb, ctx->d_bto,
-                                        ctx->d_vtl, ctx->d_bscn, scan_bytes, d_out, out_cap, d_totals, ctx->num_cus, stream);
+  BSC_STREAM_PLAN(plan);
+  if ((rc = bsc_stream_encode_begin(ctx, who, d_recs, d_core, d_aux, d_n_recs, max_recs, names, d_out, out_cap, d_totals, stream, &plan))) return rc;
+  if ((rc = bsc_reserve(&ctx->d_vtl, &ctx->cap_vtl, ((size_t)plan.n_tiles + 1u) * 128u))) return rc;
+  const int e = bsc_dev_launch_vcf_text(d_recs, d_core, d_aux, d_n_recs, max_recs, contig, contig_len, plan.d_pos, plan.d_off, plan.d_nb, plan.n_names,
+                                        ctx->d_btb, ctx->d_bto, ctx->d_vtl, ctx->d_bscn, plan.scan_bytes, d_out, out_cap, d_totals, ctx->num_cus, stream);
   if (e) return bsc_fail(BSC_ERR_HIP, "VCF text encoder launch failed: %s", hipGetErrorString((hipError_t)e));
   return BSC_OK;
 }

@@ -23,6 +23,7 @@
 #include <stdint.h>
 
 #include "fmtg_dev.h"
+#include "recstream_dev.h"
 
 #define VT_FN FMTG_FN
 #if defined(__HIPCC__)
@@ -34,11 +35,7 @@
 #define VT_CONTIG_MAX 255u
 #define VT_LINE_MAX (VT_CONTIG_MAX + 410u)
 
-/* the record's fields as the emitter reads them: one 128-byte record in eight 16-byte loads */
-struct vt_rec {
-  uint32_t w[32];
-  VT_MFN uint8_t byte(unsigned o) const { return (uint8_t)(w[o >> 2] >> (8u * (o & 3u))); }
-};
+typedef rs_rec vt_rec; /* the record's fields as the emitter reads them */
 
 struct vt_count_sink {
   unsigned len;

@@ -2,16 +2,15 @@
  * vcftextdev.hip — a block's written records as VCF TEXT on the device: for every record with emit != 0, in position order, the
  * line bsc_vcf_format_rec writes for it and '\n' (the reference's -O v; through the BGZF writer, bgzfdev.hip, its -O z).  The
  * emitter is vcftext_emit.h, the number formatter fmtg_dev.h; the host form csrc/vcf_format.c is the checker of both.  The
- * placement is bcfdev.hip's:
+ * placement — record loader, name lookup, wave prefix sum, the parts, the image's copy-out — is recstream_dev.h's, shared with
+ * the BCF encoder (bcfdev.hip):
  *
  *   bsc_vtext_size_kernel   one wave per tile of 64 records / positions: every lane the length of its line (the emitter over the
  *                           counting sink) -> line_len[i] (u16; 0 = nothing written), the tile's sum -> tile_bytes[tile]
  *   (exclusive scan of the tile sums, rocPRIM u64: sort.hip; one more entry behind the last tile = the stream's length)
  *   bsc_vtext_write_kernel  one wave per tile: lane offsets from a wave prefix sum of line_len (fetched a tile ahead: a position
  *                           without a record costs those two bytes and nothing of its record), every lane writes its line into
- *                           the wave's LDS image of the tile's span of the stream, the image starting at the span's phase within
- *                           16 bytes; then the wave copies the image out: whole 16-byte pieces as one dwordx4 store per lane, the
- *                           ragged head and tail byte by byte (the neighbouring tiles own the other bytes of those pieces).  A tile
+ *                           the wave's LDS image of the tile's span of the stream, then the wave copies the image out.  A tile
  *                           whose span does not fit the image (12 KB) goes out in 2, 4, 8 or 16 parts.
  *
  * The lengths are kept between the passes because a line costs far more arithmetic than a BCF record (six %g conversions and
@@ -37,59 +36,15 @@ static_assert(sizeof(bsc_vcf_rec) == 128, "bsc_vcf_rec is 128 bytes");
 static_assert(VT_IMG >= 4u * VT_LINE_MAX && VT_IMG % 16u == 0u, "a sixteenth of a tile of the longest lines must fit the wave's image");
 
 struct vt_args {
-  const uint8_t *recs;              /* bsc_vcf_rec[] — or NULL: */
-  const uint8_t *core, *aux;        /* bsc_vcf_core[] and the chain's aux array (the second half of a bsc_vcf_rec) */
-  const unsigned long long *n_recs; /* device: how many records (NULL: max_recs of them) */
-  uint64_t max_recs;
-  const uint32_t *name_pos; /* n_names sorted 1-based positions, or NULL */
-  const uint32_t *name_off; /* n_names + 1 offsets into name_bytes */
-  const uint8_t *name_bytes;
-  uint32_t n_names;
+  rs_src src;
   uint32_t clen1;        /* the contig's name and the tab behind it, bytes */
   uint32_t contig_w[64]; /* those bytes, zero padded */
 };
 
-__device__ __forceinline__ uint64_t vt_clamp_n(const vt_args &a) {
-  if (!a.n_recs) return a.max_recs;
-  const unsigned long long n = *a.n_recs;
-  return n < a.max_recs ? n : a.max_recs;
-}
-
-/* record / position i into registers.  probe: first the 16 bytes that hold the emit flag — false when it is 0 */
-__device__ __forceinline__ bool vt_load(vt_rec &r, const vt_args &a, uint64_t i, bool probe) {
-  const uint4 *lo = reinterpret_cast<const uint4 *>(a.recs ? a.recs + i * 128u : a.core + i * 64u);
-  const uint4 v0 = lo[0];
-  r.w[0] = v0.x; r.w[1] = v0.y; r.w[2] = v0.z; r.w[3] = v0.w;
-  if (probe && !(v0.y & 0xffu)) return false; /* bsc_vcf_core.emit */
-  const uint4 *hi = a.recs ? lo + 4 : reinterpret_cast<const uint4 *>(a.aux + i * 64u);
-#pragma unroll
-  for (int k = 1; k < 4; k++) {
-    const uint4 v = lo[k];
-    r.w[4 * k] = v.x; r.w[4 * k + 1] = v.y; r.w[4 * k + 2] = v.z; r.w[4 * k + 3] = v.w;
-  }
-#pragma unroll
-  for (int k = 0; k < 4; k++) {
-    const uint4 v = hi[k];
-    r.w[16 + 4 * k] = v.x; r.w[17 + 4 * k] = v.y; r.w[18 + 4 * k] = v.z; r.w[19 + 4 * k] = v.w;
-  }
-  return true;
-}
-
 /* the name of a flagged record (the BCF encoder's rule: rs_found set, the position listed, at most 63 bytes), as far as a host "%s"
  * would print it: up to a NUL */
 __device__ __forceinline__ unsigned vt_find_name(const vt_args &a, const vt_rec &r, const uint8_t *&id) {
-  id = nullptr;
-  if (!a.n_names || !r.byte(113)) return 0u;
-  const uint32_t pos = r.w[0];
-  uint32_t lo = 0, hi = a.n_names;
-  while (lo < hi) {
-    const uint32_t mid = (lo + hi) >> 1;
-    if (a.name_pos[mid] < pos) lo = mid + 1u; else hi = mid;
-  }
-  if (lo >= a.n_names || a.name_pos[lo] != pos) return 0u;
-  const uint32_t o0 = a.name_off[lo], o1 = a.name_off[lo + 1u];
-  id = a.name_bytes + o0;
-  uint32_t l = o1 - o0;
+  uint32_t l = rs_find_name(a.src, r, id);
   l = l > VT_ID_MAX ? VT_ID_MAX : l;
   for (uint32_t k = 0; k < l; k++)
     if (!id[k]) return k;
@@ -101,7 +56,7 @@ __device__ __forceinline__ unsigned vt_find_name(const vt_args &a, const vt_rec 
 extern "C" __global__ __launch_bounds__(256) void bsc_vtext_size_kernel(vt_args a, uint32_t n_tiles, unsigned long long *__restrict__ tile_bytes,
                                                                         uint16_t *__restrict__ line_len, unsigned long long *__restrict__ err) {
   const unsigned lane = threadIdx.x & 63u;
-  const uint64_t n = vt_clamp_n(a);
+  const uint64_t n = rs_clamp_n(a.src);
   if (blockIdx.x == 0 && threadIdx.x == 0) tile_bytes[n_tiles] = 0ull;
   unsigned n_written = 0, n_clamped = 0; /* wave-uniform */
   for (uint32_t tile = blockIdx.x * VT_WAVES + (threadIdx.x >> 6); tile < n_tiles; tile += gridDim.x * VT_WAVES) {
@@ -109,28 +64,22 @@ extern "C" __global__ __launch_bounds__(256) void bsc_vtext_size_kernel(vt_args 
     unsigned len = 0u;
     bool clamped = false;
     vt_rec r;
-    if (i < n && vt_load(r, a, i, true)) {
+    if (i < n && rs_load(r, a.src, i, -1)) {
       const uint8_t *id;
       const unsigned id_len = vt_find_name(a, r, id);
       vt_count_sink c = {0u};
       vt_emit_line(c, r, a.contig_w, a.clen1, id, id_len, clamped);
       len = c.len;
     }
-    if (i < a.max_recs) line_len[i] = (uint16_t)len;
+    if (i < a.src.max_recs) line_len[i] = (uint16_t)len;
     n_clamped += (unsigned)__popcll(__ballot(clamped));
     n_written += (unsigned)__popcll(__ballot(len != 0u));
 #pragma unroll
     for (int d = 1; d < 64; d <<= 1) len += __shfl_xor(len, d);
     if (lane == 0) tile_bytes[tile] = len;
   }
-  /* the totals once per workgroup: atomics on one word are served one after the other */
-  __shared__ unsigned s_cnt[2];
-  if (threadIdx.x < 2) s_cnt[threadIdx.x] = 0;
-  __syncthreads();
-  if (lane == 0 && n_written) atomicAdd(&s_cnt[1], n_written);
-  if (lane == 0 && n_clamped) atomicAdd(&s_cnt[0], n_clamped);
-  __syncthreads();
-  if (threadIdx.x < 2 && s_cnt[threadIdx.x]) atomicAdd(err + threadIdx.x, (unsigned long long)s_cnt[threadIdx.x]);
+  const unsigned cnt[2] = {n_clamped, n_written};
+  rs_flush_counts(cnt, err);
 }
 
 extern "C" __global__ __launch_bounds__(256) void bsc_vtext_write_kernel(vt_args a, uint32_t n_tiles, const unsigned long long *__restrict__ tile_off,
@@ -139,7 +88,7 @@ extern "C" __global__ __launch_bounds__(256) void bsc_vtext_write_kernel(vt_args
   __shared__ __attribute__((aligned(16))) uint8_t s_img[VT_WAVES][VT_IMG + 32u]; /* 15 bytes of phase in front */
   const unsigned lane = threadIdx.x & 63u, wid = threadIdx.x >> 6;
   uint8_t *const img = s_img[wid];
-  const uint64_t n = vt_clamp_n(a);
+  const uint64_t n = rs_clamp_n(a.src);
   if (blockIdx.x == 0 && threadIdx.x == 0) *total = tile_off[n_tiles];
   const uint32_t tile0 = blockIdx.x * VT_WAVES + wid;
   unsigned len_next = 0u;
@@ -156,39 +105,18 @@ extern "C" __global__ __launch_bounds__(256) void bsc_vtext_write_kernel(vt_args
     const uint8_t *id = nullptr;
     unsigned id_len = 0u;
     if (len) {
-      (void)vt_load(r, a, (uint64_t)tile * 64u + lane, false);
+      (void)rs_load(r, a.src, (uint64_t)tile * 64u + lane, 1);
       id_len = vt_find_name(a, r, id);
     }
-    /* exclusive prefix of the lengths over the wave */
-    unsigned inc = len;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const unsigned v = __shfl_up(inc, d);
-      if (lane >= (unsigned)d) inc += v;
-    }
-    const unsigned excl = inc - len;
-    const unsigned t_all = (unsigned)__builtin_amdgcn_readlane((int)inc, 63);
+    unsigned excl, t_all;
+    const unsigned inc = rs_wave_excl_scan(len, excl, t_all);
     const uint64_t g_tile = tile_off[tile];
     if (g_tile + t_all > out_cap) continue; /* the host reports the overflow from *total */
-    /* one part when the tile's span fits the image (the usual case), else the fewest parts of equal lane counts that do */
-    unsigned parts = 1u;
-    if (t_all > VT_IMG) {
-      for (parts = 2u; parts < 16u; parts <<= 1) {
-        const unsigned step = 64u / parts;
-        bool fits = true;
-        unsigned prev = 0u;
-        for (unsigned q = 0; q < parts; q++) {
-          const unsigned e = (unsigned)__shfl((int)inc, (int)(step * (q + 1u) - 1u));
-          fits = fits && e - prev <= VT_IMG;
-          prev = e;
-        }
-        if (fits) break;
-      }
-    }
+    const unsigned parts = rs_pick_parts<VT_IMG, 16u>(inc);
     const unsigned step = 64u / parts;
     unsigned b0 = 0u; /* the part's first byte within the tile */
     for (unsigned ps = 0; ps < parts; ps++) {
-      const unsigned b1 = (unsigned)__shfl((int)inc, (int)(step * (ps + 1u) - 1u)); /* one past its last */
+      const unsigned b1 = rs_lane(inc, step * (ps + 1u) - 1u); /* one past its last */
       const bool mine = len && excl >= b0 && excl < b1;
       const uint64_t g0 = g_tile + b0;
       const unsigned ph = (unsigned)(g0 & 15u);
@@ -200,21 +128,9 @@ extern "C" __global__ __launch_bounds__(256) void bsc_vtext_write_kernel(vt_args
          * with the clamped records, so a block entry fails instead (never seen: one emitter over two sinks) */
         if (w.len != len) atomicAdd(total + 1, 1ull);
       }
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-      /* the image [ph, ph + t) -> out[g0, g0 + t) */
-      const unsigned t = b1 - b0, end = ph + t;
-      uint8_t *const dst = out + (g0 - ph);
-      const unsigned head_end = ph ? (end < 16u ? end : 16u) : 0u; /* bytes [ph, head_end) singly */
-      if (lane >= ph && lane < head_end) dst[lane] = img[lane];
-      const unsigned body0 = ph ? 16u : 0u, body1 = end & ~15u;
-      for (unsigned o = body0 + 16u * lane; o < body1; o += 1024u) *reinterpret_cast<uint4 *>(dst + o) = *reinterpret_cast<const uint4 *>(img + o);
-      const unsigned tail0 = body1 > head_end ? body1 : head_end;
-      if (tail0 + lane < end) dst[tail0 + lane] = img[tail0 + lane];
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+      rs_wave_sync();
+      rs_copy_out(img, out + (g0 - ph), lane, rs_copy_ranges(ph, b1 - b0)); /* the image [ph, ph + t) -> out[g0, g0 + t) */
+      rs_wave_sync();
       b0 = b1;
     }
   }
@@ -257,15 +173,7 @@ extern "C" int bsc_dev_launch_vcf_text(const void *recs, const void *core, const
   hipStream_t s = (hipStream_t)stream;
   if (!contig_len || contig_len > VT_CONTIG_MAX) return (int)hipErrorInvalidValue;
   vt_args a;
-  a.recs = (const uint8_t *)recs;
-  a.core = (const uint8_t *)core;
-  a.aux = (const uint8_t *)aux;
-  a.n_recs = (const unsigned long long *)n_recs;
-  a.max_recs = max_recs;
-  a.name_pos = (const uint32_t *)name_pos;
-  a.name_off = (const uint32_t *)name_off;
-  a.name_bytes = (const uint8_t *)name_bytes;
-  a.n_names = name_pos ? n_names : 0u;
+  a.src = rs_make_src(recs, core, aux, n_recs, max_recs, name_pos, name_off, name_bytes, n_names);
   a.clen1 = contig_len + 1u;
   for (int k = 0; k < 64; k++) a.contig_w[k] = 0u;
   __builtin_memcpy(a.contig_w, contig, contig_len);

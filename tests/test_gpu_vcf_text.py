@@ -258,6 +258,51 @@ def test_count_on_the_device_limits_the_records(caller):
 
 
 # ---- 3. the per-position form behind the chain ---------------------------------------------------------------------------------------------
+def test_tiles_of_the_longest_lines_go_out_in_four_parts(caller):
+    """the wave's image is 12 KB: 32 lines of ~640 bytes do not fit it, 16 do — four parts of 16 lanes.  Every field at its widest: a 255-byte
+    contig name, ten-digit positions, 63-byte names, six likelihoods of twelve characters, counts beyond 32 767, all four filter bits, two
+    ALT alleles, a heterozygous call's FS; a stretch of short lines in between, so that the parts of one tile differ in what they hold."""
+    n, contig = 200, b"k" * 255
+    recs = np.zeros(n, dtype=VCF_REC)
+    core = recs["core"]
+    core["pos"] = 4_000_000_000 + 7 * np.arange(n, dtype=np.uint32)
+    core["emit"] = 1
+    core["gt"] = 1            # heterozygous: FS is written
+    core["gt_enc"] = 0x24
+    core["flt"] = 15          # q20 qd2 fs60 mq40
+    core["phred"] = 255
+    core["n_gl"] = 6
+    core["cg"] = b"H"
+    core["alt"] = b"CT"
+    core["cx_ref"] = b"ACGTA"
+    core["cx_gt"] = b"HHCGH"
+    core["fs"] = -2_000_000_000
+    core["qd"] = 4_000_000_000
+    core["dp"] = 4_000_000_000
+    core["gl"] = np.float32(-1.23457e-05)  # "-1.23457e-05"
+    recs["core"] = core
+    recs["mq"] = -2_000_000_000
+    recs["counts"] = 4_000_000_000 + np.arange(8, dtype=np.uint32)
+    recs["qual"] = 243
+    recs["rs_found"] = 1
+    short = slice(85, 115)
+    recs["counts"][short] = 5
+    recs["core"]["n_gl"][short] = 1
+    recs["core"]["dp"][short] = 7
+    recs["rs_found"][short] = 0
+    rng = np.random.default_rng(4343)
+    pos = recs["core"]["pos"].astype(np.uint32)  # every record listed: the longest name the encoder keeps, and longer ones (cut at 63)
+    nm = [b"rs" + bytes(rng.choice(list(b"0123456789"), int(rng.integers(61, 90))).tolist()) for _ in pos]
+    off = np.concatenate([[0], np.cumsum([len(x) for x in nm])]).astype(np.uint32)
+    ids = {i: nm[i][:63] for i in range(n) if recs["rs_found"][i]}
+    want = host_lines(recs, contig, ids)
+    sizes = np.array([len(w) for w in want])
+    assert sizes.max() <= 665 and sizes[:32].sum() > 12288 and sizes[:16].sum() <= 12288
+    assert sizes[short].max() < 500 < sizes[:85].min()
+    out, tot = encode_packed(caller, recs, contig, names=(pos, off, b"".join(nm)))
+    assert tot == [int(sizes.sum()), 0, n] and out[: tot[0]].tobytes() == b"".join(want)
+
+
 @pytest.fixture(scope="module")
 def synth():
     seed = 424242
