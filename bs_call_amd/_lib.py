@@ -100,6 +100,11 @@ EXPORTS = (
     "bsc_dbsnp_load_contig",
     "bsc_dbsnp_flags",
     "bsc_dbsnp_name",
+    "bsc_dbsnp_attach",
+    "bsc_dbsnp_detach",
+    "bsc_dbsnp_count",
+    "bsc_dbsnp_flags_device",
+    "bsc_dbsnp_names_device",
     "bsc_set_profiling",
     "bsc_set_reads_fused",
     "bsc_block_bcf_again",
@@ -475,6 +480,16 @@ def load():
     L.bsc_dbsnp_flags.argtypes = [vp, u32, u32, vp]
     L.bsc_dbsnp_name.restype = i32
     L.bsc_dbsnp_name.argtypes = [vp, u32, C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]
+    L.bsc_dbsnp_attach.restype = i32
+    L.bsc_dbsnp_attach.argtypes = [vp, vp, C.POINTER(u64)]
+    L.bsc_dbsnp_detach.restype = i32
+    L.bsc_dbsnp_detach.argtypes = [vp]
+    L.bsc_dbsnp_count.restype = i32
+    L.bsc_dbsnp_count.argtypes = [vp, u32, u32, C.POINTER(u32), C.POINTER(u64)]
+    L.bsc_dbsnp_flags_device.restype = i32
+    L.bsc_dbsnp_flags_device.argtypes = [vp, u32, u32, vp, vp]
+    L.bsc_dbsnp_names_device.restype = i32
+    L.bsc_dbsnp_names_device.argtypes = [vp, u32, u32, vp, vp, vp, u32, u64, vp]
     L.bsc_set_reads_fused.restype = i32
     L.bsc_set_reads_fused.argtypes = [vp, i32]
     L.bsc_bcf_stream_detach.restype = i32

@@ -883,6 +883,31 @@ class SiteCaller:
     def vcf_stats_device(self, d_core, d_gtm, stride, n, d_dbsnp=None, stream=None):
         _check(self._L.bsc_vcf_stats_device(self._h, d_core, d_gtm, stride, d_dbsnp, n, stream))
 
+    # -- a contig of the dbSNP index kept in HBM (csrc/dbsnpdev.hip) --------------------------------------
+    def dbsnp_attach(self, db):
+        """bsc_dbsnp_attach: snapshot the contig loaded in `db` (a dbsnp.DbSnpIndex) into the context; while it is attached the
+        block_*_rawdev entries take dbsnp=None / names=None as "from the attachment".  Returns the number of entries."""
+        n = C.c_uint64(0)
+        _check(self._L.bsc_dbsnp_attach(self._h, db._h, C.byref(n)))
+        return n.value
+
+    def dbsnp_detach(self):
+        _check(self._L.bsc_dbsnp_detach(self._h))
+
+    def dbsnp_count(self, x0, n):
+        """bsc_dbsnp_count: (names, name bytes) of positions x0 .. x0 + n - 1 of the attached contig — host arithmetic."""
+        k, nb = C.c_uint32(0), C.c_uint64(0)
+        _check(self._L.bsc_dbsnp_count(self._h, x0, n, C.byref(k), C.byref(nb)))
+        return k.value, nb.value
+
+    def dbsnp_flags_device(self, x0, n, d_out, stream=None):
+        """bsc_dbsnp_flags_device: d_out[n] (device pointer, any alignment) = DbSnpIndex.flags(x0, n); asynchronous on `stream`."""
+        _check(self._L.bsc_dbsnp_flags_device(self._h, x0, n, d_out, stream))
+
+    def dbsnp_names_device(self, x0, n, d_pos, d_off, d_bytes, cap_names, cap_bytes, stream=None):
+        """bsc_dbsnp_names_device: the three arrays of DbSnpIndex.names(x0, n) into device memory sized by dbsnp_count()."""
+        _check(self._L.bsc_dbsnp_names_device(self._h, x0, n, d_pos, d_off, d_bytes, cap_names, cap_bytes, stream))
+
     def site_stats(self):
         """The accumulated bsc_site_stats as a numpy record (SITE_STATS)."""
         out = np.zeros(1, dtype=SITE_STATS)

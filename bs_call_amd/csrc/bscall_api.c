@@ -21,6 +21,7 @@
 #include "bsmath.h"
 #include "bsmath_tables.h"
 #include "synth.h"
+#include "dbsnpdev_core.h"
 
 /* launchers implemented in kernels.hip */
 int bsc_dev_launch_call(const void *cts, const void *ref, uint64_t n, void *out, uint32_t out_dw, void *skip,
@@ -88,6 +89,9 @@ int bsc_dev_launch_bin_reads_multi(const void *tpl, uint32_t nr, const void *seq
 int bsc_dev_launch_bgzf(const void *src, uint64_t n, uint32_t n_members, void *slots, void *sizes, void *offs, void *scratch, uint32_t grid,
                         void *stream); /* bgzfdev.hip */
 int bsc_dev_launch_bgzf_gather(const void *slots, const void *offs, const void *sizes, uint32_t n_members, void *out, void *stream);
+int bsc_dev_launch_dbsnp_flags(const bsc_dbsnp_flat *f, uint32_t x0, uint32_t n, void *d_out, int num_cus, void *stream); /* dbsnpdev.hip */
+int bsc_dev_launch_dbsnp_names(const bsc_dbsnp_flat *f, uint32_t e0, uint32_t n_names, void *d_pos, void *d_off, void *d_bytes, int num_cus,
+                               void *stream);
 #define BSC_PREP_CNT_SLOTS 64u                               /* csrc/prepdev.hip: PREP_CNT_SLOTS */
 #define BSC_PREP_CNT_ALL (8u + 8u * BSC_PREP_CNT_SLOTS)     /* the eight shared words and the slots behind them */
 #define BSC_LN10 (2.30258509299404568402) /* the reference's LOG10 literal (include/bs_call.h:36) */
@@ -175,6 +179,15 @@ struct bsc_context {
   const bsc_bcf_names *names_up; /* set around the encoder's call of a block entry: this table is in d_bnm already */
   uint32_t names_up_n;
   uint64_t names_up_bytes;
+  struct { /* bsc_dbsnp_attach: a contig of a dbSNP index, flat (csrc/dbsnpdev_core.h) — the host's block, which the counting reads, its copy in
+            * HBM, which the kernels of dbsnpdev.hip read, and the arrays of both */
+    int on;
+    bsc_dbsnp_flat_blob blob;
+    void *d_blob;
+    bsc_dbsnp_flat host, dev;
+  } dbs;
+  int att_block;          /* set by the bsc_block_*_rawdev* entries around their call: NULL dbsnp / names mean "from the attachment" */
+  bsc_bcf_names att_names; /* what names_up points at while d_bnm holds a table the attachment made (no caller's table has this address) */
   struct { /* the last BCF block's stream was longer than the caller's room: what bsc_block_bcf_again encodes once more, from the per-position
             * arrays still in d_vout / d_out (nothing of the block is computed or counted a second time) */
     int valid, have_names, inexact;
@@ -527,6 +540,8 @@ int bsc_destroy(bsc_context *ctx) {
   hipFree(ctx->d_bto);
   hipFree(ctx->d_bscn);
   hipFree(ctx->d_bnm);
+  hipFree(ctx->dbs.d_blob);
+  bsc_dev_dbsnp_flat_free(&ctx->dbs.blob);
   if (ctx->h_names) hipHostFree(ctx->h_names);
   for (int k = 0; k < 4; k++)
     if (ctx->bcf_pool.p[k]) hipFree(ctx->bcf_pool.p[k]);
@@ -1846,6 +1861,122 @@ static int bsc_names_upload(bsc_context *ctx, const char *who, const bsc_bcf_nam
   return BSC_OK;
 }
 
+/* ---- a contig of the dbSNP index kept in HBM (csrc/dbsnpdev_core.h, csrc/dbsnpdev.hip) -------------------------------------------------- */
+/* Both are ordered against the context's own (non-blocking) stream, which the NULL stream does not wait for: a block queued by a submit
+ * form may still be reading the old arrays, and the upload must be through before the first block's kernels read the new ones. */
+static int bsc_dbsnp_drop(bsc_context *ctx) {
+  if (!ctx->dbs.on && !ctx->dbs.d_blob) return BSC_OK;
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  ctx->dbs.on = 0;
+  ctx->again.valid = 0; /* (a refused block's table was the old attachment's) */
+  (void)hipFree(ctx->dbs.d_blob);
+  ctx->dbs.d_blob = NULL;
+  bsc_dev_dbsnp_flat_free(&ctx->dbs.blob);
+  return BSC_OK;
+}
+
+int bsc_dbsnp_detach(bsc_context *ctx) {
+  if (!ctx) return bsc_fail(BSC_ERR_ARG, "bsc_dbsnp_detach: NULL argument");
+  BSC_ENTER(ctx);
+  return bsc_dbsnp_drop(ctx);
+}
+
+int bsc_dbsnp_attach(bsc_context *ctx, const bsc_dbsnp *db, uint64_t *n_snps) {
+  if (!ctx || !db) return bsc_fail(BSC_ERR_ARG, "bsc_dbsnp_attach: NULL argument");
+  if (n_snps) *n_snps = 0;
+  BSC_ENTER(ctx);
+  /* the old attachment goes FIRST: an attach that is refused (a bad prefix index, no memory) leaves NOTHING attached, so the blocks of the
+   * next contig can never be named from the previous contig's index */
+  int rc = bsc_dbsnp_drop(ctx);
+  if (rc) return rc;
+  bsc_dbsnp_flat_blob blob;
+  if ((rc = bsc_dev_dbsnp_flatten(db, &blob))) return rc; /* (its message is in the same buffer: bsc_set_error) */
+  void *d = NULL;
+  hipError_t e = hipMalloc(&d, blob.bytes ? blob.bytes : 16u);
+  if (e == hipSuccess && blob.bytes) e = hipMemcpyAsync(d, blob.blob, blob.bytes, hipMemcpyHostToDevice, ctx->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+  if (e != hipSuccess) {
+    (void)hipFree(d);
+    (void)hipGetLastError(); /* (a failed allocation stays behind as the runtime's "last error", bsc_reserve) */
+    const size_t bytes = blob.bytes;
+    bsc_dev_dbsnp_flat_free(&blob);
+    return bsc_fail(e == hipErrorOutOfMemory ? BSC_ERR_NOMEM : BSC_ERR_HIP, "bsc_dbsnp_attach: %zu bytes to the device: %s", bytes, hipGetErrorString(e));
+  }
+  ctx->dbs.blob = blob;
+  ctx->dbs.d_blob = d;
+  ctx->dbs.host = bsc_dbf_view(&blob, blob.blob);
+  ctx->dbs.dev = bsc_dbf_view(&blob, d);
+  ctx->dbs.on = 1;
+  if (n_snps) *n_snps = blob.n_entries;
+  return BSC_OK;
+}
+
+static int bsc_dbsnp_range_check(const bsc_context *ctx, const char *who, uint32_t x0, uint32_t n) {
+  if (!ctx) return bsc_fail(BSC_ERR_ARG, "%s: NULL argument", who);
+  if (!ctx->dbs.on) return bsc_fail(BSC_ERR_ARG, "%s: no dbSNP contig is attached (bsc_dbsnp_attach)", who);
+  if (x0 < 1u) return bsc_fail(BSC_ERR_ARG, "%s: positions are 1-based (x0 = 0)", who);
+  if (n && (uint64_t)x0 + n - 1u > 0xffffffffull) return bsc_fail(BSC_ERR_ARG, "%s: x0 + n - 1 = %llu is beyond 2^32 - 1", who, (unsigned long long)x0 + n - 1u);
+  return BSC_OK;
+}
+
+int bsc_dbsnp_count(const bsc_context *ctx, uint32_t x0, uint32_t n, uint32_t *n_names, uint64_t *n_bytes) {
+  int rc = bsc_dbsnp_range_check(ctx, "bsc_dbsnp_count", x0, n);
+  if (rc) return rc;
+  if (!n_names || !n_bytes) return bsc_fail(BSC_ERR_ARG, "bsc_dbsnp_count: NULL argument");
+  uint32_t e0;
+  bsc_dbf_count(&ctx->dbs.host, x0, n, &e0, n_names, n_bytes);
+  return BSC_OK;
+}
+
+int bsc_dbsnp_flags_device(bsc_context *ctx, uint32_t x0, uint32_t n, void *d_out, void *stream) {
+  int rc = bsc_dbsnp_range_check(ctx, "bsc_dbsnp_flags_device", x0, n);
+  if (rc) return rc;
+  if (!n) return BSC_OK;
+  if (!d_out) return bsc_fail(BSC_ERR_ARG, "bsc_dbsnp_flags_device: NULL argument");
+  BSC_ENTER(ctx);
+  const int e = bsc_dev_launch_dbsnp_flags(&ctx->dbs.dev, x0, n, d_out, ctx->num_cus, stream);
+  if (e) return bsc_fail(BSC_ERR_HIP, "dbSNP flags launch failed: %s", hipGetErrorString((hipError_t)e));
+  return BSC_OK;
+}
+
+int bsc_dbsnp_names_device(bsc_context *ctx, uint32_t x0, uint32_t n, void *d_pos, void *d_off, void *d_bytes, uint32_t cap_names, uint64_t cap_bytes,
+                           void *stream) {
+  int rc = bsc_dbsnp_range_check(ctx, "bsc_dbsnp_names_device", x0, n);
+  if (rc) return rc;
+  if (!n) return BSC_OK;
+  uint32_t e0, n_names;
+  uint64_t n_bytes;
+  bsc_dbf_count(&ctx->dbs.host, x0, n, &e0, &n_names, &n_bytes);
+  if (n_names > cap_names || n_bytes > cap_bytes)
+    return bsc_fail(BSC_ERR_ARG, "bsc_dbsnp_names_device: the range has %u names / %llu bytes, the room is %u / %llu", n_names, (unsigned long long)n_bytes,
+                    cap_names, (unsigned long long)cap_bytes);
+  if (!d_off || (n_names && !d_pos) || (n_bytes && !d_bytes)) return bsc_fail(BSC_ERR_ARG, "bsc_dbsnp_names_device: NULL argument");
+  if (((uintptr_t)d_pos | (uintptr_t)d_off) & 3u) return bsc_fail(BSC_ERR_ARG, "bsc_dbsnp_names_device: d_pos and d_off must be 4-byte aligned");
+  BSC_ENTER(ctx);
+  const int e = bsc_dev_launch_dbsnp_names(&ctx->dbs.dev, e0, n_names, d_pos, d_off, d_bytes, ctx->num_cus, stream);
+  if (e) return bsc_fail(BSC_ERR_HIP, "dbSNP names launch failed: %s", hipGetErrorString((hipError_t)e));
+  return BSC_OK;
+}
+
+/* a block entry's names from the attachment: the table of x .. x + sz - 1 made in d_bnm, in bsc_names_upload's layout and under its marker */
+static int bsc_names_attached(bsc_context *ctx, uint32_t x, uint32_t sz, hipStream_t s) {
+  ctx->names_up = NULL;
+  uint32_t e0, n;
+  uint64_t nb;
+  bsc_dbf_count(&ctx->dbs.host, x, sz, &e0, &n, &nb);
+  if (!n) return BSC_OK;
+  const size_t o_off = (size_t)n * 4u, o_by = o_off + ((size_t)n + 1u) * 4u, total = o_by + (size_t)nb;
+  int rc;
+  if ((rc = bsc_reserve(&ctx->d_bnm, &ctx->cap_bnm, total + 1u))) return rc;
+  const int e = bsc_dev_launch_dbsnp_names(&ctx->dbs.dev, e0, n, ctx->d_bnm, (char *)ctx->d_bnm + o_off, (char *)ctx->d_bnm + o_by, ctx->num_cus, s);
+  if (e) return bsc_fail(BSC_ERR_HIP, "dbSNP names launch failed: %s", hipGetErrorString((hipError_t)e));
+  ctx->att_names.n = n;
+  ctx->names_up = &ctx->att_names;
+  ctx->names_up_n = n;
+  ctx->names_up_bytes = nb;
+  return BSC_OK;
+}
+
 /*
  * The host half the two stream encoders (bcfdev.hip, vcftextdev.hip) share.  d_recs != NULL: packed records, *d_n_recs of them; else
  * d_core / d_aux: the per-position arrays of the reads-in chain, max_recs positions.
@@ -2118,7 +2249,9 @@ static int bsc_records_queue(bsc_context *ctx, const bsc_template *tpl, uint32_t
   if ((rc = bsc_reserve(&ctx->d_out, &ctx->cap_out, (size_t)sz * 64u))) return rc; /* the chain's aux array */
   if ((rc = bsc_reserve(&ctx->d_vout, &ctx->cap_vout, (size_t)sz * sizeof(bsc_vcf_core)))) return rc;
   if ((rc = bsc_reserve(&ctx->d_recs, &ctx->cap_recs, (size_t)(out_cap ? out_cap : 1) * sizeof(bsc_vcf_rec)))) return rc;
-  if (dbsnp && (rc = bsc_reserve(&ctx->d_vdb, &ctx->cap_vdb, (size_t)sz))) return rc;
+  /* a bsc_block_*_rawdev* entry while a dbSNP contig is attached: the flags / the names the caller does not pass are made on the device */
+  const int att = ctx->att_block && ctx->dbs.on, att_flags = att && !dbsnp, att_names = att && bcf && !bcf->names;
+  if ((dbsnp || att_flags) && (rc = bsc_reserve(&ctx->d_vdb, &ctx->cap_vdb, (size_t)sz))) return rc;
   if (!ctx->h_cnt && hipHostMalloc((void **)&ctx->h_cnt, 8 * sizeof(unsigned long long), hipHostMallocDefault) != hipSuccess)
     return bsc_fail(BSC_ERR_NOMEM, "bsc_block_records: pinned counter block");
   if (stage) { /* the caller may recycle its buffers as soon as the call returns: inputs go through the pinned staging area */
@@ -2156,10 +2289,16 @@ static int bsc_records_queue(bsc_context *ctx, const bsc_template *tpl, uint32_t
   if (!(resident && ctx->ref_resident)) HIP_TRY(hipMemcpyAsync(ctx->d_ref, ref, (size_t)sz + 2, hipMemcpyHostToDevice, s));
   if (dbsnp) HIP_TRY(hipMemcpyAsync(ctx->d_vdb, dbsnp, (size_t)sz, hipMemcpyHostToDevice, s));
   if (bcf && (rc = bsc_names_upload(ctx, "bsc_block_bcf", bcf->names, s))) return rc;
+  if (att_names && (rc = bsc_names_attached(ctx, x, sz, s))) return rc;
   const bsc_bcf_names *const names_ready = ctx->names_up;
+  const bsc_bcf_names *const enc_names = att_names ? names_ready : (bcf ? bcf->names : NULL);
   ctx->names_up = NULL;
   if (turns) bsc_h2d_turn_end(ctx, s);
-  void *d_db = dbsnp ? ctx->d_vdb : NULL;
+  if (att_flags) {
+    const int e = bsc_dev_launch_dbsnp_flags(&ctx->dbs.dev, x, sz, ctx->d_vdb, ctx->num_cus, s);
+    if (e) return bsc_fail(BSC_ERR_HIP, "dbSNP flags launch failed: %s", hipGetErrorString((hipError_t)e));
+  }
+  void *d_db = dbsnp || att_flags ? ctx->d_vdb : NULL;
   /* the chain leaves the records' emit flags once more as a byte per position: the packing pass behind it then counts from 64 bytes a tile
    * and fetches the records that are written and nothing of the others (20 M positions: 1.08 -> 0.80 ms) */
   void *d_emit = NULL; /* the packing pass counts and gathers by them; the encoder's SIZE pass reads the record lengths they hold since
@@ -2199,8 +2338,8 @@ static int bsc_records_queue(bsc_context *ctx, const bsc_template *tpl, uint32_t
     ctx->again.n_names = ctx->names_up_n;
     ctx->again.name_bytes = ctx->names_up_bytes;
     ctx->names_up = names_ready;
-    rc = bcf->text ? bsc_vcf_text_sites_device(ctx, ctx->d_vout, ctx->d_out, sz, bcf->contig, bcf->names, ctx->d_bcf, bcf->out_cap, ctx->d_btot, s)
-                   : bsc_bcf_sites_device(ctx, ctx->d_vout, ctx->d_out, sz, bcf->rid, bcf->ids, bcf->names, ctx->d_bcf, bcf->out_cap, ctx->d_btot, s);
+    rc = bcf->text ? bsc_vcf_text_sites_device(ctx, ctx->d_vout, ctx->d_out, sz, bcf->contig, enc_names, ctx->d_bcf, bcf->out_cap, ctx->d_btot, s)
+                   : bsc_bcf_sites_device(ctx, ctx->d_vout, ctx->d_out, sz, bcf->rid, bcf->ids, enc_names, ctx->d_bcf, bcf->out_cap, ctx->d_btot, s);
     ctx->emit_hint = NULL;
     ctx->names_up = NULL;
     if (rc) return rc;
@@ -2502,10 +2641,14 @@ int bsc_block_records_rawdev(bsc_context *ctx, const void *d_raw, uint32_t nr, c
   if (rc) return rc;
   *n_out = 0;
   if (prep_stats) memset(prep_stats, 0, sizeof *prep_stats);
-  if (!nr) return bsc_block_records_(ctx, NULL, 0, NULL, 0, x, y, ref, dbsnp, params, with_stats, out, out_cap, n_out, NULL);
   BSC_ENTER(ctx);
-  return bsc_block_records_rawdev_(ctx, d_raw, nr, d_seq, seq_bytes, d_misms, n_misms, seq_bytes + ins_pad + 16, prep, x, y, ref, dbsnp, params, with_stats,
+  ctx->att_block = 1; /* NULL dbsnp: the flags of the attached dbSNP contig, if there is one (bsc_records_queue); no return before it is cleared */
+  if (!nr) rc = bsc_block_records_(ctx, NULL, 0, NULL, 0, x, y, ref, dbsnp, params, with_stats, out, out_cap, n_out, NULL);
+  else
+    rc = bsc_block_records_rawdev_(ctx, d_raw, nr, d_seq, seq_bytes, d_misms, n_misms, seq_bytes + ins_pad + 16, prep, x, y, ref, dbsnp, params, with_stats,
                                    out, out_cap, n_out, prep_stats, profile, NULL);
+  ctx->att_block = 0;
+  return rc;
 }
 
 int bsc_block_bcf_rawdev(bsc_context *ctx, const void *d_raw, uint32_t nr, const void *d_seq, uint64_t seq_bytes, const void *d_misms, uint64_t n_misms,
@@ -2518,12 +2661,13 @@ int bsc_block_bcf_rawdev(bsc_context *ctx, const void *d_raw, uint32_t nr, const
   if (prep_stats) memset(prep_stats, 0, sizeof *prep_stats);
   const bsc_bcf_req req = {rid, ids, names, out, out_cap};
   ctx->bcf_bytes = 0;
+  BSC_ENTER(ctx);
+  ctx->att_block = 1; /* NULL dbsnp / names: those of the attached dbSNP contig, if there is one (bsc_records_queue); no return before it is cleared */
   if (!nr) rc = bsc_block_records_(ctx, NULL, 0, NULL, 0, x, y, ref, dbsnp, params, with_stats, NULL, 0, n_records, &req);
-  else {
-    BSC_ENTER(ctx);
+  else
     rc = bsc_block_records_rawdev_(ctx, d_raw, nr, d_seq, seq_bytes, d_misms, n_misms, seq_bytes + ins_pad + 16, prep, x, y, ref, dbsnp, params, with_stats,
                                    NULL, 0, n_records, prep_stats, profile, &req);
-  }
+  ctx->att_block = 0;
   *n_bytes = ctx->bcf_bytes;
   return rc;
 }
@@ -2565,12 +2709,13 @@ int bsc_block_bcf_rawdev_keep(bsc_context *ctx, const void *d_raw, uint32_t nr, 
   if (prep_stats) memset(prep_stats, 0, sizeof *prep_stats);
   const bsc_bcf_req req = {rid, ids, names, NULL, dev_cap};
   ctx->bcf_bytes = 0;
+  BSC_ENTER(ctx);
+  ctx->att_block = 1; /* NULL dbsnp / names: those of the attached dbSNP contig, if there is one (bsc_records_queue); no return before it is cleared */
   if (!nr) rc = bsc_block_records_(ctx, NULL, 0, NULL, 0, x, y, ref, dbsnp, params, with_stats, NULL, 0, n_records, &req);
-  else {
-    BSC_ENTER(ctx);
+  else
     rc = bsc_block_records_rawdev_(ctx, d_raw, nr, d_seq, seq_bytes, d_misms, n_misms, seq_bytes + ins_pad + 16, prep, x, y, ref, dbsnp, params, with_stats,
                                    NULL, 0, n_records, prep_stats, profile, &req);
-  }
+  ctx->att_block = 0;
   *n_bytes = ctx->bcf_bytes;
   return rc;
 }
@@ -2592,12 +2737,13 @@ int bsc_block_vcf_rawdev_keep(bsc_context *ctx, const void *d_raw, uint32_t nr, 
   if (prep_stats) memset(prep_stats, 0, sizeof *prep_stats);
   const bsc_bcf_req req = {0, NULL, names, NULL, dev_cap, 1, contig};
   ctx->bcf_bytes = 0;
+  BSC_ENTER(ctx);
+  ctx->att_block = 1; /* NULL dbsnp / names: those of the attached dbSNP contig, if there is one (bsc_records_queue); no return before it is cleared */
   if (!nr) rc = bsc_block_records_(ctx, NULL, 0, NULL, 0, x, y, ref, dbsnp, params, with_stats, NULL, 0, n_records, &req);
-  else {
-    BSC_ENTER(ctx);
+  else
     rc = bsc_block_records_rawdev_(ctx, d_raw, nr, d_seq, seq_bytes, d_misms, n_misms, seq_bytes + ins_pad + 16, prep, x, y, ref, dbsnp, params, with_stats,
                                    NULL, 0, n_records, prep_stats, profile, &req);
-  }
+  ctx->att_block = 0;
   *n_bytes = ctx->bcf_bytes;
   return rc;
 }

@@ -32,6 +32,7 @@
 #include <zlib.h>
 
 #include "../../include/bscall_amd.h"
+#include "dbsnpdev_core.h"
 
 #define DBSNP_MAGIC 0xd7278434u
 
@@ -467,5 +468,115 @@ int bsc_dbsnp_names(const bsc_dbsnp *db, uint32_t x0, uint32_t n, uint32_t *pos,
   if (fill) off[k] = (uint32_t)nb;
   *n_names = k;
   *n_bytes = nb;
+  return BSC_OK;
+}
+
+/*
+ * The loaded contig as ONE block of flat arrays (csrc/dbsnpdev_core.h has the layout and the statements that read it): what
+ * bsc_dbsnp_attach copies into HBM.  The block is a snapshot — nothing in it points back into db.  Every entry is checked here, once:
+ * its bit must be the mask's bit of its rank (the reader made both), its prefix must exist; the device never sees a bad index.
+ */
+void bsc_dev_dbsnp_flat_free(bsc_dbsnp_flat_blob *b) {
+  if (!b) return;
+  free(b->blob);
+  memset(b, 0, sizeof *b);
+}
+
+int bsc_dev_dbsnp_flatten(const bsc_dbsnp *db, bsc_dbsnp_flat_blob *out) {
+  if (!db || !out) return bsc_set_error(BSC_ERR_ARG, "bsc_dev_dbsnp_flatten: NULL argument");
+  memset(out, 0, sizeof *out);
+  const int have = db->loaded >= 0 && db->bins;
+  const uint64_t n_bins = have ? db->bins_used : 0;
+  uint64_t n_ent = 0, n_pool = 0, n_pre = 0;
+  for (uint64_t b = 0; b < n_bins; b++) {
+    const dbsnp_bin *bin = db->bins + b;
+    n_ent += (uint64_t)bin->n_entries;
+    for (int i = 0; i < bin->n_entries; i++) n_pool += (uint64_t)(bin->entries[i] >> 8) + (((bin->entries[i] >> 6) & 3) ? 0u : 2u);
+  }
+  for (uint32_t i = 0; i < db->n_prefixes; i++) n_pre += strlen(db->prefix[i]);
+  if (n_ent > 0xfffffff0ull || n_pool > 0xfffffff0ull || n_pre > 0xfffffff0ull)
+    return bsc_set_error(BSC_ERR_ARG, "bsc_dev_dbsnp_flatten: more than 2^32 entries or name bytes in one contig");
+  size_t o = 0;
+#define SECTION(field, bytes)                      \
+  do {                                             \
+    out->field = o;                                \
+    o = (o + (size_t)(bytes) + 15u) & ~(size_t)15u; \
+  } while (0)
+  SECTION(o_mask, n_bins * 8u);
+  SECTION(o_fq, n_bins * 8u);
+  SECTION(o_ent_first, (n_bins + 1u) * 4u);
+  SECTION(o_dig, (n_ent + 1u) * 4u);
+  SECTION(o_txt, (n_ent + 1u) * 4u);
+  SECTION(o_pre_off, ((uint64_t)db->n_prefixes + 1u) * 4u);
+  SECTION(o_ent, n_ent * 2u);
+  SECTION(o_pool, n_pool);
+  SECTION(o_pre_txt, n_pre);
+#undef SECTION
+  char *blob = calloc(1, o ? o : 16u);
+  if (!blob) return bsc_set_error(BSC_ERR_NOMEM, "bsc_dev_dbsnp_flatten: out of memory (%zu bytes)", o);
+  out->blob = blob;
+  out->bytes = o;
+  out->min_bin = have ? db->ctgs[db->loaded].min_bin : 0;
+  out->n_bins = (uint32_t)n_bins;
+  out->n_entries = (uint32_t)n_ent;
+  out->n_prefixes = db->n_prefixes;
+  uint64_t *mask = (uint64_t *)(blob + out->o_mask), *fq = (uint64_t *)(blob + out->o_fq);
+  uint32_t *ent_first = (uint32_t *)(blob + out->o_ent_first), *dig = (uint32_t *)(blob + out->o_dig), *txt = (uint32_t *)(blob + out->o_txt),
+           *pre_off = (uint32_t *)(blob + out->o_pre_off);
+  uint16_t *ent = (uint16_t *)(blob + out->o_ent);
+  uint8_t *pool = (uint8_t *)(blob + out->o_pool);
+  char *pre_txt = blob + out->o_pre_txt;
+  uint32_t np = 0;
+  for (uint32_t i = 0; i < db->n_prefixes; i++) {
+    const size_t l = strlen(db->prefix[i]);
+    pre_off[i] = np;
+    memcpy(pre_txt + np, db->prefix[i], l);
+    np += (uint32_t)l;
+  }
+  pre_off[db->n_prefixes] = np;
+  uint32_t e = 0, d = 0;
+  uint64_t t = 0;
+  for (uint64_t b = 0; b < n_bins; b++) {
+    const dbsnp_bin *bin = db->bins + b;
+    mask[b] = bin->mask;
+    fq[b] = bin->fq_mask;
+    ent_first[b] = e;
+    uint64_t m = bin->mask;
+    const uint8_t *nb = bin->name_buf;
+    for (int i = 0; i < bin->n_entries; i++, e++) {
+      const uint16_t en = bin->entries[i];
+      const uint64_t x = ((uint64_t)out->min_bin + b) * 64u + (en & 63u);
+      if (!m || (unsigned)__builtin_ctzll(m) != (en & 63u)) {
+        bsc_dev_dbsnp_flat_free(out);
+        return bsc_set_error(BSC_ERR_ARG, "bsc_dev_dbsnp_flatten: position %llu: the bin's entries and its mask disagree", (unsigned long long)x);
+      }
+      m &= m - 1;
+      const unsigned field = (en >> 6) & 3u, nd = en >> 8;
+      const uint32_t prefix = field ? field - 1u : (uint32_t)nb[0] | ((uint32_t)nb[1] << 8); /* low byte first: see bsc_dbsnp_name */
+      if (prefix >= db->n_prefixes) {
+        bsc_dev_dbsnp_flat_free(out);
+        return bsc_set_error(BSC_ERR_ARG, "bsc_dev_dbsnp_flatten: position %llu names prefix %u of %u", (unsigned long long)x, prefix, db->n_prefixes);
+      }
+      const unsigned take = nd + (field ? 0u : 2u);
+      ent[e] = en;
+      dig[e] = d;
+      txt[e] = (uint32_t)t;
+      memcpy(pool + d, nb, take);
+      nb += take;
+      d += take;
+      t += (uint64_t)(pre_off[prefix + 1] - pre_off[prefix]) + 2u * nd;
+      if (t > 0xfffffff0ull) {
+        bsc_dev_dbsnp_flat_free(out);
+        return bsc_set_error(BSC_ERR_ARG, "bsc_dev_dbsnp_flatten: the contig's names are longer than 2^32 bytes");
+      }
+    }
+    if (m) {
+      bsc_dev_dbsnp_flat_free(out);
+      return bsc_set_error(BSC_ERR_ARG, "bsc_dev_dbsnp_flatten: bin %llu: more mask bits than entries", (unsigned long long)(out->min_bin + b));
+    }
+  }
+  ent_first[n_bins] = e;
+  dig[e] = d;
+  txt[e] = (uint32_t)t;
   return BSC_OK;
 }

@@ -71,9 +71,46 @@ class DbSnpIndex:
                                        k.value, nb.value, C.byref(k), C.byref(nb)))
         return pos, off, by[: nb.value].tobytes()
 
+    def attach(self, caller):
+        """Keep the loaded contig in `caller`'s device memory (SiteCaller.dbsnp_attach): flags and names of its blocks are then made
+        there.  A snapshot: loading another contig afterwards does not change what is attached."""
+        return caller.dbsnp_attach(self)
+
     def name(self, x):
         """(rs_found, name, rs_len as the reference counts it) of position x."""
         buf = C.create_string_buffer(600)
         ln = C.c_size_t(0)
         r = _check(self._L.bsc_dbsnp_name(self._h, x, buf, 600, C.byref(ln)))
         return r, buf.value.decode("utf-8", "replace"), ln.value
+
+
+def detach(caller):
+    caller.dbsnp_detach()
+
+
+def count(caller, x0, n):
+    """(names, name bytes) of x0 .. x0 + n - 1 of the contig attached to `caller`."""
+    return caller.dbsnp_count(x0, n)
+
+
+def flags_device(caller, x0, n, device=None):
+    """DbSnpIndex.flags(x0, n) of the attached contig, made on the device: a torch uint8 tensor[n] on the caller's GPU."""
+    import torch
+
+    out = torch.empty(max(n, 1), dtype=torch.uint8, device=device or "cuda")
+    caller.dbsnp_flags_device(x0, n, out.data_ptr(), C.c_void_p(torch.cuda.current_stream(out.device).cuda_stream))
+    return out[:n]
+
+
+def names_device(caller, x0, n, device=None):
+    """DbSnpIndex.names(x0, n) of the attached contig, made on the device: (pos int32-viewed uint32[k], off[k + 1], bytes uint8) torch
+    tensors on the caller's GPU, sized by count()."""
+    import torch
+
+    k, nb = caller.dbsnp_count(x0, n)
+    dev = device or "cuda"
+    pos = torch.zeros(max(k, 1), dtype=torch.int32, device=dev)
+    off = torch.zeros(k + 1, dtype=torch.int32, device=dev)
+    by = torch.zeros(max(nb, 1), dtype=torch.uint8, device=dev)
+    caller.dbsnp_names_device(x0, n, pos.data_ptr(), off.data_ptr(), by.data_ptr(), k, nb, C.c_void_p(torch.cuda.current_stream(pos.device).cuda_stream))
+    return pos[:k], off, by[:nb]

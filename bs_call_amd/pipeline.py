@@ -17,7 +17,7 @@ def run(bam_path: str, reference: Dict[str, np.ndarray], bcf_path: str, sample: 
         caller: Optional[SiteCaller] = None, dbsnp=None, compressed: bool = True, date=None, left_trim=(0, 0), right_trim=(0, 0),
         min_qual: Optional[int] = None, benchmark_mode: bool = False, under_conv: Optional[float] = None, over_conv: Optional[float] = None,
         host_prep: bool = False, host_bcf: bool = False, device_reader: bool = False, shard_rank: Optional[int] = None, shard_world: int = 1,
-        reduce_device=None, text: bool = False, **reader_kw) -> dict:
+        reduce_device=None, text: bool = False, dbsnp_device: bool = False, **reader_kw) -> dict:
     """reference: contig name -> uint8 reference codes (0 = N, 1..4 = ACGT; position 1 first).  Returns a summary dict.
     under_conv / over_conv / min_qual (defaults 0.01 / 0.05 / 20, src/init_param.c:26-31) are the MODEL's parameters: without
     `caller` the run builds its SiteCaller from them; with one, they are taken from it and a differing explicit value is an error
@@ -34,7 +34,14 @@ def run(bam_path: str, reference: Dict[str, np.ndarray], bcf_path: str, sample: 
     concatenates the shards in contig order behind the header — the bytes of the single run.
     text: the output file is VCF TEXT (the reference's -O v; with `compressed`, BGZF members cut every 0xFF00 bytes: its -O z) — the header
     text, then every block's lines as the device's text encoder writes them (SiteCaller.block_vcf_rawdev: bsc_block_vcf_rawdev_keep).  Needs
-    device_reader; a sharded text run is refused."""
+    device_reader; a sharded text run is refused.
+    dbsnp_device: with a `dbsnp` and the device reader, each contig of the index is kept in HBM (SiteCaller.dbsnp_attach at the contig
+    change) and the blocks' flags and names are made there (csrc/dbsnpdev.hip) instead of on this thread — same bytes, same report."""
+    if dbsnp_device and not device_reader:
+        raise ValueError("dbsnp_device=True needs the device reader (device_reader=True)")
+    if dbsnp_device and shard_rank is not None:
+        raise ValueError("dbsnp_device=True is a single run (no shard_rank)")
+    on_device = dbsnp_device and dbsnp is not None
     if text and (shard_rank is not None or not device_reader or host_prep or host_bcf):
         raise ValueError("text=True is a single run on the device reader (device_reader=True, no shard_rank, no host_prep / host_bcf)")
     own = caller is None
@@ -103,6 +110,8 @@ def run(bam_path: str, reference: Dict[str, np.ndarray], bcf_path: str, sample: 
                         cur_tid = tid
                         if dbsnp is not None:
                             dbsnp.load_contig(name)
+                            if on_device:
+                                c.dbsnp_attach(dbsnp)
                         # the contig's GC bins (load_sequence computes them when a report is asked for), resident on the device
                         gc_start, bins = gc_bins(reference[name])
                         c.set_gc_bins_host(bins, gc_start)
@@ -113,9 +122,9 @@ def run(bam_path: str, reference: Dict[str, np.ndarray], bcf_path: str, sample: 
                         x = int(raw["pos"][0][0]) or int(raw["pos"][0][1])
                         x = x - 2 if x > 2 else 1  # process_template_vector, src/process_template.c:22-28
                     ref = block_reference(codes, x, y)
-                    flags = None if dbsnp is None else dbsnp.flags(x, y - x + 1)
+                    flags = None if dbsnp is None or on_device else dbsnp.flags(x, y - x + 1)
                     if device_reader:  # the block is in HBM already: pre-processing, calling, encoding behind it
-                        names = None if dbsnp is None else dbsnp.names(x, y - x + 1)
+                        names = None if dbsnp is None or on_device else dbsnp.names(x, y - x + 1)
                         if text:
                             blob, n_rec, st = c.block_vcf_rawdev(dblk, ref, name, names=names, left_trim=left_trim, right_trim=right_trim, min_qual=min_qual,
                                                                  reg_stop=len(codes), dbsnp=flags, with_stats=True, profile=prof)
@@ -225,3 +234,5 @@ def run(bam_path: str, reference: Dict[str, np.ndarray], bcf_path: str, sample: 
     finally:
         if own:
             c.close()
+        elif on_device:
+            c.dbsnp_detach()  # a supplied caller goes back as it came

@@ -1027,6 +1027,35 @@ int bsc_dbsnp_load_contig(bsc_dbsnp *db, const char *name, uint64_t *n_snps);
 int bsc_dbsnp_flags(const bsc_dbsnp *db, uint32_t x0, uint32_t n, uint8_t *out);
 int bsc_dbsnp_name(const bsc_dbsnp *db, uint32_t x, char *rs, size_t cap, size_t *rs_len);
 
+/*
+ * The loaded contig kept on the device (csrc/dbsnpdev_core.h, csrc/dbsnpdev.hip): the per-block products of the index — the flags the
+ * chain reads, the names table the stream encoders search — are made in HBM instead of on a host thread and uploaded.
+ *   bsc_dbsnp_attach         snapshots the contig currently loaded in db into the context (flat arrays, one upload); later
+ *                            bsc_dbsnp_load_contig / bsc_dbsnp_close calls on db do not affect it.  No contig loaded, or one the index
+ *                            does not list: an EMPTY contig is attached (flags 0, no names).  Replaces a previous attachment; *n_snps =
+ *                            entries attached.  BSC_ERR_ARG, naming the position, for an entry whose prefix the index does not have.
+ *                            The previous attachment is dropped before anything can fail: after a refused attach NOTHING is attached.
+ *   bsc_dbsnp_detach         drops the attachment (bsc_destroy does too).  Both wait for the context's own stream first: a submitted
+ *                            block may still be reading the arrays.
+ *   bsc_dbsnp_count          names and name bytes of positions x0 .. x0 + n - 1: host arithmetic, no device round trip — the sizes of
+ *                            bsc_dbsnp_names_device's outputs
+ *   bsc_dbsnp_flags_device   d_out[n] = what bsc_dbsnp_flags writes, any alignment; asynchronous on `stream`
+ *   bsc_dbsnp_names_device   d_pos[n_names] | d_off[n_names + 1] | d_bytes[n_bytes] = what bsc_dbsnp_names fills; asynchronous on
+ *                            `stream`; room for fewer than bsc_dbsnp_count's figures is BSC_ERR_ARG before anything is launched
+ * x0 >= 1, x0 + n - 1 <= 2^32 - 1; n = 0 does nothing; the three queries without an attachment are BSC_ERR_ARG.
+ *
+ * While a contig is attached, bsc_block_records_rawdev, bsc_block_bcf_rawdev, bsc_block_bcf_rawdev_keep and bsc_block_vcf_rawdev_keep
+ * read dbsnp == NULL as "the attachment's flags" and names == NULL as "the attachment's names": both are made on the context's stream
+ * ahead of the chain and the encoder (bsc_block_bcf_again encodes with the same table).  Arrays that are passed are used as before, and
+ * every other entry — and these four with nothing attached — is unchanged.
+ */
+int bsc_dbsnp_attach(bsc_context *ctx, const bsc_dbsnp *db, uint64_t *n_snps);
+int bsc_dbsnp_detach(bsc_context *ctx);
+int bsc_dbsnp_count(const bsc_context *ctx, uint32_t x0, uint32_t n, uint32_t *n_names, uint64_t *n_bytes);
+int bsc_dbsnp_flags_device(bsc_context *ctx, uint32_t x0, uint32_t n, void *d_out, void *stream);
+int bsc_dbsnp_names_device(bsc_context *ctx, uint32_t x0, uint32_t n, void *d_pos, void *d_off, void *d_bytes, uint32_t cap_names,
+                           uint64_t cap_bytes, void *stream);
+
 /* Host-side text rendering of one record as a VCF data line ("CHROM POS ID REF ALT QUAL FILTER INFO FORMAT SAMPLE",
  * tab separated, no newline): the field layout of the record the reference hands to htslib (src/print_vcf.c:160-380).
  * Returns the length written, 0 when c->emit == 0, -1 when buf is too small.  `id` NULL/"" prints ".". */

@@ -20,11 +20,11 @@
  *                     bsc_bgzf_take / _close        every block's kept stream go in, the completed members come out to the output thread
  *   at the end        bsc_report_json               output_stats
  *
- * Not a replacement of the bs_call executable (no option parsing beyond -O, regions, contig lists, dbSNP, compressed VCF): a worked
+ * Not a replacement of the bs_call executable (no option parsing beyond -O / -D, regions, contig lists, compressed VCF): a worked
  * example of the calls in order, and the C twin of bs_call_amd/pipeline.py — tests/test_gpu_pipeline.py checks that both
  * write the same bytes.
  *
- *   make bam2bcf && bs_call_amd/lib/bam2bcf [-O u|b] [--format bcf|vcf] in.bam ref.fa out.bcf report.json [sample]
+ *   make bam2bcf && bs_call_amd/lib/bam2bcf [-O u|b] [--format bcf|vcf] [-D dbsnp.idx] in.bam ref.fa out.bcf report.json [sample]
  *
  * A sharded run over ONE file (SURVEY.md 8e on real input; the reference's unit of parallelism is a process per contig set, README.md): rank r of n
  *   bam2bcf --rank r --world n in.bam ref.fa out.bcf report.json [sample]
@@ -44,6 +44,10 @@
  * and terminator, then every block's lines, encoded on the device too (bsc_block_vcf_rawdev_keep, csrc/vcftextdev.hip): with -O u the
  * reference's -O v, with -O b (the same BGZF path) its -O z.  A single run on the device reader only (no --rank / --merge, no BAM2BCF_HOST_*).  -O b needs the device reader and
  * encoder and a single run (a shard compressed on its own would cut its members elsewhere than the single run does).
+ * dbSNP (the reference's -D): -D index names the records, forces out the homozygous-reference records of the index's fq_mask sites and fills
+ * the report's dbSNP counters.  Each contig of the index is loaded by the thread that loads its reference, kept in HBM (bsc_dbsnp_attach at
+ * the contig change) and the blocks' flags and names are made there (csrc/dbsnpdev.hip): the block calls pass NULL for both.  The header is
+ * the --benchmark-mode header, which has no ##dbsnp line.  With either -O and either --format; a single run on the device reader only.
  */
 #include <pthread.h>
 #include <stdio.h>
@@ -183,6 +187,7 @@ typedef struct {
   pthread_t th;
   int running;
 } ref_job;
+static bsc_dbsnp *g_dbsnp; /* -D: the contig's entries are loaded behind its reference; the main thread attaches them (a snapshot) before the next job starts */
 static void *ref_main(void *a) {
   ref_job *j = a;
   j->codes = malloc(j->want ? j->want : 1);
@@ -192,6 +197,7 @@ static void *ref_main(void *a) {
     j->gc = malloc((size_t)(j->codes_len / 100 + 1));
     j->rc = j->gc ? bsc_gc_bins(j->codes, j->codes_len, &j->gc_start, j->gc, j->codes_len / 100 + 1, &j->n_bins) : -1;
   }
+  if (j->rc >= 0 && g_dbsnp) j->rc = bsc_dbsnp_load_contig(g_dbsnp, j->name, NULL);
   if (j->rc < 0) snprintf(j->err, sizeof j->err, "%s", bsc_last_error());
   return NULL;
 }
@@ -411,7 +417,20 @@ static int merge_main(int world, char **argv, const char *sample) {
 
 int main(int argc, char **argv) {
   int rank = -1, world = 1, merge = 0, bgzf = 0, text = 0;
-  while (argc > 2 && argv[1][0] == '-' && (argv[1][1] == '-' || argv[1][1] == 'O')) { /* --rank r --world n | --merge n | -O u|b */
+  const char *dbsnp_path = NULL;
+  if (argc == 2 && !strcmp(argv[1], "-D")) {
+    fprintf(stderr, "%s: -D takes the path of a dbSNP index (the file dbSNP_idx writes)\n", argv[0]);
+    return 2;
+  }
+  while (argc > 2 && argv[1][0] == '-' && (argv[1][1] == '-' || argv[1][1] == 'O' || argv[1][1] == 'D')) { /* --rank r --world n | --merge n | -O u|b | -D index */
+    if (argv[1][1] == 'D') { /* -D index, -Dindex */
+      dbsnp_path = argv[1][2] ? argv[1] + 2 : argv[2];
+      const int k = argv[1][2] ? 1 : 2;
+      argv[k] = argv[0];
+      argv += k;
+      argc -= k;
+      continue;
+    }
     if (argv[1][1] == 'O') { /* -O b, -Ob */
       const char *v = argv[1][2] ? argv[1] + 2 : argv[2];
       if (strcmp(v, "b") && strcmp(v, "u")) {
@@ -441,7 +460,7 @@ int main(int argc, char **argv) {
     argc -= 2;
   }
   if (argc < 5 || world < 1 || (rank >= 0 && rank >= world)) {
-    fprintf(stderr, "usage: %s [-O u|b] [--format bcf|vcf] [--rank r --world n | --merge n] in.bam ref.fa out.bcf report.json [sample]\n", argv[0]);
+    fprintf(stderr, "usage: %s [-O u|b] [--format bcf|vcf] [-D dbsnp.idx] [--rank r --world n | --merge n] in.bam ref.fa out.bcf report.json [sample]\n", argv[0]);
     return 2;
   }
   if (text && (rank >= 0 || merge > 0)) {
@@ -454,6 +473,14 @@ int main(int argc, char **argv) {
   }
   if (bgzf && (rank >= 0 || merge > 0)) {
     fprintf(stderr, "%s: -O b writes a single run's file; a sharded run (--rank / --merge) writes uncompressed BCF (-O u)\n", argv[0]);
+    return 2;
+  }
+  if (dbsnp_path && (rank >= 0 || world > 1 || merge > 0)) {
+    fprintf(stderr, "%s: -D is a single run's option; a sharded run (--rank / --world / --merge) has no dbSNP index\n", argv[0]);
+    return 2;
+  }
+  if (dbsnp_path && (getenv("BAM2BCF_HOST_PREP") || getenv("BAM2BCF_HOST_BCF") || getenv("BAM2BCF_HOST_READER"))) {
+    fprintf(stderr, "%s: -D keeps the index on the device, for the device reader's blocks: not with BAM2BCF_HOST_READER / _HOST_BCF / _HOST_PREP\n", argv[0]);
     return 2;
   }
   const char *sample = argc > 5 ? argv[5] : "SAMPLE";
@@ -470,6 +497,7 @@ int main(int argc, char **argv) {
     fprintf(stderr, "bam2bcf: -O b compresses the device encoder's streams: not with BAM2BCF_HOST_READER / _HOST_BCF / _HOST_PREP\n");
     return 2;
   }
+  if (dbsnp_path) CHECK(bsc_dbsnp_open(dbsnp_path, &g_dbsnp)); /* (before the context: a bad index costs no device) */
   const double t_start = now();
   bsc_params prm = {0.01, 0.05, 2.0, 20, 0};
   bsc_context *ctx;
@@ -636,6 +664,7 @@ int main(int argc, char **argv) {
       gc = RJ.gc;
       codes_len = RJ.codes_len;
       CHECK(bsc_set_gc_bins_host(ctx, gc, (uint32_t)RJ.n_bins, RJ.gc_start));
+      if (g_dbsnp) CHECK(bsc_dbsnp_attach(ctx, g_dbsnp, NULL)); /* what the job loaded behind the reference; the next job may load over it */
       if (cur_tid + 1 < n_ref) ref_start(&RJ, argv[2], REF_NAME(cur_tid + 1), REF_LEN(cur_tid + 1), cur_tid + 1); /* the next one, meanwhile */
     }
     const uint32_t x = host_reader ? bsc_block_start(&blk.tpl[0]) : dblk.x, y = blk.y, n = y - x + 1;
@@ -806,6 +835,7 @@ int main(int argc, char **argv) {
   rep.filter_bases[0] += passed_bases;
   memcpy(rep.base_filter, base_filter, sizeof base_filter);
   rep.total = &total;
+  rep.have_dbsnp = g_dbsnp != NULL;
   CHECK(bsc_set_gc_bins_host(ctx, NULL, 0, 0));
   uint64_t *gc_table = xrealloc(NULL, (size_t)BSC_COV_CAP * 101 * sizeof(uint64_t));
   CHECK(bsc_get_gc_stats(ctx, gc_table));
@@ -883,5 +913,6 @@ int main(int argc, char **argv) {
   if (bam) bsc_bam_close(bam);
   if (dev) bsc_bamdev_close(dev);
   bsc_destroy(ctx);
+  bsc_dbsnp_close(g_dbsnp);
   return 0;
 }

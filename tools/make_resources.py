@@ -2,7 +2,8 @@
 """profiles/r06_resources.txt: per kernel of the library, what the compiler made of HEAD's sources — VGPRs, spilled VGPRs / SGPRs,
 scratch bytes per lane, LDS bytes per workgroup (-Rpass-analysis=kernel-resource-usage), code bytes, and the static counts of
 v_readlane / v_writelane / scratch_* instructions in the listing.  Every resource figure quoted in DESIGN.md comes from this
-file; regenerate it after touching a kernel.  usage: python tools/make_resources.py [out-file]"""
+file; regenerate it after touching a kernel.  usage: python tools/make_resources.py [out-file [source.hip ...]] — with sources named, only
+those (profiles/dbsnpdev_resources.txt: python tools/make_resources.py profiles/dbsnpdev_resources.txt dbsnpdev.hip)."""
 import os
 import re
 import subprocess
@@ -12,7 +13,7 @@ import tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 out_path = sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, "profiles", "r06_resources.txt")
 FLAGS = "-O3 --offload-arch=gfx950 -fPIC -ffp-contract=off -fno-fast-math -std=c++17 -Wno-inline-asm -Wno-unused-variable -Wno-unused-function".split()
-SOURCES = ["kernels.hip", "fused.hip", "accumulate.hip", "vcfcore.hip", "sitestats.hip", "compact.hip", "prepdev.hip", "bcfdev.hip", "bamdev.hip"]
+SOURCES = sys.argv[2:] or ["kernels.hip", "fused.hip", "accumulate.hip", "vcfcore.hip", "sitestats.hip", "compact.hip", "prepdev.hip", "bcfdev.hip", "bamdev.hip"]
 
 
 def demangle(n):
