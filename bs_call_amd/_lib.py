@@ -117,6 +117,15 @@ EXPORTS = (
     "bsc_bgzf_write_device",
     "bsc_bgzf_take",
     "bsc_bgzf_close",
+    "bsc_bgzf_tell",
+    "bsc_csi_scan_device",
+    "bsc_block_csi_kept",
+    "bsc_csi_open",
+    "bsc_csi_open_detached",
+    "bsc_csi_members",
+    "bsc_csi_add",
+    "bsc_csi_finish",
+    "bsc_csi_close",
     "bsc_debug_fail_summary_alloc",
     "bsc_last_kernel_ms",
     "bsc_kernel_ms_history",
@@ -510,6 +519,24 @@ def load():
     L.bsc_bgzf_take.argtypes = [vp, C.POINTER(vp), C.POINTER(u64)]
     L.bsc_bgzf_close.restype = i32
     L.bsc_bgzf_close.argtypes = [vp, C.POINTER(vp), C.POINTER(u64)]
+    L.bsc_bgzf_tell.restype = i32
+    L.bsc_bgzf_tell.argtypes = [vp, C.POINTER(u64), C.POINTER(u64)]
+    L.bsc_csi_scan_device.restype = i32
+    L.bsc_csi_scan_device.argtypes = [vp, i32, vp, u64, vp, u32, i32, vp, u64, vp, vp]
+    L.bsc_block_csi_kept.restype = i32
+    L.bsc_block_csi_kept.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(u64), C.POINTER(u64)]
+    L.bsc_csi_open.restype = i32
+    L.bsc_csi_open.argtypes = [vp, i32, i32, i32, C.POINTER(C.c_char_p), C.POINTER(u32), C.POINTER(vp)]
+    L.bsc_csi_open_detached.restype = i32
+    L.bsc_csi_open_detached.argtypes = [i32, i32, i32, C.POINTER(C.c_char_p), C.POINTER(u32), u64, C.POINTER(vp)]
+    L.bsc_csi_members.restype = i32
+    L.bsc_csi_members.argtypes = [vp, vp, u64]
+    L.bsc_csi_add.restype = i32
+    L.bsc_csi_add.argtypes = [vp, i32, vp, u64, u64]
+    L.bsc_csi_finish.restype = C.c_long
+    L.bsc_csi_finish.argtypes = [vp, vp, u64]
+    L.bsc_csi_close.restype = None
+    L.bsc_csi_close.argtypes = [vp]
     L.bsc_block_bcf_again.restype = i32
     L.bsc_block_bcf_again.argtypes = [vp, vp, u64, C.POINTER(u64), C.POINTER(u64)]
     L.bsc_debug_fail_summary_alloc.restype = i32

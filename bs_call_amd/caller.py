@@ -83,12 +83,69 @@ class DeviceBgzf:
     def take(self):
         return self._hand_over(self._L.bsc_bgzf_take, self._h)
 
+    def tell(self):
+        """(bytes written into the logical stream so far, members completed so far): bsc_bgzf_tell."""
+        n, m = C.c_uint64(), C.c_uint64()
+        _check(self._L.bsc_bgzf_tell(self._h, C.byref(n), C.byref(m)))
+        return int(n.value), int(m.value)
+
     def close(self):
         """The last member and the end-of-file marker; the writer is gone afterwards (a second close returns b"")."""
         if self._h is None:
             return b""
         h, self._h = self._h, None
         return self._hand_over(self._L.bsc_bgzf_close, h)
+
+
+CSI_BCF, CSI_VCF = 0, 1
+CSI_ENTRY = np.dtype([("window", "<u4"), ("n_records", "<u4"), ("u_beg", "<u8")])  # bsc_csi_entry
+
+
+class CsiIndex:
+    """A CSI index made beside a compressed file (bsc_csi_*).  writer: the DeviceBgzf that writes the file — or None with header_bytes:
+    the file is compressed elsewhere with members cut every 0xFF00 bytes, and members() hands their compressed sizes over.
+    add() the entries of a block BEFORE its stream is written; finish() after the writer's close() returns the .csi file's bytes."""
+
+    def __init__(self, writer, fmt, contigs, min_shift=14, header_bytes=0):
+        self._L = _lib.load()
+        names = (C.c_char_p * max(1, len(contigs)))(*[c[0].encode() if isinstance(c[0], str) else bytes(c[0]) for c in contigs])
+        lens = (C.c_uint32 * max(1, len(contigs)))(*[int(c[1]) for c in contigs])
+        h = C.c_void_p()
+        if writer is None:
+            _check(self._L.bsc_csi_open_detached(fmt, min_shift, len(contigs), names, lens, int(header_bytes), C.byref(h)))
+        else:
+            _check(self._L.bsc_csi_open(writer._h, fmt, min_shift, len(contigs), names, lens, C.byref(h)))
+        self._h = h
+        self.min_shift = min_shift
+
+    def add(self, tid, entries, n_bytes):
+        e = np.ascontiguousarray(entries, dtype=CSI_ENTRY)
+        _check(self._L.bsc_csi_add(self._h, int(tid), _ptr(e) if len(e) else None, len(e), int(n_bytes)))
+
+    def members(self, sizes):
+        a = np.ascontiguousarray(sizes, dtype=np.uint64)
+        _check(self._L.bsc_csi_members(self._h, _ptr(a) if len(a) else None, len(a)))
+
+    def finish(self):
+        need = self._L.bsc_csi_finish(self._h, None, 0)
+        if need < 0:
+            _check(int(need))
+        out = np.empty(need, np.uint8)
+        got = self._L.bsc_csi_finish(self._h, _ptr(out), need)
+        if got < 0:
+            _check(int(got))
+        return out[:got].tobytes()
+
+    def close(self):
+        if self._h is not None:
+            self._L.bsc_csi_close(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
 
 
 class SiteCaller:
@@ -123,6 +180,33 @@ class SiteCaller:
     def bgzf(self):
         """A DeviceBgzf writer on this context (close it before the context)."""
         return DeviceBgzf(self)
+
+    def csi_scan_device(self, fmt, d_stream, n_bytes, d_sync, n_sync, min_shift, cap_entries=None, stream=None):
+        """bsc_csi_scan_device over a stream in HBM (pointers as integers; d_sync 0 / None: one interval): (entries CSI_ENTRY[], entries
+        there are, records, error bits).  cap_entries None: room for every interval and window."""
+        import torch
+
+        if cap_entries is None:
+            cap_entries = int(n_sync if d_sync else 1) + (int(n_bytes) >> 5) + 2
+        ent = torch.zeros(max(1, cap_entries) * 2, dtype=torch.int64, device="cuda")
+        tot = torch.zeros(3, dtype=torch.int64, device="cuda")
+        st = C.c_void_p(torch.cuda.current_stream().cuda_stream) if stream is None else stream
+        _check(self._L.bsc_csi_scan_device(self._h, fmt, C.c_void_p(int(d_stream) if d_stream else None), int(n_bytes),
+                                           C.c_void_p(int(d_sync)) if d_sync else None, int(n_sync), int(min_shift), C.c_void_p(ent.data_ptr()),
+                                           int(cap_entries), C.c_void_p(tot.data_ptr()), st))
+        torch.cuda.synchronize()
+        t = [int(v) for v in tot.cpu().numpy().view(np.uint64)]
+        n = min(t[0], cap_entries)
+        return ent.cpu().numpy().view(CSI_ENTRY)[:n].copy(), t[0], t[1], t[2]
+
+    def block_csi_kept(self, min_shift=14):
+        """bsc_block_csi_kept: (entries CSI_ENTRY[], records) of the stream the last *_keep call left on the device."""
+        p, n, r = C.c_void_p(), C.c_uint64(), C.c_uint64()
+        _check(self._L.bsc_block_csi_kept(self._h, int(min_shift), C.byref(p), C.byref(n), C.byref(r)))
+        if not n.value:
+            return np.zeros(0, CSI_ENTRY), int(r.value)
+        buf = (C.c_uint8 * (16 * n.value)).from_address(p.value)
+        return np.frombuffer(buf, dtype=CSI_ENTRY).copy(), int(r.value)
 
     def bgzf_compress(self, data, pieces=None):
         """BGZF bytes of `data` (bytes-like), written whole or in the given piece lengths, with the end-of-file marker."""

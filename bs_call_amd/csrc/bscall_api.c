@@ -88,6 +88,8 @@ int bsc_dev_launch_bin_reads_multi(const void *tpl, uint32_t nr, const void *seq
                                    size_t scan_tmp_bytes, void *rd, void *counters, void *stream);
 int bsc_dev_launch_bgzf(const void *src, uint64_t n, uint32_t n_members, void *slots, void *sizes, void *offs, void *scratch, uint32_t grid,
                         void *stream); /* bgzfdev.hip */
+int bsc_dev_launch_csi_scan(int format, const void *s, uint64_t n_bytes, const void *sync, uint32_t n_sync, int min_shift, void *cnt, void *off,
+                            void *scan_tmp, size_t scan_tmp_bytes, void *entries, uint64_t cap, void *totals, int num_cus, void *stream); /* csidev.hip */
 int bsc_dev_launch_bgzf_gather(const void *slots, const void *offs, const void *sizes, uint32_t n_members, void *out, void *stream);
 int bsc_dev_launch_dbsnp_flags(const bsc_dbsnp_flat *f, uint32_t x0, uint32_t n, void *d_out, int num_cus, void *stream); /* dbsnpdev.hip */
 int bsc_dev_launch_dbsnp_names(const bsc_dbsnp_flat *f, uint32_t e0, uint32_t n_names, void *d_pos, void *d_off, void *d_bytes, int num_cus,
@@ -165,6 +167,15 @@ struct bsc_context {
   size_t cap_btb, cap_bto, cap_bscn, cap_bnm, cap_bcf, cap_btot;
   void *d_vtl; /* the text encoder (vcftextdev.hip): a line's length per record / position, between its two passes */
   size_t cap_vtl;
+  /* the CSI scan (csidev.hip): runs per interval, their prefix sum, scan scratch, the entries and {entries, records, error bits} of the
+   * follow-up call bsc_block_csi_kept, its host copy; and what the last encoder call left in d_bto: for which stream, how many tiles, text */
+  void *d_cscn, *d_csof, *d_cstm, *d_csen, *d_cstot;
+  size_t cap_cscn, cap_csof, cap_cstm, cap_csen, cap_cstot;
+  bsc_csi_entry *h_csen;
+  size_t cap_hcsen;
+  const void *bto_for;
+  uint32_t bto_tiles;
+  int bto_text;
   struct { /* streams handed to the caller (bsc_bcf_stream_detach) come back here (bsc_detached_free) and are taken again by the next block:
             * no hipMalloc / hipFree — a device-wide wait — in the steady state of a run that writes behind the calling */
     void *p[4];
@@ -550,6 +561,12 @@ int bsc_destroy(bsc_context *ctx) {
   hipFree(ctx->d_bcf);
   hipFree(ctx->d_btot);
   hipFree(ctx->d_vtl);
+  hipFree(ctx->d_cscn);
+  hipFree(ctx->d_csof);
+  hipFree(ctx->d_cstm);
+  hipFree(ctx->d_csen);
+  hipFree(ctx->d_cstot);
+  free(ctx->h_csen);
   hipFree(ctx->d_emit);
   for (int i = 0; i < 2; i++)
     if (ctx->ev_raw[i]) hipEventDestroy(ctx->ev_raw[i]);
@@ -2057,6 +2074,9 @@ static int bsc_bcf_encode(bsc_context *ctx, const char *who, const void *d_recs,
   const int e = bsc_dev_launch_bcf(d_recs, d_core, d_aux, d_n_recs, max_recs, rid, ids, plan.d_pos, plan.d_off, plan.d_nb, plan.n_names, ctx->d_btb,
                                    ctx->d_bto, ctx->d_bscn, plan.scan_bytes, d_out, out_cap, d_totals, ctx->num_cus, stream, d_recs ? NULL : ctx->emit_hint);
   if (e) return bsc_fail(BSC_ERR_HIP, "BCF encoder launch failed: %s", hipGetErrorString((hipError_t)e));
+  ctx->bto_for = d_out; /* d_bto: this stream's tile offsets, until the next encoder call (bsc_block_csi_kept) */
+  ctx->bto_tiles = plan.n_tiles;
+  ctx->bto_text = 0;
   return BSC_OK;
 }
 
@@ -2109,6 +2129,9 @@ static int bsc_vcf_text_encode(bsc_context *ctx, const char *who, const void *d_
   const int e = bsc_dev_launch_vcf_text(d_recs, d_core, d_aux, d_n_recs, max_recs, contig, contig_len, plan.d_pos, plan.d_off, plan.d_nb, plan.n_names,
                                         ctx->d_btb, ctx->d_bto, ctx->d_vtl, ctx->d_bscn, plan.scan_bytes, d_out, out_cap, d_totals, ctx->num_cus, stream);
   if (e) return bsc_fail(BSC_ERR_HIP, "VCF text encoder launch failed: %s", hipGetErrorString((hipError_t)e));
+  ctx->bto_for = d_out;
+  ctx->bto_tiles = plan.n_tiles;
+  ctx->bto_text = 1;
   return BSC_OK;
 }
 
@@ -3464,6 +3487,10 @@ struct bsc_bgzf {
   void *d_pend;
   size_t cap_pend;
   uint64_t n_pend;
+  uint64_t n_logical; /* bytes written into the logical stream so far, the carry included */
+  uint64_t *msize;    /* the compressed size of every member completed so far, in stream order (bsc_csi_*) */
+  uint64_t n_msize, cap_msize;
+  struct bsc_csi *csi; /* the index that is being made beside this file: it inherits msize at bsc_bgzf_close */
   struct bsc_bgzf *next_open;
 };
 static const uint8_t bsc_bgzf_eof[28] = {0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 0x42, 0x43, 2, 0, 0x1b, 0, 3, 0, 0, 0, 0, 0, 0, 0, 0, 0};
@@ -3477,6 +3504,8 @@ static int bsc_bgzf_is_open(const bsc_bgzf *z) {
   pthread_mutex_unlock(&bsc_bgzf_mu);
   return found;
 }
+
+static void bsc_csi_writer_closed(bsc_bgzf *z, int rc);
 
 static void bsc_pool_init(bsc_context *ctx) {
   if (!ctx->pool_mu_made) {
@@ -3565,8 +3594,17 @@ static int bsc_bgzf_compress(bsc_bgzf *z, const uint8_t *src, uint64_t n) {
     }
     HIP_TRY((hipError_t)bsc_dev_launch_bgzf(src + at, bytes, nb, z->d_slots, z->d_sizes, z->d_offs, z->d_scratch, grid, ctx->stream));
     uint64_t total = 0;
+    if (z->n_msize + nb > z->cap_msize) {
+      const uint64_t cap = (z->n_msize + nb) * 2 + 64;
+      uint64_t *q = realloc(z->msize, (size_t)cap * 8);
+      if (!q) return bsc_fail(BSC_ERR_NOMEM, "bsc_bgzf: out of host memory");
+      z->msize = q;
+      z->cap_msize = cap;
+    }
     HIP_TRY(hipMemcpyAsync(&total, (uint64_t *)z->d_offs + nb, 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(z->msize + z->n_msize, z->d_sizes, (size_t)nb * 8, hipMemcpyDeviceToHost, ctx->stream)); /* the members' sizes, beside their sum */
     HIP_TRY(hipStreamSynchronize(ctx->stream));
+    z->n_msize += nb;
     if (total > (uint64_t)nb * BGZF_SLOT) return bsc_fail(BSC_ERR_HIP, "bsc_bgzf: the compressor reported %llu bytes for %u members", (unsigned long long)total, nb);
     const int rc = bsc_bgzf_reserve(z, (size_t)(z->n_pend + total));
     if (rc) return rc;
@@ -3578,6 +3616,7 @@ static int bsc_bgzf_compress(bsc_bgzf *z, const uint8_t *src, uint64_t n) {
 
 static int bsc_bgzf_feed(bsc_bgzf *z, const uint8_t *src, uint64_t n) { /* device bytes into the logical stream */
   bsc_context *ctx = z->ctx;
+  z->n_logical += n;
   if (z->carry_n) {
     const uint64_t k = n < BGZF_MEMBER - z->carry_n ? n : BGZF_MEMBER - z->carry_n;
     if (k) HIP_TRY(hipMemcpyAsync((uint8_t *)z->d_carry + z->carry_n, src, (size_t)k, hipMemcpyDeviceToDevice, ctx->stream));
@@ -3698,6 +3737,7 @@ int bsc_bgzf_close(bsc_bgzf *z, void **d_out, uint64_t *n_bytes) {
     else z->n_pend += sizeof bsc_bgzf_eof;
   }
   if (!rc) rc = bsc_bgzf_hand_over(z, d_out, n_bytes);
+  bsc_csi_writer_closed(z, rc);
   pthread_mutex_lock(&bsc_bgzf_mu);
   for (struct bsc_bgzf **q = &bsc_bgzf_open_list; *q; q = &(*q)->next_open)
     if (*q == z) {
@@ -3713,6 +3753,388 @@ int bsc_bgzf_close(bsc_bgzf *z, void **d_out, uint64_t *n_bytes) {
   hipFree(z->d_offs);
   hipFree(z->d_scratch);
   hipFree(z->d_pend);
+  free(z->msize);
   free(z);
   return rc;
+}
+
+int bsc_bgzf_tell(const bsc_bgzf *z, uint64_t *n_logical, uint64_t *n_members) {
+  if (!bsc_bgzf_is_open(z)) return bsc_fail(BSC_ERR_ARG, "bsc_bgzf_tell: not an open BGZF writer (NULL, or closed)");
+  if (n_logical) *n_logical = z->n_logical;
+  if (n_members) *n_members = z->n_msize;
+  return BSC_OK;
+}
+
+/* ---- the CSI index of a file the BGZF writer writes (csidev.hip makes a block's entries; the rest is arithmetic on offsets) --------------- */
+int bsc_csi_scan_device(bsc_context *ctx, int format, const void *d_stream, uint64_t n_bytes, const void *d_sync, uint32_t n_sync, int min_shift,
+                        void *d_entries, uint64_t cap_entries, void *d_totals, void *stream) {
+  if (!ctx || !d_totals || (!d_stream && n_bytes) || (!d_entries && cap_entries))
+    return bsc_fail(BSC_ERR_ARG, "bsc_csi_scan_device: NULL argument");
+  if (format != BSC_CSI_BCF && format != BSC_CSI_VCF) return bsc_fail(BSC_ERR_ARG, "bsc_csi_scan_device: format %d is neither BSC_CSI_BCF nor BSC_CSI_VCF", format);
+  if (min_shift < 0 || min_shift > 31) return bsc_fail(BSC_ERR_ARG, "bsc_csi_scan_device: min_shift %d is not 0 .. 31", min_shift);
+  if (!d_sync) n_sync = 1;
+  if (n_sync >= 0x7fffffffu) return bsc_fail(BSC_ERR_ARG, "bsc_csi_scan_device: too many intervals");
+  if (!n_sync && n_bytes) return bsc_fail(BSC_ERR_ARG, "bsc_csi_scan_device: no interval for %llu bytes", (unsigned long long)n_bytes);
+  BSC_ENTER(ctx);
+  hipStream_t s = (hipStream_t)stream;
+  HIP_TRY(hipMemsetAsync(d_totals, 0, 3 * sizeof(unsigned long long), s));
+  if (!n_sync) return BSC_OK;
+  size_t scan_bytes = 0;
+  int rc;
+  if (bsc_dev_scan_tmp_bytes_u64(n_sync + 1u, &scan_bytes)) return bsc_fail(BSC_ERR_HIP, "bsc_csi_scan_device: scan size query failed");
+  if ((rc = bsc_reserve(&ctx->d_cscn, &ctx->cap_cscn, ((size_t)n_sync + 1u) * 8u))) return rc;
+  if ((rc = bsc_reserve(&ctx->d_csof, &ctx->cap_csof, ((size_t)n_sync + 1u) * 8u))) return rc;
+  if ((rc = bsc_reserve(&ctx->d_cstm, &ctx->cap_cstm, scan_bytes ? scan_bytes : 1))) return rc;
+  const int e = bsc_dev_launch_csi_scan(format, d_stream, n_bytes, d_sync, n_sync, min_shift, ctx->d_cscn, ctx->d_csof, ctx->d_cstm, scan_bytes, d_entries,
+                                        cap_entries, d_totals, ctx->num_cus, stream);
+  if (e) return bsc_fail(BSC_ERR_HIP, "CSI scan launch failed: %s", hipGetErrorString((hipError_t)e));
+  return BSC_OK;
+}
+
+int bsc_block_csi_kept(bsc_context *ctx, int min_shift, const bsc_csi_entry **entries, uint64_t *n_entries, uint64_t *n_records) {
+  if (!ctx || !entries || !n_entries) return bsc_fail(BSC_ERR_ARG, "bsc_block_csi_kept: NULL argument");
+  *entries = NULL;
+  *n_entries = 0;
+  if (n_records) *n_records = 0;
+  if (!ctx->bcf_keep || ctx->rec_pending || !ctx->d_bcf || ctx->bto_for != ctx->d_bcf)
+    return bsc_fail(BSC_ERR_ARG, "bsc_block_csi_kept: the last call left no stream on the device");
+  if (min_shift < 0 || min_shift > 31) return bsc_fail(BSC_ERR_ARG, "bsc_block_csi_kept: min_shift %d is not 0 .. 31", min_shift);
+  if (!ctx->bcf_bytes) return BSC_OK;
+  BSC_ENTER(ctx);
+  /* every interval that holds a record gives one entry, and one more wherever a window boundary lies inside one: the block spans 64
+   * positions a tile */
+  const uint32_t n_sync = ctx->bto_tiles;
+  const uint64_t cap = (uint64_t)n_sync + (((uint64_t)n_sync * 64u) >> min_shift) + 2u;
+  int rc;
+  if ((rc = bsc_reserve(&ctx->d_csen, &ctx->cap_csen, (size_t)cap * sizeof(bsc_csi_entry)))) return rc;
+  if ((rc = bsc_reserve(&ctx->d_cstot, &ctx->cap_cstot, 3 * sizeof(unsigned long long)))) return rc;
+  if ((rc = bsc_csi_scan_device(ctx, ctx->bto_text ? BSC_CSI_VCF : BSC_CSI_BCF, ctx->d_bcf, ctx->bcf_bytes, ctx->d_bto, n_sync, min_shift, ctx->d_csen, cap,
+                                ctx->d_cstot, ctx->stream)))
+    return rc;
+  unsigned long long tot[3] = {0, 0, 0};
+  HIP_TRY(hipMemcpyAsync(tot, ctx->d_cstot, sizeof tot, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  if (tot[2]) return bsc_fail(BSC_ERR_ARG, "bsc_block_csi_kept: the kept stream is not whole records in position order (error bits %llu)", tot[2]);
+  if (tot[0] > cap) return bsc_fail(BSC_ERR_RANGE, "bsc_block_csi_kept: %llu entries, room for %llu", tot[0], (unsigned long long)cap);
+  if (tot[0] > ctx->cap_hcsen) {
+    free(ctx->h_csen);
+    ctx->cap_hcsen = 0;
+    ctx->h_csen = malloc((size_t)(tot[0] + tot[0] / 4) * sizeof(bsc_csi_entry));
+    if (!ctx->h_csen) return bsc_fail(BSC_ERR_NOMEM, "bsc_block_csi_kept: out of host memory");
+    ctx->cap_hcsen = (size_t)(tot[0] + tot[0] / 4);
+  }
+  if (tot[0]) {
+    HIP_TRY(hipMemcpyAsync(ctx->h_csen, ctx->d_csen, (size_t)tot[0] * sizeof(bsc_csi_entry), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+  }
+  *entries = ctx->h_csen;
+  *n_entries = tot[0];
+  if (n_records) *n_records = tot[1];
+  return BSC_OK;
+}
+
+typedef struct { /* a leaf bin: the records of one window of one contig, [u_beg, u_end) of the logical stream */
+  uint32_t window;
+  uint64_t n_records, u_beg, u_end;
+} csi_leaf;
+typedef struct {
+  csi_leaf *b;
+  uint64_t n, cap;
+} csi_ref;
+struct bsc_csi {
+  bsc_bgzf *z; /* the writer, while it is open */
+  int detached, have_members, format, min_shift, depth, n_refs;
+  char *names; /* NUL-terminated, one after the other */
+  size_t l_names;
+  csi_ref *ref;
+  int32_t last_tid;
+  uint64_t logical; /* detached: the stream's length so far; with a writer: its length at close */
+  uint64_t *msize, n_msize;
+  struct bsc_csi *next_open;
+};
+static pthread_mutex_t bsc_csi_mu = PTHREAD_MUTEX_INITIALIZER;
+static struct bsc_csi *bsc_csi_open_list;
+static int bsc_csi_is_open(const bsc_csi *ix) {
+  int found = 0;
+  pthread_mutex_lock(&bsc_csi_mu);
+  for (const struct bsc_csi *q = bsc_csi_open_list; q && !found; q = q->next_open) found = q == ix;
+  pthread_mutex_unlock(&bsc_csi_mu);
+  return found;
+}
+
+/* bsc_bgzf_close: the index beside the file takes the members' sizes over (a failed close leaves it without: bsc_csi_finish refuses) */
+static void bsc_csi_writer_closed(bsc_bgzf *z, int rc) {
+  bsc_csi *ix = z->csi;
+  if (!ix) return;
+  ix->z = NULL;
+  z->csi = NULL;
+  if (rc) return;
+  ix->msize = z->msize;
+  ix->n_msize = z->n_msize;
+  ix->logical = z->n_logical;
+  ix->have_members = 1;
+  z->msize = NULL;
+}
+
+static int bsc_csi_make(const char *who, int format, int min_shift, int n_refs, const char *const *names, const uint32_t *lens, bsc_csi **out) {
+  if (!out) return bsc_fail(BSC_ERR_ARG, "%s: out is NULL", who);
+  *out = NULL;
+  if (format != BSC_CSI_BCF && format != BSC_CSI_VCF) return bsc_fail(BSC_ERR_ARG, "%s: format %d is neither BSC_CSI_BCF nor BSC_CSI_VCF", who, format);
+  if (min_shift < 1 || min_shift > 31) return bsc_fail(BSC_ERR_ARG, "%s: min_shift %d is not 1 .. 31", who, min_shift);
+  if (n_refs < 0 || (n_refs && (!names || !lens))) return bsc_fail(BSC_ERR_ARG, "%s: NULL argument", who);
+  uint64_t longest = 0;
+  size_t l_names = 0;
+  for (int i = 0; i < n_refs; i++) {
+    if (!names[i]) return bsc_fail(BSC_ERR_ARG, "%s: contig %d has no name", who, i);
+    l_names += strlen(names[i]) + 1;
+    if (lens[i] > longest) longest = lens[i];
+  }
+  bsc_csi *ix = calloc(1, sizeof *ix);
+  if (ix) ix->names = malloc(l_names ? l_names : 1);
+  if (ix && ix->names) ix->ref = calloc((size_t)n_refs + 1, sizeof *ix->ref);
+  if (!ix || !ix->names || !ix->ref) {
+    if (ix) free(ix->names);
+    free(ix);
+    return bsc_fail(BSC_ERR_NOMEM, "%s: out of host memory", who);
+  }
+  size_t at = 0;
+  for (int i = 0; i < n_refs; i++) {
+    const size_t l = strlen(names[i]) + 1;
+    memcpy(ix->names + at, names[i], l);
+    at += l;
+  }
+  ix->l_names = l_names;
+  ix->format = format;
+  ix->min_shift = min_shift;
+  ix->n_refs = n_refs;
+  ix->last_tid = -1;
+  int depth = 0; /* htslib's rule for BCF: the levels that cover the longest contig + 256 */
+  for (uint64_t s = (uint64_t)1 << min_shift; s < longest + 256u; s <<= 3) depth++;
+  ix->depth = depth;
+  pthread_mutex_lock(&bsc_csi_mu);
+  ix->next_open = bsc_csi_open_list;
+  bsc_csi_open_list = ix;
+  pthread_mutex_unlock(&bsc_csi_mu);
+  *out = ix;
+  return BSC_OK;
+}
+
+int bsc_csi_open(bsc_bgzf *z, int format, int min_shift, int n_refs, const char *const *names, const uint32_t *lens, bsc_csi **out) {
+  if (out) *out = NULL;
+  if (!bsc_bgzf_is_open(z)) return bsc_fail(BSC_ERR_ARG, "bsc_csi_open: not an open BGZF writer (NULL, or closed)");
+  if (z->csi) return bsc_fail(BSC_ERR_ARG, "bsc_csi_open: the writer has an index already");
+  const int rc = bsc_csi_make("bsc_csi_open", format, min_shift, n_refs, names, lens, out);
+  if (rc) return rc;
+  (*out)->z = z;
+  z->csi = *out;
+  return BSC_OK;
+}
+
+int bsc_csi_open_detached(int format, int min_shift, int n_refs, const char *const *names, const uint32_t *lens, uint64_t header_bytes, bsc_csi **out) {
+  const int rc = bsc_csi_make("bsc_csi_open_detached", format, min_shift, n_refs, names, lens, out);
+  if (rc) return rc;
+  (*out)->detached = 1;
+  (*out)->logical = header_bytes;
+  return BSC_OK;
+}
+
+int bsc_csi_members(bsc_csi *ix, const uint64_t *sizes, uint64_t n_members) {
+  if (!bsc_csi_is_open(ix)) return bsc_fail(BSC_ERR_ARG, "bsc_csi_members: not an open index (NULL, or closed)");
+  if (!ix->detached || ix->have_members) return bsc_fail(BSC_ERR_ARG, "bsc_csi_members: the members' sizes come from the index's writer, or are here already");
+  if (!sizes && n_members) return bsc_fail(BSC_ERR_ARG, "bsc_csi_members: sizes is NULL");
+  if (n_members != (ix->logical + BGZF_MEMBER - 1) / BGZF_MEMBER)
+    return bsc_fail(BSC_ERR_ARG, "bsc_csi_members: %llu members, the stream's %llu bytes make %llu", (unsigned long long)n_members,
+                    (unsigned long long)ix->logical, (unsigned long long)((ix->logical + BGZF_MEMBER - 1) / BGZF_MEMBER));
+  for (uint64_t k = 0; k < n_members; k++)
+    if (sizes[k] < 28 || sizes[k] > BGZF_SLOT) return bsc_fail(BSC_ERR_ARG, "bsc_csi_members: member %llu has %llu bytes", (unsigned long long)k, (unsigned long long)sizes[k]);
+  ix->msize = malloc((size_t)(n_members ? n_members : 1) * 8);
+  if (!ix->msize) return bsc_fail(BSC_ERR_NOMEM, "bsc_csi_members: out of host memory");
+  if (n_members) memcpy(ix->msize, sizes, (size_t)n_members * 8);
+  ix->n_msize = n_members;
+  ix->have_members = 1;
+  return BSC_OK;
+}
+
+int bsc_csi_add(bsc_csi *ix, int32_t tid, const bsc_csi_entry *entries, uint64_t n, uint64_t n_bytes) {
+  if (!bsc_csi_is_open(ix)) return bsc_fail(BSC_ERR_ARG, "bsc_csi_add: not an open index (NULL, or closed)");
+  if (ix->have_members || (!ix->detached && !ix->z)) return bsc_fail(BSC_ERR_ARG, "bsc_csi_add: the index's writer is closed");
+  if (!entries && n) return bsc_fail(BSC_ERR_ARG, "bsc_csi_add: entries is NULL");
+  if (tid < 0 || tid >= ix->n_refs) return bsc_fail(BSC_ERR_ARG, "bsc_csi_add: contig %d of %d", tid, ix->n_refs);
+  if (tid < ix->last_tid) return bsc_fail(BSC_ERR_ARG, "bsc_csi_add: entries out of order: contig %d behind contig %d", tid, ix->last_tid);
+  if ((n == 0) != (n_bytes == 0)) return bsc_fail(BSC_ERR_ARG, "bsc_csi_add: %llu entries for a stream of %llu bytes", (unsigned long long)n, (unsigned long long)n_bytes);
+  csi_ref *r = &ix->ref[tid];
+  const uint64_t n_win = ix->depth * 3 >= 32 ? (uint64_t)1 << 32 : (uint64_t)1 << (3 * ix->depth);
+  for (uint64_t i = 0; i < n; i++) { /* everything is checked before anything is added */
+    const bsc_csi_entry *e = &entries[i];
+    const uint64_t prev_w = i ? entries[i - 1].window : (r->n ? r->b[r->n - 1].window : 0);
+    if (!e->n_records) return bsc_fail(BSC_ERR_ARG, "bsc_csi_add: entry %llu has no records", (unsigned long long)i);
+    if (e->window < prev_w) return bsc_fail(BSC_ERR_ARG, "bsc_csi_add: entries out of order: window %u behind window %llu", e->window, (unsigned long long)prev_w);
+    if (e->window >= n_win) return bsc_fail(BSC_ERR_ARG, "bsc_csi_add: window %u lies beyond the contigs' %d levels", e->window, ix->depth);
+    if (i ? e->u_beg <= entries[i - 1].u_beg : e->u_beg != 0)
+      return bsc_fail(BSC_ERR_ARG, "bsc_csi_add: entries out of order: entry %llu begins at %llu", (unsigned long long)i, (unsigned long long)e->u_beg);
+    if (e->u_beg >= n_bytes) return bsc_fail(BSC_ERR_ARG, "bsc_csi_add: entry %llu begins at %llu of %llu bytes", (unsigned long long)i, (unsigned long long)e->u_beg, (unsigned long long)n_bytes);
+  }
+  if (r->n + n > r->cap) {
+    const uint64_t cap = (r->n + n) * 2 + 16;
+    csi_leaf *q = realloc(r->b, (size_t)cap * sizeof *q);
+    if (!q) return bsc_fail(BSC_ERR_NOMEM, "bsc_csi_add: out of host memory");
+    r->b = q;
+    r->cap = cap;
+  }
+  const uint64_t base = ix->detached ? ix->logical : ix->z->n_logical;
+  for (uint64_t i = 0; i < n; i++) {
+    const uint64_t u_end = base + (i + 1 < n ? entries[i + 1].u_beg : n_bytes);
+    if (r->n && r->b[r->n - 1].window == entries[i].window) { /* the window goes on: across an interval of the scan, or across blocks */
+      r->b[r->n - 1].n_records += entries[i].n_records;
+      r->b[r->n - 1].u_end = u_end;
+    } else {
+      const csi_leaf l = {entries[i].window, entries[i].n_records, base + entries[i].u_beg, u_end};
+      r->b[r->n++] = l;
+    }
+  }
+  ix->last_tid = tid;
+  if (ix->detached) ix->logical += n_bytes;
+  return BSC_OK;
+}
+
+typedef struct {
+  uint8_t *p;
+  size_t n, cap;
+  int bad;
+} csi_buf;
+static void csi_put(csi_buf *b, const void *src, size_t n) {
+  if (b->bad) return;
+  if (b->n + n > b->cap) {
+    const size_t cap = (b->n + n) * 2 + 256;
+    uint8_t *q = realloc(b->p, cap);
+    if (!q) {
+      b->bad = 1;
+      return;
+    }
+    b->p = q;
+    b->cap = cap;
+  }
+  memcpy(b->p + b->n, src, n);
+  b->n += n;
+}
+static void csi_put32(csi_buf *b, uint32_t v) {
+  const uint8_t x[4] = {(uint8_t)v, (uint8_t)(v >> 8), (uint8_t)(v >> 16), (uint8_t)(v >> 24)};
+  csi_put(b, x, 4);
+}
+static void csi_put64(csi_buf *b, uint64_t v) {
+  csi_put32(b, (uint32_t)v);
+  csi_put32(b, (uint32_t)(v >> 32));
+}
+static uint32_t csi_crc32(const uint8_t *p, size_t n) { /* the gzip CRC, a byte at a time: an index is kilobytes */
+  static uint32_t tab[256];
+  static int made;
+  if (!made) {
+    for (uint32_t i = 0; i < 256; i++) {
+      uint32_t c = i;
+      for (int k = 0; k < 8; k++) c = (c & 1u) ? (c >> 1) ^ 0xEDB88320u : c >> 1;
+      tab[i] = c;
+    }
+    __atomic_store_n(&made, 1, __ATOMIC_RELEASE);
+  }
+  uint32_t c = 0xFFFFFFFFu;
+  for (size_t i = 0; i < n; i++) c = tab[(c ^ p[i]) & 0xffu] ^ (c >> 8);
+  return c ^ 0xFFFFFFFFu;
+}
+
+long bsc_csi_finish(bsc_csi *ix, void *buf, uint64_t cap) {
+  if (!bsc_csi_is_open(ix)) return bsc_fail(BSC_ERR_ARG, "bsc_csi_finish: not an open index (NULL, or closed)");
+  if (!ix->have_members) return bsc_fail(BSC_ERR_ARG, "bsc_csi_finish: the file is not closed yet (bsc_bgzf_close, or bsc_csi_members, comes first)");
+  if (!buf && cap) return bsc_fail(BSC_ERR_ARG, "bsc_csi_finish: buf is NULL");
+  if (ix->n_msize != (ix->logical + BGZF_MEMBER - 1) / BGZF_MEMBER)
+    return bsc_fail(BSC_ERR_ARG, "bsc_csi_finish: %llu members for a stream of %llu bytes", (unsigned long long)ix->n_msize, (unsigned long long)ix->logical);
+  uint64_t *coff = malloc((size_t)(ix->n_msize + 1) * 8);
+  if (!coff) return bsc_fail(BSC_ERR_NOMEM, "bsc_csi_finish: out of host memory");
+  coff[0] = 0;
+  for (uint64_t k = 0; k < ix->n_msize; k++) coff[k + 1] = coff[k] + ix->msize[k];
+#define VOFF(u) (coff[(u) / BGZF_MEMBER] << 16 | (u) % BGZF_MEMBER)
+  csi_buf b = {NULL, 0, 0, 0};
+  csi_put(&b, "CSI\1", 4);
+  csi_put32(&b, (uint32_t)ix->min_shift);
+  csi_put32(&b, (uint32_t)ix->depth);
+  if (ix->format == BSC_CSI_VCF) { /* the tabix block */
+    csi_put32(&b, (uint32_t)(28 + ix->l_names));
+    const uint32_t tbx[7] = {2, 1, 2, 0, '#', 0, (uint32_t)ix->l_names};
+    for (int k = 0; k < 7; k++) csi_put32(&b, tbx[k]);
+    csi_put(&b, ix->names, ix->l_names);
+  } else csi_put32(&b, 0);
+  csi_put32(&b, (uint32_t)ix->n_refs);
+  const uint64_t leaf0 = (((uint64_t)1 << (3 * ix->depth)) - 1) / 7, pseudo = (((uint64_t)1 << (3 * (ix->depth + 1))) - 1) / 7 + 1;
+  int rc = BSC_OK;
+  for (int t = 0; t < ix->n_refs && !rc; t++) {
+    const csi_ref *r = &ix->ref[t];
+    csi_put32(&b, r->n ? (uint32_t)(r->n + 1) : 0);
+    uint64_t recs = 0;
+    for (uint64_t k = 0; k < r->n; k++) {
+      const csi_leaf *l = &r->b[k];
+      if (l->u_end > ix->logical || l->u_beg >= l->u_end) {
+        rc = bsc_fail(BSC_ERR_ARG, "bsc_csi_finish: a block of %llu .. %llu was added, the file's stream has %llu bytes", (unsigned long long)l->u_beg,
+                      (unsigned long long)l->u_end, (unsigned long long)ix->logical);
+        break;
+      }
+      csi_put32(&b, (uint32_t)(leaf0 + l->window));
+      csi_put64(&b, VOFF(l->u_beg));
+      csi_put32(&b, 1);
+      csi_put64(&b, VOFF(l->u_beg));
+      csi_put64(&b, VOFF(l->u_end));
+      recs += l->n_records;
+    }
+    if (r->n && !rc) {
+      csi_put32(&b, (uint32_t)pseudo);
+      csi_put64(&b, 0);
+      csi_put32(&b, 2);
+      csi_put64(&b, VOFF(r->b[0].u_beg));
+      csi_put64(&b, VOFF(r->b[r->n - 1].u_end));
+      csi_put64(&b, recs);
+      csi_put64(&b, 0);
+    }
+  }
+#undef VOFF
+  csi_put64(&b, 0); /* n_no_coor */
+  free(coff);
+  if (!rc && b.bad) rc = bsc_fail(BSC_ERR_NOMEM, "bsc_csi_finish: out of host memory");
+  if (rc) {
+    free(b.p);
+    return rc;
+  }
+  /* the file: stored members of 0xFF00 bytes, the end-of-file marker */
+  const uint64_t nm = (b.n + BGZF_MEMBER - 1) / BGZF_MEMBER, need = b.n + nm * 31 + sizeof bsc_bgzf_eof;
+  if (buf && cap >= need) {
+    uint8_t *o = buf;
+    for (uint64_t k = 0; k < nm; k++) {
+      const uint8_t *src = b.p + k * BGZF_MEMBER;
+      const uint32_t len = (uint32_t)(b.n - k * BGZF_MEMBER < BGZF_MEMBER ? b.n - k * BGZF_MEMBER : BGZF_MEMBER), size = 31 + len, crc = csi_crc32(src, len);
+      const uint8_t h[23] = {0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 'B', 'C', 2, 0, (uint8_t)(size - 1), (uint8_t)((size - 1) >> 8), 1,
+                             (uint8_t)len, (uint8_t)(len >> 8), (uint8_t)~len, (uint8_t)(~len >> 8)};
+      memcpy(o, h, 23);
+      memcpy(o + 23, src, len);
+      const uint8_t tl[8] = {(uint8_t)crc, (uint8_t)(crc >> 8), (uint8_t)(crc >> 16), (uint8_t)(crc >> 24), (uint8_t)len, (uint8_t)(len >> 8), 0, 0};
+      memcpy(o + 23 + len, tl, 8);
+      o += size;
+    }
+    memcpy(o, bsc_bgzf_eof, sizeof bsc_bgzf_eof);
+  }
+  free(b.p);
+  return (long)need;
+}
+
+void bsc_csi_close(bsc_csi *ix) {
+  if (!bsc_csi_is_open(ix)) return;
+  pthread_mutex_lock(&bsc_csi_mu);
+  for (struct bsc_csi **q = &bsc_csi_open_list; *q; q = &(*q)->next_open)
+    if (*q == ix) {
+      *q = ix->next_open;
+      break;
+    }
+  pthread_mutex_unlock(&bsc_csi_mu);
+  if (ix->z && bsc_bgzf_is_open(ix->z)) ix->z->csi = NULL;
+  for (int t = 0; t < ix->n_refs; t++) free(ix->ref[t].b);
+  free(ix->ref);
+  free(ix->names);
+  free(ix->msize);
+  free(ix);
 }

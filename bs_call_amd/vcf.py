@@ -219,3 +219,197 @@ def write_vcf_blobs(path, header: str, blobs, compressed=False):
         if pend:
             f.write(_bgzf_block(bytes(pend)))
         f.write(BGZF_EOF)
+
+
+# ---- region queries through a CSI index (CSIv1): what bam2bcf --index / bsc_csi_* write beside a compressed file --------------------
+def read_csi(path):
+    """A .csi file parsed: {"min_shift", "depth", "aux" (bytes), "names" (the tabix block's, [] for BCF), "refs": [{bin: (loffset,
+    [(beg, end), ...])}, ...], "n_no_coor"}.  Virtual offsets are integers (file offset of the member << 16 | offset inside it)."""
+    import gzip
+    import struct
+
+    with gzip.open(path, "rb") as f:
+        b = f.read()
+    if b[:4] != b"CSI\x01":
+        raise ValueError("%s: not a CSI index" % path)
+    min_shift, depth, l_aux = struct.unpack_from("<iii", b, 4)
+    aux = b[16 : 16 + l_aux]
+    at = 16 + l_aux
+    names = []
+    if l_aux >= 28:
+        l_nm = struct.unpack_from("<i", aux, 24)[0]
+        names = [n.decode() for n in aux[28 : 28 + l_nm].split(b"\0")[:-1]]
+    (n_ref,) = struct.unpack_from("<i", b, at)
+    at += 4
+    refs = []
+    for _ in range(n_ref):
+        (n_bin,) = struct.unpack_from("<i", b, at)
+        at += 4
+        bins = {}
+        for _ in range(n_bin):
+            bin_, loff, n_chunk = struct.unpack_from("<IQi", b, at)
+            at += 16
+            bins[bin_] = (loff, [struct.unpack_from("<QQ", b, at + 16 * k) for k in range(n_chunk)])
+            at += 16 * n_chunk
+        refs.append(bins)
+    n_no_coor = struct.unpack_from("<Q", b, at)[0] if at + 8 <= len(b) else 0
+    return {"min_shift": min_shift, "depth": depth, "aux": aux, "names": names, "refs": refs, "n_no_coor": n_no_coor}
+
+
+def csi_reg2bins(beg, end, min_shift, depth):
+    """The bins of every level that overlap [beg, end) (0-based, half open): the CSI specification's reg2bins."""
+    bins = []
+    if beg >= end:
+        return bins
+    end -= 1
+    s, t = min_shift + 3 * depth, 0
+    for level in range(depth + 1):
+        bins.extend(range(t + (beg >> s), t + (end >> s) + 1))
+        s -= 3
+        t += 1 << (3 * level)
+    return bins
+
+
+def csi_chunks(index, tid, beg, end):
+    """The chunks [(vbeg, vend), ...] of the file that may hold records of contig tid in [beg, end): the bins of reg2bins over all levels,
+    without the chunks that end at or before the loffset of the first existing bin — found as htslib finds it: the leaf of beg, then its
+    previous siblings, then the parents —, sorted, adjacent ones merged."""
+    if tid < 0 or tid >= len(index["refs"]) or beg >= end:
+        return []
+    bins = index["refs"][tid]
+    min_shift, depth = index["min_shift"], index["depth"]
+    pseudo = ((1 << (3 * (depth + 1))) - 1) // 7 + 1
+    b = ((1 << (3 * depth)) - 1) // 7 + (beg >> min_shift)
+    min_off = 0
+    while True:
+        if b in bins and b != pseudo:
+            min_off = bins[b][0]
+            break
+        if b == 0:
+            break
+        parent = (b - 1) >> 3
+        b = b - 1 if b > (parent << 3) + 1 else parent
+    got = []
+    for k in csi_reg2bins(beg, end, min_shift, depth):
+        if k in bins and k != pseudo:
+            got += [c for c in bins[k][1] if c[1] > min_off]
+    got.sort()
+    out = []
+    for c in got:
+        if out and c[0] <= out[-1][1]:
+            out[-1] = (out[-1][0], max(out[-1][1], c[1]))
+        else:
+            out.append((c[0], c[1]))
+    return out
+
+
+class _BgzfReader:
+    """Members of a BGZF file read at their file offsets; a position is a virtual offset, kept normalised: the end of a member is the
+    beginning of the next."""
+
+    def __init__(self, f):
+        self.f = f
+        self.coff, self.data, self.bsize, self.uoff = -1, b"", 0, 0
+
+    def _load(self, coff):
+        import struct
+        import zlib
+
+        self.f.seek(coff)
+        h = self.f.read(18)
+        if len(h) < 18:
+            self.coff, self.data, self.bsize = coff, b"", 0
+            return
+        if h[:4] != b"\x1f\x8b\x08\x04" or h[12:14] != b"BC":
+            raise ValueError("not a BGZF member at %d" % coff)
+        bsize = struct.unpack("<H", h[16:18])[0] + 1
+        body = self.f.read(bsize - 18)
+        self.coff, self.data, self.bsize = coff, zlib.decompress(body[:-8], -15), bsize
+
+    def seek(self, voff):
+        if voff >> 16 != self.coff:
+            self._load(voff >> 16)
+        self.uoff = voff & 0xFFFF
+        self._norm()
+
+    def _norm(self):
+        while self.bsize and self.uoff >= len(self.data):
+            self._load(self.coff + self.bsize)
+            self.uoff = 0
+
+    def tell(self):
+        return self.coff << 16 | self.uoff
+
+    def read(self, n):
+        out = bytearray()
+        while n and self.bsize:
+            k = self.data[self.uoff : self.uoff + n]
+            out += k
+            n -= len(k)
+            self.uoff += len(k)
+            self._norm()
+        return bytes(out)
+
+    def readline(self):
+        out = bytearray()
+        while self.bsize:
+            e = self.data.find(b"\n", self.uoff)
+            if e >= 0:
+                out += self.data[self.uoff : e + 1]
+                self.uoff = e + 1
+                self._norm()
+                break
+            out += self.data[self.uoff :]
+            self.uoff = len(self.data)
+            self._norm()
+        return bytes(out)
+
+
+def fetch(path, contig, beg, end, index=None):
+    """The records of `contig` (a name, or the header's 0-based contig number) whose 0-based position lies in [beg, end), from the
+    BGZF-compressed BCF or VCF file `path` through its CSI index (`index`: a read_csi result; default path + ".csi"): raw BCF2 records
+    (l_shared and l_indiv included) or text lines with their newline, in file order.  Only the index's chunks are read."""
+    import re
+    import struct
+
+    ix = index if index is not None else read_csi(path + ".csi")
+    out = []
+    with open(path, "rb") as f:
+        r = _BgzfReader(f)
+        r.seek(0)
+        is_bcf = r.data[:5] == b"BCF\x02\x02"
+        if isinstance(contig, str):
+            if is_bcf:
+                r.read(5)
+                (l_text,) = struct.unpack("<I", r.read(4))
+                names = re.findall(r"^##contig=<ID=([^,>]+)", r.read(l_text).decode("utf-8", "replace"), flags=re.M)
+            else:
+                names = ix["names"]
+            if contig not in names:
+                return out
+            tid = names.index(contig)
+        else:
+            tid = int(contig)
+        name = None
+        if not is_bcf and tid < len(ix["names"]):
+            name = ix["names"][tid].encode()
+        for vbeg, vend in csi_chunks(ix, tid, beg, end):
+            r.seek(vbeg)
+            while r.bsize and r.tell() < vend:
+                if is_bcf:
+                    h = r.read(8)
+                    if len(h) < 8:
+                        break
+                    l_shared, l_indiv = struct.unpack("<II", h)
+                    body = r.read(l_shared + l_indiv)
+                    rid, pos = struct.unpack_from("<ii", body, 0)
+                    if rid == tid and beg <= pos < end:
+                        out.append(h + body)
+                else:
+                    line = r.readline()
+                    if not line or line[:1] == b"#":
+                        continue
+                    cols = line.split(b"\t", 2)
+                    if (name is None or cols[0] == name) and beg <= int(cols[1]) - 1 < end:
+                        out.append(line)
+    return out

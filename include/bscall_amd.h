@@ -953,6 +953,68 @@ int bsc_bgzf_write(bsc_bgzf *z, const void *src, uint64_t n);
 int bsc_bgzf_write_device(bsc_bgzf *z, const void *d_src, uint64_t n);
 int bsc_bgzf_take(bsc_bgzf *z, void **d_out, uint64_t *n_bytes);
 int bsc_bgzf_close(bsc_bgzf *z, void **d_out, uint64_t *n_bytes);
+/* what an index beside the file needs of the writer: *n_logical = the bytes written into the logical stream so far, *n_members = the members
+ * completed so far (their compressed sizes are kept as they are produced; bsc_csi_finish reads them).  Either pointer may be NULL. */
+int bsc_bgzf_tell(const bsc_bgzf *z, uint64_t *n_logical, uint64_t *n_members);
+
+/*
+ * A CSI index (CSIv1) of a compressed BCF / VCF file, made WHILE the file is written: the record-level work runs on the device
+ * (csrc/csidev.hip, csrc/csidev_core.h), the host never walks the output stream.  The writer cuts members at fixed logical offsets, so a
+ * record's virtual offset is arithmetic on its offset u in the uncompressed stream: voff(u) = coff[u / 0xFF00] << 16 | u % 0xFF00, coff[k] the
+ * file offset of member k and coff[n_members] that of the end-of-file marker.
+ *
+ *   bsc_csi_entry          a run of consecutive records of one block's stream that share a window (0-based position >> min_shift): the
+ *                          window, the records, the offset of the first one in the block's stream
+ *   bsc_csi_scan_device    d_stream[0, n_bytes): whole BCF2 records of one contig in position order (BSC_CSI_BCF) or whole VCF data lines
+ *                          (BSC_CSI_VCF); d_sync[n_sync + 1]: ascending offsets, each a record start or n_bytes, d_sync[0] = 0 and
+ *                          d_sync[n_sync] = n_bytes (equal neighbours: an empty interval) — what the encoders leave as tile offsets; NULL
+ *                          (n_sync is then ignored): one interval, walked by one lane, for small streams.  A lane walks an interval.
+ *                          d_entries[<= cap_entries] in stream order; a run that continues across an interval boundary comes out as ADJACENT
+ *                          entries with the same window, one per interval it touches (bsc_csi_add merges them).  d_totals: three device u64
+ *                          {entries there are — also when that exceeds cap_entries: none is written beyond it —, records walked, error bits:
+ *                          not 0 when a record left its interval (1), a position went backwards inside an interval (2), a text line had no
+ *                          position (4) or the offsets were not ascending (8); the walk of that interval stops there}.  0 <= min_shift <= 31.
+ *                          Asynchronous on `stream`; uses workspaces of the context (one scan in flight per context).
+ *   bsc_block_csi_kept     the follow-up of bsc_block_bcf_rawdev_keep / bsc_block_vcf_rawdev_keep / bsc_block_bcf_again, BEFORE the stream is
+ *                          detached: scans the kept stream by the encoder's own tile offsets on the context's stream, waits, and returns the
+ *                          entries in memory of the context (valid until the next call of this function on it).  A malformed stream
+ *                          (never seen: the encoder wrote it) is BSC_ERR_ARG.
+ *   bsc_csi_open           an index beside the file writer z writes (BSC_ERR_ARG for a NULL or closed writer); names / lens: the header's
+ *                          contigs.  depth = the smallest d with 2^(min_shift + 3 d) >= the longest contig + 256.
+ *   bsc_csi_open_detached  the same without a writer, for a file compressed elsewhere with members cut every 0xFF00 bytes: the logical
+ *                          stream starts with header_bytes bytes and grows by every block added; bsc_csi_members hands over the members'
+ *                          compressed sizes (all of them, once, after the last block) in the place of bsc_bgzf_close
+ *   bsc_csi_add            the entries of a block of contig tid whose n_bytes-long stream is written NEXT: the writer's logical length is
+ *                          the block's base.  Adjacent entries with one window — inside the block or across blocks — become one.  Blocks in
+ *                          file order: tid never descends, windows never descend within a contig, u_beg ascends from 0 and stays below
+ *                          n_bytes, every entry has records; anything else is BSC_ERR_ARG and leaves the index as it was.
+ *   bsc_csi_finish         after bsc_bgzf_close (before: BSC_ERR_ARG): the .csi file's bytes — itself BGZF, one stored member per 0xFF00
+ *                          bytes and the end-of-file marker — into buf[cap]; returns their number; buf NULL / cap too small: the size needed
+ *                          and nothing written
+ *   bsc_csi_close          frees the index (NULL: nothing)
+ * Contents, one rule for every builder: header "CSI\1", min_shift, depth, l_aux, aux, n_ref; l_aux = 0 for BCF, for VCF the tabix block
+ * {format 2, col_seq 1, col_beg 2, col_end 0, meta '#', skip 0, l_nm} and the NUL-terminated names.  Per contig the leaf bins that hold
+ * records, ascending: bin = ((1 << 3 depth) - 1) / 7 + window, loffset = its one chunk's begin, the chunk [voff(first record's start),
+ * voff(last record's end)]; then the pseudo-bin ((1 << 3 (depth + 1)) - 1) / 7 + 1, loffset 0, chunks (voff of the contig's first record,
+ * voff behind its last) and (records, 0).  A contig without records: n_bin = 0.  n_no_coor = 0.  Sparse bins are NOT folded into their
+ * parents as htslib does — a size optimisation the format does not require.
+ */
+#define BSC_CSI_BCF 0
+#define BSC_CSI_VCF 1
+typedef struct {
+  uint32_t window, n_records;
+  uint64_t u_beg;
+} bsc_csi_entry;
+typedef struct bsc_csi bsc_csi;
+int bsc_csi_scan_device(bsc_context *ctx, int format, const void *d_stream, uint64_t n_bytes, const void *d_sync, uint32_t n_sync, int min_shift,
+                        void *d_entries, uint64_t cap_entries, void *d_totals, void *stream);
+int bsc_block_csi_kept(bsc_context *ctx, int min_shift, const bsc_csi_entry **entries, uint64_t *n_entries, uint64_t *n_records);
+int bsc_csi_open(bsc_bgzf *z, int format, int min_shift, int n_refs, const char *const *names, const uint32_t *lens, bsc_csi **out);
+int bsc_csi_open_detached(int format, int min_shift, int n_refs, const char *const *names, const uint32_t *lens, uint64_t header_bytes, bsc_csi **out);
+int bsc_csi_members(bsc_csi *ix, const uint64_t *sizes, uint64_t n_members);
+int bsc_csi_add(bsc_csi *ix, int32_t tid, const bsc_csi_entry *entries, uint64_t n, uint64_t n_bytes);
+long bsc_csi_finish(bsc_csi *ix, void *buf, uint64_t cap);
+void bsc_csi_close(bsc_csi *ix);
 /* bsc_block_bcf_rawdev with the stream left on the device (room: dev_cap bytes; BSC_ERR_ARG and the length needed in *n_bytes when it does
  * not fit), and bytes [off, off + n) of that stream -> dst, queued on the context's stream (bsc_synchronize before dst is read): a contig-sized
  * block's stream is gigabytes — read in pieces through a small page-locked buffer it costs no page-locking of its own */

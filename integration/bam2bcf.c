@@ -18,13 +18,15 @@
  *   output            fwrite                        bcf_write's write (-O u)
  *     + BGZF          bsc_bgzf_write[_device]       -O b: hts_open(..., "wb")'s BGZF layer, ON THE DEVICE (csrc/bgzfdev.hip): the header and
  *                     bsc_bgzf_take / _close        every block's kept stream go in, the completed members come out to the output thread
+ *     + index         bsc_block_csi_kept            --index: bcf_index_build / tbx_index_build's product, made beside the file: a block's
+ *                     bsc_csi_add / _finish         kept stream is scanned on the device (csrc/csidev.hip) before it goes to the compressor
  *   at the end        bsc_report_json               output_stats
  *
  * Not a replacement of the bs_call executable (no option parsing beyond -O / -D, regions, contig lists, compressed VCF): a worked
  * example of the calls in order, and the C twin of bs_call_amd/pipeline.py — tests/test_gpu_pipeline.py checks that both
  * write the same bytes.
  *
- *   make bam2bcf && bs_call_amd/lib/bam2bcf [-O u|b] [--format bcf|vcf] [-D dbsnp.idx] in.bam ref.fa out.bcf report.json [sample]
+ *   make bam2bcf && bs_call_amd/lib/bam2bcf [-O u|b] [--format bcf|vcf] [--index] [-D dbsnp.idx] in.bam ref.fa out.bcf report.json [sample]
  *
  * A sharded run over ONE file (SURVEY.md 8e on real input; the reference's unit of parallelism is a process per contig set, README.md): rank r of n
  *   bam2bcf --rank r --world n in.bam ref.fa out.bcf report.json [sample]
@@ -44,6 +46,11 @@
  * and terminator, then every block's lines, encoded on the device too (bsc_block_vcf_rawdev_keep, csrc/vcftextdev.hip): with -O u the
  * reference's -O v, with -O b (the same BGZF path) its -O z.  A single run on the device reader only (no --rank / --merge, no BAM2BCF_HOST_*).  -O b needs the device reader and
  * encoder and a single run (a shard compressed on its own would cut its members elsewhere than the single run does).
+ * Index: --index (with -O b, either format) writes out.bcf.csi, a CSI index (min_shift 14) of the compressed file, while the file is written: the
+ * block's kept stream is scanned where it lies, right behind the encoder on the context's stream (bsc_block_csi_kept: the runs of records per
+ * 16 384-position window and their offsets), the entries are noted at the writer's logical length (bsc_csi_add) before the stream goes into
+ * the compressor, and bsc_csi_finish turns the offsets into virtual offsets from the members' compressed sizes once the file is closed.  The
+ * data file's bytes are those of the run without --index.  Without -O b, or with --rank / --merge / BAM2BCF_HOST_*: refused.
  * dbSNP (the reference's -D): -D index names the records, forces out the homozygous-reference records of the index's fq_mask sites and fills
  * the report's dbSNP counters.  Each contig of the index is loaded by the thread that loads its reference, kept in HBM (bsc_dbsnp_attach at
  * the contig change) and the blocks' flags and names are made there (csrc/dbsnpdev.hip): the block calls pass NULL for both.  The header is
@@ -416,7 +423,7 @@ static int merge_main(int world, char **argv, const char *sample) {
 }
 
 int main(int argc, char **argv) {
-  int rank = -1, world = 1, merge = 0, bgzf = 0, text = 0;
+  int rank = -1, world = 1, merge = 0, bgzf = 0, text = 0, index = 0;
   const char *dbsnp_path = NULL;
   if (argc == 2 && !strcmp(argv[1], "-D")) {
     fprintf(stderr, "%s: -D takes the path of a dbSNP index (the file dbSNP_idx writes)\n", argv[0]);
@@ -444,6 +451,13 @@ int main(int argc, char **argv) {
       argc -= k;
       continue;
     }
+    if (!strcmp(argv[1], "--index")) { /* no value */
+      index = 1;
+      argv[1] = argv[0];
+      argv += 1;
+      argc -= 1;
+      continue;
+    }
     if (!strcmp(argv[1], "--rank")) rank = atoi(argv[2]);
     else if (!strcmp(argv[1], "--world")) world = atoi(argv[2]);
     else if (!strcmp(argv[1], "--merge")) merge = atoi(argv[2]);
@@ -460,7 +474,7 @@ int main(int argc, char **argv) {
     argc -= 2;
   }
   if (argc < 5 || world < 1 || (rank >= 0 && rank >= world)) {
-    fprintf(stderr, "usage: %s [-O u|b] [--format bcf|vcf] [-D dbsnp.idx] [--rank r --world n | --merge n] in.bam ref.fa out.bcf report.json [sample]\n", argv[0]);
+    fprintf(stderr, "usage: %s [-O u|b] [--format bcf|vcf] [--index] [-D dbsnp.idx] [--rank r --world n | --merge n] in.bam ref.fa out.bcf report.json [sample]\n", argv[0]);
     return 2;
   }
   if (text && (rank >= 0 || merge > 0)) {
@@ -473,6 +487,14 @@ int main(int argc, char **argv) {
   }
   if (bgzf && (rank >= 0 || merge > 0)) {
     fprintf(stderr, "%s: -O b writes a single run's file; a sharded run (--rank / --merge) writes uncompressed BCF (-O u)\n", argv[0]);
+    return 2;
+  }
+  if (index && (!bgzf || rank >= 0 || world > 1 || merge > 0)) {
+    fprintf(stderr, "%s: --index indexes a single run's compressed file: it needs -O b and no --rank / --world / --merge\n", argv[0]);
+    return 2;
+  }
+  if (index && (getenv("BAM2BCF_HOST_PREP") || getenv("BAM2BCF_HOST_BCF") || getenv("BAM2BCF_HOST_READER"))) {
+    fprintf(stderr, "%s: --index scans the device encoder's streams: not with BAM2BCF_HOST_READER / _HOST_BCF / _HOST_PREP\n", argv[0]);
     return 2;
   }
   if (dbsnp_path && (rank >= 0 || world > 1 || merge > 0)) {
@@ -536,6 +558,7 @@ int main(int argc, char **argv) {
   }
   const int n_ref = N_REFS();
   bsc_bgzf *zw = NULL;
+  bsc_csi *csi = NULL;
   if (!sharded) {
     const char **names = calloc((size_t)n_ref + 1, sizeof *names);
     uint32_t *lens = calloc((size_t)n_ref + 1, sizeof *lens);
@@ -559,6 +582,7 @@ int main(int argc, char **argv) {
       CHECK(bsc_bgzf_open(ctx, &zw));
       CHECK(bsc_bgzf_write(zw, hb, hn));
       free(hb);
+      if (index) CHECK(bsc_csi_open(zw, text ? BSC_CSI_VCF : BSC_CSI_BCF, 14, n_ref, names, lens, &csi)); /* (it keeps its own copy of the names) */
     } else write_header(out, n_ref, names, lens, sample, text);
     free(names);
     free(lens);
@@ -693,6 +717,13 @@ int main(int argc, char **argv) {
       CHECK(rc);
       t_gpu += (t1 = now()) - t0;
       t0 = t1;
+      if (n_bytes && csi) { /* the index's entries of this block, while the encoder's tile offsets are still the stream's: noted at the writer's
+                             * logical length, before the stream goes in */
+        const bsc_csi_entry *ce = NULL;
+        uint64_t cn = 0;
+        CHECK(bsc_block_csi_kept(ctx, 14, &ce, &cn, NULL));
+        CHECK(bsc_csi_add(csi, dblk.tid, ce, cn, n_bytes));
+      }
       if (n_bytes) { /* the stream changes hands: the output thread reads it out and writes it while this one goes on to the next block */
         void *d_stream = NULL;
         uint64_t n_det = 0;
@@ -791,6 +822,23 @@ int main(int argc, char **argv) {
       writer_push(&W, j);
     }
     file_at += n_z;
+    if (csi) { /* the members' sizes are all there: the index's virtual offsets, and the .csi file */
+      const long need = bsc_csi_finish(csi, NULL, 0);
+      CHECK(need);
+      uint8_t *ib = xrealloc(NULL, (size_t)need);
+      CHECK(bsc_csi_finish(csi, ib, (uint64_t)need));
+      char *ip = xrealloc(NULL, strlen(argv[3]) + 8);
+      sprintf(ip, "%s.csi", argv[3]);
+      FILE *fi = fopen(ip, "wb");
+      if (!fi || fwrite(ib, 1, (size_t)need, fi) != (size_t)need || fclose(fi)) {
+        perror(ip);
+        return 1;
+      }
+      free(ip);
+      free(ib);
+      bsc_csi_close(csi);
+      csi = NULL;
+    }
   }
   if (W.started) { /* the output thread writes what it still holds, then goes */
     pthread_mutex_lock(&W.mu);
