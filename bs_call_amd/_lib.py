@@ -173,6 +173,13 @@ EXPORTS = (
     "bsc_last_raw_block_ms",
     "bsc_reads_chain_len_device",
     "bsc_bcf_sites_len_device",
+    "bsc_meth_params_default",
+    "bsc_meth_format_rec",
+    "bsc_meth_block_device",
+    "bsc_meth_sites_device",
+    "bsc_block_meth_kept",
+    "bsc_meth_stream_read",
+    "bsc_meth_stream_detach",
 )
 
 
@@ -184,6 +191,15 @@ class Params(C.Structure):
         ("min_qual", C.c_int32),
         ("device", C.c_int32),
     ]
+
+
+class MethParams(C.Structure):
+    """bsc_meth_params; the defaults are bsc_meth_params_default's."""
+
+    _fields_ = [("contexts", C.c_int32), ("min_cov", C.c_uint32), ("min_phred", C.c_uint32), ("pass_only", C.c_int32)]
+
+    def __init__(self, contexts=0, min_cov=1, min_phred=0, pass_only=0):
+        super().__init__(int(contexts), int(min_cov), int(min_phred), int(pass_only))
 
 
 class VcfParams(C.Structure):
@@ -671,5 +687,19 @@ def load():
     L.bsc_last_raw_block_ms.argtypes = [vp, C.POINTER(C.c_float)]
     L.bsc_bcf_stream_read.restype = i32
     L.bsc_bcf_stream_read.argtypes = [vp, u64, u64, vp]
+    L.bsc_meth_params_default.restype = None
+    L.bsc_meth_params_default.argtypes = [C.POINTER(MethParams)]
+    L.bsc_meth_format_rec.restype = C.c_long
+    L.bsc_meth_format_rec.argtypes = [vp, C.c_char_p, C.POINTER(MethParams), vp, C.c_size_t]
+    L.bsc_meth_block_device.restype = i32
+    L.bsc_meth_block_device.argtypes = [vp, vp, vp, u64, C.c_char_p, C.POINTER(MethParams), vp, u64, vp, vp]
+    L.bsc_meth_sites_device.restype = i32
+    L.bsc_meth_sites_device.argtypes = [vp, vp, vp, u32, C.c_char_p, C.POINTER(MethParams), vp, u64, vp, vp]
+    L.bsc_block_meth_kept.restype = i32
+    L.bsc_block_meth_kept.argtypes = [vp, C.c_char_p, C.POINTER(MethParams), u64, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)]
+    L.bsc_meth_stream_read.restype = i32
+    L.bsc_meth_stream_read.argtypes = [vp, u64, u64, vp]
+    L.bsc_meth_stream_detach.restype = i32
+    L.bsc_meth_stream_detach.argtypes = [vp, C.POINTER(vp), C.POINTER(u64)]
     _lib = L
     return L

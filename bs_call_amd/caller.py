@@ -641,9 +641,11 @@ class SiteCaller:
         return out[: nb.value].tobytes(), nr.value, st[0]
 
     def block_bcf_rawdev(self, blk, ref, rid, names=None, left_trim=(0, 0), right_trim=(0, 0), min_qual=20, all_positions=False, reg_start=1,
-                         reg_stop=0xFFFFFFFF, dbsnp=None, with_stats=False, cap=None, profile=None, ids=None):
+                         reg_stop=0xFFFFFFFF, dbsnp=None, with_stats=False, cap=None, profile=None, ids=None, keep=False):
         """bsc_block_bcf_rawdev: a block of the DEVICE reader (bamdev.DeviceBamReader.device_blocks(): raw templates, reads and lists in HBM)
-        -> the block's BCF bytes; nothing of the reads crosses PCIe a second time.  Returns (bytes, n_records, PREP_STATS record)."""
+        -> the block's BCF bytes; nothing of the reads crosses PCIe a second time.  Returns (bytes, n_records, PREP_STATS record).
+        keep: bsc_block_bcf_rawdev_keep + bsc_bcf_stream_read — the same bytes, the stream and the block's arrays left on the device for
+        block_csi_kept / block_meth_kept."""
         from .abi import PREP_PARAMS, PREP_STATS
 
         x, y = int(blk.x), int(blk.y)
@@ -655,10 +657,10 @@ class SiteCaller:
         if ids is None:
             ids = _lib.BcfIds()
             self._L.bsc_bcf_default_ids(C.byref(ids))
-        nm, keep = self._bcf_names(names)
+        nm, keep_nm = self._bcf_names(names)
         cap_given = cap
         cap = 64 + 192 * n if cap is None else int(cap)
-        out = np.empty(max(cap, 1), dtype=np.uint8)
+        out = None if keep else np.empty(max(cap, 1), dtype=np.uint8)
         par = np.zeros(1, dtype=PREP_PARAMS)
         par["left_trim"][0], par["right_trim"][0], par["min_qual"][0] = left_trim, right_trim, min_qual
         p = _lib.VcfParams(1 if all_positions else 0, reg_start, reg_stop)
@@ -667,6 +669,11 @@ class SiteCaller:
         pf = None if profile is None else _lib.ReadProfile(None, 0, 0, profile.counts.ctypes.data, profile.counts.shape[0], profile.used)
 
         def go(stats, st_, pf_):
+            if keep:
+                return self._L.bsc_block_bcf_rawdev_keep(self._h, blk.d_tpl, blk.nr, blk.d_seq, blk.seq_bytes, blk.d_misms, blk.n_misms, blk.ins_pad, _ptr(par),
+                                                         x, y, _ptr(ref), None if db is None else _ptr(db), C.byref(p), stats, rid, C.byref(ids),
+                                                         None if nm is None else C.addressof(nm), cap, C.byref(nb), C.byref(nr), _ptr(st_),
+                                                         None if pf_ is None else C.byref(pf_))
             return self._L.bsc_block_bcf_rawdev(self._h, blk.d_tpl, blk.nr, blk.d_seq, blk.seq_bytes, blk.d_misms, blk.n_misms, blk.ins_pad, _ptr(par), x, y,
                                                 _ptr(ref), None if db is None else _ptr(db), C.byref(p), stats, rid, C.byref(ids),
                                                 None if nm is None else C.addressof(nm), _ptr(out), cap, C.byref(nb), C.byref(nr), _ptr(st_),
@@ -675,12 +682,17 @@ class SiteCaller:
         rc = go(1 if with_stats else 0, st, pf)
         if rc == -1 and nb.value > cap and cap_given is None:
             cap = int(nb.value)
-            out = np.empty(cap, dtype=np.uint8)
-            rc = self._L.bsc_block_bcf_again(self._h, _ptr(out), cap, C.byref(nb), C.byref(nr))
+            out = None if keep else np.empty(cap, dtype=np.uint8)
+            rc = self._L.bsc_block_bcf_again(self._h, None if keep else _ptr(out), cap, C.byref(nb), C.byref(nr))
         _check(rc)
-        del keep
+        del keep_nm
         if pf is not None:
             profile.used = int(pf.used)
+        if keep:
+            out = np.empty(max(int(nb.value), 1), dtype=np.uint8)
+            if nb.value:
+                _check(self._L.bsc_bcf_stream_read(self._h, 0, nb.value, _ptr(out)))
+                self.synchronize()
         return out[: nb.value].tobytes(), nr.value, st[0]
 
     def block_bcf_submit(self, templates, seq, x, y, ref, rid, out, names=None, all_positions=False, reg_start=1, reg_stop=0xFFFFFFFF, dbsnp=None,
@@ -807,6 +819,44 @@ class SiteCaller:
             _check(self._L.bsc_bcf_stream_read(self._h, 0, nb.value, _ptr(out)))
             self.synchronize()
         return out[: nb.value].tobytes(), nr.value, st[0]
+
+    # -- the per-cytosine methylation table on the device (csrc/methdev.hip) -------------------------------
+    @staticmethod
+    def _meth_params(params):
+        if params is None:
+            return _lib.MethParams()
+        if isinstance(params, _lib.MethParams):
+            return params
+        return _lib.MethParams(**params)
+
+    def meth_block_device(self, d_recs, d_n_recs, max_recs, contig, d_out, out_cap, d_totals, params=None, stream=None):
+        """bsc_meth_block_device: packed records in HBM -> their bedMethyl lines in HBM (asynchronous on `stream`); d_totals: four u64."""
+        mp = self._meth_params(params)
+        _check(self._L.bsc_meth_block_device(self._h, d_recs, d_n_recs, max_recs, self._contig_bytes(contig), C.byref(mp), d_out, out_cap, d_totals, stream))
+
+    def meth_sites_device(self, d_core, d_aux, n, contig, d_out, out_cap, d_totals, params=None, stream=None):
+        """bsc_meth_sites_device: the per-position arrays of reads_chain_device (d_core, d_aux) -> the bedMethyl lines."""
+        mp = self._meth_params(params)
+        _check(self._L.bsc_meth_sites_device(self._h, d_core, d_aux, n, self._contig_bytes(contig), C.byref(mp), d_out, out_cap, d_totals, stream))
+
+    def block_meth_kept(self, contig, params=None, cap=None):
+        """bsc_block_meth_kept + bsc_meth_stream_read: the bedMethyl table of the block the last *_keep call called (block_vcf_rawdev,
+        block_bcf_rawdev(keep=True)), from the arrays that block left on the device.  params: a _lib.MethParams, a dict of its fields, or
+        None (CpG, every covered site).  Returns (bytes, lines, (sum of a, sum of b)).  cap: the room on the device (default: asked for
+        and given on a second call)."""
+        mp = self._meth_params(params)
+        nb, nl, sums = C.c_uint64(0), C.c_uint64(0), (C.c_uint64 * 2)()
+        room = 1 << 16 if cap is None else int(cap)
+        rc = self._L.bsc_block_meth_kept(self._h, self._contig_bytes(contig), C.byref(mp), room, C.byref(nb), C.byref(nl), sums)
+        if rc == -1 and nb.value > room and cap is None:
+            room = int(nb.value)
+            rc = self._L.bsc_block_meth_kept(self._h, self._contig_bytes(contig), C.byref(mp), room, C.byref(nb), C.byref(nl), sums)
+        _check(rc)
+        out = np.empty(max(int(nb.value), 1), dtype=np.uint8)
+        if nb.value:
+            _check(self._L.bsc_meth_stream_read(self._h, 0, nb.value, _ptr(out)))
+            self.synchronize()
+        return out[: nb.value].tobytes(), int(nl.value), (int(sums[0]), int(sums[1]))
 
     def blocks_records(self, blocks, ref, out=None, all_positions=False, reg_start=1, reg_stop=0xFFFFFFFF, dbsnp=None, with_stats=False,
                        submit_only=False):

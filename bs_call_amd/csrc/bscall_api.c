@@ -82,6 +82,9 @@ int bsc_dev_launch_vcf_text(const void *recs, const void *core, const void *aux,
                             void *tile_bytes, void *tile_off, void *line_len, void *scan_tmp, size_t scan_tmp_bytes, void *out, uint64_t out_cap,
                             void *totals, int num_cus, void *stream); /* vcftextdev.hip */
 int bsc_dev_launch_fmt_g(const void *v, uint64_t n, void *out16, int num_cus, void *stream);
+int bsc_dev_launch_meth(const void *recs, const void *core, const void *aux, const void *n_recs, uint64_t max_recs, const void *emit, const char *contig,
+                        uint32_t contig_len, const bsc_meth_params *par, void *tile_bytes, void *tile_off, void *line_len, void *scan_tmp,
+                        size_t scan_tmp_bytes, void *out, uint64_t out_cap, void *totals, int num_cus, void *stream); /* methdev.hip */
 int bsc_dev_launch_ref_pad(const void *packed, const void *d_blk, uint32_t n_blk, void *padded, uint32_t n_pos, int num_cus, void *stream);
 int bsc_dev_launch_bin_reads_multi(const void *tpl, uint32_t nr, const void *seq, uint64_t seq_bytes, const void *d_blk, uint32_t n_blk,
                                    uint32_t n_bins, void *tflag, void *bin_cnt, void *bin_off, void *bin_cur, void *scan_tmp,
@@ -167,6 +170,13 @@ struct bsc_context {
   size_t cap_btb, cap_bto, cap_bscn, cap_bnm, cap_bcf, cap_btot;
   void *d_vtl; /* the text encoder (vcftextdev.hip): a line's length per record / position, between its two passes */
   size_t cap_vtl;
+  /* the methylation table's encoder (methdev.hip), with workspaces of its own — a kept stream's tile offsets in d_bto stay what they are: bytes
+   * per tile, their prefix sum, scan scratch, a line's length per record / position; bsc_block_meth_kept: the table, {length, lines, sum a,
+   * sum b}, the table's length, and whether d_vout / d_out / again.{sz, emit} still are the arrays of ONE kept block */
+  void *d_mtb, *d_mto, *d_mscn, *d_mll, *d_meth, *d_mtot;
+  size_t cap_mtb, cap_mto, cap_mscn, cap_mll, cap_meth, cap_mtot;
+  uint64_t meth_bytes;
+  int meth_src;
   /* the CSI scan (csidev.hip): runs per interval, their prefix sum, scan scratch, the entries and {entries, records, error bits} of the
    * follow-up call bsc_block_csi_kept, its host copy; and what the last encoder call left in d_bto: for which stream, how many tiles, text */
   void *d_cscn, *d_csof, *d_cstm, *d_csen, *d_cstot;
@@ -561,6 +571,12 @@ int bsc_destroy(bsc_context *ctx) {
   hipFree(ctx->d_bcf);
   hipFree(ctx->d_btot);
   hipFree(ctx->d_vtl);
+  hipFree(ctx->d_mtb);
+  hipFree(ctx->d_mto);
+  hipFree(ctx->d_mscn);
+  hipFree(ctx->d_mll);
+  hipFree(ctx->d_meth);
+  hipFree(ctx->d_mtot);
   hipFree(ctx->d_cscn);
   hipFree(ctx->d_csof);
   hipFree(ctx->d_cstm);
@@ -1073,7 +1089,7 @@ int bsc_vcf_records(bsc_context *ctx, const void *gtm, uint32_t gtm_stride, cons
   if (n == 0) return BSC_OK;
   if (!gtm || !skip || !ref || !out) return bsc_fail(BSC_ERR_ARG, "bsc_vcf_records: NULL buffer");
   BSC_ENTER(ctx);
-  ctx->again.valid = 0; /* (d_out is about to be rewritten) */
+  ctx->again.valid = ctx->meth_src = 0; /* (d_out is about to be rewritten) */
   if ((rc = bsc_reserve(&ctx->d_out, &ctx->cap_out, (size_t)n * gtm_stride))) return rc;
   if ((rc = bsc_reserve(&ctx->d_skip, &ctx->cap_skip, (size_t)n))) return rc;
   if ((rc = bsc_reserve(&ctx->d_ref, &ctx->cap_ref, (size_t)n + 2))) return rc;
@@ -1101,7 +1117,7 @@ int bsc_block_submit(bsc_context *ctx, const bsc_template *tpl, uint32_t nr, con
   if (y < x) return bsc_fail(BSC_ERR_ARG, "bsc_block_submit: y (%u) < x (%u)", y, x);
   if ((rc = bsc_accumulate_queue2(ctx, tpl, nr, seq, seq_bytes, x, y, ref, 1))) return rc;
   const uint64_t sz = (uint64_t)y - x + 1;
-  ctx->again.valid = 0; /* (d_out is about to be rewritten) */
+  ctx->again.valid = ctx->meth_src = 0; /* (d_out is about to be rewritten) */
   if ((rc = bsc_reserve(&ctx->d_out, &ctx->cap_out, (size_t)sz * out_stride))) return rc;
   if ((rc = bsc_reserve(&ctx->d_skip, &ctx->cap_skip, (size_t)sz))) return rc;
   if ((rc = bsc_call_sites_device(ctx, ctx->d_cts, ctx->d_ref, sz, ctx->d_out, out_stride, ctx->d_skip, ctx->stream)))
@@ -1170,7 +1186,7 @@ static int bsc_blocks_submit_to_(bsc_context *ctx, const bsc_block_desc *blocks,
   if ((rc = bsc_reserve(&ctx->d_seq, &ctx->cap_seq, (size_t)(seq_bytes ? seq_bytes : 1)))) return rc;
   if ((rc = bsc_reserve(&ctx->d_cts, &ctx->cap_cts, (size_t)P * 104u))) return rc;
   if ((rc = bsc_reserve(&ctx->d_ref, &ctx->cap_ref, (size_t)P))) return rc;
-  ctx->again.valid = 0; /* (d_out is about to be rewritten) */
+  ctx->again.valid = ctx->meth_src = 0; /* (d_out is about to be rewritten) */
   if ((rc = bsc_reserve(&ctx->d_out, &ctx->cap_out, (size_t)P * out_stride))) return rc;
   if ((rc = bsc_reserve(&ctx->d_skip, &ctx->cap_skip, (size_t)P))) return rc;
   if ((rc = bsc_reserve(&ctx->d_mblk, &ctx->cap_mblk, (size_t)n_blocks * sizeof(bsc_chain_mblock)))) return rc;
@@ -1824,6 +1840,7 @@ int bsc_vcf_compact_device(bsc_context *ctx, const void *d_core, const void *d_g
   if (gtm_stride == 0 && !emit && !ctx->no_emit_bytes) { /* no flags from the chain kernel: the counting pass leaves them */
     if ((rc = bsc_reserve(&ctx->d_emit, &ctx->cap_emit, (size_t)n + 64u))) return rc;
     emit_ws = ctx->d_emit;
+    ctx->meth_src = 0; /* (a kept block's flags are about to be rewritten) */
   }
   int e = bsc_dev_launch_compact(d_core, d_gtm, gtm_stride, d_dbsnp, n, ctx->d_tcnt, ctx->d_toff, ctx->d_scantmp, scan_bytes,
                                  d_out, out_cap, d_count, emit, emit_ws, ctx->num_cus, stream);
@@ -2268,7 +2285,7 @@ static int bsc_records_queue(bsc_context *ctx, const bsc_template *tpl, uint32_t
     if ((rc = bsc_reserve(&ctx->d_seq, &ctx->cap_seq, (size_t)(seq_bytes ? seq_bytes : 1)))) return rc;
   }
   if ((rc = bsc_reserve(&ctx->d_ref, &ctx->cap_ref, (size_t)sz + 2))) return rc;
-  ctx->again.valid = 0; /* (d_out is about to be rewritten) */
+  ctx->again.valid = ctx->meth_src = 0; /* (d_out is about to be rewritten) */
   if ((rc = bsc_reserve(&ctx->d_out, &ctx->cap_out, (size_t)sz * 64u))) return rc; /* the chain's aux array */
   if ((rc = bsc_reserve(&ctx->d_vout, &ctx->cap_vout, (size_t)sz * sizeof(bsc_vcf_core)))) return rc;
   if ((rc = bsc_reserve(&ctx->d_recs, &ctx->cap_recs, (size_t)(out_cap ? out_cap : 1) * sizeof(bsc_vcf_rec)))) return rc;
@@ -2349,6 +2366,7 @@ static int bsc_records_queue(bsc_context *ctx, const bsc_template *tpl, uint32_t
   if (bcf) { /* the encoder takes the records where the chain left them (no packing pass); {length, refused, records} come back behind the verdict */
     ctx->emit_hint = d_emit;
     ctx->again.sz = sz;
+    ctx->meth_src = -1; /* ONE block's arrays: bsc_block_meth_kept's source once the block has come back kept (bsc_bcf_finish) */
     ctx->again.rid = bcf->rid;
     ctx->again.text = bcf->text;
     if (bcf->text) {
@@ -2394,6 +2412,7 @@ static int bsc_bcf_finish(bsc_context *ctx, uint8_t *out, int inexact) {
   ctx->bcf_copied = ctx->bcf_copied < bytes ? ctx->bcf_copied : bytes;
   const char *const who = ctx->again.text ? "bsc_block_vcf" : "bsc_block_bcf"; /* (again.* describe the block in flight since bsc_records_queue) */
   /* the chain never forms such a record; a block entry refuses them for both formats (the device-level text entries write them clamped) */
+  if (ctx->meth_src < 0) ctx->meth_src = ctx->bcf_keep && !bad;
   if (bad) return bsc_fail(BSC_ERR_ARG, "%s: %llu records with a genotype beyond 9 or more than 6 likelihoods", who, bad);
   if (bytes > ctx->bcf_cap) {
     ctx->again.valid = 1; /* bsc_block_bcf_again: the encoder alone, into the room it asks for */
@@ -2861,6 +2880,107 @@ int bsc_bcf_stream_read(bsc_context *ctx, uint64_t off, uint64_t n, void *dst) {
   return BSC_OK;
 }
 
+/* ---- the per-cytosine methylation table (methdev.hip): the line bsc_meth_format_rec writes, per record that gives one ---------------- */
+static void bsc_pool_init(bsc_context *ctx); /* (with the BGZF writer, below) */
+static void *bsc_pool_get(bsc_context *ctx, size_t need, size_t *cap);
+static void bsc_pool_book(bsc_context *ctx, void *p, size_t cap);
+static int bsc_meth_encode(bsc_context *ctx, const char *who, const void *d_recs, const void *d_core, const void *d_aux, const void *d_n_recs,
+                           uint64_t max_recs, const void *d_emit, const char *contig, const bsc_meth_params *par, void *d_out, uint64_t out_cap,
+                           void *d_totals, void *stream) {
+  uint32_t contig_len = 0;
+  int rc;
+  if ((rc = bsc_stream_args_check(ctx, who, d_recs, d_core, d_aux, d_n_recs, max_recs, d_out, out_cap, d_totals))) return rc;
+  if ((rc = bsc_contig_check(who, contig, &contig_len))) return rc;
+  if (!par) return bsc_fail(BSC_ERR_ARG, "%s: NULL argument", who);
+  if (par->contexts != BSC_METH_CPG && par->contexts != BSC_METH_ALL)
+    return bsc_fail(BSC_ERR_ARG, "%s: contexts is %d, not BSC_METH_CPG or BSC_METH_ALL", who, (int)par->contexts);
+  BSC_ENTER(ctx);
+  hipStream_t s = (hipStream_t)stream;
+  const uint32_t n_tiles = (uint32_t)((max_recs + 63u) / 64u);
+  size_t scan_bytes = 0;
+  if (bsc_dev_scan_tmp_bytes_u64(n_tiles + 1u, &scan_bytes)) return bsc_fail(BSC_ERR_HIP, "%s: scan size query failed", who);
+  if ((rc = bsc_reserve(&ctx->d_mtb, &ctx->cap_mtb, ((size_t)n_tiles + 1u) * 8u))) return rc;
+  if ((rc = bsc_reserve(&ctx->d_mto, &ctx->cap_mto, ((size_t)n_tiles + 1u) * 8u))) return rc;
+  if ((rc = bsc_reserve(&ctx->d_mscn, &ctx->cap_mscn, scan_bytes ? scan_bytes : 1))) return rc;
+  if ((rc = bsc_reserve(&ctx->d_mll, &ctx->cap_mll, ((size_t)n_tiles + 1u) * 128u))) return rc;
+  HIP_TRY(hipMemsetAsync(d_totals, 0, 4 * sizeof(unsigned long long), s));
+  const int e = bsc_dev_launch_meth(d_recs, d_core, d_aux, d_n_recs, max_recs, d_emit, contig, contig_len, par, ctx->d_mtb, ctx->d_mto, ctx->d_mll,
+                                    ctx->d_mscn, scan_bytes, d_out, out_cap, d_totals, ctx->num_cus, stream);
+  if (e) return bsc_fail(BSC_ERR_HIP, "methylation table encoder launch failed: %s", hipGetErrorString((hipError_t)e));
+  return BSC_OK;
+}
+
+int bsc_meth_block_device(bsc_context *ctx, const void *d_recs, const void *d_n_recs, uint64_t max_recs, const char *contig,
+                          const bsc_meth_params *params, void *d_out, uint64_t out_cap, void *d_totals, void *stream) {
+  if (!d_n_recs || (max_recs && !d_recs)) return bsc_fail(BSC_ERR_ARG, "bsc_meth_block_device: NULL argument");
+  /* (no records at all: the per-position form over zero positions — nothing is read) */
+  return bsc_meth_encode(ctx, "bsc_meth_block_device", d_recs, NULL, NULL, d_recs ? d_n_recs : NULL, max_recs, NULL, contig, params, d_out, out_cap,
+                         d_totals, stream);
+}
+
+int bsc_meth_sites_device(bsc_context *ctx, const void *d_core, const void *d_aux, uint32_t n, const char *contig, const bsc_meth_params *params,
+                          void *d_out, uint64_t out_cap, void *d_totals, void *stream) {
+  return bsc_meth_encode(ctx, "bsc_meth_sites_device", NULL, d_core, d_aux, NULL, n, NULL, contig, params, d_out, out_cap, d_totals, stream);
+}
+
+/* the table of the block the last _keep call called: from d_vout / d_out, which stay what the chain left until the next block, by the chain's
+ * byte per position where the block has one — into d_meth, a buffer that is not the kept stream's */
+int bsc_block_meth_kept(bsc_context *ctx, const char *contig, const bsc_meth_params *p, uint64_t dev_cap, uint64_t *n_bytes, uint64_t *n_lines,
+                        uint64_t sums[2]) {
+  if (!ctx || !n_bytes || !n_lines) return bsc_fail(BSC_ERR_ARG, "bsc_block_meth_kept: NULL argument");
+  *n_bytes = *n_lines = 0;
+  if (sums) sums[0] = sums[1] = 0;
+  if (ctx->meth_src != 1 || ctx->rec_pending || ctx->pending_sz)
+    return bsc_fail(BSC_ERR_ARG, "bsc_block_meth_kept: the last call left no single block's arrays on the device");
+  BSC_ENTER(ctx);
+  hipStream_t s = ctx->stream;
+  int rc;
+  ctx->meth_bytes = 0;
+  /* a buffer that came back (bsc_detached_free), the smallest that will do: the large ones are the kept streams' */
+  if (!ctx->d_meth && ctx->pool_mu_made) ctx->d_meth = bsc_pool_get(ctx, (size_t)(dev_cap ? dev_cap : 1), &ctx->cap_meth);
+  if ((rc = bsc_reserve(&ctx->d_meth, &ctx->cap_meth, (size_t)(dev_cap ? dev_cap : 1)))) return rc;
+  if ((rc = bsc_reserve(&ctx->d_mtot, &ctx->cap_mtot, 4 * sizeof(unsigned long long)))) return rc;
+  if ((rc = bsc_meth_encode(ctx, "bsc_block_meth_kept", NULL, ctx->d_vout, ctx->d_out, NULL, ctx->again.sz, ctx->again.emit, contig, p, ctx->d_meth, dev_cap,
+                            ctx->d_mtot, s)))
+    return rc;
+  unsigned long long tot[4] = {0, 0, 0, 0};
+  HIP_TRY(hipMemcpyAsync(tot, ctx->d_mtot, sizeof tot, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  *n_bytes = tot[0];
+  *n_lines = tot[1];
+  if (sums) sums[0] = tot[2], sums[1] = tot[3];
+  if (tot[0] > dev_cap)
+    return bsc_fail(BSC_ERR_ARG, "bsc_block_meth_kept: the block's table has %llu bytes, dev_cap is %llu", tot[0], (unsigned long long)dev_cap);
+  ctx->meth_bytes = tot[0];
+  return BSC_OK;
+}
+
+int bsc_meth_stream_read(bsc_context *ctx, uint64_t off, uint64_t n, void *dst) {
+  if (!ctx || (!dst && n)) return bsc_fail(BSC_ERR_ARG, "bsc_meth_stream_read: NULL argument");
+  if (off + n > ctx->meth_bytes || off + n > ctx->cap_meth) return bsc_fail(BSC_ERR_ARG, "bsc_meth_stream_read: beyond the table's end");
+  if (!n) return BSC_OK;
+  BSC_ENTER(ctx);
+  HIP_TRY(hipMemcpyAsync(dst, (const char *)ctx->d_meth + off, (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+  return BSC_OK;
+}
+
+int bsc_meth_stream_detach(bsc_context *ctx, void **d_stream, uint64_t *n_bytes) {
+  if (!ctx || !d_stream || !n_bytes) return bsc_fail(BSC_ERR_ARG, "bsc_meth_stream_detach: NULL argument");
+  *d_stream = NULL;
+  *n_bytes = 0;
+  if (!ctx->d_meth || !ctx->meth_bytes) return bsc_fail(BSC_ERR_ARG, "bsc_meth_stream_detach: the last call left no table on the device");
+  BSC_ENTER(ctx);
+  bsc_pool_init(ctx);
+  if (!ctx->s_det) HIP_TRY(hipStreamCreateWithFlags(&ctx->s_det, hipStreamNonBlocking));
+  *d_stream = ctx->d_meth;
+  *n_bytes = ctx->meth_bytes;
+  bsc_pool_book(ctx, ctx->d_meth, ctx->cap_meth);
+  ctx->d_meth = NULL;
+  ctx->cap_meth = 0;
+  ctx->meth_bytes = 0;
+  return BSC_OK;
+}
+
 /* The split form: queue the block and return; bsc_block_records_fetch waits and completes it.  stage != 0: the inputs go
  * through the pinned staging area, so the caller's buffers are free at once; 0: they are read where they lie and must stay
  * unchanged until the fetch (`out` must stay valid until then either way). */
@@ -2981,7 +3101,7 @@ static int bsc_blocks_queue(bsc_context *ctx, const bsc_block_desc *blocks, uint
   if ((rc = bsc_reserve(&ctx->d_tpl, &ctx->cap_tpl, (size_t)(nr ? nr : 1) * sizeof(bsc_template)))) return rc;
   if ((rc = bsc_reserve(&ctx->d_seq, &ctx->cap_seq, (size_t)(seq_bytes ? seq_bytes : 1)))) return rc;
   if ((rc = bsc_reserve(&ctx->d_ref, &ctx->cap_ref, (size_t)ref64))) return rc;
-  ctx->again.valid = 0; /* (d_out is about to be rewritten) */
+  ctx->again.valid = ctx->meth_src = 0; /* (d_out is about to be rewritten) */
   if ((rc = bsc_reserve(&ctx->d_out, &ctx->cap_out, (size_t)P * 64u))) return rc; /* the chain's aux array */
   if ((rc = bsc_reserve(&ctx->d_vout, &ctx->cap_vout, (size_t)P * sizeof(bsc_vcf_core)))) return rc;
   if ((rc = bsc_reserve(&ctx->d_recs, &ctx->cap_recs, (size_t)(out_cap ? out_cap : 1) * sizeof(bsc_vcf_rec)))) return rc;
@@ -3290,7 +3410,7 @@ int bsc_vcf_stats(bsc_context *ctx, const bsc_vcf_core *core, const void *gtm, u
   if (n == 0) return BSC_OK;
   if (!core || !gtm) return bsc_fail(BSC_ERR_ARG, "bsc_vcf_stats: NULL buffer");
   BSC_ENTER(ctx);
-  ctx->again.valid = 0; /* (d_out is about to be rewritten) */
+  ctx->again.valid = ctx->meth_src = 0; /* (d_out is about to be rewritten) */
   if ((rc = bsc_reserve(&ctx->d_out, &ctx->cap_out, (size_t)n * gtm_stride))) return rc;
   if ((rc = bsc_reserve(&ctx->d_vout, &ctx->cap_vout, (size_t)n * sizeof(bsc_vcf_core)))) return rc;
   if (dbsnp && (rc = bsc_reserve(&ctx->d_vdb, &ctx->cap_vdb, (size_t)n))) return rc;

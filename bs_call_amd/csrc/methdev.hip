@@ -1,0 +1,313 @@
+/*
+ * methdev.hip — a block's cytosines as a bedMethyl table on the device: for every record that gives a line (include/bscall_amd.h has
+ * the rule and the columns; the reference's src/print_vcf.c:442-515 the sites and the counts), in position order, the line
+ * bsc_meth_format_rec writes for it.  The host form csrc/methbed.c is the checker.  The placement — wave prefix sum, the parts, the
+ * image's copy-out — is recstream_dev.h's, shared with the BCF encoder (bcfdev.hip) and the VCF text encoder (vcftextdev.hip):
+ *
+ *   bsc_meth_size_kernel   one wave per tile of 64 records / positions: every lane the length of its line (the emitter over the
+ *                          counting sink) -> line_len[i] (u16; 0 = no line), the tile's sum -> tile_bytes[tile]; lines, sum of a, sum
+ *                          of b -> totals[1 .. 3]
+ *   (exclusive scan of the tile sums, rocPRIM u64: sort.hip; one more entry behind the last tile = the stream's length)
+ *   bsc_meth_write_kernel  one wave per tile that has bytes: lane offsets from a wave prefix sum of line_len, every lane writes its
+ *                          line into the wave's LDS image of the tile's span of the stream, then the wave copies the image out.  A
+ *                          tile whose span does not fit the image (4 KB) goes out in 2, 4 or 8 parts.
+ *
+ * Whether a record gives a line is decided from its first 16 bytes (emit, gt, flt, phred, cg) and, behind them, its counts: a
+ * position that gives none costs those 16 bytes (their 64-byte sector) — or, with the chain's byte per position (emit: not 0 <=> the
+ * record is written), a position without a record costs that byte.  Half of a record is never read: GL, FS, QD, DP, MQ, AMQ.
+ *
+ * All arithmetic is integer: the decimal conversion divides by constants, the percentage is found by bisection over 0 .. 100 (a
+ * 64-bit division by a variable would be expanded through a floating-point reciprocal).
+ *
+ * Longest line: the contig's name (<= 255 bytes) + 111 = 366 bytes:
+ *   "\t" start 10 "\t" end 10 "\t" name 3 "\t" score 4 "\t" strand 1 "\t" start 10 "\t" end 10 "\t"                          = 56
+ *   rgb 9 "\t" coverage 10 "\t" pct 2 "\t" a 10 "\t" b 10 "\t" GQ 3 "\t" filter 4 "\n"   (pct 100: rgb 7, b 8 digits)        = 55
+ * a line's length fits 16 bits, eight lines always fit the image.
+ */
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "../../include/bscall_amd.h"
+#include "recstream_dev.h"
+
+static_assert(sizeof(bsc_vcf_rec) == 128 && sizeof(bsc_vcf_core) == 64, "bsc_vcf_rec is 128 bytes, its core the first 64");
+
+#define MB_WAVES 4u
+#define MB_CONTIG_MAX 255u
+#define MB_LINE_MAX (MB_CONTIG_MAX + 111u)
+#define MB_IMG 4096u /* the wave's image: a tile of 64 ordinary lines (~60 bytes each) in one part */
+#define MB_PARTS 8u
+static_assert(MB_IMG >= (RS_LANES / MB_PARTS) * MB_LINE_MAX && MB_IMG % 16u == 0u, "an eighth of a tile of the longest lines must fit the wave's image");
+static_assert(MB_LINE_MAX <= 0xffffu, "a line's length is kept in 16 bits");
+
+struct mb_args {
+  rs_src src;
+  const uint8_t *emit; /* the chain's byte per position (not 0 <=> a record is written), or NULL */
+  int32_t all_contexts;
+  uint32_t min_cov, min_phred;
+  int32_t pass_only;
+  uint32_t clen1;        /* the contig's name and the tab behind it, bytes */
+  uint32_t contig_w[64]; /* those bytes, zero padded */
+};
+
+/* what a line is made of */
+struct mb_site {
+  uint32_t pos, a, b;
+  unsigned minus, label, flt, phred; /* label: 0 CG, 1 CHG, 2 CHH, 3 CHN */
+};
+
+/* record / position i: does it give a line, and of what.  known: the caller knows it does (the size pass said so) — the loads leave
+ * together; otherwise the record's first 16 bytes decide whether the others are fetched. */
+__device__ __forceinline__ bool mb_site_of(mb_site &s, const mb_args &a, uint64_t i, bool known) {
+  const uint4 *lo = reinterpret_cast<const uint4 *>(a.src.recs ? a.src.recs + i * 128u : a.src.core + i * 64u);
+  const uint4 *hi = a.src.recs ? lo + 4 : reinterpret_cast<const uint4 *>(a.src.aux + i * 64u);
+  const uint4 v0 = lo[0];
+  const unsigned emit = v0.y & 0xffu, gt = (v0.y >> 8) & 0xffu, flt = v0.z & 0xffu, phred = (v0.z >> 8) & 0xffu, cg = v0.z >> 24;
+  if (!known) {
+    if (!emit || (gt != 4u && gt != 7u)) return false;
+    if (cg != 'C' && !(a.all_contexts && cg == 'H')) return false;
+    if (phred < a.min_phred || (a.pass_only && flt)) return false;
+  }
+  const uint4 v1 = lo[1], c1 = hi[1]; /* bytes 16 .. 31 (cx_gt: 19 .. 23), counts[4 .. 7] */
+  s.minus = gt == 7u;
+  s.a = s.minus ? c1.z : c1.y; /* counts[6] : counts[5] */
+  s.b = s.minus ? c1.x : c1.w; /* counts[4] : counts[7] */
+  const uint64_t cov = (uint64_t)s.a + s.b;
+  if (!known && cov < (uint64_t)(a.min_cov > 1u ? a.min_cov : 1u)) return false;
+  s.pos = v0.x;
+  s.flt = flt;
+  s.phred = phred;
+  s.label = 0u;
+  if (cg != 'C') {
+    const unsigned n2 = s.minus ? v1.x >> 24 : v1.y >> 24; /* cx_gt[0] = byte 19, cx_gt[4] = byte 23 */
+    if (n2 == (s.minus ? 'C' : 'G')) s.label = 1u;
+    else s.label = (n2 == 'A' || n2 == 'C' || n2 == 'G' || n2 == 'T') ? 2u : 3u;
+  }
+  return true;
+}
+
+struct mb_count_sink {
+  unsigned len;
+  __device__ __forceinline__ void u8(unsigned) { len++; }
+  __device__ __forceinline__ void bytes(uint64_t, unsigned n) { len += n; }
+  __device__ __forceinline__ void words(const uint32_t *, unsigned n_bytes) { len += n_bytes; }
+};
+struct mb_write_sink {
+  uint8_t *p;
+  unsigned len;
+  __device__ __forceinline__ void u8(unsigned v) { p[len++] = (uint8_t)v; }
+  /* the low n (<= 8) bytes of bits, the lowest first, and not one more */
+  __device__ __forceinline__ void bytes(uint64_t bits, unsigned n) {
+    for (unsigned k = 0; k < n; k++) p[len + k] = (uint8_t)(bits >> (8u * k));
+    len += n;
+  }
+  /* n_bytes of w, rounded up to whole dwords: up to 3 bytes behind them are garbage until the line's next column lands on them (a
+   * line goes on for 30 bytes at least behind its contig) */
+  __device__ __forceinline__ void words(const uint32_t *w, unsigned n_bytes) {
+    for (unsigned k = 0u; 4u * k < n_bytes; k++) __builtin_memcpy(p + len + 4u * k, &w[k], 4);
+    len += n_bytes;
+  }
+};
+
+/* v < 10^8 in decimal, the first digit in the lowest byte */
+__device__ __forceinline__ uint64_t mb_dec8(uint32_t v, unsigned &n) {
+  uint64_t acc = 0ull;
+  n = 0u;
+  do {
+    const uint32_t q = v / 10u;
+    acc = acc << 8 | (uint64_t)('0' + (v - q * 10u));
+    v = q;
+    n++;
+  } while (v);
+  return acc;
+}
+
+/* v < 10^16 in decimal and sep behind it */
+template <class S>
+__device__ __forceinline__ void mb_put_dec(S &s, uint64_t v, unsigned sep) {
+  unsigned n;
+  if (v >= 100000000ull) {
+    const uint64_t top = v / 100000000ull;
+    uint32_t low = (uint32_t)(v - top * 100000000ull);
+    const uint64_t c = mb_dec8((uint32_t)top, n);
+    s.bytes(c, n);
+    uint64_t acc = 0ull;
+    for (int i = 0; i < 8; i++) {
+      const uint32_t q = low / 10u;
+      acc = acc << 8 | (uint64_t)('0' + (low - q * 10u));
+      low = q;
+    }
+    s.bytes(acc, 8u);
+  } else {
+    const uint64_t c = mb_dec8((uint32_t)v, n);
+    s.bytes(c, n);
+  }
+  s.u8(sep);
+}
+
+/* (200 a + n) / (2 n), n = a + b > 0: the largest q of 0 .. 100 with 2 n q <= 200 a + n */
+__device__ __forceinline__ unsigned mb_pct(uint64_t a, uint64_t n) {
+  const uint64_t num = 200ull * a + n, den = 2ull * n;
+  unsigned lo = 0u, hi = 100u;
+  while (lo < hi) {
+    const unsigned mid = (lo + hi + 1u) >> 1;
+    if (den * mid <= num) lo = mid; else hi = mid - 1u;
+  }
+  return lo;
+}
+
+#define MB_STR4(a, b, c, d) ((uint64_t)(a) | (uint64_t)(b) << 8 | (uint64_t)(c) << 16 | (uint64_t)(d) << 24)
+
+template <class S>
+__device__ __forceinline__ void mb_emit_line(S &s, const mb_site &m, const uint32_t *contig_w, unsigned clen1) {
+  const uint64_t cov = (uint64_t)m.a + m.b;
+  const unsigned pct = mb_pct(m.a, cov);
+  const uint32_t start = m.pos - 1u;
+  s.words(contig_w, clen1);
+  mb_put_dec(s, start, '\t');
+  mb_put_dec(s, m.pos, '\t');
+  if (m.label == 0u) s.bytes(MB_STR4('C', 'G', '\t', 0), 3u);
+  else s.bytes(MB_STR4('C', 'H', m.label == 1u ? 'G' : (m.label == 2u ? 'H' : 'N'), '\t'), 4u);
+  mb_put_dec(s, cov < 1000ull ? cov : 1000ull, '\t');
+  s.bytes((uint64_t)(m.minus ? '-' : '+') | (uint64_t)'\t' << 8, 2u);
+  mb_put_dec(s, start, '\t');
+  mb_put_dec(s, m.pos, '\t');
+  { /* itemRgb: green up to 50 %, red from there */
+    const unsigned k = pct / 10u;
+    const unsigned r = k < 5u ? (k ? 5u + 50u * k : 0u) : 255u, g = k <= 5u ? 255u : (k < 10u ? 5u + 50u * (10u - k) : 0u);
+    mb_put_dec(s, r, ',');
+    mb_put_dec(s, g, ',');
+    s.bytes((uint64_t)'0' | (uint64_t)'\t' << 8, 2u);
+  }
+  mb_put_dec(s, cov, '\t');
+  mb_put_dec(s, pct, '\t');
+  mb_put_dec(s, m.a, '\t');
+  mb_put_dec(s, m.b, '\t');
+  mb_put_dec(s, m.phred, '\t');
+  s.bytes((m.flt == 0u ? MB_STR4('P', 'A', 'S', 'S') : ((m.flt & 128u) ? MB_STR4('m', 'a', 'c', '1') : MB_STR4('f', 'a', 'i', 'l'))) | (uint64_t)'\n' << 32, 5u);
+}
+
+/* n_tiles = tiles of max_recs; tile_bytes[n_tiles] = 0 (so that the scan's last output is the stream's length); sums[0] += lines,
+ * sums[1] += their a, sums[2] += their b */
+extern "C" __global__ __launch_bounds__(256) void bsc_meth_size_kernel(mb_args a, uint32_t n_tiles, unsigned long long *__restrict__ tile_bytes,
+                                                                       uint16_t *__restrict__ line_len, unsigned long long *__restrict__ sums) {
+  __shared__ unsigned long long s_sum[3];
+  const unsigned lane = threadIdx.x & 63u;
+  const uint64_t n = rs_clamp_n(a.src);
+  if (threadIdx.x < 3u) s_sum[threadIdx.x] = 0ull;
+  if (blockIdx.x == 0 && threadIdx.x == 0) tile_bytes[n_tiles] = 0ull;
+  __syncthreads();
+  unsigned long long n_lines = 0ull, sum_a = 0ull, sum_b = 0ull; /* this lane's */
+  for (uint32_t tile = blockIdx.x * MB_WAVES + (threadIdx.x >> 6); tile < n_tiles; tile += gridDim.x * MB_WAVES) {
+    const uint64_t i = (uint64_t)tile * 64u + lane;
+    unsigned len = 0u;
+    mb_site m;
+    if (i < n && (!a.emit || a.emit[i]) && mb_site_of(m, a, i, false)) {
+      mb_count_sink c = {0u};
+      mb_emit_line(c, m, a.contig_w, a.clen1);
+      len = c.len;
+      n_lines++;
+      sum_a += m.a;
+      sum_b += m.b;
+    }
+    if (i < a.src.max_recs) line_len[i] = (uint16_t)len;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) len += __shfl_xor(len, d);
+    if (lane == 0) tile_bytes[tile] = len;
+  }
+  /* once per wave into the workgroup's words, once per workgroup into the totals (atomics on one word are served one after the other) */
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    n_lines += __shfl_xor(n_lines, d);
+    sum_a += __shfl_xor(sum_a, d);
+    sum_b += __shfl_xor(sum_b, d);
+  }
+  if (lane == 0 && n_lines) {
+    atomicAdd(&s_sum[0], n_lines);
+    atomicAdd(&s_sum[1], sum_a);
+    atomicAdd(&s_sum[2], sum_b);
+  }
+  __syncthreads();
+  if (threadIdx.x < 3u && s_sum[threadIdx.x]) atomicAdd(sums + threadIdx.x, s_sum[threadIdx.x]);
+}
+
+extern "C" __global__ __launch_bounds__(256) void bsc_meth_write_kernel(mb_args a, uint32_t n_tiles, const unsigned long long *__restrict__ tile_off,
+                                                                        const uint16_t *__restrict__ line_len, uint8_t *__restrict__ out, uint64_t out_cap,
+                                                                        unsigned long long *__restrict__ total) {
+  __shared__ __attribute__((aligned(16))) uint8_t s_img[MB_WAVES][MB_IMG + 32u]; /* 15 bytes of phase in front */
+  const unsigned lane = threadIdx.x & 63u, wid = threadIdx.x >> 6;
+  uint8_t *const img = s_img[wid];
+  const uint64_t n = rs_clamp_n(a.src);
+  if (blockIdx.x == 0 && threadIdx.x == 0) *total = tile_off[n_tiles];
+  for (uint32_t tile = blockIdx.x * MB_WAVES + wid; tile < n_tiles; tile += gridDim.x * MB_WAVES) {
+    if ((uint64_t)tile * 64u >= n) break; /* wave-uniform; later tiles of this wave lie further out still */
+    const uint64_t g_tile = tile_off[tile], g_end = tile_off[tile + 1u];
+    if (g_end == g_tile) continue;  /* no line in this tile: nothing of it is read */
+    if (g_end > out_cap) continue;  /* the host reports the overflow from *total */
+    const uint64_t i = (uint64_t)tile * 64u + lane;
+    const unsigned len = i < n ? line_len[i] : 0u;
+    mb_site m;
+    if (len) (void)mb_site_of(m, a, i, true);
+    unsigned excl, t_all;
+    const unsigned inc = rs_wave_excl_scan(len, excl, t_all);
+    const unsigned parts = rs_pick_parts<MB_IMG, MB_PARTS>(inc);
+    const unsigned step = 64u / parts;
+    unsigned b0 = 0u; /* the part's first byte within the tile */
+    for (unsigned ps = 0; ps < parts; ps++) {
+      const unsigned b1 = rs_lane(inc, step * (ps + 1u) - 1u); /* one past its last */
+      const bool mine = len && excl >= b0 && excl < b1;
+      const uint64_t g0 = g_tile + b0;
+      const unsigned ph = (unsigned)(g0 & 15u);
+      if (mine) {
+        mb_write_sink w = {img + ph + (excl - b0), 0u};
+        mb_emit_line(w, m, a.contig_w, a.clen1);
+      }
+      rs_wave_sync();
+      rs_copy_out(img, out + (g0 - ph), lane, rs_copy_ranges(ph, b1 - b0)); /* the image [ph, ph + t) -> out[g0, g0 + t) */
+      rs_wave_sync();
+      b0 = b1;
+    }
+  }
+}
+
+extern "C" int bsc_dev_scan_u64(const void *in, void *out, uint32_t n, void *tmp, size_t tmp_bytes, void *stream); /* sort.hip */
+
+/*
+ * recs[<= max_recs] packed records, *n_recs of them (device u64) — or, recs == NULL, core[max_recs] / aux[max_recs] as the reads-in
+ * chain leaves them, emit its byte per position or NULL — -> out[<= out_cap] lines; totals[0] = the stream's length (also when it
+ * exceeds out_cap: then only the tiles that fit whole are written), totals[1 .. 3] += lines, the sum of their a, of their b (the
+ * caller zeroes them).  contig: the name, contig_len (1 .. 255) bytes, checked by the caller.  tile_bytes / tile_off: max_recs / 64
+ * (rounded up) + 1 u64 each; line_len: max_recs u16; scan_tmp: bsc_dev_scan_tmp_bytes_u64 of the tiles + 1.
+ */
+extern "C" int bsc_dev_launch_meth(const void *recs, const void *core, const void *aux, const void *n_recs, uint64_t max_recs, const void *emit,
+                                   const char *contig, uint32_t contig_len, const bsc_meth_params *par, void *tile_bytes, void *tile_off, void *line_len,
+                                   void *scan_tmp, size_t scan_tmp_bytes, void *out, uint64_t out_cap, void *totals, int num_cus, void *stream) {
+  hipStream_t s = (hipStream_t)stream;
+  if (!contig_len || contig_len > MB_CONTIG_MAX || !par) return (int)hipErrorInvalidValue;
+  mb_args a;
+  a.src = rs_make_src(recs, core, aux, n_recs, max_recs, NULL, NULL, NULL, 0u);
+  a.emit = recs ? NULL : (const uint8_t *)emit;
+  a.all_contexts = par->contexts == BSC_METH_ALL;
+  a.min_cov = par->min_cov;
+  a.min_phred = par->min_phred;
+  a.pass_only = par->pass_only != 0;
+  a.clen1 = contig_len + 1u;
+  for (int k = 0; k < 64; k++) a.contig_w[k] = 0u;
+  __builtin_memcpy(a.contig_w, contig, contig_len);
+  ((char *)a.contig_w)[contig_len] = '\t';
+  const uint64_t nt64 = (max_recs + 63u) / 64u;
+  if (nt64 > 0x7fffffffull) return (int)hipErrorInvalidValue;
+  const uint32_t n_tiles = (uint32_t)nt64;
+  unsigned grid = (n_tiles + MB_WAVES - 1u) / MB_WAVES;
+  if (grid > (unsigned)num_cus * 8u) grid = (unsigned)num_cus * 8u;
+  if (grid == 0) grid = 1;
+  hipLaunchKernelGGL(bsc_meth_size_kernel, dim3(grid), dim3(256), 0, s, a, n_tiles, (unsigned long long *)tile_bytes, (uint16_t *)line_len,
+                     (unsigned long long *)totals + 1);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return (int)e;
+  const int rc = bsc_dev_scan_u64(tile_bytes, tile_off, n_tiles + 1u, scan_tmp, scan_tmp_bytes, stream);
+  if (rc) return rc;
+  hipLaunchKernelGGL(bsc_meth_write_kernel, dim3(grid), dim3(256), 0, s, a, n_tiles, (const unsigned long long *)tile_off, (const uint16_t *)line_len,
+                     (uint8_t *)out, out_cap, (unsigned long long *)totals);
+  return (int)hipGetLastError();
+}

@@ -17,7 +17,7 @@ def run(bam_path: str, reference: Dict[str, np.ndarray], bcf_path: str, sample: 
         caller: Optional[SiteCaller] = None, dbsnp=None, compressed: bool = True, date=None, left_trim=(0, 0), right_trim=(0, 0),
         min_qual: Optional[int] = None, benchmark_mode: bool = False, under_conv: Optional[float] = None, over_conv: Optional[float] = None,
         host_prep: bool = False, host_bcf: bool = False, device_reader: bool = False, shard_rank: Optional[int] = None, shard_world: int = 1,
-        reduce_device=None, text: bool = False, dbsnp_device: bool = False, **reader_kw) -> dict:
+        reduce_device=None, text: bool = False, dbsnp_device: bool = False, meth_path: Optional[str] = None, meth_params=None, **reader_kw) -> dict:
     """reference: contig name -> uint8 reference codes (0 = N, 1..4 = ACGT; position 1 first).  Returns a summary dict.
     under_conv / over_conv / min_qual (defaults 0.01 / 0.05 / 20, src/init_param.c:26-31) are the MODEL's parameters: without
     `caller` the run builds its SiteCaller from them; with one, they are taken from it and a differing explicit value is an error
@@ -36,7 +36,13 @@ def run(bam_path: str, reference: Dict[str, np.ndarray], bcf_path: str, sample: 
     text, then every block's lines as the device's text encoder writes them (SiteCaller.block_vcf_rawdev: bsc_block_vcf_rawdev_keep).  Needs
     device_reader; a sharded text run is refused.
     dbsnp_device: with a `dbsnp` and the device reader, each contig of the index is kept in HBM (SiteCaller.dbsnp_attach at the contig
-    change) and the blocks' flags and names are made there (csrc/dbsnpdev.hip) instead of on this thread — same bytes, same report."""
+    change) and the blocks' flags and names are made there (csrc/dbsnpdev.hip) instead of on this thread — same bytes, same report.
+    meth_path: the per-cytosine methylation table (bedMethyl; include/bscall_amd.h has the line) of the same run, written beside the output:
+    every block's lines from the arrays the block left on the device (SiteCaller.block_meth_kept, csrc/methdev.hip); with `compressed`,
+    BGZF like the main file.  meth_params: a _lib.MethParams or a dict of its fields (default: CpG cytosines, every covered site).  Needs
+    device_reader and is refused where text=True is; the main file and the report are those of the run without it."""
+    if meth_path is not None and (shard_rank is not None or not device_reader or host_prep or host_bcf):
+        raise ValueError("meth_path is a single run on the device reader (device_reader=True, no shard_rank, no host_prep / host_bcf)")
     if dbsnp_device and not device_reader:
         raise ValueError("dbsnp_device=True needs the device reader (device_reader=True)")
     if dbsnp_device and shard_rank is not None:
@@ -62,6 +68,7 @@ def run(bam_path: str, reference: Dict[str, np.ndarray], bcf_path: str, sample: 
         passed = np.zeros(2, dtype=np.uint64)
         per_contig = []
         n_blocks = n_records = 0
+        meth_blobs, meth_lines = [], 0
         c.reset_site_stats()
         sharded = shard_rank is not None
         if sharded:
@@ -93,7 +100,7 @@ def run(bam_path: str, reference: Dict[str, np.ndarray], bcf_path: str, sample: 
                                      dbsnp_header=None if dbsnp is None else dbsnp.header, benchmark_mode=benchmark_mode)
 
             def block_blobs():
-                nonlocal n_blocks, n_records, base_filter, passed
+                nonlocal n_blocks, n_records, base_filter, passed, meth_lines
                 before, cur_tid = c.site_totals(), -1
                 for item in (rd.device_blocks() if device_reader else rd.blocks()):
                     if device_reader:
@@ -130,7 +137,11 @@ def run(bam_path: str, reference: Dict[str, np.ndarray], bcf_path: str, sample: 
                                                                  reg_stop=len(codes), dbsnp=flags, with_stats=True, profile=prof)
                         else:
                             blob, n_rec, st = c.block_bcf_rawdev(dblk, ref, tid, names=names, left_trim=left_trim, right_trim=right_trim, min_qual=min_qual,
-                                                                 reg_stop=len(codes), dbsnp=flags, with_stats=True, profile=prof)
+                                                                 reg_stop=len(codes), dbsnp=flags, with_stats=True, profile=prof, keep=meth_path is not None)
+                        if meth_path is not None:  # the same block's table, from what it left on the device
+                            mb, ml, _ = c.block_meth_kept(name, meth_params)
+                            meth_blobs.append(mb)
+                            meth_lines += ml
                         recs = None
                     elif host_prep:  # round 4's split: the process thread's per-template work here, then the block
                         tpl, pseq, st = prepare_templates(raw, seq, ms, left_trim, right_trim, min_qual, profile=prof, x=x, ref=ref)
@@ -167,6 +178,8 @@ def run(bam_path: str, reference: Dict[str, np.ndarray], bcf_path: str, sample: 
                 vcf.write_vcf_blobs(bcf_path, header, block_blobs(), compressed)
             else:
                 vcf.write_bcf(bcf_path, header, block_blobs(), compressed)  # blocks go to the writer as they are formed
+            if meth_path is not None:
+                vcf.write_vcf_blobs(meth_path, "", meth_blobs, compressed)
             cts, bases = rd.filter_counts()
         cts[0] += int(passed[0])
         bases[0] += int(passed[1])
@@ -230,7 +243,10 @@ def run(bam_path: str, reference: Dict[str, np.ndarray], bcf_path: str, sample: 
         if report_path and (not sharded or shard_rank == 0):
             with open(report_path, "w") as f:
                 f.write(report_text)
-        return {"blocks": n_blocks, "records": n_records, "report": report_text, "filter_cts": cts, "contigs": [n for n, _ in per_contig]}
+        summary = {"blocks": n_blocks, "records": n_records, "report": report_text, "filter_cts": cts, "contigs": [n for n, _ in per_contig]}
+        if meth_path is not None:
+            summary["meth_lines"] = meth_lines
+        return summary
     finally:
         if own:
             c.close()

@@ -1060,6 +1060,60 @@ int bsc_block_vcf_rawdev_keep(bsc_context *ctx, const void *d_raw, uint32_t nr, 
                               uint64_t ins_pad, const bsc_prep_params *prep, uint32_t x, uint32_t y, const uint8_t *ref, const uint8_t *dbsnp,
                               const bsc_vcf_params *params, int with_stats, const char *contig, const bsc_bcf_names *names, uint64_t dev_cap,
                               uint64_t *n_bytes, uint64_t *n_records, bsc_prep_stats *prep_stats, bsc_read_profile *profile);
+/*
+ * The per-cytosine methylation table (bedMethyl) on the device (csrc/methdev.hip; the host form csrc/methbed.c is its checker): the
+ * third encoder over a block's records, and the first whose output is the caller's result rather than a serialisation of it.  The
+ * reference has the rule for its report's CpG_ref_meth / CpG_nonref_meth histograms only (src/print_vcf.c:442-515); a record gives a
+ * line iff
+ *   core.emit != 0;  core.gt == 4 (CC, strand '+') or 7 (GG, strand '-');  core.cg == 'C', or 'H' with contexts == BSC_METH_ALL;
+ *   a + b >= max(1, min_cov), a the non-converted and b the converted count of the strand: counts[5], counts[7] for '+',
+ *   counts[6], counts[4] for '-' (:450-451, :472-473, and the reference's `if(a + b)`);  core.phred >= min_phred;
+ *   !pass_only || core.flt == 0.
+ * The line: 15 tab-separated columns and '\n', every number plain decimal —
+ *   chrom  start = pos - 1  end = pos  name  score = min(a + b, 1000)  strand  start  end  itemRgb  a + b  pct  a  b  GQ = phred  FILTER
+ *   name      "CG" for cg == 'C'; else by the called second neighbour (cx_gt[4] for '+', cx_gt[0] for '-'): "CHG" when it is 'G' ('+') /
+ *             'C' ('-'), "CHH" for one of the other three of A C G T, "CHN" for anything else
+ *   pct       (200 a + (a + b)) / (2 (a + b)) in 64 bits: 100 a / (a + b) rounded half up
+ *   itemRgb   entry pct / 10 of 0,255,0 55,255,0 105,255,0 155,255,0 205,255,0 255,255,0 255,205,0 255,155,0 255,105,0 255,55,0 255,0,0
+ *   FILTER    the text bsc_vcf_format_rec writes in that column: PASS, mac1 (flt & 128), fail
+ * contig: 1 .. 255 bytes without a tab or a newline (BSC_ERR_ARG otherwise).  The longest line is the contig's name + 111 bytes.
+ *   bsc_meth_format_rec     the host form: returns the length written (no NUL), 0 when the record gives no line, the length needed —
+ *                           and nothing written — when cap is too small, < 0 for a bad argument
+ *   bsc_meth_block_device   d_recs[<= max_recs] packed records in HBM, *d_n_recs of them (a device u64) -> d_out[<= out_cap] bytes
+ *                           (16-byte aligned); d_totals = four device u64 {length of the stream, lines, sum of a, sum of b}; a stream
+ *                           longer than out_cap is cut at a 64-record boundary, its full length still in d_totals[0].  Asynchronous
+ *                           on `stream`; uses workspaces of the context (one encoding in flight per context).
+ *   bsc_meth_sites_device   the same from the per-position arrays bsc_reads_chain_device leaves (d_core[n], d_aux[n]); a position
+ *                           without a record costs the 16 bytes that hold its emit flag
+ *   bsc_block_meth_kept     the follow-up of bsc_block_bcf_rawdev_keep / bsc_block_vcf_rawdev_keep (and of bsc_block_bcf_again behind
+ *                           them): the table of THAT block, from the per-position arrays it left in HBM, into a buffer of the
+ *                           context's own (room: dev_cap bytes).  The kept BCF / text stream, its tile offsets and bsc_block_csi_kept
+ *                           are untouched, before or after.  dev_cap too small: BSC_ERR_ARG with *n_bytes = the room needed, and the
+ *                           call may be repeated.  sums = {sum of a, sum of b} (may be NULL).  BSC_ERR_ARG when the last call on the
+ *                           context left no single block's arrays: nothing kept, a block pending, the batched entries.  Waits.
+ *   bsc_meth_stream_read    bytes [off, off + n) of that table -> dst, queued on the context's stream (bsc_bcf_stream_read's twin)
+ *   bsc_meth_stream_detach  the table handed over like bsc_bcf_stream_detach hands the kept stream over: bsc_detached_read / _wait /
+ *                           _free or bsc_bgzf_write_device on it (it counts against the four pooled buffers out); the context forgets it
+ * Not built: a combined-strand line per CpG dinucleotide, bigWig, the batched and host-buffer block entries.
+ */
+#define BSC_METH_CPG 0
+#define BSC_METH_ALL 1
+typedef struct {
+  int32_t contexts;   /* BSC_METH_CPG: CpG cytosines only; BSC_METH_ALL: CHG / CHH too */
+  uint32_t min_cov;   /* a + b at least this (and at least 1) */
+  uint32_t min_phred; /* core.phred at least this */
+  int32_t pass_only;  /* not 0: records with FILTER PASS only */
+} bsc_meth_params;
+void bsc_meth_params_default(bsc_meth_params *p); /* {BSC_METH_CPG, 1, 0, 0} */
+long bsc_meth_format_rec(const bsc_vcf_rec *r, const char *contig, const bsc_meth_params *p, char *buf, size_t cap);
+int bsc_meth_block_device(bsc_context *ctx, const void *d_recs, const void *d_n_recs, uint64_t max_recs, const char *contig,
+                          const bsc_meth_params *params, void *d_out, uint64_t out_cap, void *d_totals, void *stream);
+int bsc_meth_sites_device(bsc_context *ctx, const void *d_core, const void *d_aux, uint32_t n, const char *contig, const bsc_meth_params *params,
+                          void *d_out, uint64_t out_cap, void *d_totals, void *stream);
+int bsc_block_meth_kept(bsc_context *ctx, const char *contig, const bsc_meth_params *p, uint64_t dev_cap, uint64_t *n_bytes, uint64_t *n_lines,
+                        uint64_t sums[2]);
+int bsc_meth_stream_read(bsc_context *ctx, uint64_t off, uint64_t n, void *dst);
+int bsc_meth_stream_detach(bsc_context *ctx, void **d_stream, uint64_t *n_bytes);
 /* with bsc_set_profiling: device time (HIP events on the context's stream) of the most recent raw block — bsc_block_records_raw[dev],
  * bsc_block_bcf_raw[dev][_keep] — from its first pre-processing launch to the last launch it queued, the host's wait for the prepared size included */
 int bsc_last_raw_block_ms(bsc_context *ctx, float *ms);

@@ -55,6 +55,12 @@
  * the report's dbSNP counters.  Each contig of the index is loaded by the thread that loads its reference, kept in HBM (bsc_dbsnp_attach at
  * the contig change) and the blocks' flags and names are made there (csrc/dbsnpdev.hip): the block calls pass NULL for both.  The header is
  * the --benchmark-mode header, which has no ##dbsnp line.  With either -O and either --format; a single run on the device reader only.
+ * Methylation table: --meth out.bed writes, beside the BCF / VCF of the same run, the bedMethyl line of every cytosine the rule of
+ * include/bscall_amd.h admits (CpG cytosines called CC / GG; --meth-all: CHG / CHH too; --meth-min-cov N, --meth-min-gq N, --meth-pass: the
+ * thresholds), encoded on the device from the arrays the block call left there (bsc_block_meth_kept, csrc/methdev.hip) — nothing is read
+ * back out of the records' stream.  The table changes hands like the block's stream (bsc_meth_stream_detach) and goes through the same
+ * output thread, as one more job of its own file; with -O b through a second BGZF writer.  With either --format, with -D and --index; the
+ * BCF / VCF, the .csi and the report are those of the run without it.  A single run on the device reader only.
  */
 #include <pthread.h>
 #include <stdio.h>
@@ -107,7 +113,7 @@ static void *pinned(size_t n) { /* page-locked: the copy-out is a true DMA, queu
  * ONE writer: three of them writing pieces of one file in parallel were 2.5 x slower (0.70 s against 0.28 for the 2.9 GB of a contig-sized
  * block: writes to one inode take turns anyway).  Page-locking a host buffer for a whole stream would cost more than the calling. */
 #define PIECE ((size_t)32 << 20)
-#define N_JOB 3
+#define N_JOB 4 /* (a block is two jobs with --meth) */
 typedef struct {
   void *d;        /* the stream on the device; NULL: only close_fd */
   uint64_t n, at; /* its length, where it goes in the file */
@@ -424,7 +430,13 @@ static int merge_main(int world, char **argv, const char *sample) {
 
 int main(int argc, char **argv) {
   int rank = -1, world = 1, merge = 0, bgzf = 0, text = 0, index = 0;
-  const char *dbsnp_path = NULL;
+  const char *dbsnp_path = NULL, *meth_path = NULL;
+  bsc_meth_params mpar;
+  bsc_meth_params_default(&mpar);
+  if (argc >= 2 && !strcmp(argv[argc - 1], "--meth") && (argc == 2 || strcmp(argv[argc - 2], "--meth"))) {
+    fprintf(stderr, "%s: --meth takes the path of the methylation table to write (bedMethyl)\n", argv[0]);
+    return 2;
+  }
   if (argc == 2 && !strcmp(argv[1], "-D")) {
     fprintf(stderr, "%s: -D takes the path of a dbSNP index (the file dbSNP_idx writes)\n", argv[0]);
     return 2;
@@ -451,8 +463,10 @@ int main(int argc, char **argv) {
       argc -= k;
       continue;
     }
-    if (!strcmp(argv[1], "--index")) { /* no value */
-      index = 1;
+    if (!strcmp(argv[1], "--index") || !strcmp(argv[1], "--meth-all") || !strcmp(argv[1], "--meth-pass")) { /* no value */
+      if (argv[1][2] == 'i') index = 1;
+      else if (argv[1][7] == 'a') mpar.contexts = BSC_METH_ALL;
+      else mpar.pass_only = 1;
       argv[1] = argv[0];
       argv += 1;
       argc -= 1;
@@ -461,6 +475,17 @@ int main(int argc, char **argv) {
     if (!strcmp(argv[1], "--rank")) rank = atoi(argv[2]);
     else if (!strcmp(argv[1], "--world")) world = atoi(argv[2]);
     else if (!strcmp(argv[1], "--merge")) merge = atoi(argv[2]);
+    else if (!strcmp(argv[1], "--meth")) meth_path = argv[2];
+    else if (!strcmp(argv[1], "--meth-min-cov") || !strcmp(argv[1], "--meth-min-gq")) {
+      char *end = NULL;
+      const unsigned long v = strtoul(argv[2], &end, 10);
+      if (!argv[2][0] || *end || argv[2][0] == '-' || v > 0xfffffffful) {
+        fprintf(stderr, "%s: %s takes a count, not '%s'\n", argv[0], argv[1], argv[2]);
+        return 2;
+      }
+      if (argv[1][11] == 'c') mpar.min_cov = (uint32_t)v;
+      else mpar.min_phred = (uint32_t)v;
+    }
     else if (!strcmp(argv[1], "--format")) { /* bcf: BCF2 records (the default).  vcf: text lines, encoded on the device as well */
       if (strcmp(argv[2], "bcf") && strcmp(argv[2], "vcf")) {
         fprintf(stderr, "%s: --format takes bcf or vcf, not '%s'\n", argv[0], argv[2]);
@@ -474,7 +499,7 @@ int main(int argc, char **argv) {
     argc -= 2;
   }
   if (argc < 5 || world < 1 || (rank >= 0 && rank >= world)) {
-    fprintf(stderr, "usage: %s [-O u|b] [--format bcf|vcf] [--index] [-D dbsnp.idx] [--rank r --world n | --merge n] in.bam ref.fa out.bcf report.json [sample]\n", argv[0]);
+    fprintf(stderr, "usage: %s [-O u|b] [--format bcf|vcf] [--index] [-D dbsnp.idx] [--meth out.bed [--meth-all] [--meth-min-cov n] [--meth-min-gq n] [--meth-pass]] [--rank r --world n | --merge n] in.bam ref.fa out.bcf report.json [sample]\n", argv[0]);
     return 2;
   }
   if (text && (rank >= 0 || merge > 0)) {
@@ -503,6 +528,14 @@ int main(int argc, char **argv) {
   }
   if (dbsnp_path && (getenv("BAM2BCF_HOST_PREP") || getenv("BAM2BCF_HOST_BCF") || getenv("BAM2BCF_HOST_READER"))) {
     fprintf(stderr, "%s: -D keeps the index on the device, for the device reader's blocks: not with BAM2BCF_HOST_READER / _HOST_BCF / _HOST_PREP\n", argv[0]);
+    return 2;
+  }
+  if (meth_path && (rank >= 0 || world > 1 || merge > 0)) {
+    fprintf(stderr, "%s: --meth writes a single run's table; a sharded run (--rank / --world / --merge) has none\n", argv[0]);
+    return 2;
+  }
+  if (meth_path && (getenv("BAM2BCF_HOST_PREP") || getenv("BAM2BCF_HOST_BCF") || getenv("BAM2BCF_HOST_READER"))) {
+    fprintf(stderr, "%s: --meth encodes what the device reader's blocks leave on the device: not with BAM2BCF_HOST_READER / _HOST_BCF / _HOST_PREP\n", argv[0]);
     return 2;
   }
   const char *sample = argc > 5 ? argv[5] : "SAMPLE";
@@ -557,6 +590,19 @@ int main(int argc, char **argv) {
     return 1;
   }
   const int n_ref = N_REFS();
+  int meth_fd = -1;
+  uint64_t meth_at = 0, meth_lines = 0;
+  bsc_bgzf *zm = NULL;
+  if (meth_path) {
+    FILE *mf = fopen(meth_path, "wb");
+    if (!mf) {
+      perror(meth_path);
+      return 1;
+    }
+    meth_fd = dup(fileno(mf));
+    fclose(mf);
+    if (bgzf) CHECK(bsc_bgzf_open(ctx, &zm));
+  }
   bsc_bgzf *zw = NULL;
   bsc_csi *csi = NULL;
   if (!sharded) {
@@ -724,6 +770,30 @@ int main(int argc, char **argv) {
         CHECK(bsc_block_csi_kept(ctx, 14, &ce, &cn, NULL));
         CHECK(bsc_csi_add(csi, dblk.tid, ce, cn, n_bytes));
       }
+      if (n_bytes && meth_path) { /* the block's methylation table, from the arrays the call left on the device: a buffer and a job of its own */
+        uint64_t m_cap = (uint64_t)n * (mpar.contexts == BSC_METH_ALL ? 16 : 4) + 4096, m_bytes = 0, m_lines = 0;
+        int mrc = bsc_block_meth_kept(ctx, REF_NAME(dblk.tid), &mpar, m_cap, &m_bytes, &m_lines, NULL);
+        if (mrc == BSC_ERR_ARG && m_bytes > m_cap) mrc = bsc_block_meth_kept(ctx, REF_NAME(dblk.tid), &mpar, m_bytes, &m_bytes, &m_lines, NULL);
+        CHECK(mrc);
+        meth_lines += m_lines;
+        if (m_bytes) {
+          void *d_m = NULL;
+          uint64_t n_m = 0;
+          CHECK(bsc_meth_stream_detach(ctx, &d_m, &n_m));
+          if (zm) {
+            CHECK(bsc_bgzf_write_device(zm, d_m, n_m));
+            CHECK(bsc_detached_free(ctx, d_m));
+            d_m = NULL;
+            n_m = 0;
+            CHECK(bsc_bgzf_take(zm, &d_m, &n_m));
+          }
+          if (n_m) {
+            const out_job j = {d_m, n_m, meth_at, meth_fd, 0};
+            writer_push(&W, j);
+          }
+          meth_at += n_m;
+        }
+      }
       if (n_bytes) { /* the stream changes hands: the output thread reads it out and writes it while this one goes on to the next block */
         void *d_stream = NULL;
         uint64_t n_det = 0;
@@ -840,6 +910,17 @@ int main(int argc, char **argv) {
       csi = NULL;
     }
   }
+  if (zm) { /* the table's last member and its end-of-file marker */
+    void *d_z = NULL;
+    uint64_t n_z = 0;
+    CHECK(bsc_bgzf_close(zm, &d_z, &n_z));
+    zm = NULL;
+    if (n_z) {
+      const out_job j = {d_z, n_z, meth_at, meth_fd, 0};
+      writer_push(&W, j);
+    }
+    meth_at += n_z;
+  }
   if (W.started) { /* the output thread writes what it still holds, then goes */
     pthread_mutex_lock(&W.mu);
     W.quit = 1;
@@ -852,6 +933,10 @@ int main(int argc, char **argv) {
     }
     t_enc += (t1 = now()) - t0;
     t0 = t1;
+  }
+  if (meth_fd >= 0 && close(meth_fd)) {
+    perror(meth_path);
+    return 1;
   }
   const double t_loop_end = now();
   if (cur_tid >= 0) {
@@ -938,6 +1023,7 @@ int main(int argc, char **argv) {
     fwrite(text, 1, (size_t)need, fr);
     fclose(fr);
     printf("%llu blocks, %llu records written\n", (unsigned long long)n_blocks, (unsigned long long)n_records);
+    if (meth_path) printf("%llu methylation table lines written\n", (unsigned long long)meth_lines);
   }
   if (getenv("BAM2BCF_TIMING")) {
     uint64_t rc4[4] = {0, 0, 0, 0};
