@@ -180,6 +180,10 @@ EXPORTS = (
     "bsc_block_meth_kept",
     "bsc_meth_stream_read",
     "bsc_meth_stream_detach",
+    "bsc_meth_cpg_format_recs",
+    "bsc_meth_cpg_block_device",
+    "bsc_meth_cpg_sites_device",
+    "bsc_block_meth_cpg_kept",
 )
 
 
@@ -701,5 +705,13 @@ def load():
     L.bsc_meth_stream_read.argtypes = [vp, u64, u64, vp]
     L.bsc_meth_stream_detach.restype = i32
     L.bsc_meth_stream_detach.argtypes = [vp, C.POINTER(vp), C.POINTER(u64)]
+    L.bsc_meth_cpg_format_recs.restype = C.c_long
+    L.bsc_meth_cpg_format_recs.argtypes = [vp, C.c_size_t, C.c_char_p, C.POINTER(MethParams), vp, C.c_size_t, C.POINTER(u64)]
+    L.bsc_meth_cpg_block_device.restype = i32
+    L.bsc_meth_cpg_block_device.argtypes = [vp, vp, vp, u64, C.c_char_p, C.POINTER(MethParams), vp, u64, vp, vp]
+    L.bsc_meth_cpg_sites_device.restype = i32
+    L.bsc_meth_cpg_sites_device.argtypes = [vp, vp, vp, u32, C.c_char_p, C.POINTER(MethParams), vp, u64, vp, vp]
+    L.bsc_block_meth_cpg_kept.restype = i32
+    L.bsc_block_meth_cpg_kept.argtypes = [vp, C.c_char_p, C.POINTER(MethParams), u64, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)]
     _lib = L
     return L

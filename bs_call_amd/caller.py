@@ -839,24 +839,37 @@ class SiteCaller:
         mp = self._meth_params(params)
         _check(self._L.bsc_meth_sites_device(self._h, d_core, d_aux, n, self._contig_bytes(contig), C.byref(mp), d_out, out_cap, d_totals, stream))
 
-    def block_meth_kept(self, contig, params=None, cap=None):
+    def meth_cpg_block_device(self, d_recs, d_n_recs, max_recs, contig, d_out, out_cap, d_totals, params=None, stream=None):
+        """bsc_meth_cpg_block_device: packed records in HBM -> the combined-strand CpG table (one line per dinucleotide) in HBM
+        (asynchronous on `stream`); d_totals: FIVE u64 {length, lines, sum of A, sum of B, pairs written}."""
+        mp = self._meth_params(params)
+        _check(self._L.bsc_meth_cpg_block_device(self._h, d_recs, d_n_recs, max_recs, self._contig_bytes(contig), C.byref(mp), d_out, out_cap, d_totals, stream))
+
+    def meth_cpg_sites_device(self, d_core, d_aux, n, contig, d_out, out_cap, d_totals, params=None, stream=None):
+        """bsc_meth_cpg_sites_device: the per-position arrays of reads_chain_device (d_core, d_aux) -> the combined-strand CpG table."""
+        mp = self._meth_params(params)
+        _check(self._L.bsc_meth_cpg_sites_device(self._h, d_core, d_aux, n, self._contig_bytes(contig), C.byref(mp), d_out, out_cap, d_totals, stream))
+
+    def block_meth_kept(self, contig, params=None, cap=None, merge=False):
         """bsc_block_meth_kept + bsc_meth_stream_read: the bedMethyl table of the block the last *_keep call called (block_vcf_rawdev,
         block_bcf_rawdev(keep=True)), from the arrays that block left on the device.  params: a _lib.MethParams, a dict of its fields, or
         None (CpG, every covered site).  Returns (bytes, lines, (sum of a, sum of b)).  cap: the room on the device (default: asked for
-        and given on a second call)."""
+        and given on a second call).  merge: the combined-strand table, one line per CpG dinucleotide (bsc_block_meth_cpg_kept); the
+        sums are then (sum of A, sum of B, pairs written)."""
         mp = self._meth_params(params)
-        nb, nl, sums = C.c_uint64(0), C.c_uint64(0), (C.c_uint64 * 2)()
+        entry = self._L.bsc_block_meth_cpg_kept if merge else self._L.bsc_block_meth_kept
+        nb, nl, sums = C.c_uint64(0), C.c_uint64(0), (C.c_uint64 * (3 if merge else 2))()
         room = 1 << 16 if cap is None else int(cap)
-        rc = self._L.bsc_block_meth_kept(self._h, self._contig_bytes(contig), C.byref(mp), room, C.byref(nb), C.byref(nl), sums)
+        rc = entry(self._h, self._contig_bytes(contig), C.byref(mp), room, C.byref(nb), C.byref(nl), sums)
         if rc == -1 and nb.value > room and cap is None:
             room = int(nb.value)
-            rc = self._L.bsc_block_meth_kept(self._h, self._contig_bytes(contig), C.byref(mp), room, C.byref(nb), C.byref(nl), sums)
+            rc = entry(self._h, self._contig_bytes(contig), C.byref(mp), room, C.byref(nb), C.byref(nl), sums)
         _check(rc)
         out = np.empty(max(int(nb.value), 1), dtype=np.uint8)
         if nb.value:
             _check(self._L.bsc_meth_stream_read(self._h, 0, nb.value, _ptr(out)))
             self.synchronize()
-        return out[: nb.value].tobytes(), int(nl.value), (int(sums[0]), int(sums[1]))
+        return out[: nb.value].tobytes(), int(nl.value), tuple(int(v) for v in sums)
 
     def blocks_records(self, blocks, ref, out=None, all_positions=False, reg_start=1, reg_stop=0xFFFFFFFF, dbsnp=None, with_stats=False,
                        submit_only=False):

@@ -84,7 +84,7 @@ int bsc_dev_launch_vcf_text(const void *recs, const void *core, const void *aux,
 int bsc_dev_launch_fmt_g(const void *v, uint64_t n, void *out16, int num_cus, void *stream);
 int bsc_dev_launch_meth(const void *recs, const void *core, const void *aux, const void *n_recs, uint64_t max_recs, const void *emit, const char *contig,
                         uint32_t contig_len, const bsc_meth_params *par, void *tile_bytes, void *tile_off, void *line_len, void *scan_tmp,
-                        size_t scan_tmp_bytes, void *out, uint64_t out_cap, void *totals, int num_cus, void *stream); /* methdev.hip */
+                        size_t scan_tmp_bytes, void *out, uint64_t out_cap, void *totals, int cpg, int num_cus, void *stream); /* methdev.hip */
 int bsc_dev_launch_ref_pad(const void *packed, const void *d_blk, uint32_t n_blk, void *padded, uint32_t n_pos, int num_cus, void *stream);
 int bsc_dev_launch_bin_reads_multi(const void *tpl, uint32_t nr, const void *seq, uint64_t seq_bytes, const void *d_blk, uint32_t n_blk,
                                    uint32_t n_bins, void *tflag, void *bin_cnt, void *bin_off, void *bin_cur, void *scan_tmp,
@@ -2880,13 +2880,14 @@ int bsc_bcf_stream_read(bsc_context *ctx, uint64_t off, uint64_t n, void *dst) {
   return BSC_OK;
 }
 
-/* ---- the per-cytosine methylation table (methdev.hip): the line bsc_meth_format_rec writes, per record that gives one ---------------- */
+/* ---- the methylation tables (methdev.hip): per cytosine, the line bsc_meth_format_rec writes per record that gives one; cpg != 0: per CpG
+ * dinucleotide, the table bsc_meth_cpg_format_recs writes (d_totals: five u64) ------------------------------------------------------------ */
 static void bsc_pool_init(bsc_context *ctx); /* (with the BGZF writer, below) */
 static void *bsc_pool_get(bsc_context *ctx, size_t need, size_t *cap);
 static void bsc_pool_book(bsc_context *ctx, void *p, size_t cap);
 static int bsc_meth_encode(bsc_context *ctx, const char *who, const void *d_recs, const void *d_core, const void *d_aux, const void *d_n_recs,
-                           uint64_t max_recs, const void *d_emit, const char *contig, const bsc_meth_params *par, void *d_out, uint64_t out_cap,
-                           void *d_totals, void *stream) {
+                           uint64_t max_recs, const void *d_emit, const char *contig, const bsc_meth_params *par, int cpg, void *d_out,
+                           uint64_t out_cap, void *d_totals, void *stream) {
   uint32_t contig_len = 0;
   int rc;
   if ((rc = bsc_stream_args_check(ctx, who, d_recs, d_core, d_aux, d_n_recs, max_recs, d_out, out_cap, d_totals))) return rc;
@@ -2894,6 +2895,7 @@ static int bsc_meth_encode(bsc_context *ctx, const char *who, const void *d_recs
   if (!par) return bsc_fail(BSC_ERR_ARG, "%s: NULL argument", who);
   if (par->contexts != BSC_METH_CPG && par->contexts != BSC_METH_ALL)
     return bsc_fail(BSC_ERR_ARG, "%s: contexts is %d, not BSC_METH_CPG or BSC_METH_ALL", who, (int)par->contexts);
+  if (cpg && par->contexts != BSC_METH_CPG) return bsc_fail(BSC_ERR_ARG, "%s: contexts must be BSC_METH_CPG: only a CpG has a partner strand", who);
   BSC_ENTER(ctx);
   hipStream_t s = (hipStream_t)stream;
   const uint32_t n_tiles = (uint32_t)((max_recs + 63u) / 64u);
@@ -2903,9 +2905,9 @@ static int bsc_meth_encode(bsc_context *ctx, const char *who, const void *d_recs
   if ((rc = bsc_reserve(&ctx->d_mto, &ctx->cap_mto, ((size_t)n_tiles + 1u) * 8u))) return rc;
   if ((rc = bsc_reserve(&ctx->d_mscn, &ctx->cap_mscn, scan_bytes ? scan_bytes : 1))) return rc;
   if ((rc = bsc_reserve(&ctx->d_mll, &ctx->cap_mll, ((size_t)n_tiles + 1u) * 128u))) return rc;
-  HIP_TRY(hipMemsetAsync(d_totals, 0, 4 * sizeof(unsigned long long), s));
+  HIP_TRY(hipMemsetAsync(d_totals, 0, (cpg ? 5 : 4) * sizeof(unsigned long long), s));
   const int e = bsc_dev_launch_meth(d_recs, d_core, d_aux, d_n_recs, max_recs, d_emit, contig, contig_len, par, ctx->d_mtb, ctx->d_mto, ctx->d_mll,
-                                    ctx->d_mscn, scan_bytes, d_out, out_cap, d_totals, ctx->num_cus, stream);
+                                    ctx->d_mscn, scan_bytes, d_out, out_cap, d_totals, cpg, ctx->num_cus, stream);
   if (e) return bsc_fail(BSC_ERR_HIP, "methylation table encoder launch failed: %s", hipGetErrorString((hipError_t)e));
   return BSC_OK;
 }
@@ -2914,24 +2916,37 @@ int bsc_meth_block_device(bsc_context *ctx, const void *d_recs, const void *d_n_
                           const bsc_meth_params *params, void *d_out, uint64_t out_cap, void *d_totals, void *stream) {
   if (!d_n_recs || (max_recs && !d_recs)) return bsc_fail(BSC_ERR_ARG, "bsc_meth_block_device: NULL argument");
   /* (no records at all: the per-position form over zero positions — nothing is read) */
-  return bsc_meth_encode(ctx, "bsc_meth_block_device", d_recs, NULL, NULL, d_recs ? d_n_recs : NULL, max_recs, NULL, contig, params, d_out, out_cap,
+  return bsc_meth_encode(ctx, "bsc_meth_block_device", d_recs, NULL, NULL, d_recs ? d_n_recs : NULL, max_recs, NULL, contig, params, 0, d_out, out_cap,
                          d_totals, stream);
+}
+
+int bsc_meth_cpg_block_device(bsc_context *ctx, const void *d_recs, const void *d_n_recs, uint64_t max_recs, const char *contig,
+                              const bsc_meth_params *params, void *d_out, uint64_t out_cap, void *d_totals, void *stream) {
+  if (!d_n_recs || (max_recs && !d_recs)) return bsc_fail(BSC_ERR_ARG, "bsc_meth_cpg_block_device: NULL argument");
+  return bsc_meth_encode(ctx, "bsc_meth_cpg_block_device", d_recs, NULL, NULL, d_recs ? d_n_recs : NULL, max_recs, NULL, contig, params, 1, d_out,
+                         out_cap, d_totals, stream);
 }
 
 int bsc_meth_sites_device(bsc_context *ctx, const void *d_core, const void *d_aux, uint32_t n, const char *contig, const bsc_meth_params *params,
                           void *d_out, uint64_t out_cap, void *d_totals, void *stream) {
-  return bsc_meth_encode(ctx, "bsc_meth_sites_device", NULL, d_core, d_aux, NULL, n, NULL, contig, params, d_out, out_cap, d_totals, stream);
+  return bsc_meth_encode(ctx, "bsc_meth_sites_device", NULL, d_core, d_aux, NULL, n, NULL, contig, params, 0, d_out, out_cap, d_totals, stream);
+}
+
+int bsc_meth_cpg_sites_device(bsc_context *ctx, const void *d_core, const void *d_aux, uint32_t n, const char *contig, const bsc_meth_params *params,
+                              void *d_out, uint64_t out_cap, void *d_totals, void *stream) {
+  return bsc_meth_encode(ctx, "bsc_meth_cpg_sites_device", NULL, d_core, d_aux, NULL, n, NULL, contig, params, 1, d_out, out_cap, d_totals, stream);
 }
 
 /* the table of the block the last _keep call called: from d_vout / d_out, which stay what the chain left until the next block, by the chain's
  * byte per position where the block has one — into d_meth, a buffer that is not the kept stream's */
-int bsc_block_meth_kept(bsc_context *ctx, const char *contig, const bsc_meth_params *p, uint64_t dev_cap, uint64_t *n_bytes, uint64_t *n_lines,
-                        uint64_t sums[2]) {
-  if (!ctx || !n_bytes || !n_lines) return bsc_fail(BSC_ERR_ARG, "bsc_block_meth_kept: NULL argument");
+static int bsc_meth_kept(bsc_context *ctx, const char *who, int cpg, const char *contig, const bsc_meth_params *p, uint64_t dev_cap, uint64_t *n_bytes,
+                         uint64_t *n_lines, uint64_t *sums) {
+  const int n_sums = cpg ? 3 : 2;
+  if (!ctx || !n_bytes || !n_lines) return bsc_fail(BSC_ERR_ARG, "%s: NULL argument", who);
   *n_bytes = *n_lines = 0;
-  if (sums) sums[0] = sums[1] = 0;
+  for (int k = 0; sums && k < n_sums; k++) sums[k] = 0;
   if (ctx->meth_src != 1 || ctx->rec_pending || ctx->pending_sz)
-    return bsc_fail(BSC_ERR_ARG, "bsc_block_meth_kept: the last call left no single block's arrays on the device");
+    return bsc_fail(BSC_ERR_ARG, "%s: the last call left no single block's arrays on the device", who);
   BSC_ENTER(ctx);
   hipStream_t s = ctx->stream;
   int rc;
@@ -2939,20 +2954,28 @@ int bsc_block_meth_kept(bsc_context *ctx, const char *contig, const bsc_meth_par
   /* a buffer that came back (bsc_detached_free), the smallest that will do: the large ones are the kept streams' */
   if (!ctx->d_meth && ctx->pool_mu_made) ctx->d_meth = bsc_pool_get(ctx, (size_t)(dev_cap ? dev_cap : 1), &ctx->cap_meth);
   if ((rc = bsc_reserve(&ctx->d_meth, &ctx->cap_meth, (size_t)(dev_cap ? dev_cap : 1)))) return rc;
-  if ((rc = bsc_reserve(&ctx->d_mtot, &ctx->cap_mtot, 4 * sizeof(unsigned long long)))) return rc;
-  if ((rc = bsc_meth_encode(ctx, "bsc_block_meth_kept", NULL, ctx->d_vout, ctx->d_out, NULL, ctx->again.sz, ctx->again.emit, contig, p, ctx->d_meth, dev_cap,
-                            ctx->d_mtot, s)))
+  if ((rc = bsc_reserve(&ctx->d_mtot, &ctx->cap_mtot, 5 * sizeof(unsigned long long)))) return rc;
+  if ((rc = bsc_meth_encode(ctx, who, NULL, ctx->d_vout, ctx->d_out, NULL, ctx->again.sz, ctx->again.emit, contig, p, cpg, ctx->d_meth, dev_cap, ctx->d_mtot, s)))
     return rc;
-  unsigned long long tot[4] = {0, 0, 0, 0};
-  HIP_TRY(hipMemcpyAsync(tot, ctx->d_mtot, sizeof tot, hipMemcpyDeviceToHost, s));
+  unsigned long long tot[5] = {0, 0, 0, 0, 0};
+  HIP_TRY(hipMemcpyAsync(tot, ctx->d_mtot, (size_t)(2 + n_sums) * sizeof tot[0], hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
   *n_bytes = tot[0];
   *n_lines = tot[1];
-  if (sums) sums[0] = tot[2], sums[1] = tot[3];
-  if (tot[0] > dev_cap)
-    return bsc_fail(BSC_ERR_ARG, "bsc_block_meth_kept: the block's table has %llu bytes, dev_cap is %llu", tot[0], (unsigned long long)dev_cap);
+  for (int k = 0; sums && k < n_sums; k++) sums[k] = tot[2 + k];
+  if (tot[0] > dev_cap) return bsc_fail(BSC_ERR_ARG, "%s: the block's table has %llu bytes, dev_cap is %llu", who, tot[0], (unsigned long long)dev_cap);
   ctx->meth_bytes = tot[0];
   return BSC_OK;
+}
+
+int bsc_block_meth_kept(bsc_context *ctx, const char *contig, const bsc_meth_params *p, uint64_t dev_cap, uint64_t *n_bytes, uint64_t *n_lines,
+                        uint64_t sums[2]) {
+  return bsc_meth_kept(ctx, "bsc_block_meth_kept", 0, contig, p, dev_cap, n_bytes, n_lines, sums);
+}
+
+int bsc_block_meth_cpg_kept(bsc_context *ctx, const char *contig, const bsc_meth_params *p, uint64_t dev_cap, uint64_t *n_bytes, uint64_t *n_lines,
+                            uint64_t sums[3]) {
+  return bsc_meth_kept(ctx, "bsc_block_meth_cpg_kept", 1, contig, p, dev_cap, n_bytes, n_lines, sums);
 }
 
 int bsc_meth_stream_read(bsc_context *ctx, uint64_t off, uint64_t n, void *dst) {

@@ -1,6 +1,7 @@
-"""The per-cytosine methylation table (bedMethyl): the host form of the line (bsc_meth_format_rec, csrc/methbed.c — the checker of the
-device's encoder, csrc/methdev.hip) and a reader of the files bam2bcf --meth / pipeline.run(meth_path=...) write.  include/bscall_amd.h
-has the rule and the columns."""
+"""The methylation tables (bedMethyl): the host form of the per-cytosine line (bsc_meth_format_rec, csrc/methbed.c) and of the
+combined-strand CpG table (bsc_meth_cpg_format_recs, csrc/methcpg.c) — the checkers of the device's encoders, csrc/methdev.hip — and a
+reader of the files bam2bcf --meth [--meth-merge] / pipeline.run(meth_path=..., meth_merge=...) write.  include/bscall_amd.h has the rules
+and the columns."""
 import ctypes as C
 import gzip
 
@@ -48,6 +49,25 @@ def format_recs(recs, contig, p=None):
             raise ValueError("bsc_meth_format_rec: bad argument")
         out.append(buf.raw[:n])
     return b"".join(out)
+
+
+def format_cpg_recs(recs, contig, p=None, totals=False):
+    """The combined-strand CpG table of packed records (VCF_REC[]) in order: one line per CpG dinucleotide, both strands' counts added
+    (bsc_meth_cpg_format_recs, csrc/methcpg.c — the checker of the device's combined encoder).  totals: return (bytes, [length, lines,
+    sum of A, sum of B, pairs written]) instead of the bytes alone."""
+    L = _lib.load()
+    rb = np.ascontiguousarray(recs).view(np.uint8).reshape(-1, 128)
+    p = params() if p is None else p
+    name = contig if isinstance(contig, (bytes, bytearray)) else str(contig).encode()
+    tot = (C.c_uint64 * 5)()
+    base = rb.ctypes.data if len(rb) else None
+    n = L.bsc_meth_cpg_format_recs(base, len(rb), name, C.byref(p), None, 0, tot)
+    if n < 0:
+        raise ValueError("bsc_meth_cpg_format_recs: bad argument")
+    buf = C.create_string_buffer(max(n, 1))
+    if L.bsc_meth_cpg_format_recs(base, len(rb), name, C.byref(p), buf, n, tot) != n:
+        raise ValueError("bsc_meth_cpg_format_recs: the length changed between two calls")
+    return (buf.raw[:n], [int(v) for v in tot]) if totals else buf.raw[:n]
 
 
 def parse_bed(data):

@@ -17,7 +17,8 @@ def run(bam_path: str, reference: Dict[str, np.ndarray], bcf_path: str, sample: 
         caller: Optional[SiteCaller] = None, dbsnp=None, compressed: bool = True, date=None, left_trim=(0, 0), right_trim=(0, 0),
         min_qual: Optional[int] = None, benchmark_mode: bool = False, under_conv: Optional[float] = None, over_conv: Optional[float] = None,
         host_prep: bool = False, host_bcf: bool = False, device_reader: bool = False, shard_rank: Optional[int] = None, shard_world: int = 1,
-        reduce_device=None, text: bool = False, dbsnp_device: bool = False, meth_path: Optional[str] = None, meth_params=None, **reader_kw) -> dict:
+        reduce_device=None, text: bool = False, dbsnp_device: bool = False, meth_path: Optional[str] = None, meth_params=None, meth_merge: bool = False,
+        **reader_kw) -> dict:
     """reference: contig name -> uint8 reference codes (0 = N, 1..4 = ACGT; position 1 first).  Returns a summary dict.
     under_conv / over_conv / min_qual (defaults 0.01 / 0.05 / 20, src/init_param.c:26-31) are the MODEL's parameters: without
     `caller` the run builds its SiteCaller from them; with one, they are taken from it and a differing explicit value is an error
@@ -40,7 +41,13 @@ def run(bam_path: str, reference: Dict[str, np.ndarray], bcf_path: str, sample: 
     meth_path: the per-cytosine methylation table (bedMethyl; include/bscall_amd.h has the line) of the same run, written beside the output:
     every block's lines from the arrays the block left on the device (SiteCaller.block_meth_kept, csrc/methdev.hip); with `compressed`,
     BGZF like the main file.  meth_params: a _lib.MethParams or a dict of its fields (default: CpG cytosines, every covered site).  Needs
-    device_reader and is refused where text=True is; the main file and the report are those of the run without it."""
+    device_reader and is refused where text=True is; the main file and the report are those of the run without it.  meth_merge: the table
+    is the combined-strand one, a line per CpG dinucleotide with both strands' counts added (bsc_block_meth_cpg_kept); needs meth_path and
+    CpG-only meth_params."""
+    if meth_merge and meth_path is None:
+        raise ValueError("meth_merge=True combines the strands of the table meth_path names: it needs meth_path")
+    if meth_merge and meth_params is not None and (meth_params.contexts if hasattr(meth_params, "contexts") else meth_params.get("contexts", 0)) != 0:
+        raise ValueError("meth_merge=True is the CpG table: only a CpG has a partner strand (meth_params.contexts must be BSC_METH_CPG)")
     if meth_path is not None and (shard_rank is not None or not device_reader or host_prep or host_bcf):
         raise ValueError("meth_path is a single run on the device reader (device_reader=True, no shard_rank, no host_prep / host_bcf)")
     if dbsnp_device and not device_reader:
@@ -139,7 +146,7 @@ def run(bam_path: str, reference: Dict[str, np.ndarray], bcf_path: str, sample: 
                             blob, n_rec, st = c.block_bcf_rawdev(dblk, ref, tid, names=names, left_trim=left_trim, right_trim=right_trim, min_qual=min_qual,
                                                                  reg_stop=len(codes), dbsnp=flags, with_stats=True, profile=prof, keep=meth_path is not None)
                         if meth_path is not None:  # the same block's table, from what it left on the device
-                            mb, ml, _ = c.block_meth_kept(name, meth_params)
+                            mb, ml, _ = c.block_meth_kept(name, meth_params, merge=meth_merge)
                             meth_blobs.append(mb)
                             meth_lines += ml
                         recs = None

@@ -1094,7 +1094,7 @@ int bsc_block_vcf_rawdev_keep(bsc_context *ctx, const void *d_raw, uint32_t nr, 
  *   bsc_meth_stream_read    bytes [off, off + n) of that table -> dst, queued on the context's stream (bsc_bcf_stream_read's twin)
  *   bsc_meth_stream_detach  the table handed over like bsc_bcf_stream_detach hands the kept stream over: bsc_detached_read / _wait /
  *                           _free or bsc_bgzf_write_device on it (it counts against the four pooled buffers out); the context forgets it
- * Not built: a combined-strand line per CpG dinucleotide, bigWig, the batched and host-buffer block entries.
+ * Not built: bigWig, the batched and host-buffer block entries.  (The combined-strand line per CpG dinucleotide: bsc_meth_cpg_*, below.)
  */
 #define BSC_METH_CPG 0
 #define BSC_METH_ALL 1
@@ -1114,6 +1114,52 @@ int bsc_block_meth_kept(bsc_context *ctx, const char *contig, const bsc_meth_par
                         uint64_t sums[2]);
 int bsc_meth_stream_read(bsc_context *ctx, uint64_t off, uint64_t n, void *dst);
 int bsc_meth_stream_detach(bsc_context *ctx, void **d_stream, uint64_t *n_bytes);
+/*
+ * The combined-strand CpG table (csrc/methdev.hip: bsc_meth_cpg_size_kernel / _write_kernel; the host form csrc/methcpg.c is its checker):
+ * one line per CpG dinucleotide, both strands' counts added.  A CpG is one site read from two strands: the C at p shows on the '+' strand,
+ * the G at p + 1 is the '-' strand's C.  The reference pairs the two for its report only (prev_cpg_x, src/print_vcf.c:442-475).  This is the
+ * one encoder whose line depends on a record's neighbours.  The rule, from which the host form, the tests' Python form and the kernels are
+ * each written:
+ *   HALVES   a record is a half iff it passes the per-cytosine rule with contexts = BSC_METH_CPG, except the coverage threshold:
+ *            core.emit != 0;  core.gt == 4 (plus half) or 7 (minus half);  core.cg == 'C';  core.phred >= min_phred;
+ *            !pass_only || core.flt == 0;  a + b >= 1 (a, b as above: counts[5], counts[7] for plus, counts[6], counts[4] for minus).
+ *   PAIRS    a plus half at position p and a minus half at p + 1 (compared in 64 bits: 2^32 - 1 has no partner) that is the NEXT record
+ *            form a pair.  Packed form: record i + 1 with pos == p + 1.  Per-position form: index i + 1, with the same pos test, and its
+ *            emit byte not 0 where that array is given.  Every other half is a single.  A record is a half of at most one pair (CC and GG
+ *            exclude each other).  Records at or beyond the count (*d_n_recs, n) do not exist, whatever their bytes hold.
+ *   LINES    a pair gives ONE line, placed at its plus half; a single gives one line; a minus half that belongs to a pair gives none.
+ *            A and B are the sums of the halves' a and b, in 64 bits.  The line is written iff A + B >= max(1, min_cov): the threshold
+ *            is on the sum (a pair below it gives no line at all).
+ *   COLUMNS  the 15 columns of the per-cytosine table:
+ *            start    the plus position - 1; for a single minus half at q: q - 2.  Modulo 2^32, as pos - 1 above.
+ *            end      start + 2, in 64 bits (2^32 + 1 at most); thick start / thick end repeat start / end
+ *            name     CG
+ *            strand   '.' for a pair, '+' or '-' for a single
+ *            score    min(A + B, 1000);  coverage A + B;  pct and itemRgb from A and A + B exactly as above;  then A, B
+ *            GQ       the smaller phred of the halves
+ *            FILTER   from the OR of the halves' flt: fail if flt & 127, else mac1 if flt & 128, else PASS
+ * Consequences: lines come out in record order with strictly increasing start (positions increase); no carry between blocks is needed —
+ * the reader starts a new block only where two positions or more are uncovered (src/get_template_vector.c:141-147), so two adjacent
+ * positions that both have records lie in one block.  contexts == BSC_METH_ALL is refused (BSC_ERR_ARG; -1 from the host form): only a CpG
+ * has a partner strand here.  The longest line is the contig's name + 111 bytes, as above: the name is a byte shorter, A + B (2^34 - 4 at
+ * most) a digit longer.
+ *   bsc_meth_cpg_format_recs   the host form: the table of recs[0 .. n) in order -> buf; returns the length written, the length needed —
+ *                              and nothing written — when cap is too small, < 0 for a bad argument.  totals (may be NULL) = {length,
+ *                              lines, sum of A, sum of B, pairs written}
+ *   bsc_meth_cpg_block_device  bsc_meth_block_device's twin;  d_totals = FIVE device u64 {length, lines, sum of A, sum of B, pairs written}
+ *   bsc_meth_cpg_sites_device  bsc_meth_sites_device's twin
+ *   bsc_block_meth_cpg_kept    bsc_block_meth_kept's twin: the same source arrays, the same emit-byte gate, the same conditions, into the same
+ *                              buffer of the context — bsc_meth_stream_read / _detach serve it unchanged.  sums = {sum of A, sum of B,
+ *                              pairs written} (may be NULL)
+ */
+long bsc_meth_cpg_format_recs(const bsc_vcf_rec *recs, size_t n, const char *contig, const bsc_meth_params *p, char *buf, size_t cap,
+                              uint64_t totals[5]);
+int bsc_meth_cpg_block_device(bsc_context *ctx, const void *d_recs, const void *d_n_recs, uint64_t max_recs, const char *contig,
+                              const bsc_meth_params *params, void *d_out, uint64_t out_cap, void *d_totals, void *stream);
+int bsc_meth_cpg_sites_device(bsc_context *ctx, const void *d_core, const void *d_aux, uint32_t n, const char *contig, const bsc_meth_params *params,
+                              void *d_out, uint64_t out_cap, void *d_totals, void *stream);
+int bsc_block_meth_cpg_kept(bsc_context *ctx, const char *contig, const bsc_meth_params *p, uint64_t dev_cap, uint64_t *n_bytes, uint64_t *n_lines,
+                            uint64_t sums[3]);
 /* with bsc_set_profiling: device time (HIP events on the context's stream) of the most recent raw block — bsc_block_records_raw[dev],
  * bsc_block_bcf_raw[dev][_keep] — from its first pre-processing launch to the last launch it queued, the host's wait for the prepared size included */
 int bsc_last_raw_block_ms(bsc_context *ctx, float *ms);

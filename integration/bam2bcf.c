@@ -60,7 +60,8 @@
  * thresholds), encoded on the device from the arrays the block call left there (bsc_block_meth_kept, csrc/methdev.hip) — nothing is read
  * back out of the records' stream.  The table changes hands like the block's stream (bsc_meth_stream_detach) and goes through the same
  * output thread, as one more job of its own file; with -O b through a second BGZF writer.  With either --format, with -D and --index; the
- * BCF / VCF, the .csi and the report are those of the run without it.  A single run on the device reader only.
+ * BCF / VCF, the .csi and the report are those of the run without it.  A single run on the device reader only.  --meth-merge: the table
+ * is the combined-strand one — a line per CpG dinucleotide, both strands' counts added (bsc_block_meth_cpg_kept); not with --meth-all.
  */
 #include <pthread.h>
 #include <stdio.h>
@@ -429,7 +430,7 @@ static int merge_main(int world, char **argv, const char *sample) {
 }
 
 int main(int argc, char **argv) {
-  int rank = -1, world = 1, merge = 0, bgzf = 0, text = 0, index = 0;
+  int rank = -1, world = 1, merge = 0, bgzf = 0, text = 0, index = 0, meth_merge = 0;
   const char *dbsnp_path = NULL, *meth_path = NULL;
   bsc_meth_params mpar;
   bsc_meth_params_default(&mpar);
@@ -463,8 +464,9 @@ int main(int argc, char **argv) {
       argc -= k;
       continue;
     }
-    if (!strcmp(argv[1], "--index") || !strcmp(argv[1], "--meth-all") || !strcmp(argv[1], "--meth-pass")) { /* no value */
+    if (!strcmp(argv[1], "--index") || !strcmp(argv[1], "--meth-all") || !strcmp(argv[1], "--meth-pass") || !strcmp(argv[1], "--meth-merge")) { /* no value */
       if (argv[1][2] == 'i') index = 1;
+      else if (argv[1][7] == 'm') meth_merge = 1;
       else if (argv[1][7] == 'a') mpar.contexts = BSC_METH_ALL;
       else mpar.pass_only = 1;
       argv[1] = argv[0];
@@ -499,7 +501,7 @@ int main(int argc, char **argv) {
     argc -= 2;
   }
   if (argc < 5 || world < 1 || (rank >= 0 && rank >= world)) {
-    fprintf(stderr, "usage: %s [-O u|b] [--format bcf|vcf] [--index] [-D dbsnp.idx] [--meth out.bed [--meth-all] [--meth-min-cov n] [--meth-min-gq n] [--meth-pass]] [--rank r --world n | --merge n] in.bam ref.fa out.bcf report.json [sample]\n", argv[0]);
+    fprintf(stderr, "usage: %s [-O u|b] [--format bcf|vcf] [--index] [-D dbsnp.idx] [--meth out.bed [--meth-merge | --meth-all] [--meth-min-cov n] [--meth-min-gq n] [--meth-pass]] [--rank r --world n | --merge n] in.bam ref.fa out.bcf report.json [sample]\n", argv[0]);
     return 2;
   }
   if (text && (rank >= 0 || merge > 0)) {
@@ -528,6 +530,14 @@ int main(int argc, char **argv) {
   }
   if (dbsnp_path && (getenv("BAM2BCF_HOST_PREP") || getenv("BAM2BCF_HOST_BCF") || getenv("BAM2BCF_HOST_READER"))) {
     fprintf(stderr, "%s: -D keeps the index on the device, for the device reader's blocks: not with BAM2BCF_HOST_READER / _HOST_BCF / _HOST_PREP\n", argv[0]);
+    return 2;
+  }
+  if (meth_merge && !meth_path) {
+    fprintf(stderr, "%s: --meth-merge combines the strands of the table --meth writes: it needs --meth out.bed\n", argv[0]);
+    return 2;
+  }
+  if (meth_merge && mpar.contexts == BSC_METH_ALL) {
+    fprintf(stderr, "%s: --meth-merge with --meth-all: only a CpG has a partner strand to combine with\n", argv[0]);
     return 2;
   }
   if (meth_path && (rank >= 0 || world > 1 || merge > 0)) {
@@ -772,8 +782,10 @@ int main(int argc, char **argv) {
       }
       if (n_bytes && meth_path) { /* the block's methylation table, from the arrays the call left on the device: a buffer and a job of its own */
         uint64_t m_cap = (uint64_t)n * (mpar.contexts == BSC_METH_ALL ? 16 : 4) + 4096, m_bytes = 0, m_lines = 0;
-        int mrc = bsc_block_meth_kept(ctx, REF_NAME(dblk.tid), &mpar, m_cap, &m_bytes, &m_lines, NULL);
-        if (mrc == BSC_ERR_ARG && m_bytes > m_cap) mrc = bsc_block_meth_kept(ctx, REF_NAME(dblk.tid), &mpar, m_bytes, &m_bytes, &m_lines, NULL);
+        int (*const meth_kept)(bsc_context *, const char *, const bsc_meth_params *, uint64_t, uint64_t *, uint64_t *, uint64_t *) =
+            meth_merge ? bsc_block_meth_cpg_kept : bsc_block_meth_kept;
+        int mrc = meth_kept(ctx, REF_NAME(dblk.tid), &mpar, m_cap, &m_bytes, &m_lines, NULL);
+        if (mrc == BSC_ERR_ARG && m_bytes > m_cap) mrc = meth_kept(ctx, REF_NAME(dblk.tid), &mpar, m_bytes, &m_bytes, &m_lines, NULL);
         CHECK(mrc);
         meth_lines += m_lines;
         if (m_bytes) {
