@@ -184,6 +184,15 @@ EXPORTS = (
     "bsc_meth_cpg_block_device",
     "bsc_meth_cpg_sites_device",
     "bsc_block_meth_cpg_kept",
+    "bsc_meth_regions_sum_recs",
+    "bsc_meth_regions_format",
+    "bsc_meth_regions_parse_bed",
+    "bsc_meth_bed_free",
+    "bsc_meth_regions_attach",
+    "bsc_meth_regions_sites_device",
+    "bsc_block_meth_regions_kept",
+    "bsc_meth_regions_read",
+    "bsc_meth_regions_reset",
 )
 
 
@@ -204,6 +213,13 @@ class MethParams(C.Structure):
 
     def __init__(self, contexts=0, min_cov=1, min_phred=0, pass_only=0):
         super().__init__(int(contexts), int(min_cov), int(min_phred), int(pass_only))
+
+
+class MethBed(C.Structure):
+    """bsc_meth_bed: what bsc_meth_regions_parse_bed returns (a region is two u32: REGION in methbed.py)."""
+
+    _fields_ = [("n_contigs", C.c_uint32), ("contigs", C.POINTER(C.c_char_p)), ("first", C.POINTER(C.c_uint64)), ("n_regions", C.c_uint64),
+                ("regions", C.c_void_p), ("names", C.POINTER(C.c_char_p))]
 
 
 class VcfParams(C.Structure):
@@ -713,5 +729,23 @@ def load():
     L.bsc_meth_cpg_sites_device.argtypes = [vp, vp, vp, u32, C.c_char_p, C.POINTER(MethParams), vp, u64, vp, vp]
     L.bsc_block_meth_cpg_kept.restype = i32
     L.bsc_block_meth_cpg_kept.argtypes = [vp, C.c_char_p, C.POINTER(MethParams), u64, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)]
+    L.bsc_meth_regions_sum_recs.restype = i32
+    L.bsc_meth_regions_sum_recs.argtypes = [vp, C.c_size_t, C.POINTER(MethParams), vp, C.c_size_t, vp]
+    L.bsc_meth_regions_format.restype = C.c_long
+    L.bsc_meth_regions_format.argtypes = [C.c_char_p, vp, vp, vp, C.c_size_t, vp, C.c_size_t]
+    L.bsc_meth_regions_parse_bed.restype = i32
+    L.bsc_meth_regions_parse_bed.argtypes = [vp, C.c_size_t, C.POINTER(C.POINTER(MethBed))]
+    L.bsc_meth_bed_free.restype = None
+    L.bsc_meth_bed_free.argtypes = [C.POINTER(MethBed)]
+    L.bsc_meth_regions_attach.restype = i32
+    L.bsc_meth_regions_attach.argtypes = [vp, vp, u64]
+    L.bsc_meth_regions_sites_device.restype = i32
+    L.bsc_meth_regions_sites_device.argtypes = [vp, vp, vp, u32, u32, C.POINTER(MethParams), vp]
+    L.bsc_block_meth_regions_kept.restype = i32
+    L.bsc_block_meth_regions_kept.argtypes = [vp, C.POINTER(MethParams), C.POINTER(u64), C.POINTER(u64)]
+    L.bsc_meth_regions_read.restype = i32
+    L.bsc_meth_regions_read.argtypes = [vp, vp, u64]
+    L.bsc_meth_regions_reset.restype = i32
+    L.bsc_meth_regions_reset.argtypes = [vp]
     _lib = L
     return L

@@ -850,6 +850,51 @@ class SiteCaller:
         mp = self._meth_params(params)
         _check(self._L.bsc_meth_cpg_sites_device(self._h, d_core, d_aux, n, self._contig_bytes(contig), C.byref(mp), d_out, out_cap, d_totals, stream))
 
+    @staticmethod
+    def _regions_array(regions):
+        """(start, end) pairs, or a structured array with those fields, as contiguous uint32[n, 2]."""
+        r = np.asarray(regions)
+        if r.dtype.names:
+            r = np.stack([r["start"], r["end"]], axis=1) if len(r) else np.zeros((0, 2), np.uint32)
+        r = r.reshape(-1, 2)
+        if len(r) and (r.min() < 0 or r.max() > 0xFFFFFFFF):
+            raise ValueError("a region's coordinates are 0 .. 2^32 - 1")
+        return np.ascontiguousarray(r, dtype=np.uint32)
+
+    def meth_regions_attach(self, regions):
+        """bsc_meth_regions_attach: the regions of ONE contig — (start, end) pairs, 0-based and half-open as in BED, sorted by (start, end) —
+        uploaded, their accumulators zeroed.  An empty list detaches.  Refused (BscError) when unsorted or start > end: the previous
+        attachment then stays.  Returns the count."""
+        r = self._regions_array(regions)
+        _check(self._L.bsc_meth_regions_attach(self._h, _ptr(r) if len(r) else None, len(r)))
+        self._n_meth_regions = len(r)
+        return len(r)
+
+    def meth_regions_sites_device(self, d_core, d_aux, n, x0, params=None, stream=None):
+        """bsc_meth_regions_sites_device: the per-position arrays of reads_chain_device (entry i = position x0 + i) added into the attached
+        regions' accumulators {sites, sum of a, sum of b, sum of pct} (csrc/methregionsdev.hip; asynchronous on `stream`)."""
+        mp = self._meth_params(params)
+        _check(self._L.bsc_meth_regions_sites_device(self._h, d_core, d_aux, n, x0, C.byref(mp), stream))
+
+    def block_meth_regions_kept(self, params=None):
+        """bsc_block_meth_regions_kept: the block the last *_keep call called, added into the attached regions' accumulators from the arrays
+        it left on the device.  Returns the block's own (sites, sum of a, sum of b)."""
+        mp = self._meth_params(params)
+        ns, sums = C.c_uint64(0), (C.c_uint64 * 3)()
+        _check(self._L.bsc_block_meth_regions_kept(self._h, C.byref(mp), C.byref(ns), sums))
+        return tuple(int(v) for v in sums)
+
+    def meth_regions_read(self):
+        """bsc_meth_regions_read: the accumulators as uint64[n, 4] — per attached region {sites, A, B, P} (waits)."""
+        n = getattr(self, "_n_meth_regions", 0)
+        acc = np.zeros((n, 4), dtype=np.uint64)
+        _check(self._L.bsc_meth_regions_read(self._h, _ptr(acc) if n else None, n))
+        return acc
+
+    def meth_regions_reset(self):
+        """bsc_meth_regions_reset: the accumulators zeroed, the regions stay."""
+        _check(self._L.bsc_meth_regions_reset(self._h))
+
     def block_meth_kept(self, contig, params=None, cap=None, merge=False):
         """bsc_block_meth_kept + bsc_meth_stream_read: the bedMethyl table of the block the last *_keep call called (block_vcf_rawdev,
         block_bcf_rawdev(keep=True)), from the arrays that block left on the device.  params: a _lib.MethParams, a dict of its fields, or

@@ -85,6 +85,9 @@ int bsc_dev_launch_fmt_g(const void *v, uint64_t n, void *out16, int num_cus, vo
 int bsc_dev_launch_meth(const void *recs, const void *core, const void *aux, const void *n_recs, uint64_t max_recs, const void *emit, const char *contig,
                         uint32_t contig_len, const bsc_meth_params *par, void *tile_bytes, void *tile_off, void *line_len, void *scan_tmp,
                         size_t scan_tmp_bytes, void *out, uint64_t out_cap, void *totals, int cpg, int num_cus, void *stream); /* methdev.hip */
+int bsc_dev_launch_meth_regions(const void *core, const void *aux, const void *emit, uint64_t n, uint32_t x0, const bsc_meth_params *par, void *planes,
+                                void *scan, void *scan_tmp, size_t scan_tmp_bytes, const void *regions, uint32_t r_lo, uint32_t r_hi, void *acc,
+                                int num_cus, void *stream); /* methregionsdev.hip */
 int bsc_dev_launch_ref_pad(const void *packed, const void *d_blk, uint32_t n_blk, void *padded, uint32_t n_pos, int num_cus, void *stream);
 int bsc_dev_launch_bin_reads_multi(const void *tpl, uint32_t nr, const void *seq, uint64_t seq_bytes, const void *d_blk, uint32_t n_blk,
                                    uint32_t n_bins, void *tflag, void *bin_cnt, void *bin_off, void *bin_cur, void *scan_tmp,
@@ -177,6 +180,17 @@ struct bsc_context {
   size_t cap_mtb, cap_mto, cap_mscn, cap_mll, cap_meth, cap_mtot;
   uint64_t meth_bytes;
   int meth_src;
+  uint32_t meth_x; /* that block's first position: entry i of its arrays is position meth_x + i (bsc_block_meth_regions_kept) */
+  struct { /* bsc_meth_regions_attach: a contig's regions, sorted by (start, end), and their accumulators in HBM; on the host the starts and the
+            * running maximum of the ends, for the candidate range of a block; the workspaces of the reduction (methregionsdev.hip): the four
+            * planes of tile sums, their prefix sums, scan scratch; the stream of the last accumulating call */
+    uint64_t n;
+    void *d_reg, *d_acc;
+    uint32_t *h_start, *h_maxend;
+    void *d_pl, *d_sc, *d_tmp;
+    size_t cap_pl, cap_sc, cap_tmp;
+    hipStream_t last;
+  } mr;
   /* the CSI scan (csidev.hip): runs per interval, their prefix sum, scan scratch, the entries and {entries, records, error bits} of the
    * follow-up call bsc_block_csi_kept, its host copy; and what the last encoder call left in d_bto: for which stream, how many tiles, text */
   void *d_cscn, *d_csof, *d_cstm, *d_csen, *d_cstot;
@@ -577,6 +591,13 @@ int bsc_destroy(bsc_context *ctx) {
   hipFree(ctx->d_mll);
   hipFree(ctx->d_meth);
   hipFree(ctx->d_mtot);
+  hipFree(ctx->mr.d_reg);
+  hipFree(ctx->mr.d_acc);
+  free(ctx->mr.h_start);
+  free(ctx->mr.h_maxend);
+  hipFree(ctx->mr.d_pl);
+  hipFree(ctx->mr.d_sc);
+  hipFree(ctx->mr.d_tmp);
   hipFree(ctx->d_cscn);
   hipFree(ctx->d_csof);
   hipFree(ctx->d_cstm);
@@ -2367,6 +2388,7 @@ static int bsc_records_queue(bsc_context *ctx, const bsc_template *tpl, uint32_t
     ctx->emit_hint = d_emit;
     ctx->again.sz = sz;
     ctx->meth_src = -1; /* ONE block's arrays: bsc_block_meth_kept's source once the block has come back kept (bsc_bcf_finish) */
+    ctx->meth_x = x;
     ctx->again.rid = bcf->rid;
     ctx->again.text = bcf->text;
     if (bcf->text) {
@@ -2976,6 +2998,178 @@ int bsc_block_meth_kept(bsc_context *ctx, const char *contig, const bsc_meth_par
 int bsc_block_meth_cpg_kept(bsc_context *ctx, const char *contig, const bsc_meth_params *p, uint64_t dev_cap, uint64_t *n_bytes, uint64_t *n_lines,
                             uint64_t sums[3]) {
   return bsc_meth_kept(ctx, "bsc_block_meth_cpg_kept", 1, contig, p, dev_cap, n_bytes, n_lines, sums);
+}
+
+/* ---- the per-region methylation summary (methregionsdev.hip): include/bscall_amd.h has the rule, csrc/methregions.c the host form ------------ */
+/* what may still be adding into the accumulators: the context's stream and the stream of the last accumulating call */
+static int bsc_meth_regions_quiet(bsc_context *ctx) {
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  if (ctx->mr.last != ctx->stream) HIP_TRY(hipStreamSynchronize(ctx->mr.last));
+  ctx->mr.last = ctx->stream; /* (the caller's stream is not named again: it may be gone by the next call) */
+  return BSC_OK;
+}
+
+int bsc_meth_regions_attach(bsc_context *ctx, const bsc_meth_region *regions, uint64_t n) {
+  if (!ctx || (n && !regions)) return bsc_fail(BSC_ERR_ARG, "bsc_meth_regions_attach: NULL argument");
+  if (n > (1ull << 27)) return bsc_fail(BSC_ERR_ARG, "bsc_meth_regions_attach: %llu regions, more than 2^27", (unsigned long long)n);
+  for (uint64_t k = 0; k < n; k++) {
+    if (regions[k].start > regions[k].end)
+      return bsc_fail(BSC_ERR_ARG, "bsc_meth_regions_attach: region %llu has start %u > end %u", (unsigned long long)k, regions[k].start, regions[k].end);
+    if (k && (regions[k].start < regions[k - 1].start || (regions[k].start == regions[k - 1].start && regions[k].end < regions[k - 1].end)))
+      return bsc_fail(BSC_ERR_ARG, "bsc_meth_regions_attach: region %llu lies before region %llu: sort by (start, end)", (unsigned long long)k,
+                      (unsigned long long)k - 1);
+  }
+  BSC_ENTER(ctx);
+  int rc;
+  void *d_reg = NULL, *d_acc = NULL;
+  uint32_t *h_start = NULL, *h_maxend = NULL;
+  if (n) { /* the new attachment whole, before the old one goes: a refusal leaves the old one */
+    h_start = malloc((size_t)n * sizeof *h_start);
+    h_maxend = malloc((size_t)n * sizeof *h_maxend);
+    hipError_t e = h_start && h_maxend ? hipMalloc(&d_reg, (size_t)n * sizeof *regions) : hipErrorOutOfMemory;
+    if (e == hipSuccess) e = hipMalloc(&d_acc, (size_t)n * 32u);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_reg, regions, (size_t)n * sizeof *regions, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(d_acc, 0, (size_t)n * 32u, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    if (e != hipSuccess) {
+      (void)hipFree(d_reg);
+      (void)hipFree(d_acc);
+      (void)hipGetLastError();
+      free(h_start);
+      free(h_maxend);
+      return bsc_fail(e == hipErrorOutOfMemory ? BSC_ERR_NOMEM : BSC_ERR_HIP, "bsc_meth_regions_attach: %llu regions to the device: %s",
+                      (unsigned long long)n, hipGetErrorString(e));
+    }
+    uint32_t run = 0;
+    for (uint64_t k = 0; k < n; k++) {
+      h_start[k] = regions[k].start;
+      h_maxend[k] = run = regions[k].end > run ? regions[k].end : run;
+    }
+  }
+  if ((rc = bsc_meth_regions_quiet(ctx))) { /* (a kernel of the old attachment may still be adding) */
+    (void)hipFree(d_reg);
+    (void)hipFree(d_acc);
+    free(h_start);
+    free(h_maxend);
+    return rc;
+  }
+  (void)hipFree(ctx->mr.d_reg);
+  (void)hipFree(ctx->mr.d_acc);
+  free(ctx->mr.h_start);
+  free(ctx->mr.h_maxend);
+  ctx->mr.d_reg = d_reg;
+  ctx->mr.d_acc = d_acc;
+  ctx->mr.h_start = h_start;
+  ctx->mr.h_maxend = h_maxend;
+  ctx->mr.n = n;
+  ctx->mr.last = ctx->stream;
+  return BSC_OK;
+}
+
+/* first index k of v[0 .. n) with v[k] >= key (v non-decreasing) */
+static uint64_t bsc_lower_bound_u32(const uint32_t *v, uint64_t n, uint64_t key) {
+  uint64_t lo = 0, hi = n;
+  while (lo < hi) {
+    const uint64_t mid = lo + (hi - lo) / 2;
+    if ((uint64_t)v[mid] >= key) hi = mid; else lo = mid + 1;
+  }
+  return lo;
+}
+
+/* the reduction over d_core[n] / d_aux[n] (entry i = position x0 + i) on stream s: planes and their scans in the context's workspaces, the
+ * region pass over the candidates.  d_emit: the chain's byte per position or NULL */
+static int bsc_meth_regions_run(bsc_context *ctx, const char *who, const void *d_core, const void *d_aux, const void *d_emit, uint32_t n, uint32_t x0,
+                                const bsc_meth_params *par, int always, hipStream_t s) {
+  /* a region holds the site at pos iff start < pos <= end; the array holds x0 .. x0 + n - 1: start < x0 + n - 1 and end >= x0.  The range
+   * [lo, hi) is a superset: by the running maximum of the ends, a region before lo ends before x0 — one behind it may, too */
+  const uint64_t hi = bsc_lower_bound_u32(ctx->mr.h_start, ctx->mr.n, (uint64_t)x0 + n - 1u);
+  const uint64_t lo = bsc_lower_bound_u32(ctx->mr.h_maxend, ctx->mr.n, x0);
+  if (lo >= hi && !always) return BSC_OK;
+  const uint32_t n_tiles = (uint32_t)(((uint64_t)n + 63u) / 64u);
+  size_t scan_bytes = 0;
+  int rc;
+  if (bsc_dev_scan_tmp_bytes_u64(n_tiles + 1u, &scan_bytes)) return bsc_fail(BSC_ERR_HIP, "%s: scan size query failed", who);
+  if ((rc = bsc_reserve(&ctx->mr.d_pl, &ctx->mr.cap_pl, ((size_t)n_tiles + 1u) * 32u))) return rc;
+  if ((rc = bsc_reserve(&ctx->mr.d_sc, &ctx->mr.cap_sc, ((size_t)n_tiles + 1u) * 32u))) return rc;
+  if ((rc = bsc_reserve(&ctx->mr.d_tmp, &ctx->mr.cap_tmp, scan_bytes ? scan_bytes : 1))) return rc;
+  ctx->mr.last = s;
+  const int e = bsc_dev_launch_meth_regions(d_core, d_aux, d_emit, n, x0, par, ctx->mr.d_pl, ctx->mr.d_sc, ctx->mr.d_tmp, scan_bytes, ctx->mr.d_reg,
+                                            (uint32_t)lo, (uint32_t)(hi > lo ? hi : lo), ctx->mr.d_acc, ctx->num_cus, (void *)s);
+  if (e) return bsc_fail(BSC_ERR_HIP, "%s: launch failed: %s", who, hipGetErrorString((hipError_t)e));
+  return BSC_OK;
+}
+
+static int bsc_meth_regions_params_check(const char *who, const bsc_meth_params *par) {
+  if (!par) return bsc_fail(BSC_ERR_ARG, "%s: NULL argument", who);
+  if (par->contexts != BSC_METH_CPG && par->contexts != BSC_METH_ALL)
+    return bsc_fail(BSC_ERR_ARG, "%s: contexts is %d, not BSC_METH_CPG or BSC_METH_ALL", who, (int)par->contexts);
+  return BSC_OK;
+}
+
+int bsc_meth_regions_sites_device(bsc_context *ctx, const void *d_core, const void *d_aux, uint32_t n, uint32_t x0, const bsc_meth_params *params,
+                                  void *stream) {
+  static const char who[] = "bsc_meth_regions_sites_device";
+  int rc;
+  if (!ctx || (n && (!d_core || !d_aux))) return bsc_fail(BSC_ERR_ARG, "%s: NULL argument", who);
+  if ((rc = bsc_meth_regions_params_check(who, params))) return rc;
+  if (((uintptr_t)d_core | (uintptr_t)d_aux) & 15u) return bsc_fail(BSC_ERR_ARG, "%s: the arrays must be 16-byte aligned", who);
+  if (!ctx->mr.n) return bsc_fail(BSC_ERR_ARG, "%s: no regions are attached (bsc_meth_regions_attach)", who);
+  if (x0 < 1u) return bsc_fail(BSC_ERR_ARG, "%s: positions are 1-based (x0 = 0)", who);
+  if (n && (uint64_t)x0 + n - 1u > 0xffffffffull) return bsc_fail(BSC_ERR_ARG, "%s: x0 + n - 1 = %llu is beyond 2^32 - 1", who, (unsigned long long)x0 + n - 1u);
+  if (!n) return BSC_OK;
+  BSC_ENTER(ctx);
+  return bsc_meth_regions_run(ctx, who, d_core, d_aux, NULL, n, x0, params, 0, (hipStream_t)stream);
+}
+
+int bsc_block_meth_regions_kept(bsc_context *ctx, const bsc_meth_params *params, uint64_t *n_sites, uint64_t sums[3]) {
+  static const char who[] = "bsc_block_meth_regions_kept";
+  int rc;
+  if (!ctx) return bsc_fail(BSC_ERR_ARG, "%s: NULL argument", who);
+  if (n_sites) *n_sites = 0;
+  for (int k = 0; sums && k < 3; k++) sums[k] = 0;
+  if ((rc = bsc_meth_regions_params_check(who, params))) return rc;
+  if (ctx->meth_src != 1 || ctx->rec_pending || ctx->pending_sz)
+    return bsc_fail(BSC_ERR_ARG, "%s: the last call left no single block's arrays on the device", who);
+  if (!ctx->mr.n) return bsc_fail(BSC_ERR_ARG, "%s: no regions are attached (bsc_meth_regions_attach)", who);
+  const uint32_t n = ctx->again.sz, x0 = ctx->meth_x;
+  if (!n) return BSC_OK;
+  BSC_ENTER(ctx);
+  hipStream_t s = ctx->stream;
+  if ((rc = bsc_meth_regions_quiet(ctx))) return rc; /* (a device-level call on another stream may still be adding) */
+  if ((rc = bsc_meth_regions_run(ctx, who, ctx->d_vout, ctx->d_out, ctx->again.emit, n, x0, params, 1, s))) return rc;
+  const size_t stride = (size_t)(((uint64_t)n + 63u) / 64u) + 1u; /* the scans' last entries: the block's totals */
+  unsigned long long tot[3] = {0, 0, 0};
+  for (int k = 0; k < 3; k++)
+    HIP_TRY(hipMemcpyAsync(&tot[k], (const unsigned long long *)ctx->mr.d_sc + (size_t)k * stride + (stride - 1u), sizeof tot[k], hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  if (n_sites) *n_sites = tot[0];
+  for (int k = 0; sums && k < 3; k++) sums[k] = tot[k];
+  return BSC_OK;
+}
+
+int bsc_meth_regions_read(bsc_context *ctx, uint64_t *acc_host, uint64_t n) {
+  if (!ctx || (n && !acc_host)) return bsc_fail(BSC_ERR_ARG, "bsc_meth_regions_read: NULL argument");
+  if (n != ctx->mr.n)
+    return bsc_fail(BSC_ERR_ARG, "bsc_meth_regions_read: %llu regions are attached, not %llu", (unsigned long long)ctx->mr.n, (unsigned long long)n);
+  if (!n) return BSC_OK;
+  BSC_ENTER(ctx);
+  int rc = bsc_meth_regions_quiet(ctx);
+  if (rc) return rc;
+  HIP_TRY(hipMemcpyAsync(acc_host, ctx->mr.d_acc, (size_t)n * 32u, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  return BSC_OK;
+}
+
+int bsc_meth_regions_reset(bsc_context *ctx) {
+  if (!ctx) return bsc_fail(BSC_ERR_ARG, "bsc_meth_regions_reset: NULL argument");
+  if (!ctx->mr.n) return BSC_OK;
+  BSC_ENTER(ctx);
+  int rc = bsc_meth_regions_quiet(ctx);
+  if (rc) return rc;
+  HIP_TRY(hipMemsetAsync(ctx->mr.d_acc, 0, (size_t)ctx->mr.n * 32u, ctx->stream));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  ctx->mr.last = ctx->stream;
+  return BSC_OK;
 }
 
 int bsc_meth_stream_read(bsc_context *ctx, uint64_t off, uint64_t n, void *dst) {

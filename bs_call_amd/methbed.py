@@ -70,6 +70,114 @@ def format_cpg_recs(recs, contig, p=None, totals=False):
     return (buf.raw[:n], [int(v) for v in tot]) if totals else buf.raw[:n]
 
 
+REGION = np.dtype([("start", "<u4"), ("end", "<u4")])  # bsc_meth_region
+
+
+def _regions(regions):
+    r = np.asarray(regions)
+    if not r.dtype.names:
+        r = r.reshape(-1, 2)
+        if len(r) and (r.min() < 0 or r.max() > 0xFFFFFFFF):
+            raise ValueError("a region's coordinates are 0 .. 2^32 - 1")
+        r = np.ascontiguousarray(r, dtype=np.uint32).view(REGION).reshape(-1)
+    return np.ascontiguousarray(r, dtype=REGION)
+
+
+def parse_regions(data):
+    """BED text (bytes) -> {contig: (regions, names)}, the contigs in order of first appearance, each contig's regions (dtype REGION)
+    stably sorted by (start, end), names = their fourth column or "." (bsc_meth_regions_parse_bed, csrc/methregions.c; include/bscall_amd.h
+    says which lines are taken, skipped and refused).  ValueError with the line's number for a malformed line."""
+    L = _lib.load()
+    out = C.POINTER(_lib.MethBed)()
+    buf = C.create_string_buffer(bytes(data), max(len(data), 1))  # exactly the text: no terminator is promised
+    if L.bsc_meth_regions_parse_bed(C.cast(buf, C.c_void_p) if len(data) else None, len(data), C.byref(out)) != 0:
+        raise ValueError(L.bsc_last_error().decode(errors="replace"))
+    try:
+        b = out.contents
+        res = {}
+        for c in range(b.n_contigs):
+            lo, hi = int(b.first[c]), int(b.first[c + 1])
+            regs = np.zeros(hi - lo, dtype=REGION)
+            if hi > lo:
+                C.memmove(regs.ctypes.data, b.regions + 8 * lo, 8 * (hi - lo))
+            res[b.contigs[c].decode()] = (regs, [b.names[k].decode() for k in range(lo, hi)])
+        return res
+    finally:
+        L.bsc_meth_bed_free(out)
+
+
+def read_regions(path):
+    """A BED file of regions, plain or gzip, as parse_regions returns it."""
+    with open(path, "rb") as f:
+        data = f.read()
+    if data[:2] == b"\x1f\x8b":
+        data = gzip.decompress(data)
+    return parse_regions(data)
+
+
+def window_regions(length, window):
+    """The fixed tiles of a contig of `length` bases: [k window, min((k + 1) window, length)) (bam2bcf --meth-window)."""
+    if window < 1:
+        raise ValueError("a window has at least one base")
+    starts = np.arange(0, int(length), int(window), dtype=np.uint64)
+    out = np.zeros(len(starts), dtype=REGION)
+    out["start"] = starts
+    out["end"] = np.minimum(starts + np.uint64(window), np.uint64(length))
+    return out
+
+
+def region_summary(lines_or_records, regions, p=None):
+    """The accumulators uint64[n, 4] = per region {sites, A, B, P} of ONE contig's cytosines: lines_or_records is either rows of a
+    per-cytosine table (dtype BED: read_bed / parse_bed; every row is a site at pos = start + 1, with its a, b and pct) or packed records
+    (VCF_REC[]; the rule of include/bscall_amd.h under the parameters p, by bsc_meth_regions_sum_recs).  regions: (start, end) pairs or
+    dtype REGION, in any order."""
+    regs = _regions(regions)
+    acc = np.zeros((len(regs), 4), dtype=np.uint64)
+    x = np.asarray(lines_or_records)
+    if x.dtype == BED:
+        start = x["start"].astype(np.uint64)
+        order = np.argsort(start, kind="stable")
+        start = start[order]
+        a, b = x["a"][order].astype(np.uint64), x["b"][order].astype(np.uint64)
+        cov = a + b
+        pct = (np.uint64(200) * a + cov) // np.maximum(np.uint64(2) * cov, np.uint64(1))
+        cum = np.zeros((len(start) + 1, 4), dtype=np.uint64)
+        cum[1:, 0] = np.arange(1, len(start) + 1)
+        cum[1:, 1], cum[1:, 2], cum[1:, 3] = np.cumsum(a), np.cumsum(b), np.cumsum(pct)
+        lo = np.searchsorted(start, regs["start"].astype(np.uint64), "left")
+        hi = np.maximum(np.searchsorted(start, regs["end"].astype(np.uint64), "left"), lo)
+        return cum[hi] - cum[lo]
+    L = _lib.load()
+    rb = np.ascontiguousarray(x).view(np.uint8).reshape(-1, 128)
+    p = params() if p is None else p
+    if L.bsc_meth_regions_sum_recs(rb.ctypes.data if len(rb) else None, len(rb), C.byref(p), regs.ctypes.data if len(regs) else None, len(regs),
+                                   acc.ctypes.data if len(regs) else None) != 0:
+        raise ValueError(L.bsc_last_error().decode(errors="replace"))
+    return acc
+
+
+def format_regions(contig, regions, names, acc):
+    """The summary's lines (bytes) of one contig: ten columns per region — chrom start end name sites A+B A B level mean
+    (bsc_meth_regions_format).  names: a string per region, or None for "."."""
+    L = _lib.load()
+    regs = _regions(regions)
+    acc = np.ascontiguousarray(acc, dtype=np.uint64).reshape(-1, 4)
+    if len(acc) != len(regs) or (names is not None and len(names) != len(regs)):
+        raise ValueError("as many accumulators and names as regions")
+    name = contig if isinstance(contig, (bytes, bytearray)) else str(contig).encode()
+    nm = None
+    if names is not None:
+        nm = (C.c_char_p * max(len(regs), 1))(*[(s if isinstance(s, (bytes, bytearray)) else str(s).encode()) for s in names])
+    rp, ap = (regs.ctypes.data, acc.ctypes.data) if len(regs) else (None, None)
+    n = L.bsc_meth_regions_format(name, rp, nm, ap, len(regs), None, 0)
+    if n < 0:
+        raise ValueError("bsc_meth_regions_format: bad argument")
+    buf = C.create_string_buffer(max(n, 1))
+    if L.bsc_meth_regions_format(name, rp, nm, ap, len(regs), buf, n) != n:
+        raise ValueError("bsc_meth_regions_format: the length changed between two calls")
+    return buf.raw[:n]
+
+
 def parse_bed(data):
     rows = [ln.split(b"\t") for ln in data.split(b"\n") if ln]
     out = np.zeros(len(rows), dtype=BED)

@@ -18,7 +18,7 @@ def run(bam_path: str, reference: Dict[str, np.ndarray], bcf_path: str, sample: 
         min_qual: Optional[int] = None, benchmark_mode: bool = False, under_conv: Optional[float] = None, over_conv: Optional[float] = None,
         host_prep: bool = False, host_bcf: bool = False, device_reader: bool = False, shard_rank: Optional[int] = None, shard_world: int = 1,
         reduce_device=None, text: bool = False, dbsnp_device: bool = False, meth_path: Optional[str] = None, meth_params=None, meth_merge: bool = False,
-        **reader_kw) -> dict:
+        meth_regions=None, meth_regions_path: Optional[str] = None, meth_window: Optional[int] = None, **reader_kw) -> dict:
     """reference: contig name -> uint8 reference codes (0 = N, 1..4 = ACGT; position 1 first).  Returns a summary dict.
     under_conv / over_conv / min_qual (defaults 0.01 / 0.05 / 20, src/init_param.c:26-31) are the MODEL's parameters: without
     `caller` the run builds its SiteCaller from them; with one, they are taken from it and a differing explicit value is an error
@@ -43,7 +43,40 @@ def run(bam_path: str, reference: Dict[str, np.ndarray], bcf_path: str, sample: 
     BGZF like the main file.  meth_params: a _lib.MethParams or a dict of its fields (default: CpG cytosines, every covered site).  Needs
     device_reader and is refused where text=True is; the main file and the report are those of the run without it.  meth_merge: the table
     is the combined-strand one, a line per CpG dinucleotide with both strands' counts added (bsc_block_meth_cpg_kept); needs meth_path and
-    CpG-only meth_params."""
+    CpG-only meth_params.
+    meth_regions / meth_window with meth_regions_path: the per-region methylation summary of the same run (include/bscall_amd.h has the rule
+    and the ten columns), summed on the device: a contig's regions are attached at the contig change, every block adds its cytosines
+    (SiteCaller.block_meth_regions_kept, csrc/methregionsdev.hip), the sums are read at the next contig change and at the end.
+    meth_regions: the path of a BED file, or a list of (contig, start, end[, name]) — 0-based, half-open; sorted here as the BED reader
+    sorts, stably by (start, end) —, or what methbed.parse_regions returns.  meth_window=n in its place: fixed tiles of n bases over every
+    contig.  meth_params apply; meth_path is not needed.  The file is plain text, contigs in the order their blocks come; a contig without
+    a block gives no line.  The same conditions as meth_path."""
+    want_regions = meth_regions is not None or meth_window is not None
+    if meth_regions is not None and meth_window is not None:
+        raise ValueError("meth_regions and meth_window exclude each other: the regions are the given ones or the fixed tiles")
+    if want_regions != (meth_regions_path is not None):
+        raise ValueError("meth_regions / meth_window and meth_regions_path go together: the regions to sum and the summary to write")
+    if meth_window is not None and int(meth_window) < 1:
+        raise ValueError("meth_window is a count of bases, 1 or more")
+    if want_regions and (shard_rank is not None or not device_reader or host_prep or host_bcf):
+        raise ValueError("meth_regions is a single run on the device reader (device_reader=True, no shard_rank, no host_prep / host_bcf)")
+    region_sets = None
+    if meth_regions is not None:
+        from . import methbed
+
+        if isinstance(meth_regions, (str, bytes)) or hasattr(meth_regions, "__fspath__"):
+            region_sets = methbed.read_regions(meth_regions)
+        elif isinstance(meth_regions, dict):
+            region_sets = meth_regions
+        else:
+            region_sets = {}
+            for row in meth_regions:
+                region_sets.setdefault(str(row[0]), []).append((int(row[1]), int(row[2]), str(row[3]) if len(row) > 3 else "."))
+            for k, rows in region_sets.items():
+                rows.sort(key=lambda r: (r[0], r[1]))  # (stable)
+                regs = np.zeros(len(rows), dtype=methbed.REGION)
+                regs["start"], regs["end"] = [r[0] for r in rows], [r[1] for r in rows]
+                region_sets[k] = (regs, [r[2] for r in rows])
     if meth_merge and meth_path is None:
         raise ValueError("meth_merge=True combines the strands of the table meth_path names: it needs meth_path")
     if meth_merge and meth_params is not None and (meth_params.contexts if hasattr(meth_params, "contexts") else meth_params.get("contexts", 0)) != 0:
@@ -76,6 +109,7 @@ def run(bam_path: str, reference: Dict[str, np.ndarray], bcf_path: str, sample: 
         per_contig = []
         n_blocks = n_records = 0
         meth_blobs, meth_lines = [], 0
+        region_out, region_cur = [], None  # the summary's lines, contig by contig; (name, regions, names) of the contig attached
         c.reset_site_stats()
         sharded = shard_rank is not None
         if sharded:
@@ -106,8 +140,16 @@ def run(bam_path: str, reference: Dict[str, np.ndarray], bcf_path: str, sample: 
                                      mapq_thresh=reader_kw.get("mapq_thresh", 20), min_qual=min_qual, date=date,
                                      dbsnp_header=None if dbsnp is None else dbsnp.header, benchmark_mode=benchmark_mode)
 
+            def regions_flush():
+                nonlocal region_cur
+                if region_cur is not None:
+                    from . import methbed
+
+                    region_out.append(methbed.format_regions(region_cur[0], region_cur[1], region_cur[2], c.meth_regions_read()))
+                region_cur = None
+
             def block_blobs():
-                nonlocal n_blocks, n_records, base_filter, passed, meth_lines
+                nonlocal n_blocks, n_records, base_filter, passed, meth_lines, region_cur
                 before, cur_tid = c.site_totals(), -1
                 for item in (rd.device_blocks() if device_reader else rd.blocks()):
                     if device_reader:
@@ -122,6 +164,16 @@ def run(bam_path: str, reference: Dict[str, np.ndarray], bcf_path: str, sample: 
                             per_contig.append((refs[cur_tid][0], after - before))
                             before = after
                         cur_tid = tid
+                        if want_regions:
+                            regions_flush()
+                            if meth_window is not None:
+                                from . import methbed
+
+                                region_cur = (name, methbed.window_regions(refs[tid][1], int(meth_window)), None)
+                            else:
+                                region_cur = (name, *region_sets[name]) if name in region_sets else None
+                            if c.meth_regions_attach(region_cur[1] if region_cur else []) == 0:
+                                region_cur = None
                         if dbsnp is not None:
                             dbsnp.load_contig(name)
                             if on_device:
@@ -144,7 +196,10 @@ def run(bam_path: str, reference: Dict[str, np.ndarray], bcf_path: str, sample: 
                                                                  reg_stop=len(codes), dbsnp=flags, with_stats=True, profile=prof)
                         else:
                             blob, n_rec, st = c.block_bcf_rawdev(dblk, ref, tid, names=names, left_trim=left_trim, right_trim=right_trim, min_qual=min_qual,
-                                                                 reg_stop=len(codes), dbsnp=flags, with_stats=True, profile=prof, keep=meth_path is not None)
+                                                                 reg_stop=len(codes), dbsnp=flags, with_stats=True, profile=prof,
+                                                                 keep=meth_path is not None or want_regions)
+                        if region_cur is not None:  # the block's cytosines into the attached regions' sums
+                            c.block_meth_regions_kept(meth_params)
                         if meth_path is not None:  # the same block's table, from what it left on the device
                             mb, ml, _ = c.block_meth_kept(name, meth_params, merge=meth_merge)
                             meth_blobs.append(mb)
@@ -187,6 +242,10 @@ def run(bam_path: str, reference: Dict[str, np.ndarray], bcf_path: str, sample: 
                 vcf.write_bcf(bcf_path, header, block_blobs(), compressed)  # blocks go to the writer as they are formed
             if meth_path is not None:
                 vcf.write_vcf_blobs(meth_path, "", meth_blobs, compressed)
+            if want_regions:
+                regions_flush()
+                with open(meth_regions_path, "wb") as f:
+                    f.write(b"".join(region_out))
             cts, bases = rd.filter_counts()
         cts[0] += int(passed[0])
         bases[0] += int(passed[1])
@@ -253,9 +312,14 @@ def run(bam_path: str, reference: Dict[str, np.ndarray], bcf_path: str, sample: 
         summary = {"blocks": n_blocks, "records": n_records, "report": report_text, "filter_cts": cts, "contigs": [n for n, _ in per_contig]}
         if meth_path is not None:
             summary["meth_lines"] = meth_lines
+        if want_regions:
+            summary["meth_region_lines"] = sum(b.count(b"\n") for b in region_out)
         return summary
     finally:
         if own:
             c.close()
-        elif on_device:
-            c.dbsnp_detach()  # a supplied caller goes back as it came
+        else:  # a supplied caller goes back as it came
+            if on_device:
+                c.dbsnp_detach()
+            if want_regions:
+                c.meth_regions_attach([])

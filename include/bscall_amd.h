@@ -1160,6 +1160,84 @@ int bsc_meth_cpg_sites_device(bsc_context *ctx, const void *d_core, const void *
                               void *d_out, uint64_t out_cap, void *d_totals, void *stream);
 int bsc_block_meth_cpg_kept(bsc_context *ctx, const char *contig, const bsc_meth_params *p, uint64_t dev_cap, uint64_t *n_bytes, uint64_t *n_lines,
                             uint64_t sums[3]);
+/*
+ * The per-region methylation summary (csrc/methregionsdev.hip: bsc_meth_regions_tile_kernel / _region_kernel; the host form
+ * csrc/methregions.c is its checker): the first output that is a REDUCTION over positions — per interval of a BED file (promoters, CpG
+ * islands, fixed tiles), the cytosines inside it added up, instead of a table of every cytosine pulled off the device and mapped on the
+ * host.  The rule, from which the host form, the tests' Python form and the kernels are each written:
+ *   SITE      a record that gives a line under the per-cytosine rule of bsc_meth_format_rec with the given bsc_meth_params (contexts,
+ *             min_cov, min_phred, pass_only: exactly as written there).  Its values: a, the non-converted count, and b, the converted
+ *             count (counts[5] / counts[7] for CC, counts[6] / counts[4] for GG), and pct = (200 a + (a + b)) / (2 (a + b)) in 64 bits.
+ *             The summary counts cytosines, not dinucleotides: a CpG that straddles a region's border gives the half that lies inside;
+ *             sum of a and sum of b are those of either table.
+ *   REGION    bsc_meth_region {start, end}: 0-based and half-open, as in BED.  It contains the site at 1-based position pos iff
+ *             start < pos <= end — the site's bedMethyl start pos - 1 lies in [start, end).  pos == 0 belongs to no region;
+ *             start == end is legal and empty; start > end is refused.  Regions may overlap, nest and repeat: each is summed alone.
+ *   SUMS      four u64 per region: {sites, A = sum of a, B = sum of b, P = sum of pct}.  All integers, added in 64 bits from the first
+ *             add (a lane's a may be 2^32 - 1).
+ *   LINE      ten tab-separated columns and '\n', plain decimal, no header:
+ *               chrom  start  end  name  sites  A + B  A  B  level  mean
+ *             name: the BED's fourth column, or "." when there is none;  level = (200 A + (A + B)) / (2 (A + B)), the pct formula on
+ *             the sums (the pooled level; "." when A + B == 0, which sites != 0 excludes);  mean = (2 P + sites) / (2 sites), the
+ *             sites' mean pct rounded half up;  level and mean are "." when sites == 0.
+ * Host forms (csrc/methregions.c):
+ *   bsc_meth_regions_sum_recs   adds the rule over packed records recs[0 .. n) into acc[n_regions][4] (NOT zeroed here); a plain loop
+ *   bsc_meth_regions_format     the lines of regions[0 .. n) of one contig -> buf; names: n strings, NULL or a NULL entry = ".".  Returns
+ *                               the length written, the length needed — and nothing written — when cap is too small, < 0 for a bad
+ *                               argument (a contig or a name that is empty, longer than 255 bytes or holds a tab or a newline)
+ *   bsc_meth_regions_parse_bed  BED text -> *out (bsc_meth_bed_free).  A line is three or more columns separated by tabs — or, where the
+ *                               line holds no tab, by single spaces; the fourth column is the name.  '#', "track" and "browser" lines and
+ *                               empty lines are skipped, a '\r' before the '\n' is dropped.  Anything else is refused (BSC_ERR_ARG) with
+ *                               the 1-based line number in bsc_last_error: fewer than three columns, a coordinate that is not all digits
+ *                               or is >= 2^32, start > end, an empty contig name (or one longer than 255 bytes), a final line without
+ *                               '\n'.  The result lists the contigs in order of first appearance; contig c's regions are
+ *                               regions[first[c] .. first[c + 1]), STABLY sorted by (start, end), names[] beside them.
+ * On the device the per-position arrays are dense — entry i is position x0 + i — so an interval is a difference of two prefix sums,
+ * whatever its length and however regions overlap: a tile pass (one wave per 64 positions: the four sums of the tile), an exclusive scan
+ * of the four planes, and a region pass (one wave per CANDIDATE region: prefix(i_hi) - prefix(i_lo), the partial tiles at the two ends
+ * evaluated again) that adds into the region's accumulators.  Candidates: the attached regions whose index lies in [lo, hi), from two
+ * binary searches on the host over the starts and the running maximum of the ends — a superset; a chromosome-long region listed first
+ * makes lo = 0 for every block.
+ *   bsc_meth_regions_attach        regions[0 .. n) of ONE contig, sorted by (start, end), uploaded; their accumulators zeroed.  n == 0
+ *                                  detaches.  Unsorted input, start > end or n > 2^27: BSC_ERR_ARG, and the previous attachment stays.
+ *                                  As bsc_dbsnp_attach: once per contig; freed by bsc_destroy.  Waits.
+ *   bsc_meth_regions_sites_device  accumulates from d_core[n] / d_aux[n]: entry i is position x0 + i (x0 >= 1, x0 + n - 1 < 2^32), and
+ *                                  where it gives a site its core.pos equals that — what bsc_reads_chain_device leaves.  Asynchronous on
+ *                                  `stream`; a region's accumulators are read, added to and stored by ONE wave per call, so calls must
+ *                                  be ordered one behind the other (one stream).  BSC_ERR_ARG with nothing attached.
+ *   bsc_block_meth_regions_kept    the follow-up of the _keep block calls: preconditions and refusals of bsc_block_meth_kept; from the
+ *                                  arrays that block left in HBM, by the chain's emit byte per position, with the block's own x.
+ *                                  sums (may be NULL) = the block's {sites, sum of a, sum of b} whether or not a region holds them;
+ *                                  *n_sites (may be NULL) = sums[0].  The kept stream, the methylation table, bsc_block_csi_kept and
+ *                                  the report are untouched; before or after them.  Waits.
+ *   bsc_meth_regions_read          the accumulators -> acc_host[n][4], n = the attached count; waits for the context's stream and the
+ *                                  stream of the last accumulating call
+ *   bsc_meth_regions_reset         zeroes them (waits likewise)
+ * Not built: a packed-records device form (packed records are not dense in position), the batched and host-buffer block entries.
+ */
+typedef struct {
+  uint32_t start, end; /* 0-based, half-open */
+} bsc_meth_region;
+typedef struct {
+  uint32_t n_contigs;
+  char **contigs;           /* in order of first appearance */
+  uint64_t *first;          /* n_contigs + 1 */
+  uint64_t n_regions;
+  bsc_meth_region *regions; /* contig by contig, each sorted by (start, end), stably */
+  char **names;             /* beside them: the fourth column, or "." */
+} bsc_meth_bed;
+int bsc_meth_regions_sum_recs(const bsc_vcf_rec *recs, size_t n, const bsc_meth_params *p, const bsc_meth_region *regions, size_t n_regions,
+                              uint64_t *acc);
+long bsc_meth_regions_format(const char *contig, const bsc_meth_region *regions, const char *const *names, const uint64_t *acc, size_t n, char *buf,
+                             size_t cap);
+int bsc_meth_regions_parse_bed(const char *text, size_t len, bsc_meth_bed **out);
+void bsc_meth_bed_free(bsc_meth_bed *bed);
+int bsc_meth_regions_attach(bsc_context *ctx, const bsc_meth_region *regions, uint64_t n);
+int bsc_meth_regions_sites_device(bsc_context *ctx, const void *d_core, const void *d_aux, uint32_t n, uint32_t x0, const bsc_meth_params *params,
+                                  void *stream);
+int bsc_block_meth_regions_kept(bsc_context *ctx, const bsc_meth_params *params, uint64_t *n_sites, uint64_t sums[3]);
+int bsc_meth_regions_read(bsc_context *ctx, uint64_t *acc_host, uint64_t n);
+int bsc_meth_regions_reset(bsc_context *ctx);
 /* with bsc_set_profiling: device time (HIP events on the context's stream) of the most recent raw block — bsc_block_records_raw[dev],
  * bsc_block_bcf_raw[dev][_keep] — from its first pre-processing launch to the last launch it queued, the host's wait for the prepared size included */
 int bsc_last_raw_block_ms(bsc_context *ctx, float *ms);

@@ -62,6 +62,12 @@
  * output thread, as one more job of its own file; with -O b through a second BGZF writer.  With either --format, with -D and --index; the
  * BCF / VCF, the .csi and the report are those of the run without it.  A single run on the device reader only.  --meth-merge: the table
  * is the combined-strand one — a line per CpG dinucleotide, both strands' counts added (bsc_block_meth_cpg_kept); not with --meth-all.
+ *
+ * --meth-regions regions.bed --meth-regions-out out.tsv: the per-region methylation summary — per interval of the BED file the cytosines
+ * inside it added up on the device (bsc_meth_regions_attach at the contig change, where -D attaches; bsc_block_meth_regions_kept behind
+ * every block; bsc_meth_regions_read at the next contig change and at the end), ten columns a region: chrom start end name sites A+B A B
+ * level mean.  --meth-window n in the BED's place: fixed tiles of n bases over every contig.  The --meth-* thresholds and --meth-all
+ * apply; --meth is not needed.  Contigs come out in the order their blocks do (the BAM header's); a contig without a block gives no line.
  */
 #include <pthread.h>
 #include <stdio.h>
@@ -429,9 +435,28 @@ static int merge_main(int world, char **argv, const char *sample) {
   return 0;
 }
 
+/* --meth-regions: the attached contig's accumulators read and its lines appended */
+static uint64_t regions_flush(bsc_context *ctx, FILE *f, const char *contig, const bsc_meth_region *regs, const char *const *names, uint64_t n) {
+  if (!n) return 0;
+  uint64_t *acc = xrealloc(NULL, (size_t)n * 4 * sizeof *acc);
+  CHECK(bsc_meth_regions_read(ctx, acc, n));
+  const long need = bsc_meth_regions_format(contig, regs, names, acc, (size_t)n, NULL, 0);
+  CHECK(need);
+  char *buf = xrealloc(NULL, (size_t)need);
+  CHECK(bsc_meth_regions_format(contig, regs, names, acc, (size_t)n, buf, (size_t)need));
+  if (fwrite(buf, 1, (size_t)need, f) != (size_t)need) {
+    perror("--meth-regions-out");
+    exit(1);
+  }
+  free(buf);
+  free(acc);
+  return n;
+}
+
 int main(int argc, char **argv) {
   int rank = -1, world = 1, merge = 0, bgzf = 0, text = 0, index = 0, meth_merge = 0;
-  const char *dbsnp_path = NULL, *meth_path = NULL;
+  const char *dbsnp_path = NULL, *meth_path = NULL, *regions_path = NULL, *regions_out_path = NULL;
+  uint32_t meth_window = 0;
   bsc_meth_params mpar;
   bsc_meth_params_default(&mpar);
   if (argc >= 2 && !strcmp(argv[argc - 1], "--meth") && (argc == 2 || strcmp(argv[argc - 2], "--meth"))) {
@@ -478,6 +503,17 @@ int main(int argc, char **argv) {
     else if (!strcmp(argv[1], "--world")) world = atoi(argv[2]);
     else if (!strcmp(argv[1], "--merge")) merge = atoi(argv[2]);
     else if (!strcmp(argv[1], "--meth")) meth_path = argv[2];
+    else if (!strcmp(argv[1], "--meth-regions")) regions_path = argv[2];
+    else if (!strcmp(argv[1], "--meth-regions-out")) regions_out_path = argv[2];
+    else if (!strcmp(argv[1], "--meth-window")) {
+      char *end = NULL;
+      const unsigned long v = strtoul(argv[2], &end, 10);
+      if (!argv[2][0] || *end || argv[2][0] == '-' || v < 1 || v > 0xfffffffful) {
+        fprintf(stderr, "%s: --meth-window takes a count of bases, 1 or more, not '%s'\n", argv[0], argv[2]);
+        return 2;
+      }
+      meth_window = (uint32_t)v;
+    }
     else if (!strcmp(argv[1], "--meth-min-cov") || !strcmp(argv[1], "--meth-min-gq")) {
       char *end = NULL;
       const unsigned long v = strtoul(argv[2], &end, 10);
@@ -501,7 +537,7 @@ int main(int argc, char **argv) {
     argc -= 2;
   }
   if (argc < 5 || world < 1 || (rank >= 0 && rank >= world)) {
-    fprintf(stderr, "usage: %s [-O u|b] [--format bcf|vcf] [--index] [-D dbsnp.idx] [--meth out.bed [--meth-merge | --meth-all] [--meth-min-cov n] [--meth-min-gq n] [--meth-pass]] [--rank r --world n | --merge n] in.bam ref.fa out.bcf report.json [sample]\n", argv[0]);
+    fprintf(stderr, "usage: %s [-O u|b] [--format bcf|vcf] [--index] [-D dbsnp.idx] [--meth out.bed [--meth-merge | --meth-all] [--meth-min-cov n] [--meth-min-gq n] [--meth-pass]] [--meth-regions regions.bed | --meth-window n --meth-regions-out out.tsv] [--rank r --world n | --merge n] in.bam ref.fa out.bcf report.json [sample]\n", argv[0]);
     return 2;
   }
   if (text && (rank >= 0 || merge > 0)) {
@@ -548,8 +584,50 @@ int main(int argc, char **argv) {
     fprintf(stderr, "%s: --meth encodes what the device reader's blocks leave on the device: not with BAM2BCF_HOST_READER / _HOST_BCF / _HOST_PREP\n", argv[0]);
     return 2;
   }
+  if (regions_path && meth_window) {
+    fprintf(stderr, "%s: --meth-regions and --meth-window exclude each other: the regions are the BED file's or the fixed tiles\n", argv[0]);
+    return 2;
+  }
+  if ((regions_path || meth_window) && !regions_out_path) {
+    fprintf(stderr, "%s: --meth-regions / --meth-window need --meth-regions-out out.tsv, the summary to write\n", argv[0]);
+    return 2;
+  }
+  if (regions_out_path && !regions_path && !meth_window) {
+    fprintf(stderr, "%s: --meth-regions-out needs --meth-regions regions.bed or --meth-window n\n", argv[0]);
+    return 2;
+  }
+  if (regions_out_path && (rank >= 0 || world > 1 || merge > 0)) {
+    fprintf(stderr, "%s: --meth-regions sums a single run's blocks; a sharded run (--rank / --world / --merge) has none\n", argv[0]);
+    return 2;
+  }
+  if (regions_out_path && (getenv("BAM2BCF_HOST_PREP") || getenv("BAM2BCF_HOST_BCF") || getenv("BAM2BCF_HOST_READER"))) {
+    fprintf(stderr, "%s: --meth-regions sums what the device reader's blocks leave on the device: not with BAM2BCF_HOST_READER / _HOST_BCF / _HOST_PREP\n", argv[0]);
+    return 2;
+  }
   const char *sample = argc > 5 ? argv[5] : "SAMPLE";
   if (merge > 0) return merge_main(merge, argv, sample);
+  bsc_meth_bed *rbed = NULL; /* (before the context: a bad BED file costs no device) */
+  if (regions_path) {
+    FILE *bf = fopen(regions_path, "rb");
+    if (!bf) {
+      perror(regions_path);
+      return 1;
+    }
+    char *bt = NULL;
+    size_t bn = 0, bcap = 0;
+    for (;;) {
+      if (bn + 65536 > bcap) bt = xrealloc(bt, bcap = bcap ? bcap * 2 : (size_t)1 << 20);
+      const size_t got = fread(bt + bn, 1, bcap - bn, bf);
+      if (!got) break;
+      bn += got;
+    }
+    fclose(bf);
+    if (bsc_meth_regions_parse_bed(bt, bn, &rbed) < 0) {
+      fprintf(stderr, "%s: %s\n", regions_path, bsc_last_error());
+      return 1;
+    }
+    free(bt);
+  }
   const int sharded = rank >= 0;
   const int host_prep = getenv("BAM2BCF_HOST_PREP") != NULL;
   const int host_bcf = host_prep || getenv("BAM2BCF_HOST_BCF") != NULL;
@@ -600,6 +678,37 @@ int main(int argc, char **argv) {
     return 1;
   }
   const int n_ref = N_REFS();
+  /* the per-region summary: which of the BED's contigs is which of the header's, the file, and the contig whose regions are attached */
+  FILE *rout = NULL;
+  int64_t *rbed_of = NULL; /* per tid: the BED's contig, or -1 */
+  bsc_meth_region *rwin = NULL; /* --meth-window: the current contig's tiles */
+  uint64_t r_n = 0, region_lines = 0;
+  const bsc_meth_region *r_regs = NULL;
+  const char *const *r_names = NULL;
+  if (regions_out_path) {
+    rout = fopen(regions_out_path, "wb");
+    if (!rout) {
+      perror(regions_out_path);
+      return 1;
+    }
+    if (rbed) {
+      rbed_of = xrealloc(NULL, ((size_t)n_ref + 1) * sizeof *rbed_of);
+      for (int i = 0; i < n_ref; i++) rbed_of[i] = -1;
+      uint64_t skipped = 0;
+      uint32_t skipped_contigs = 0;
+      for (uint32_t c = 0; c < rbed->n_contigs; c++) {
+        int t = 0;
+        while (t < n_ref && strcmp(REF_NAME(t), rbed->contigs[c])) t++;
+        if (t < n_ref) rbed_of[t] = c;
+        else {
+          skipped += rbed->first[c + 1] - rbed->first[c];
+          skipped_contigs++;
+        }
+      }
+      if (skipped)
+        fprintf(stderr, "bam2bcf: %llu regions on %u contigs the BAM header does not name were skipped\n", (unsigned long long)skipped, skipped_contigs);
+    }
+  }
   int meth_fd = -1;
   uint64_t meth_at = 0, meth_lines = 0;
   bsc_bgzf *zm = NULL;
@@ -703,6 +812,7 @@ int main(int argc, char **argv) {
         for (int i = 0; i < 14; i++) d[i] += after[i] - before[i];
         memcpy(before, after, sizeof before);
       }
+      if (rout && cur_tid >= 0) region_lines += regions_flush(ctx, rout, REF_NAME(cur_tid), r_regs, r_names, r_n);
       cur_tid = blk.tid;
       ctot[cur_tid].name = REF_NAME(cur_tid);
       if (sharded) { /* this contig's shard; the one before is closed by the output thread behind its last piece */
@@ -745,6 +855,27 @@ int main(int argc, char **argv) {
       codes_len = RJ.codes_len;
       CHECK(bsc_set_gc_bins_host(ctx, gc, (uint32_t)RJ.n_bins, RJ.gc_start));
       if (g_dbsnp) CHECK(bsc_dbsnp_attach(ctx, g_dbsnp, NULL)); /* what the job loaded behind the reference; the next job may load over it */
+      if (rout) { /* this contig's regions, their accumulators zeroed: the BED's, or the fixed tiles */
+        r_n = 0;
+        r_regs = NULL;
+        r_names = NULL;
+        if (meth_window) {
+          const uint64_t len = REF_LEN(cur_tid);
+          r_n = (len + meth_window - 1) / meth_window;
+          rwin = xrealloc(rwin, (size_t)r_n * sizeof *rwin);
+          for (uint64_t k = 0; k < r_n; k++) {
+            rwin[k].start = (uint32_t)(k * meth_window);
+            rwin[k].end = (uint32_t)((k + 1) * meth_window < len ? (k + 1) * meth_window : len);
+          }
+          r_regs = rwin;
+        } else if (rbed_of[cur_tid] >= 0) {
+          const uint64_t f0 = rbed->first[rbed_of[cur_tid]];
+          r_n = rbed->first[rbed_of[cur_tid] + 1] - f0;
+          r_regs = rbed->regions + f0;
+          r_names = (const char *const *)rbed->names + f0;
+        }
+        CHECK(bsc_meth_regions_attach(ctx, r_regs, r_n));
+      }
       if (cur_tid + 1 < n_ref) ref_start(&RJ, argv[2], REF_NAME(cur_tid + 1), REF_LEN(cur_tid + 1), cur_tid + 1); /* the next one, meanwhile */
     }
     const uint32_t x = host_reader ? bsc_block_start(&blk.tpl[0]) : dblk.x, y = blk.y, n = y - x + 1;
@@ -780,6 +911,7 @@ int main(int argc, char **argv) {
         CHECK(bsc_block_csi_kept(ctx, 14, &ce, &cn, NULL));
         CHECK(bsc_csi_add(csi, dblk.tid, ce, cn, n_bytes));
       }
+      if (n_bytes && r_n) CHECK(bsc_block_meth_regions_kept(ctx, &mpar, NULL, NULL)); /* the block's cytosines into the attached regions' sums */
       if (n_bytes && meth_path) { /* the block's methylation table, from the arrays the call left on the device: a buffer and a job of its own */
         uint64_t m_cap = (uint64_t)n * (mpar.contexts == BSC_METH_ALL ? 16 : 4) + 4096, m_bytes = 0, m_lines = 0;
         int (*const meth_kept)(bsc_context *, const char *, const bsc_meth_params *, uint64_t, uint64_t *, uint64_t *, uint64_t *) =
@@ -950,6 +1082,16 @@ int main(int argc, char **argv) {
     perror(meth_path);
     return 1;
   }
+  if (rout) { /* the last contig's lines */
+    if (cur_tid >= 0) region_lines += regions_flush(ctx, rout, REF_NAME(cur_tid), r_regs, r_names, r_n);
+    if (fclose(rout)) {
+      perror(regions_out_path);
+      return 1;
+    }
+    free(rwin);
+    free(rbed_of);
+    bsc_meth_bed_free(rbed);
+  }
   const double t_loop_end = now();
   if (cur_tid >= 0) {
     CHECK(bsc_get_site_totals(ctx, after));
@@ -1036,6 +1178,7 @@ int main(int argc, char **argv) {
     fclose(fr);
     printf("%llu blocks, %llu records written\n", (unsigned long long)n_blocks, (unsigned long long)n_records);
     if (meth_path) printf("%llu methylation table lines written\n", (unsigned long long)meth_lines);
+    if (regions_out_path) printf("%llu methylation region lines written\n", (unsigned long long)region_lines);
   }
   if (getenv("BAM2BCF_TIMING")) {
     uint64_t rc4[4] = {0, 0, 0, 0};
