@@ -193,6 +193,15 @@ EXPORTS = (
     "bsc_block_meth_regions_kept",
     "bsc_meth_regions_read",
     "bsc_meth_regions_reset",
+    "bsc_bw_params_default",
+    "bsc_bigwig_sections_recs",
+    "bsc_bigwig_open",
+    "bsc_bigwig_add",
+    "bsc_bigwig_finish",
+    "bsc_bigwig_close",
+    "bsc_bigwig_sites_device",
+    "bsc_block_bigwig_kept",
+    "bsc_bigwig_stream_read",
 )
 
 
@@ -213,6 +222,15 @@ class MethParams(C.Structure):
 
     def __init__(self, contexts=0, min_cov=1, min_phred=0, pass_only=0):
         super().__init__(int(contexts), int(min_cov), int(min_phred), int(pass_only))
+
+
+class BwParams(C.Structure):
+    """bsc_bw_params; the defaults are bsc_bw_params_default's."""
+
+    _fields_ = [("items_per_section", C.c_uint32), ("reduction", C.c_uint32)]
+
+    def __init__(self, items_per_section=1024, reduction=1024):
+        super().__init__(int(items_per_section), int(reduction))
 
 
 class MethBed(C.Structure):
@@ -747,5 +765,24 @@ def load():
     L.bsc_meth_regions_read.argtypes = [vp, vp, u64]
     L.bsc_meth_regions_reset.restype = i32
     L.bsc_meth_regions_reset.argtypes = [vp]
+    pu64 = C.POINTER(u64)
+    L.bsc_bw_params_default.restype = None
+    L.bsc_bw_params_default.argtypes = [C.POINTER(BwParams)]
+    L.bsc_bigwig_sections_recs.restype = i32
+    L.bsc_bigwig_sections_recs.argtypes = [vp, C.c_size_t, u32, C.POINTER(MethParams), C.POINTER(BwParams), vp, u64, pu64, vp, pu64, vp, pu64]
+    L.bsc_bigwig_open.restype = i32
+    L.bsc_bigwig_open.argtypes = [C.c_int, u32, C.POINTER(C.c_char_p), vp, C.POINTER(BwParams), C.POINTER(vp)]
+    L.bsc_bigwig_add.restype = i32
+    L.bsc_bigwig_add.argtypes = [vp, u32, vp, u64, vp, u64, vp, u64]
+    L.bsc_bigwig_finish.restype = i32
+    L.bsc_bigwig_finish.argtypes = [vp]
+    L.bsc_bigwig_close.restype = None
+    L.bsc_bigwig_close.argtypes = [vp]
+    L.bsc_bigwig_sites_device.restype = i32
+    L.bsc_bigwig_sites_device.argtypes = [vp, vp, vp, u32, u32, u32, C.POINTER(MethParams), C.POINTER(BwParams), vp, u64, vp, u64, vp, u64, vp, vp]
+    L.bsc_block_bigwig_kept.restype = i32
+    L.bsc_block_bigwig_kept.argtypes = [vp, u32, C.POINTER(MethParams), C.POINTER(BwParams), pu64, pu64, C.POINTER(vp), pu64, C.POINTER(vp), pu64]
+    L.bsc_bigwig_stream_read.restype = i32
+    L.bsc_bigwig_stream_read.argtypes = [vp, u64, u64, vp]
     _lib = L
     return L

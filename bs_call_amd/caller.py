@@ -895,6 +895,46 @@ class SiteCaller:
         """bsc_meth_regions_reset: the accumulators zeroed, the regions stay."""
         _check(self._L.bsc_meth_regions_reset(self._h))
 
+    # -- the methylation bigWig track on the device (csrc/bigwigdev.hip) ------------------------------------
+    @staticmethod
+    def _bw_params(params):
+        if params is None:
+            return _lib.BwParams()
+        if isinstance(params, _lib.BwParams):
+            return params
+        return _lib.BwParams(**params)
+
+    def bigwig_sites_device(self, d_core, d_aux, n, x0, chrom_id, d_out, out_cap, d_sections, sec_cap, d_zoom, zoom_cap, d_totals, params=None,
+                            bw_params=None, stream=None):
+        """bsc_bigwig_sites_device: the per-position arrays of reads_chain_device (entry i = position x0 + i) -> the block's bigWig data stream
+        in d_out, the sections' and the level-0 windows' 40-byte summaries, and d_totals: six u64 {bytes, sites, sections, windows, sum of m,
+        sum of m * m} (asynchronous on `stream`).  An array whose room is too small is not written; the needs are in d_totals."""
+        mp, bp = self._meth_params(params), self._bw_params(bw_params)
+        _check(self._L.bsc_bigwig_sites_device(self._h, d_core, d_aux, n, x0, chrom_id, C.byref(mp), C.byref(bp), d_out, out_cap, d_sections, sec_cap,
+                                               d_zoom, zoom_cap, d_totals, stream))
+
+    def block_bigwig_kept(self, chrom_id, params=None, bw_params=None):
+        """bsc_block_bigwig_kept + bsc_bigwig_stream_read: the bigWig data of the block the last *_keep call called, from the arrays it left on
+        the device.  Returns (stream bytes, sites, sections, zoom0): the two summaries as bigwig.BW_SUM arrays (copies)."""
+        from .bigwig import BW_SUM
+
+        mp, bp = self._meth_params(params), self._bw_params(bw_params)
+        nb, ns, nsec, nz = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        p_sec, p_zoom = C.c_void_p(None), C.c_void_p(None)
+        _check(self._L.bsc_block_bigwig_kept(self._h, chrom_id, C.byref(mp), C.byref(bp), C.byref(nb), C.byref(ns), C.byref(p_sec), C.byref(nsec),
+                                             C.byref(p_zoom), C.byref(nz)))
+        grab = lambda p, k: np.frombuffer(C.string_at(p.value, 40 * k), dtype=BW_SUM).copy() if k else np.zeros(0, dtype=BW_SUM)
+        sections, zoom0 = grab(p_sec, nsec.value), grab(p_zoom, nz.value)
+        return self.bigwig_stream_read(0, nb.value), int(ns.value), sections, zoom0
+
+    def bigwig_stream_read(self, off, n):
+        """bsc_bigwig_stream_read: bytes [off, off + n) of the stream block_bigwig_kept left on the device (waits)."""
+        out = np.empty(max(int(n), 1), dtype=np.uint8)
+        if n:
+            _check(self._L.bsc_bigwig_stream_read(self._h, off, n, _ptr(out)))
+            self.synchronize()
+        return out[:n].tobytes()
+
     def block_meth_kept(self, contig, params=None, cap=None, merge=False):
         """bsc_block_meth_kept + bsc_meth_stream_read: the bedMethyl table of the block the last *_keep call called (block_vcf_rawdev,
         block_bcf_rawdev(keep=True)), from the arrays that block left on the device.  params: a _lib.MethParams, a dict of its fields, or

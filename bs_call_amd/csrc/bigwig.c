@@ -1,0 +1,645 @@
+/*
+ * bigwig.c — the methylation bigWig track on the host: the host form of a block's data stream and summaries over packed records
+ * (bsc_bigwig_sections_recs), and the writer of the file (bsc_bigwig_open / _add / _finish / _close).  include/bscall_amd.h has the rule
+ * (site, value, summary, stream, pyramid, file layout); everything here is written from that text.
+ *
+ * bsc_bigwig_sections_recs is the CHECKER of the device's kernels (csrc/bigwigdev.hip): for any record bytes the device leaves the bytes
+ * and the summaries this file leaves — tests/test_gpu_bigwig.py compares them.  Plain C, nothing shared with the device code but the table
+ * of the 1001 floats, which the device copies entries of.  The writer never walks the data bytes: a section's place is arithmetic on the
+ * counts, the two trees and the zoom levels are arithmetic on the summaries, all in integers until a float is stored.
+ * integration/bigwig_san.c drives the writer under the address and undefined-behaviour sanitizers.
+ */
+#include <errno.h>
+#include <pthread.h>
+#include <stdlib.h>
+#include <string.h>
+#include <unistd.h>
+
+#include "../../include/bscall_amd.h"
+
+int bsc_set_error(int code, const char *fmt, ...); /* bscall_api.c: the message bsc_last_error returns */
+
+#define BW_MAGIC 0x888FFC26u
+#define BW_NODE 256u  /* items a tree node */
+#define BW_ZBLOCK 512u /* records a zoom block */
+#define BW_LEVELS 8
+
+void bsc_bw_params_default(bsc_bw_params *p) {
+  if (!p) return;
+  p->items_per_section = 1024;
+  p->reduction = 1024;
+}
+
+/* (float)(m / 10.0), m = 0 .. 1000: the table the device copies entries of (bsc_bigwig_sites_device uploads it verbatim) */
+static float bw_value_tab[1001];
+static pthread_once_t bw_value_once = PTHREAD_ONCE_INIT;
+static void bw_value_make(void) {
+  for (int m = 0; m <= 1000; m++) bw_value_tab[m] = (float)((double)m / 10.0);
+}
+const float *bsc_bw_values(void) {
+  pthread_once(&bw_value_once, bw_value_make);
+  return bw_value_tab;
+}
+
+static int bw_params_ok(const bsc_bw_params *p) { return p && p->items_per_section >= 1 && p->items_per_section <= 65535 && p->reduction >= 1; }
+
+/* the per-cytosine rule of bsc_meth_format_rec, restated: 1 and the site's a, b when the record gives a line */
+static int bw_site(const bsc_vcf_rec *r, const bsc_meth_params *p, uint64_t *a, uint64_t *b) {
+  const bsc_vcf_core *c = &r->core;
+  if (!c->emit || (c->gt != 4 && c->gt != 7)) return 0;
+  if (c->cg != 'C' && !(p->contexts == BSC_METH_ALL && c->cg == 'H')) return 0;
+  const int minus = c->gt == 7;
+  *a = minus ? r->counts[6] : r->counts[5];
+  *b = minus ? r->counts[4] : r->counts[7];
+  if (*a + *b < (p->min_cov > 1 ? p->min_cov : 1)) return 0;
+  if (c->phred < p->min_phred) return 0;
+  if (p->pass_only && c->flt) return 0;
+  return 1;
+}
+
+static void put32(uint8_t *q, uint32_t v) {
+  q[0] = (uint8_t)v;
+  q[1] = (uint8_t)(v >> 8);
+  q[2] = (uint8_t)(v >> 16);
+  q[3] = (uint8_t)(v >> 24);
+}
+
+static void sum_first(bsc_bw_sum *s, uint32_t start, uint32_t m) {
+  s->start = start;
+  s->end = start + 1u;
+  s->count = 1;
+  s->min_m = s->max_m = m;
+  s->_pad = 0;
+  s->sum_m = m;
+  s->sum_m2 = (uint64_t)m * m;
+}
+
+static void sum_merge(bsc_bw_sum *s, const bsc_bw_sum *t) {
+  s->count += t->count;
+  s->sum_m += t->sum_m;
+  s->sum_m2 += t->sum_m2;
+  if (t->min_m < s->min_m) s->min_m = t->min_m;
+  if (t->max_m > s->max_m) s->max_m = t->max_m;
+  if (t->start < s->start) s->start = t->start;
+  if (t->end > s->end) s->end = t->end;
+}
+
+int bsc_bigwig_sections_recs(const bsc_vcf_rec *recs, size_t n, uint32_t chrom_id, const bsc_meth_params *params, const bsc_bw_params *bw_params,
+                             void *out, uint64_t cap, uint64_t *n_bytes, bsc_bw_sum *sections, uint64_t *n_sections, bsc_bw_sum *zoom0,
+                             uint64_t *n_zoom0) {
+  static const char who[] = "bsc_bigwig_sections_recs";
+  if (!params || !bw_params || !n_bytes || !n_sections || !n_zoom0 || (n && !recs) || (cap && !out) || (*n_sections && !sections) ||
+      (*n_zoom0 && !zoom0))
+    return bsc_set_error(BSC_ERR_ARG, "%s: NULL argument", who);
+  if (params->contexts != BSC_METH_CPG && params->contexts != BSC_METH_ALL)
+    return bsc_set_error(BSC_ERR_ARG, "%s: contexts is %d, not BSC_METH_CPG or BSC_METH_ALL", who, (int)params->contexts);
+  if (!bw_params_ok(bw_params)) return bsc_set_error(BSC_ERR_ARG, "%s: items_per_section is 1 .. 65535, reduction 1 or more", who);
+  const uint64_t S = bw_params->items_per_section, red = bw_params->reduction;
+  const uint64_t sec_room = *n_sections, zoom_room = *n_zoom0;
+  const float *val = bsc_bw_values();
+  uint64_t a, b;
+  /* the counts first: nothing is written unless all of it fits */
+  uint64_t sites = 0, windows = 0, last_w = 0;
+  for (size_t i = 0; i < n; i++) {
+    if (!bw_site(&recs[i], params, &a, &b)) continue;
+    const uint64_t w = (uint32_t)(recs[i].core.pos - 1u) / red;
+    if (!sites || w != last_w) windows++;
+    last_w = w;
+    sites++;
+  }
+  const uint64_t secs = (sites + S - 1) / S;
+  *n_bytes = 24 * secs + 8 * sites;
+  *n_sections = secs;
+  *n_zoom0 = windows;
+  if (*n_bytes > cap || secs > sec_room || windows > zoom_room)
+    return bsc_set_error(BSC_ERR_ARG, "%s: %llu bytes, %llu sections and %llu windows do not fit the room given", who, (unsigned long long)*n_bytes,
+                         (unsigned long long)secs, (unsigned long long)windows);
+  uint64_t rank = 0, nw = 0;
+  for (size_t i = 0; i < n; i++) {
+    if (!bw_site(&recs[i], params, &a, &b)) continue;
+    const uint32_t start = recs[i].core.pos - 1u;
+    const uint32_t m = (uint32_t)((2000 * a + (a + b)) / (2 * (a + b)));
+    const uint64_t k = rank / S, in = rank % S;
+    uint8_t *sec = (uint8_t *)out + k * (24 + 8 * S);
+    bsc_bw_sum one;
+    sum_first(&one, start, m);
+    if (!in) { /* the section's first site: its header */
+      const uint64_t left = sites - k * S;
+      put32(sec, chrom_id);
+      put32(sec + 4, start);
+      put32(sec + 12, 0);
+      put32(sec + 16, 1);
+      sec[20] = 2;
+      sec[21] = 0;
+      sec[22] = (uint8_t)(left < S ? left : S);
+      sec[23] = (uint8_t)((left < S ? left : S) >> 8);
+      sections[k] = one;
+    } else {
+      sum_merge(&sections[k], &one);
+    }
+    put32(sec + 8, start + 1u); /* (the last site's stays) */
+    put32(sec + 24 + 8 * in, start);
+    memcpy(sec + 24 + 8 * in + 4, &val[m], 4);
+    const uint64_t w = start / red;
+    if (!rank || w != last_w) zoom0[nw++] = one; else sum_merge(&zoom0[nw - 1], &one);
+    last_w = w;
+    rank++;
+  }
+  return BSC_OK;
+}
+
+/* ---- the writer ------------------------------------------------------------------------------------------------------------------------- */
+typedef struct {
+  uint32_t tid;
+  bsc_bw_sum s;
+  uint64_t off; /* a section's place in the file (not used by a zoom record) */
+} bw_rec;
+
+typedef struct { /* a leaf item of an R-tree */
+  uint32_t c0, s0, c1, e1;
+  uint64_t off, size;
+} rt_item;
+
+typedef struct {
+  uint8_t *p;
+  size_t n, cap;
+  int oom;
+} bw_buf;
+
+struct bsc_bigwig {
+  int fd;
+  uint32_t n_refs, key_size;
+  char **names;
+  uint32_t *lens;
+  bsc_bw_params par;
+  uint64_t data_start; /* fullDataOffset: the section count, the streams behind it */
+  uint64_t data_bytes;
+  bw_rec *sec;
+  uint64_t n_sec, cap_sec;
+  bw_rec *z0;
+  uint64_t n_z0, cap_z0;
+  int have_last, finished;
+  uint32_t last_tid, last_end;
+};
+
+static void *buf_room(bw_buf *b, size_t k) {
+  if (b->oom) return NULL;
+  if (b->n + k > b->cap) {
+    size_t cap = b->cap ? b->cap : 4096;
+    while (cap < b->n + k) cap *= 2;
+    uint8_t *q = realloc(b->p, cap);
+    if (!q) {
+      b->oom = 1;
+      return NULL;
+    }
+    b->p = q;
+    b->cap = cap;
+  }
+  b->n += k;
+  return b->p + b->n - k;
+}
+static void buf_u8(bw_buf *b, uint8_t v) {
+  uint8_t *q = buf_room(b, 1);
+  if (q) q[0] = v;
+}
+static void buf_u16(bw_buf *b, uint16_t v) {
+  uint8_t *q = buf_room(b, 2);
+  if (q) q[0] = (uint8_t)v, q[1] = (uint8_t)(v >> 8);
+}
+static void buf_u32(bw_buf *b, uint32_t v) {
+  uint8_t *q = buf_room(b, 4);
+  if (q) put32(q, v);
+}
+static void buf_u64(bw_buf *b, uint64_t v) {
+  buf_u32(b, (uint32_t)v);
+  buf_u32(b, (uint32_t)(v >> 32));
+}
+static void buf_f32(bw_buf *b, float f) {
+  uint32_t v;
+  memcpy(&v, &f, 4);
+  buf_u32(b, v);
+}
+static void buf_f64(bw_buf *b, double f) {
+  uint64_t v;
+  memcpy(&v, &f, 8);
+  buf_u64(b, v);
+}
+
+/* every byte of p[0 .. n) at file offset off, or -1 with errno */
+static int write_all(int fd, const void *p, uint64_t n, uint64_t off) {
+  const uint8_t *q = p;
+  while (n) {
+    const ssize_t w = pwrite(fd, q, n > (1u << 30) ? (1u << 30) : (size_t)n, (off_t)off);
+    if (w < 0) {
+      if (errno == EINTR) continue;
+      return -1;
+    }
+    if (w == 0) {
+      errno = EIO;
+      return -1;
+    }
+    q += w;
+    off += (uint64_t)w;
+    n -= (uint64_t)w;
+  }
+  return 0;
+}
+
+/* the levels of a tree over n items with BW_NODE a node, bottom-up: cnt[l] items in nodes[l] nodes; returns the level count */
+static int tree_levels(uint64_t n, uint64_t cnt[12], uint64_t nodes[12]) {
+  int l = 0;
+  cnt[0] = n;
+  nodes[0] = n ? (n + BW_NODE - 1) / BW_NODE : 1;
+  while (nodes[l] > 1) {
+    cnt[l + 1] = nodes[l];
+    nodes[l + 1] = (cnt[l + 1] + BW_NODE - 1) / BW_NODE;
+    l++;
+  }
+  return l + 1;
+}
+
+static uint64_t chrom_tree_bytes(uint32_t n_refs, uint32_t key_size) {
+  uint64_t cnt[12], nodes[12], bytes = 32;
+  const int levels = tree_levels(n_refs, cnt, nodes);
+  for (int l = 0; l < levels; l++) bytes += 4 * nodes[l] + cnt[l] * ((uint64_t)key_size + 8);
+  return bytes;
+}
+
+typedef struct {
+  const char *name;
+  uint32_t id;
+} bw_name;
+static int by_name(const void *x, const void *y) { /* memcmp order of the zero-padded keys = the names as unsigned byte strings */
+  const bw_name *a = x, *b = y;
+  const int c = strcmp(a->name, b->name);
+  return c ? c : (a->id > b->id) - (a->id < b->id);
+}
+
+/* the chromosome B+ tree at file offset `at` */
+static int chrom_tree_put(bw_buf *b, const bsc_bigwig *bw, uint64_t at) {
+  const uint32_t n = bw->n_refs, key = bw->key_size;
+  const uint64_t item = (uint64_t)key + 8;
+  uint64_t cnt[12], nodes[12], start[12];
+  const int levels = tree_levels(n, cnt, nodes);
+  bw_name *order = malloc((n ? n : 1) * sizeof *order);
+  if (!order) return -1;
+  for (uint32_t k = 0; k < n; k++) {
+    order[k].name = bw->names[k];
+    order[k].id = k;
+  }
+  qsort(order, n, sizeof *order, by_name);
+  buf_u32(b, 0x78CA8C91u);
+  buf_u32(b, BW_NODE);
+  buf_u32(b, key);
+  buf_u32(b, 8);
+  buf_u64(b, n);
+  buf_u64(b, 0);
+  start[levels - 1] = at + 32;
+  for (int l = levels - 1; l > 0; l--) start[l - 1] = start[l] + 4 * nodes[l] + cnt[l] * item;
+  for (int l = levels - 1; l >= 0; l--) {
+    uint64_t span = 1; /* leaf items under one item of this level */
+    for (int k = 0; k < l; k++) span *= BW_NODE;
+    for (uint64_t j = 0; j < nodes[l]; j++) {
+      const uint64_t lo = j * BW_NODE, hi = lo + BW_NODE < cnt[l] ? lo + BW_NODE : cnt[l];
+      buf_u8(b, l == 0);
+      buf_u8(b, 0);
+      buf_u16(b, (uint16_t)(hi - lo));
+      for (uint64_t i = lo; i < hi; i++) {
+        const uint32_t id = order[i * span].id; /* the item's — or its subtree's first — contig */
+        const size_t len = strlen(bw->names[id]);
+        uint8_t *q = buf_room(b, key);
+        if (q) {
+          memset(q, 0, key);
+          memcpy(q, bw->names[id], len);
+        }
+        if (l == 0) {
+          buf_u32(b, id);
+          buf_u32(b, bw->lens[id]);
+        } else {
+          buf_u64(b, start[l - 1] + i * 4 + i * BW_NODE * item); /* child i: every node before it is full */
+        }
+      }
+    }
+  }
+  free(order);
+  return b->oom ? -1 : 0;
+}
+
+static int lex_less(uint32_t c, uint32_t p, uint32_t c2, uint32_t p2) { return c < c2 || (c == c2 && p < p2); }
+
+/* an R-tree over it[0 .. n) at file offset `at`; end_off: where the data it indexes end */
+static int rtree_put(bw_buf *b, const rt_item *it, uint64_t n, uint64_t at, uint64_t end_off) {
+  uint64_t cnt[12], nodes[12], start[12];
+  const int levels = tree_levels(n, cnt, nodes);
+  rt_item *bound[12] = {0}; /* per level, per node: its bounds (off, size unused) */
+  int rc = 0;
+  for (int l = 0; l < levels && !rc; l++) {
+    bound[l] = malloc((size_t)nodes[l] * sizeof **bound);
+    if (!bound[l]) {
+      rc = -1;
+      break;
+    }
+    const rt_item *src = l ? bound[l - 1] : it;
+    for (uint64_t j = 0; j < nodes[l]; j++) {
+      const uint64_t lo = j * BW_NODE, hi = lo + BW_NODE < cnt[l] ? lo + BW_NODE : cnt[l];
+      rt_item v = {0, 0, 0, 0, 0, 0};
+      for (uint64_t i = lo; i < hi; i++) {
+        if (i == lo || lex_less(src[i].c0, src[i].s0, v.c0, v.s0)) v.c0 = src[i].c0, v.s0 = src[i].s0;
+        if (i == lo || lex_less(v.c1, v.e1, src[i].c1, src[i].e1)) v.c1 = src[i].c1, v.e1 = src[i].e1;
+      }
+      bound[l][j] = v;
+    }
+  }
+  if (!rc) {
+    const rt_item all = bound[levels - 1][0];
+    buf_u32(b, 0x2468ACE0u);
+    buf_u32(b, BW_NODE);
+    buf_u64(b, n);
+    buf_u32(b, all.c0);
+    buf_u32(b, all.s0);
+    buf_u32(b, all.c1);
+    buf_u32(b, all.e1);
+    buf_u64(b, end_off);
+    buf_u32(b, 1);
+    buf_u32(b, 0);
+    start[levels - 1] = at + 48;
+    for (int l = levels - 1; l > 0; l--) start[l - 1] = start[l] + 4 * nodes[l] + 24 * cnt[l];
+    for (int l = levels - 1; l >= 0; l--) {
+      const rt_item *src = l ? bound[l - 1] : it;
+      const uint64_t below = l > 1 ? 24 : 32; /* an item's size one level down */
+      for (uint64_t j = 0; j < nodes[l]; j++) {
+        const uint64_t lo = j * BW_NODE, hi = lo + BW_NODE < cnt[l] ? lo + BW_NODE : cnt[l];
+        buf_u8(b, l == 0);
+        buf_u8(b, 0);
+        buf_u16(b, (uint16_t)(hi - lo));
+        for (uint64_t i = lo; i < hi; i++) {
+          buf_u32(b, src[i].c0);
+          buf_u32(b, src[i].s0);
+          buf_u32(b, src[i].c1);
+          buf_u32(b, src[i].e1);
+          if (l == 0) {
+            buf_u64(b, src[i].off);
+            buf_u64(b, src[i].size);
+          } else {
+            buf_u64(b, start[l - 1] + i * 4 + i * BW_NODE * below);
+          }
+        }
+      }
+    }
+  }
+  for (int l = 0; l < levels; l++) free(bound[l]);
+  return rc || b->oom ? -1 : 0;
+}
+
+int bsc_bigwig_open(int fd, uint32_t n_refs, const char *const *names, const uint32_t *lens, const bsc_bw_params *bw_params, bsc_bigwig **out) {
+  static const char who[] = "bsc_bigwig_open";
+  if (out) *out = NULL;
+  if (!out || fd < 0 || (n_refs && (!names || !lens))) return bsc_set_error(BSC_ERR_ARG, "%s: NULL argument", who);
+  if (!bw_params_ok(bw_params)) return bsc_set_error(BSC_ERR_ARG, "%s: items_per_section is 1 .. 65535, reduction 1 or more", who);
+  bsc_bigwig *bw = calloc(1, sizeof *bw);
+  if (!bw) return bsc_set_error(BSC_ERR_NOMEM, "%s: out of memory", who);
+  bw->fd = fd;
+  bw->par = *bw_params;
+  bw->names = calloc(n_refs ? n_refs : 1, sizeof *bw->names);
+  bw->lens = calloc(n_refs ? n_refs : 1, sizeof *bw->lens);
+  int bad = !bw->names || !bw->lens;
+  for (uint32_t k = 0; k < n_refs && !bad; k++) {
+    if (!names[k]) {
+      bsc_bigwig_close(bw);
+      return bsc_set_error(BSC_ERR_ARG, "%s: contig %u has no name", who, k);
+    }
+    const size_t len = strlen(names[k]);
+    if (len > 65535) {
+      bsc_bigwig_close(bw);
+      return bsc_set_error(BSC_ERR_ARG, "%s: contig %u has a name of %zu bytes", who, k, len);
+    }
+    bw->names[k] = malloc(len + 1);
+    if (!bw->names[k]) {
+      bad = 1;
+      break;
+    }
+    memcpy(bw->names[k], names[k], len + 1);
+    bw->lens[k] = lens[k];
+    bw->n_refs = k + 1;
+    if (len > bw->key_size) bw->key_size = (uint32_t)len;
+  }
+  if (bad) {
+    bsc_bigwig_close(bw);
+    return bsc_set_error(BSC_ERR_NOMEM, "%s: out of memory", who);
+  }
+  bw->data_start = 296 + chrom_tree_bytes(n_refs, bw->key_size);
+  *out = bw;
+  return BSC_OK;
+}
+
+void bsc_bigwig_close(bsc_bigwig *bw) {
+  if (!bw) return;
+  for (uint32_t k = 0; bw->names && k < bw->n_refs; k++) free(bw->names[k]);
+  free(bw->names);
+  free(bw->lens);
+  free(bw->sec);
+  free(bw->z0);
+  free(bw);
+}
+
+static int grow(void **p, uint64_t *cap, uint64_t need, size_t item) {
+  if (need <= *cap) return 0;
+  uint64_t c = *cap ? *cap : 1024;
+  while (c < need) c *= 2;
+  void *q = realloc(*p, (size_t)c * item);
+  if (!q) return -1;
+  *p = q;
+  *cap = c;
+  return 0;
+}
+
+int bsc_bigwig_add(bsc_bigwig *bw, uint32_t tid, const void *data, uint64_t n_bytes, const bsc_bw_sum *sections, uint64_t n_sections,
+                   const bsc_bw_sum *zoom0, uint64_t n_zoom0) {
+  static const char who[] = "bsc_bigwig_add";
+  if (!bw || (n_bytes && !data) || (n_sections && !sections) || (n_zoom0 && !zoom0)) return bsc_set_error(BSC_ERR_ARG, "%s: NULL argument", who);
+  if (bw->finished) return bsc_set_error(BSC_ERR_ARG, "%s: the file is finished", who);
+  if (tid >= bw->n_refs) return bsc_set_error(BSC_ERR_ARG, "%s: contig %u of %u", who, tid, bw->n_refs);
+  if (bw->have_last && tid < bw->last_tid) return bsc_set_error(BSC_ERR_ARG, "%s: contig %u behind contig %u", who, tid, bw->last_tid);
+  if (!n_sections) {
+    if (n_bytes || n_zoom0) return bsc_set_error(BSC_ERR_ARG, "%s: bytes or windows without a section", who);
+    return BSC_OK;
+  }
+  if (!n_zoom0) return bsc_set_error(BSC_ERR_ARG, "%s: sections without a window", who);
+  const uint64_t S = bw->par.items_per_section, red = bw->par.reduction;
+  uint64_t sites = 0, zsites = 0;
+  uint32_t end = bw->have_last && tid == bw->last_tid ? bw->last_end : 0;
+  if (sections[0].start < end)
+    return bsc_set_error(BSC_ERR_ARG, "%s: contig %u: start %u lies below the previous end %u", who, tid, sections[0].start, end);
+  for (uint64_t k = 0; k < n_sections; k++) {
+    const bsc_bw_sum *s = &sections[k];
+    if (!s->count || s->count > S || (k + 1 < n_sections && s->count != S) || s->start < end || s->end <= s->start || s->end - s->start < s->count)
+      return bsc_set_error(BSC_ERR_ARG, "%s: section %llu is not one of %llu sites in order", who, (unsigned long long)k, (unsigned long long)S);
+    end = s->end;
+    sites += s->count;
+  }
+  if (24 * n_sections + 8 * sites != n_bytes)
+    return bsc_set_error(BSC_ERR_ARG, "%s: %llu sections of %llu sites are not %llu bytes", who, (unsigned long long)n_sections,
+                         (unsigned long long)sites, (unsigned long long)n_bytes);
+  for (uint64_t k = 0; k < n_zoom0; k++) {
+    const bsc_bw_sum *z = &zoom0[k];
+    if (!z->count || z->end <= z->start || (z->end - 1u) / red != z->start / red || (k && z->start / red <= zoom0[k - 1].start / red))
+      return bsc_set_error(BSC_ERR_ARG, "%s: window %llu is not one window of %llu bases in order", who, (unsigned long long)k, (unsigned long long)red);
+    zsites += z->count;
+  }
+  if (zsites != sites || zoom0[0].start != sections[0].start || zoom0[n_zoom0 - 1].end != end)
+    return bsc_set_error(BSC_ERR_ARG, "%s: the windows do not hold the sections' sites", who);
+  if (grow((void **)&bw->sec, &bw->cap_sec, bw->n_sec + n_sections, sizeof *bw->sec)) return bsc_set_error(BSC_ERR_NOMEM, "%s: out of memory", who);
+  if (grow((void **)&bw->z0, &bw->cap_z0, bw->n_z0 + n_zoom0, sizeof *bw->z0)) return bsc_set_error(BSC_ERR_NOMEM, "%s: out of memory", who);
+  const uint64_t base = bw->data_start + 8 + bw->data_bytes;
+  if (write_all(bw->fd, data, n_bytes, base)) return bsc_set_error(BSC_ERR_ARG, "%s: write failed: %s", who, strerror(errno));
+  for (uint64_t k = 0; k < n_sections; k++) {
+    bw->sec[bw->n_sec].tid = tid;
+    bw->sec[bw->n_sec].s = sections[k];
+    bw->sec[bw->n_sec].s._pad = 0;
+    bw->sec[bw->n_sec++].off = base + k * (24 + 8 * S);
+  }
+  for (uint64_t k = 0; k < n_zoom0; k++) {
+    bw_rec *prev = bw->n_z0 ? &bw->z0[bw->n_z0 - 1] : NULL;
+    if (!k && prev && prev->tid == tid && prev->s.start / red == zoom0[0].start / red) { /* a window two blocks share */
+      sum_merge(&prev->s, &zoom0[0]);
+      continue;
+    }
+    bw->z0[bw->n_z0].tid = tid;
+    bw->z0[bw->n_z0].s = zoom0[k];
+    bw->z0[bw->n_z0].off = 0;
+    bw->z0[bw->n_z0++].s._pad = 0;
+  }
+  bw->data_bytes += n_bytes;
+  bw->have_last = 1;
+  bw->last_tid = tid;
+  bw->last_end = end;
+  return BSC_OK;
+}
+
+/* a zoom level's records at file offset `at`: the count, the blocks, the R-tree over the blocks; *index = the tree's offset */
+static int zoom_level_put(bw_buf *b, const bw_rec *r, uint64_t n, uint64_t at, uint64_t *index) {
+  const uint64_t b0 = b->n;
+  rt_item *it = malloc((size_t)(n ? n : 1) * sizeof *it); /* (at most one block per record) */
+  if (!it) return -1;
+  uint64_t n_it = 0;
+  buf_u32(b, (uint32_t)n);
+  for (uint64_t i = 0; i < n;) {
+    uint64_t j = i;
+    while (j < n && j - i < BW_ZBLOCK && r[j].tid == r[i].tid) j++;
+    const rt_item v = {r[i].tid, r[i].s.start, r[i].tid, r[j - 1].s.end, at + (b->n - b0), 32 * (j - i)};
+    it[n_it++] = v;
+    for (; i < j; i++) {
+      const bsc_bw_sum *s = &r[i].s;
+      buf_u32(b, r[i].tid);
+      buf_u32(b, s->start);
+      buf_u32(b, s->end);
+      buf_u32(b, s->count);
+      buf_f32(b, (float)((double)s->min_m / 10.0));
+      buf_f32(b, (float)((double)s->max_m / 10.0));
+      buf_f32(b, (float)((double)s->sum_m / 10.0));
+      buf_f32(b, (float)((double)s->sum_m2 / 100.0));
+    }
+  }
+  *index = at + (b->n - b0);
+  const int rc = rtree_put(b, it, n_it, *index, *index);
+  free(it);
+  return rc;
+}
+
+int bsc_bigwig_finish(bsc_bigwig *bw) {
+  static const char who[] = "bsc_bigwig_finish";
+  if (!bw) return bsc_set_error(BSC_ERR_ARG, "%s: NULL argument", who);
+  if (bw->finished) return bsc_set_error(BSC_ERR_ARG, "%s: the file is finished", who);
+  if (bw->n_z0 > 0xffffffffull) return bsc_set_error(BSC_ERR_ARG, "%s: more than 2^32 - 1 zoom records", who);
+  bw_buf head = {0}, tail = {0};
+  int rc = 0, levels = 0;
+  uint64_t z_red[BW_LEVELS] = {0}, z_data[BW_LEVELS] = {0}, z_index[BW_LEVELS] = {0};
+  const uint64_t index_at = bw->data_start + 8 + bw->data_bytes;
+  /* the sections' index */
+  rt_item *it = malloc((size_t)(bw->n_sec ? bw->n_sec : 1) * sizeof *it);
+  uint64_t covered = 0, min_m = 0, max_m = 0, sum_m = 0, sum_m2 = 0;
+  if (!it) rc = -1;
+  for (uint64_t k = 0; k < bw->n_sec && !rc; k++) {
+    const bw_rec *s = &bw->sec[k];
+    const rt_item v = {s->tid, s->s.start, s->tid, s->s.end, s->off, 24 + 8 * (uint64_t)s->s.count};
+    it[k] = v;
+    if (!k || s->s.min_m < min_m) min_m = s->s.min_m;
+    if (!k || s->s.max_m > max_m) max_m = s->s.max_m;
+    covered += s->s.count;
+    sum_m += s->s.sum_m;
+    sum_m2 += s->s.sum_m2;
+  }
+  if (!rc) rc = rtree_put(&tail, it, bw->n_sec, index_at, index_at);
+  free(it);
+  /* the pyramid */
+  bw_rec *cur = bw->z0, *own = NULL;
+  uint64_t n_cur = bw->n_z0, width = bw->par.reduction;
+  for (int l = 0; l < BW_LEVELS && !rc; l++) {
+    if (l) {
+      if (n_cur <= 256) break;
+      width *= 4; /* (reduction < 2^32, 4^7 = 2^14: 64 bits hold it) */
+      bw_rec *next = malloc((size_t)n_cur * sizeof *next);
+      if (!next) {
+        rc = -1;
+        break;
+      }
+      uint64_t m = 0;
+      for (uint64_t i = 0; i < n_cur; i++) {
+        if (m && next[m - 1].tid == cur[i].tid && next[m - 1].s.start / width == cur[i].s.start / width) sum_merge(&next[m - 1].s, &cur[i].s);
+        else next[m++] = cur[i];
+      }
+      free(own);
+      cur = own = next;
+      n_cur = m;
+    }
+    z_red[l] = width < 0xffffffffull ? width : 0xffffffffull;
+    z_data[l] = index_at + tail.n;
+    rc = zoom_level_put(&tail, cur, n_cur, z_data[l], &z_index[l]);
+    levels = l + 1;
+  }
+  free(own);
+  buf_u32(&tail, BW_MAGIC);
+  /* the header, the zoom headers, the total summary, the chromosome tree, the section count */
+  buf_u32(&head, BW_MAGIC);
+  buf_u16(&head, 4);
+  buf_u16(&head, (uint16_t)levels);
+  buf_u64(&head, 296);
+  buf_u64(&head, bw->data_start);
+  buf_u64(&head, index_at);
+  buf_u16(&head, 0);
+  buf_u16(&head, 0);
+  buf_u64(&head, 0);
+  buf_u64(&head, 256);
+  buf_u32(&head, 0);
+  buf_u64(&head, 0);
+  for (int l = 0; l < BW_LEVELS; l++) {
+    buf_u32(&head, l < levels ? (uint32_t)z_red[l] : 0);
+    buf_u32(&head, 0);
+    buf_u64(&head, l < levels ? z_data[l] : 0);
+    buf_u64(&head, l < levels ? z_index[l] : 0);
+  }
+  buf_u64(&head, covered);
+  buf_f64(&head, (double)min_m / 10.0);
+  buf_f64(&head, (double)max_m / 10.0);
+  buf_f64(&head, (double)sum_m / 10.0);
+  buf_f64(&head, (double)sum_m2 / 100.0);
+  if (!rc) rc = chrom_tree_put(&head, bw, 296);
+  buf_u64(&head, bw->n_sec);
+  if (!rc && (head.oom || tail.oom)) rc = -1;
+  if (rc) {
+    free(head.p);
+    free(tail.p);
+    return bsc_set_error(BSC_ERR_NOMEM, "%s: out of memory", who);
+  }
+  if (head.n != bw->data_start + 8) {
+    free(head.p);
+    free(tail.p);
+    return bsc_set_error(BSC_ERR_ARG, "%s: the head is %zu bytes, not %llu", who, head.n, (unsigned long long)bw->data_start + 8);
+  }
+  if (write_all(bw->fd, tail.p, tail.n, index_at) || write_all(bw->fd, head.p, head.n, 0))
+    rc = bsc_set_error(BSC_ERR_ARG, "%s: write failed: %s", who, strerror(errno));
+  free(head.p);
+  free(tail.p);
+  if (!rc) bw->finished = 1;
+  return rc;
+}

@@ -88,6 +88,11 @@ int bsc_dev_launch_meth(const void *recs, const void *core, const void *aux, con
 int bsc_dev_launch_meth_regions(const void *core, const void *aux, const void *emit, uint64_t n, uint32_t x0, const bsc_meth_params *par, void *planes,
                                 void *scan, void *scan_tmp, size_t scan_tmp_bytes, const void *regions, uint32_t r_lo, uint32_t r_hi, void *acc,
                                 int num_cus, void *stream); /* methregionsdev.hip */
+int bsc_dev_launch_bigwig(const void *core, const void *aux, const void *emit, uint64_t n, uint32_t x0, uint32_t chrom_id, const bsc_meth_params *par,
+                          const bsc_bw_params *bwp, const void *val, void *cnt, void *off, void *hcnt, void *hoff, void *scan_tmp, size_t scan_tmp_bytes,
+                          void *sites, void *wbeg, void *out, uint64_t out_cap, void *sections, uint64_t sec_cap, void *zoom, uint64_t zoom_cap,
+                          void *totals, int num_cus, void *stream); /* bigwigdev.hip */
+const float *bsc_bw_values(void);                                    /* bigwig.c: (float)(m / 10.0), m = 0 .. 1000 */
 int bsc_dev_launch_ref_pad(const void *packed, const void *d_blk, uint32_t n_blk, void *padded, uint32_t n_pos, int num_cus, void *stream);
 int bsc_dev_launch_bin_reads_multi(const void *tpl, uint32_t nr, const void *seq, uint64_t seq_bytes, const void *d_blk, uint32_t n_blk,
                                    uint32_t n_bins, void *tflag, void *bin_cnt, void *bin_off, void *bin_cur, void *scan_tmp,
@@ -191,6 +196,18 @@ struct bsc_context {
     size_t cap_pl, cap_sc, cap_tmp;
     hipStream_t last;
   } mr;
+  struct { /* the bigWig track (bigwigdev.hip): the 1001 floats; the workspaces of a call — sites per tile and window heads per tile with their
+            * prefix sums, scan scratch, the compact {start, m} sites, the windows' first ranks; bsc_block_bigwig_kept: the block's stream, its
+            * section and window summaries, the six totals, the host copies of the summaries, the stream's length */
+    void *d_val;
+    void *d_cnt, *d_off, *d_hcnt, *d_hoff, *d_tmp, *d_sites, *d_wbeg;
+    size_t cap_cnt, cap_off, cap_hcnt, cap_hoff, cap_tmp, cap_sites, cap_wbeg;
+    void *d_data, *d_sec, *d_zoom, *d_tot;
+    size_t cap_data, cap_sec, cap_zoom, cap_tot;
+    bsc_bw_sum *h_sec, *h_zoom;
+    size_t cap_hsec, cap_hzoom;
+    uint64_t bytes;
+  } bw;
   /* the CSI scan (csidev.hip): runs per interval, their prefix sum, scan scratch, the entries and {entries, records, error bits} of the
    * follow-up call bsc_block_csi_kept, its host copy; and what the last encoder call left in d_bto: for which stream, how many tiles, text */
   void *d_cscn, *d_csof, *d_cstm, *d_csen, *d_cstot;
@@ -598,6 +615,20 @@ int bsc_destroy(bsc_context *ctx) {
   hipFree(ctx->mr.d_pl);
   hipFree(ctx->mr.d_sc);
   hipFree(ctx->mr.d_tmp);
+  hipFree(ctx->bw.d_val);
+  hipFree(ctx->bw.d_cnt);
+  hipFree(ctx->bw.d_off);
+  hipFree(ctx->bw.d_hcnt);
+  hipFree(ctx->bw.d_hoff);
+  hipFree(ctx->bw.d_tmp);
+  hipFree(ctx->bw.d_sites);
+  hipFree(ctx->bw.d_wbeg);
+  hipFree(ctx->bw.d_data);
+  hipFree(ctx->bw.d_sec);
+  hipFree(ctx->bw.d_zoom);
+  hipFree(ctx->bw.d_tot);
+  free(ctx->bw.h_sec);
+  free(ctx->bw.h_zoom);
   hipFree(ctx->d_cscn);
   hipFree(ctx->d_csof);
   hipFree(ctx->d_cstm);
@@ -3169,6 +3200,131 @@ int bsc_meth_regions_reset(bsc_context *ctx) {
   HIP_TRY(hipMemsetAsync(ctx->mr.d_acc, 0, (size_t)ctx->mr.n * 32u, ctx->stream));
   HIP_TRY(hipStreamSynchronize(ctx->stream));
   ctx->mr.last = ctx->stream;
+  return BSC_OK;
+}
+
+/* ---- the methylation bigWig track (bigwigdev.hip): include/bscall_amd.h has the rule, csrc/bigwig.c the host form and the file's writer ------ */
+static int bsc_bigwig_params_check(const char *who, const bsc_meth_params *par, const bsc_bw_params *bwp) {
+  if (!par || !bwp) return bsc_fail(BSC_ERR_ARG, "%s: NULL argument", who);
+  if (par->contexts != BSC_METH_CPG && par->contexts != BSC_METH_ALL)
+    return bsc_fail(BSC_ERR_ARG, "%s: contexts is %d, not BSC_METH_CPG or BSC_METH_ALL", who, (int)par->contexts);
+  if (bwp->items_per_section < 1u || bwp->items_per_section > 65535u || bwp->reduction < 1u)
+    return bsc_fail(BSC_ERR_ARG, "%s: items_per_section is 1 .. 65535, reduction 1 or more", who);
+  return BSC_OK;
+}
+
+/* the kernels over d_core[n] / d_aux[n] (entry i = position x0 + i, n >= 1) on stream s, in the context's workspaces */
+static int bsc_bigwig_run(bsc_context *ctx, const char *who, const void *d_core, const void *d_aux, const void *d_emit, uint32_t n, uint32_t x0,
+                          uint32_t chrom_id, const bsc_meth_params *par, const bsc_bw_params *bwp, void *d_out, uint64_t out_cap, void *d_sections,
+                          uint64_t sec_cap, void *d_zoom, uint64_t zoom_cap, void *d_totals, hipStream_t s) {
+  const uint32_t n_tiles = (uint32_t)(((uint64_t)n + 63u) / 64u);
+  size_t scan_bytes = 0;
+  int rc;
+  if (bsc_dev_scan_tmp_bytes_u64(n_tiles + 1u, &scan_bytes)) return bsc_fail(BSC_ERR_HIP, "%s: scan size query failed", who);
+  if (!ctx->bw.d_val) { /* the table of the 1001 floats, uploaded verbatim (the host's copy is static) */
+    HIP_TRY(hipMalloc(&ctx->bw.d_val, 1001 * sizeof(float)));
+    HIP_TRY(hipMemcpy(ctx->bw.d_val, bsc_bw_values(), 1001 * sizeof(float), hipMemcpyHostToDevice));
+  }
+  if ((rc = bsc_reserve(&ctx->bw.d_cnt, &ctx->bw.cap_cnt, ((size_t)n_tiles + 1u) * 8u))) return rc;
+  if ((rc = bsc_reserve(&ctx->bw.d_off, &ctx->bw.cap_off, ((size_t)n_tiles + 1u) * 8u))) return rc;
+  if ((rc = bsc_reserve(&ctx->bw.d_hcnt, &ctx->bw.cap_hcnt, ((size_t)n_tiles + 1u) * 8u))) return rc;
+  if ((rc = bsc_reserve(&ctx->bw.d_hoff, &ctx->bw.cap_hoff, ((size_t)n_tiles + 1u) * 8u))) return rc;
+  if ((rc = bsc_reserve(&ctx->bw.d_tmp, &ctx->bw.cap_tmp, scan_bytes ? scan_bytes : 1))) return rc;
+  if ((rc = bsc_reserve(&ctx->bw.d_sites, &ctx->bw.cap_sites, (size_t)n * 8u))) return rc;
+  if ((rc = bsc_reserve(&ctx->bw.d_wbeg, &ctx->bw.cap_wbeg, ((size_t)n + 1u) * 4u))) return rc;
+  const int e = bsc_dev_launch_bigwig(d_core, d_aux, d_emit, n, x0, chrom_id, par, bwp, ctx->bw.d_val, ctx->bw.d_cnt, ctx->bw.d_off, ctx->bw.d_hcnt,
+                                      ctx->bw.d_hoff, ctx->bw.d_tmp, scan_bytes, ctx->bw.d_sites, ctx->bw.d_wbeg, d_out, out_cap, d_sections, sec_cap,
+                                      d_zoom, zoom_cap, d_totals, ctx->num_cus, (void *)s);
+  if (e) return bsc_fail(BSC_ERR_HIP, "%s: launch failed: %s", who, hipGetErrorString((hipError_t)e));
+  return BSC_OK;
+}
+
+int bsc_bigwig_sites_device(bsc_context *ctx, const void *d_core, const void *d_aux, uint32_t n, uint32_t x0, uint32_t chrom_id,
+                            const bsc_meth_params *params, const bsc_bw_params *bw_params, void *d_out, uint64_t out_cap, void *d_sections,
+                            uint64_t sec_cap, void *d_zoom, uint64_t zoom_cap, void *d_totals, void *stream) {
+  static const char who[] = "bsc_bigwig_sites_device";
+  int rc;
+  if (!ctx || !d_totals || (n && (!d_core || !d_aux)) || (out_cap && !d_out) || (sec_cap && !d_sections) || (zoom_cap && !d_zoom))
+    return bsc_fail(BSC_ERR_ARG, "%s: NULL argument", who);
+  if ((rc = bsc_bigwig_params_check(who, params, bw_params))) return rc;
+  if (((uintptr_t)d_core | (uintptr_t)d_aux) & 15u) return bsc_fail(BSC_ERR_ARG, "%s: the arrays must be 16-byte aligned", who);
+  if (((uintptr_t)d_out | (uintptr_t)d_sections | (uintptr_t)d_zoom | (uintptr_t)d_totals) & 7u)
+    return bsc_fail(BSC_ERR_ARG, "%s: the outputs must be 8-byte aligned", who);
+  if (x0 < 1u) return bsc_fail(BSC_ERR_ARG, "%s: positions are 1-based (x0 = 0)", who);
+  if (n && (uint64_t)x0 + n - 1u > 0xffffffffull) return bsc_fail(BSC_ERR_ARG, "%s: x0 + n - 1 = %llu is beyond 2^32 - 1", who, (unsigned long long)x0 + n - 1u);
+  BSC_ENTER(ctx);
+  if (!n) { /* no position, no site: nothing to launch */
+    HIP_TRY(hipMemsetAsync(d_totals, 0, 6 * sizeof(unsigned long long), (hipStream_t)stream));
+    return BSC_OK;
+  }
+  return bsc_bigwig_run(ctx, who, d_core, d_aux, NULL, n, x0, chrom_id, params, bw_params, d_out, out_cap, d_sections, sec_cap, d_zoom, zoom_cap,
+                        d_totals, (hipStream_t)stream);
+}
+
+static int bsc_host_room(bsc_bw_sum **p, size_t *cap, uint64_t need) {
+  if (need <= *cap) return BSC_OK;
+  free(*p);
+  *cap = 0;
+  *p = malloc((size_t)(need + need / 4) * sizeof **p);
+  if (!*p) return bsc_fail(BSC_ERR_NOMEM, "bsc_block_bigwig_kept: out of host memory");
+  *cap = (size_t)(need + need / 4);
+  return BSC_OK;
+}
+
+int bsc_block_bigwig_kept(bsc_context *ctx, uint32_t chrom_id, const bsc_meth_params *params, const bsc_bw_params *bw_params, uint64_t *n_bytes,
+                          uint64_t *n_sites, const bsc_bw_sum **sections, uint64_t *n_sections, const bsc_bw_sum **zoom0, uint64_t *n_zoom0) {
+  static const char who[] = "bsc_block_bigwig_kept";
+  int rc;
+  if (!ctx || !n_bytes || !sections || !n_sections || !zoom0 || !n_zoom0) return bsc_fail(BSC_ERR_ARG, "%s: NULL argument", who);
+  *n_bytes = *n_sections = *n_zoom0 = 0;
+  *sections = *zoom0 = NULL;
+  if (n_sites) *n_sites = 0;
+  ctx->bw.bytes = 0;
+  if ((rc = bsc_bigwig_params_check(who, params, bw_params))) return rc;
+  if (ctx->meth_src != 1 || ctx->rec_pending || ctx->pending_sz)
+    return bsc_fail(BSC_ERR_ARG, "%s: the last call left no single block's arrays on the device", who);
+  const uint32_t n = ctx->again.sz, x0 = ctx->meth_x;
+  if (!n) return BSC_OK;
+  BSC_ENTER(ctx);
+  hipStream_t s = ctx->stream;
+  /* room for the most a block of n positions can give: every position a site */
+  const uint64_t S = bw_params->items_per_section, red = bw_params->reduction;
+  const uint64_t sec_cap = ((uint64_t)n + S - 1) / S, out_cap = 24 * sec_cap + 8 * (uint64_t)n;
+  const uint64_t span = ((uint64_t)n + red - 1) / red + 1, zoom_cap = span < n ? span : n;
+  if ((rc = bsc_reserve(&ctx->bw.d_data, &ctx->bw.cap_data, (size_t)out_cap))) return rc;
+  if ((rc = bsc_reserve(&ctx->bw.d_sec, &ctx->bw.cap_sec, (size_t)sec_cap * sizeof(bsc_bw_sum)))) return rc;
+  if ((rc = bsc_reserve(&ctx->bw.d_zoom, &ctx->bw.cap_zoom, (size_t)zoom_cap * sizeof(bsc_bw_sum)))) return rc;
+  if ((rc = bsc_reserve(&ctx->bw.d_tot, &ctx->bw.cap_tot, 6 * sizeof(unsigned long long)))) return rc;
+  if ((rc = bsc_bigwig_run(ctx, who, ctx->d_vout, ctx->d_out, ctx->again.emit, n, x0, chrom_id, params, bw_params, ctx->bw.d_data, out_cap, ctx->bw.d_sec,
+                           sec_cap, ctx->bw.d_zoom, zoom_cap, ctx->bw.d_tot, s)))
+    return rc;
+  unsigned long long tot[6] = {0, 0, 0, 0, 0, 0};
+  HIP_TRY(hipMemcpyAsync(tot, ctx->bw.d_tot, sizeof tot, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  *n_bytes = tot[0];
+  if (n_sites) *n_sites = tot[1];
+  *n_sections = tot[2];
+  *n_zoom0 = tot[3];
+  if (tot[0] > out_cap || tot[2] > sec_cap || tot[3] > zoom_cap)
+    return bsc_fail(BSC_ERR_ARG, "%s: the block's %llu bytes, %llu sections, %llu windows are beyond the room of %llu, %llu, %llu", who, tot[0], tot[2],
+                    tot[3], (unsigned long long)out_cap, (unsigned long long)sec_cap, (unsigned long long)zoom_cap);
+  if ((rc = bsc_host_room(&ctx->bw.h_sec, &ctx->bw.cap_hsec, tot[2]))) return rc;
+  if ((rc = bsc_host_room(&ctx->bw.h_zoom, &ctx->bw.cap_hzoom, tot[3]))) return rc;
+  if (tot[2]) HIP_TRY(hipMemcpyAsync(ctx->bw.h_sec, ctx->bw.d_sec, (size_t)tot[2] * sizeof(bsc_bw_sum), hipMemcpyDeviceToHost, s));
+  if (tot[3]) HIP_TRY(hipMemcpyAsync(ctx->bw.h_zoom, ctx->bw.d_zoom, (size_t)tot[3] * sizeof(bsc_bw_sum), hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  *sections = ctx->bw.h_sec;
+  *zoom0 = ctx->bw.h_zoom;
+  ctx->bw.bytes = tot[0];
+  return BSC_OK;
+}
+
+int bsc_bigwig_stream_read(bsc_context *ctx, uint64_t off, uint64_t n, void *dst) {
+  if (!ctx || (!dst && n)) return bsc_fail(BSC_ERR_ARG, "bsc_bigwig_stream_read: NULL argument");
+  if (off + n > ctx->bw.bytes || off + n > ctx->bw.cap_data) return bsc_fail(BSC_ERR_ARG, "bsc_bigwig_stream_read: beyond the stream's end");
+  if (!n) return BSC_OK;
+  BSC_ENTER(ctx);
+  HIP_TRY(hipMemcpyAsync(dst, (const char *)ctx->bw.d_data + off, (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
   return BSC_OK;
 }
 

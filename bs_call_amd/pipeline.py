@@ -18,7 +18,8 @@ def run(bam_path: str, reference: Dict[str, np.ndarray], bcf_path: str, sample: 
         min_qual: Optional[int] = None, benchmark_mode: bool = False, under_conv: Optional[float] = None, over_conv: Optional[float] = None,
         host_prep: bool = False, host_bcf: bool = False, device_reader: bool = False, shard_rank: Optional[int] = None, shard_world: int = 1,
         reduce_device=None, text: bool = False, dbsnp_device: bool = False, meth_path: Optional[str] = None, meth_params=None, meth_merge: bool = False,
-        meth_regions=None, meth_regions_path: Optional[str] = None, meth_window: Optional[int] = None, **reader_kw) -> dict:
+        meth_regions=None, meth_regions_path: Optional[str] = None, meth_window: Optional[int] = None, bigwig_path: Optional[str] = None,
+        bigwig_section: int = 1024, bigwig_zoom: int = 1024, **reader_kw) -> dict:
     """reference: contig name -> uint8 reference codes (0 = N, 1..4 = ACGT; position 1 first).  Returns a summary dict.
     under_conv / over_conv / min_qual (defaults 0.01 / 0.05 / 20, src/init_param.c:26-31) are the MODEL's parameters: without
     `caller` the run builds its SiteCaller from them; with one, they are taken from it and a differing explicit value is an error
@@ -50,7 +51,16 @@ def run(bam_path: str, reference: Dict[str, np.ndarray], bcf_path: str, sample: 
     meth_regions: the path of a BED file, or a list of (contig, start, end[, name]) — 0-based, half-open; sorted here as the BED reader
     sorts, stably by (start, end) —, or what methbed.parse_regions returns.  meth_window=n in its place: fixed tiles of n bases over every
     contig.  meth_params apply; meth_path is not needed.  The file is plain text, contigs in the order their blocks come; a contig without
-    a block gives no line.  The same conditions as meth_path."""
+    a block gives no line.  The same conditions as meth_path.
+    bigwig_path: the methylation bigWig track of the same run (include/bscall_amd.h has the rule and the file's layout): every block's data
+    sections and summaries from the arrays it left on the device (SiteCaller.block_bigwig_kept, csrc/bigwigdev.hip), the file by
+    bigwig.Writer.  bigwig_section: sites a section (1 .. 65535); bigwig_zoom: the width of a level-0 zoom window.  meth_params apply; the
+    track is per cytosine whatever meth_merge says; meth_path is not needed.  The same conditions as meth_path."""
+    want_bw = bigwig_path is not None
+    if want_bw and (shard_rank is not None or not device_reader or host_prep or host_bcf):
+        raise ValueError("bigwig_path is a single run on the device reader (device_reader=True, no shard_rank, no host_prep / host_bcf)")
+    if want_bw and not (1 <= int(bigwig_section) <= 65535 and 1 <= int(bigwig_zoom) <= 0xFFFFFFFF):
+        raise ValueError("bigwig_section is 1 .. 65535 sites, bigwig_zoom 1 or more bases")
     want_regions = meth_regions is not None or meth_window is not None
     if meth_regions is not None and meth_window is not None:
         raise ValueError("meth_regions and meth_window exclude each other: the regions are the given ones or the fixed tiles")
@@ -90,6 +100,7 @@ def run(bam_path: str, reference: Dict[str, np.ndarray], bcf_path: str, sample: 
     on_device = dbsnp_device and dbsnp is not None
     if text and (shard_rank is not None or not device_reader or host_prep or host_bcf):
         raise ValueError("text=True is a single run on the device reader (device_reader=True, no shard_rank, no host_prep / host_bcf)")
+    bw_writer = None
     own = caller is None
     if own:
         under_conv = 0.01 if under_conv is None else under_conv
@@ -109,6 +120,7 @@ def run(bam_path: str, reference: Dict[str, np.ndarray], bcf_path: str, sample: 
         per_contig = []
         n_blocks = n_records = 0
         meth_blobs, meth_lines = [], 0
+        bw_sites = 0
         region_out, region_cur = [], None  # the summary's lines, contig by contig; (name, regions, names) of the contig attached
         c.reset_site_stats()
         sharded = shard_rank is not None
@@ -140,6 +152,12 @@ def run(bam_path: str, reference: Dict[str, np.ndarray], bcf_path: str, sample: 
                                      mapq_thresh=reader_kw.get("mapq_thresh", 20), min_qual=min_qual, date=date,
                                      dbsnp_header=None if dbsnp is None else dbsnp.header, benchmark_mode=benchmark_mode)
 
+            if want_bw:
+                from . import bigwig
+
+                bw_writer = bigwig.Writer(bigwig_path, refs, int(bigwig_section), int(bigwig_zoom))
+                bw_par = {"items_per_section": int(bigwig_section), "reduction": int(bigwig_zoom)}
+
             def regions_flush():
                 nonlocal region_cur
                 if region_cur is not None:
@@ -149,7 +167,7 @@ def run(bam_path: str, reference: Dict[str, np.ndarray], bcf_path: str, sample: 
                 region_cur = None
 
             def block_blobs():
-                nonlocal n_blocks, n_records, base_filter, passed, meth_lines, region_cur
+                nonlocal n_blocks, n_records, base_filter, passed, meth_lines, region_cur, bw_sites
                 before, cur_tid = c.site_totals(), -1
                 for item in (rd.device_blocks() if device_reader else rd.blocks()):
                     if device_reader:
@@ -197,9 +215,13 @@ def run(bam_path: str, reference: Dict[str, np.ndarray], bcf_path: str, sample: 
                         else:
                             blob, n_rec, st = c.block_bcf_rawdev(dblk, ref, tid, names=names, left_trim=left_trim, right_trim=right_trim, min_qual=min_qual,
                                                                  reg_stop=len(codes), dbsnp=flags, with_stats=True, profile=prof,
-                                                                 keep=meth_path is not None or want_regions)
+                                                                 keep=meth_path is not None or want_regions or want_bw)
                         if region_cur is not None:  # the block's cytosines into the attached regions' sums
                             c.block_meth_regions_kept(meth_params)
+                        if want_bw:  # the block's bigWig sections and summaries, appended to the track's file
+                            data, ns, secs, zoom0 = c.block_bigwig_kept(tid, meth_params, bw_par)
+                            bw_writer.add(tid, data, secs, zoom0)
+                            bw_sites += ns
                         if meth_path is not None:  # the same block's table, from what it left on the device
                             mb, ml, _ = c.block_meth_kept(name, meth_params, merge=meth_merge)
                             meth_blobs.append(mb)
@@ -242,6 +264,8 @@ def run(bam_path: str, reference: Dict[str, np.ndarray], bcf_path: str, sample: 
                 vcf.write_bcf(bcf_path, header, block_blobs(), compressed)  # blocks go to the writer as they are formed
             if meth_path is not None:
                 vcf.write_vcf_blobs(meth_path, "", meth_blobs, compressed)
+            if want_bw:
+                bw_writer.finish()
             if want_regions:
                 regions_flush()
                 with open(meth_regions_path, "wb") as f:
@@ -312,10 +336,14 @@ def run(bam_path: str, reference: Dict[str, np.ndarray], bcf_path: str, sample: 
         summary = {"blocks": n_blocks, "records": n_records, "report": report_text, "filter_cts": cts, "contigs": [n for n, _ in per_contig]}
         if meth_path is not None:
             summary["meth_lines"] = meth_lines
+        if want_bw:
+            summary["bigwig_sites"] = bw_sites
         if want_regions:
             summary["meth_region_lines"] = sum(b.count(b"\n") for b in region_out)
         return summary
     finally:
+        if bw_writer is not None:
+            bw_writer.close()
         if own:
             c.close()
         else:  # a supplied caller goes back as it came

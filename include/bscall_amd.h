@@ -1094,7 +1094,8 @@ int bsc_block_vcf_rawdev_keep(bsc_context *ctx, const void *d_raw, uint32_t nr, 
  *   bsc_meth_stream_read    bytes [off, off + n) of that table -> dst, queued on the context's stream (bsc_bcf_stream_read's twin)
  *   bsc_meth_stream_detach  the table handed over like bsc_bcf_stream_detach hands the kept stream over: bsc_detached_read / _wait /
  *                           _free or bsc_bgzf_write_device on it (it counts against the four pooled buffers out); the context forgets it
- * Not built: bigWig, the batched and host-buffer block entries.  (The combined-strand line per CpG dinucleotide: bsc_meth_cpg_*, below.)
+ * Not built: the batched and host-buffer block entries.  (The combined-strand line per CpG dinucleotide: bsc_meth_cpg_*, the bigWig track:
+ * bsc_bigwig_*, both below.)
  */
 #define BSC_METH_CPG 0
 #define BSC_METH_ALL 1
@@ -1238,6 +1239,116 @@ int bsc_meth_regions_sites_device(bsc_context *ctx, const void *d_core, const vo
 int bsc_block_meth_regions_kept(bsc_context *ctx, const bsc_meth_params *params, uint64_t *n_sites, uint64_t sums[3]);
 int bsc_meth_regions_read(bsc_context *ctx, uint64_t *acc_host, uint64_t n);
 int bsc_meth_regions_reset(bsc_context *ctx);
+/*
+ * The methylation bigWig track (csrc/bigwigdev.hip: the bsc_bigwig_*_kernel family; csrc/bigwig.c holds the host form, which is their
+ * checker, and the writer of the file): the file genome browsers and deepTools open — the methylation level per cytosine with its
+ * zoom pyramid —, made from the per-position arrays a block call left in HBM.  The reference's users get it from a second program that
+ * reads the BCF back.  Every number is an exact integer until the moment a float is written; no result depends on an order of summation;
+ * blocks merge exactly.  The rule, from which the host form, the tests' Python forms and the kernels are each written:
+ *   SITE      a record that gives a line under the per-cytosine rule of bsc_meth_format_rec with the given bsc_meth_params (contexts —
+ *             BSC_METH_ALL included —, min_cov, min_phred, pass_only: exactly as written there), with the same a and b.
+ *             start = pos - 1.  Sites come in record order, their starts strictly increasing.
+ *   VALUE     m = (2000 a + (a + b)) / (2 (a + b)) in 64 bits: 1000 a / (a + b) rounded half up, 0 .. 1000, tenths of a percent.  The float
+ *             written is (float)(m / 10.0): C double division, then the conversion.  The host makes the table of these 1001 floats once
+ *             and the device copies entries of it: the device does no floating-point arithmetic here.
+ *   SUMMARY   bsc_bw_sum, 40 bytes, of a run of sites: start = the first site's start, end = the last site's start + 1, count, min_m,
+ *             max_m, sum_m, sum_m2 (the sum of m * m: at most count * 10^6).  Two runs merge by adding count, sum_m and sum_m2, taking
+ *             the smaller min_m, the larger max_m, the earlier start and the later end.
+ *   PARAMS    bsc_bw_params {items_per_section S: 1 .. 65535, default 1024;  reduction: >= 1, default 1024}.
+ *   STREAM    of a block: section k holds the block's sites of rank [k S, (k + 1) S); sections lie back to back, uncompressed.  A section:
+ *               chromId u32, chromStart u32 = its first site's start, chromEnd u32 = its last site's start + 1, itemStep u32 = 0,
+ *               itemSpan u32 = 1, type u8 = 2 (varStep), reserved u8 = 0, itemCount u16          (24 bytes)
+ *               itemCount x {start u32, value f32}
+ *             little-endian.  Section k starts at byte k (24 + 8 S); only the last is short; n_bytes = 24 n_sections + 8 n_sites.
+ *             A section never spans two blocks (a tiny block gives a tiny section).
+ *   PER BLOCK sections[n_sections]: the summary of each section;  zoom0[n_windows]: the summaries of the windows w = start / reduction
+ *             that hold at least one site, ascending.
+ *   PYRAMID   (host, integers) level 0 is the blocks' zoom0 one behind the other; where a block's last window and the next block's
+ *             first window lie on one contig and have the same w they merge.  Level l has windows of reduction * 4^l (64 bits): it is
+ *             made by merging consecutive records of level l - 1 with equal start / (reduction * 4^l) on one contig.  Level 0 always
+ *             exists; level l exists iff level l - 1 has more than 256 records; at most 8 levels.
+ *   FILE      bbiFile version 4 as its published description states it, little-endian; readers follow offsets, the order is ours:
+ *               0        header, 64 bytes: magic u32 = 0x888FFC26, version u16 = 4, zoomLevels u16, chromosomeTreeOffset u64,
+ *                        fullDataOffset u64, fullIndexOffset u64, fieldCount u16 = 0, definedFieldCount u16 = 0, autoSqlOffset u64 = 0,
+ *                        totalSummaryOffset u64, uncompressBufSize u32 = 0 (nothing is compressed), extensionOffset u64 = 0
+ *               64       8 zoom headers of 24 bytes {reductionLevel u32 = min(reduction * 4^l, 2^32 - 1), reserved u32 = 0,
+ *                        dataOffset u64, indexOffset u64}; unused ones zero
+ *               256      total summary, 40 bytes {basesCovered u64 = the sites, minVal, maxVal, sumData, sumSquares f64} =
+ *                        min_m / 10.0, max_m / 10.0, sum_m / 10.0, sum_m2 / 100.0 over everything; all zero with no site
+ *               296      chromosome B+ tree: header 32 bytes {0x78CA8C91 u32, blockSize u32 = 256, keySize u32 = the longest name's
+ *                        length, valSize u32 = 8, itemCount u64 = n_refs, reserved u64 = 0}; a node is {isLeaf u8, reserved u8 = 0,
+ *                        count u16} and exactly count items (no padding); a leaf item key[keySize] (zero padded), chromId u32,
+ *                        chromSize u32; a non-leaf item key[keySize], childOffset u64.  Every contig of the BAM header is listed, keys in
+ *                        ascending memcmp order (readers search the tree); chromId = the contig's index in the BAM header, the order
+ *                        the data are written in (what the R-tree needs).  Built bottom-up, up to 256 items a node, until one node is
+ *                        left; written root first, level by level; a non-leaf key is its child's first key.  No contig: an empty leaf.
+ *               fullDataOffset    u64 sectionCount, then the blocks' streams
+ *               fullIndexOffset   R-tree over the sections: header 48 bytes {0x2468ACE0 u32, blockSize u32 = 256, itemCount u64,
+ *                        startChromIx, startBase, endChromIx, endBase u32 (of everything; zero with no item), endFileOffset u64 = where
+ *                        the indexed data end, itemsPerSlot u32 = 1, reserved u32 = 0}; a node {isLeaf u8, reserved u8, count u16} and
+ *                        count items; a leaf item, 32 bytes: startChromIx, startBase, endChromIx, endBase u32, dataOffset u64, dataSize
+ *                        u64; a non-leaf item, 24 bytes: the four bounds, childOffset u64.  Bottom-up with 256 a node until one node is
+ *                        left, written root first, level by level; a node's start is the lexicographic minimum of its items' (chrom,
+ *                        base) starts, its end the maximum of their ends.  No item: the root is an empty leaf.
+ *               per level         u32 recordCount; its zoom blocks — up to 512 records of 32 bytes {chromId, chromStart, chromEnd,
+ *                        validCount u32, minVal, maxVal, sumData, sumSquares f32} = (float)(min_m / 10.0), (float)(max_m / 10.0),
+ *                        (float)(sum_m / 10.0), (float)(sum_m2 / 100.0); a block never spans two contigs —; then an R-tree with one leaf
+ *                        item per block.  The level's dataOffset names the recordCount, its indexOffset the R-tree.
+ *               end      u32 0x888FFC26
+ *             The bytes are UCSC-unpinned, as the BCF bytes are htslib-unpinned: no UCSC or pyBigWig reader has seen them here;
+ *             bs_call_amd/bigwig.py reads them back by the offsets alone.
+ * Host (csrc/bigwig.c):
+ *   bsc_bw_params_default      {1024, 1024}
+ *   bsc_bigwig_sections_recs   the host form over packed records recs[0 .. n): the stream -> out[cap], the summaries -> sections[] and
+ *                              zoom0[].  *n_sections and *n_zoom0 hold the ROOM of the two arrays on entry and the counts on return.  Where
+ *                              any of the three rooms is too small: BSC_ERR_ARG, the three needs reported and nothing written.
+ *   bsc_bigwig_open            a writer on a descriptor it may pwrite to (not closed here); names / lens: the BAM header's contigs
+ *   bsc_bigwig_add             a block's stream appended (pwrite) and its entries kept.  BSC_ERR_ARG — nothing written — for a tid lower
+ *                              than the last or not in the header, a start below the previous end on the same tid, or entries that do
+ *                              not describe n_bytes (every section but the last of S sites, 24 n_sections + 8 n_sites = n_bytes)
+ *   bsc_bigwig_finish          section count, R-tree, zoom levels, total summary, header, the closing magic; every write checked
+ *                              (BSC_ERR_ARG with errno's text).  Once.
+ *   bsc_bigwig_close           frees the writer (an unfinished file stays without a header: not a bigWig)
+ * Device:
+ *   bsc_bigwig_sites_device    from d_core[n] / d_aux[n], entry i = position x0 + i (x0 >= 1, x0 + n - 1 < 2^32; as
+ *                              bsc_meth_regions_sites_device): the stream -> d_out[out_cap] (8-byte aligned), the summaries ->
+ *                              d_sections[sec_cap], d_zoom[zoom_cap], and d_totals = six device u64 {n_bytes, n_sites, n_sections,
+ *                              n_windows, sum of m, sum of m * m}.  An array whose room is too small is not written at all — the needs are
+ *                              in d_totals, and nothing partial is to be trusted.  Asynchronous on `stream`; workspaces of the context
+ *                              (one call in flight per context).
+ *   bsc_block_bigwig_kept      the follow-up of the _keep block calls: preconditions and refusals of bsc_block_meth_kept; from the
+ *                              arrays that block left in HBM, by the chain's emit byte per position, with the block's own x, into buffers
+ *                              of its own.  *sections / *zoom0: the context's host copies, good until the next call.  The kept stream,
+ *                              its tile offsets, the methylation tables, bsc_block_csi_kept and the region accumulators are untouched;
+ *                              before or after them.  BSC_ERR_ARG with the sizes should a room be too small.  Waits.
+ *   bsc_bigwig_stream_read     bytes [off, off + n) of that block's stream -> dst, queued on the context's stream
+ * Not built: zlib-compressed sections (the device DEFLATE encoder makes BGZF members; a zlib wrapper needs Adler-32 and a change of
+ * bgzfdev.hip), a coverage track, sharded runs, the batched and host-buffer block entries.
+ */
+typedef struct {
+  uint32_t items_per_section; /* 1 .. 65535 */
+  uint32_t reduction;         /* >= 1: the width of a level-0 zoom window */
+} bsc_bw_params;
+typedef struct {
+  uint32_t start, end, count, min_m, max_m, _pad;
+  uint64_t sum_m, sum_m2;
+} bsc_bw_sum;
+typedef struct bsc_bigwig bsc_bigwig;
+void bsc_bw_params_default(bsc_bw_params *p);
+int bsc_bigwig_sections_recs(const bsc_vcf_rec *recs, size_t n, uint32_t chrom_id, const bsc_meth_params *params, const bsc_bw_params *bw_params,
+                             void *out, uint64_t cap, uint64_t *n_bytes, bsc_bw_sum *sections, uint64_t *n_sections, bsc_bw_sum *zoom0,
+                             uint64_t *n_zoom0);
+int bsc_bigwig_open(int fd, uint32_t n_refs, const char *const *names, const uint32_t *lens, const bsc_bw_params *bw_params, bsc_bigwig **bw);
+int bsc_bigwig_add(bsc_bigwig *bw, uint32_t tid, const void *data, uint64_t n_bytes, const bsc_bw_sum *sections, uint64_t n_sections,
+                   const bsc_bw_sum *zoom0, uint64_t n_zoom0);
+int bsc_bigwig_finish(bsc_bigwig *bw);
+void bsc_bigwig_close(bsc_bigwig *bw);
+int bsc_bigwig_sites_device(bsc_context *ctx, const void *d_core, const void *d_aux, uint32_t n, uint32_t x0, uint32_t chrom_id,
+                            const bsc_meth_params *params, const bsc_bw_params *bw_params, void *d_out, uint64_t out_cap, void *d_sections,
+                            uint64_t sec_cap, void *d_zoom, uint64_t zoom_cap, void *d_totals, void *stream);
+int bsc_block_bigwig_kept(bsc_context *ctx, uint32_t chrom_id, const bsc_meth_params *params, const bsc_bw_params *bw_params, uint64_t *n_bytes,
+                          uint64_t *n_sites, const bsc_bw_sum **sections, uint64_t *n_sections, const bsc_bw_sum **zoom0, uint64_t *n_zoom0);
+int bsc_bigwig_stream_read(bsc_context *ctx, uint64_t off, uint64_t n, void *dst);
 /* with bsc_set_profiling: device time (HIP events on the context's stream) of the most recent raw block — bsc_block_records_raw[dev],
  * bsc_block_bcf_raw[dev][_keep] — from its first pre-processing launch to the last launch it queued, the host's wait for the prepared size included */
 int bsc_last_raw_block_ms(bsc_context *ctx, float *ms);

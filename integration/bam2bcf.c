@@ -63,6 +63,12 @@
  * BCF / VCF, the .csi and the report are those of the run without it.  A single run on the device reader only.  --meth-merge: the table
  * is the combined-strand one — a line per CpG dinucleotide, both strands' counts added (bsc_block_meth_cpg_kept); not with --meth-all.
  *
+ * --meth-bigwig out.bw: the methylation level per cytosine as a bigWig track (include/bscall_amd.h has the rule and the file's layout): every
+ * block's data sections and summaries on the device (bsc_block_bigwig_kept, csrc/bigwigdev.hip), read into a host buffer and handed to the
+ * output thread as one more job, which bsc_bigwig_add places in the track's own file; bsc_bigwig_finish writes the indexes, the zoom levels and
+ * the header at the end.  --meth-bigwig-section n: sites a section (default 1024); --meth-bigwig-zoom n: the level-0 zoom window (default
+ * 1024).  The --meth-* thresholds and --meth-all apply; the track is per cytosine even with --meth-merge; --meth is not needed.
+ *
  * --meth-regions regions.bed --meth-regions-out out.tsv: the per-region methylation summary — per interval of the BED file the cytosines
  * inside it added up on the device (bsc_meth_regions_attach at the contig change, where -D attaches; bsc_block_meth_regions_kept behind
  * every block; bsc_meth_regions_read at the next contig change and at the end), ten columns a region: chrom start end name sites A+B A B
@@ -125,6 +131,13 @@ typedef struct {
   void *d;        /* the stream on the device; NULL: only close_fd */
   uint64_t n, at; /* its length, where it goes in the file */
   int fd, close_fd;
+  /* --meth-bigwig: a block's data in a host buffer of the job's own with copies of its summaries, for bsc_bigwig_add (which places them in the
+   * track's file itself); freed here */
+  bsc_bigwig *bw;
+  uint32_t bw_tid;
+  void *bw_data;
+  bsc_bw_sum *bw_sec, *bw_zoom;
+  uint64_t bw_n_sec, bw_n_zoom;
 } out_job;
 typedef struct {
   bsc_context *ctx;
@@ -175,6 +188,15 @@ static void *writer_main(void *a) {
         k ^= 1;
       }
       if (bsc_detached_free(w->ctx, j.d) < 0) bad = 1;
+    }
+    if (j.bw) {
+      if (bsc_bigwig_add(j.bw, j.bw_tid, j.bw_data, j.n, j.bw_sec, j.bw_n_sec, j.bw_zoom, j.bw_n_zoom) < 0) {
+        fprintf(stderr, "bam2bcf: %s\n", bsc_last_error());
+        bad = 1;
+      }
+      free(j.bw_data);
+      free(j.bw_sec);
+      free(j.bw_zoom);
     }
     if (j.close_fd && j.fd >= 0) close(j.fd);
     pthread_mutex_lock(&w->mu);
@@ -455,8 +477,10 @@ static uint64_t regions_flush(bsc_context *ctx, FILE *f, const char *contig, con
 
 int main(int argc, char **argv) {
   int rank = -1, world = 1, merge = 0, bgzf = 0, text = 0, index = 0, meth_merge = 0;
-  const char *dbsnp_path = NULL, *meth_path = NULL, *regions_path = NULL, *regions_out_path = NULL;
+  const char *dbsnp_path = NULL, *meth_path = NULL, *regions_path = NULL, *regions_out_path = NULL, *bigwig_path = NULL;
   uint32_t meth_window = 0;
+  bsc_bw_params bwpar;
+  bsc_bw_params_default(&bwpar);
   bsc_meth_params mpar;
   bsc_meth_params_default(&mpar);
   if (argc >= 2 && !strcmp(argv[argc - 1], "--meth") && (argc == 2 || strcmp(argv[argc - 2], "--meth"))) {
@@ -514,6 +538,18 @@ int main(int argc, char **argv) {
       }
       meth_window = (uint32_t)v;
     }
+    else if (!strcmp(argv[1], "--meth-bigwig")) bigwig_path = argv[2];
+    else if (!strcmp(argv[1], "--meth-bigwig-section") || !strcmp(argv[1], "--meth-bigwig-zoom")) {
+      char *end = NULL;
+      const int sec = argv[1][14] == 's';
+      const unsigned long v = strtoul(argv[2], &end, 10);
+      if (!argv[2][0] || *end || argv[2][0] == '-' || v < 1 || v > (sec ? 65535ul : 0xfffffffful)) {
+        fprintf(stderr, "%s: %s takes a count of %s, not '%s'\n", argv[0], argv[1], sec ? "sites, 1 .. 65535" : "bases, 1 or more", argv[2]);
+        return 2;
+      }
+      if (sec) bwpar.items_per_section = (uint32_t)v;
+      else bwpar.reduction = (uint32_t)v;
+    }
     else if (!strcmp(argv[1], "--meth-min-cov") || !strcmp(argv[1], "--meth-min-gq")) {
       char *end = NULL;
       const unsigned long v = strtoul(argv[2], &end, 10);
@@ -537,7 +573,7 @@ int main(int argc, char **argv) {
     argc -= 2;
   }
   if (argc < 5 || world < 1 || (rank >= 0 && rank >= world)) {
-    fprintf(stderr, "usage: %s [-O u|b] [--format bcf|vcf] [--index] [-D dbsnp.idx] [--meth out.bed [--meth-merge | --meth-all] [--meth-min-cov n] [--meth-min-gq n] [--meth-pass]] [--meth-regions regions.bed | --meth-window n --meth-regions-out out.tsv] [--rank r --world n | --merge n] in.bam ref.fa out.bcf report.json [sample]\n", argv[0]);
+    fprintf(stderr, "usage: %s [-O u|b] [--format bcf|vcf] [--index] [-D dbsnp.idx] [--meth out.bed [--meth-merge | --meth-all] [--meth-min-cov n] [--meth-min-gq n] [--meth-pass]] [--meth-regions regions.bed | --meth-window n --meth-regions-out out.tsv] [--meth-bigwig out.bw [--meth-bigwig-section n] [--meth-bigwig-zoom n]: the methylation level as a bigWig track, per cytosine even with --meth-merge, under the --meth-* thresholds and --meth-all] [--rank r --world n | --merge n] in.bam ref.fa out.bcf report.json [sample]\n", argv[0]);
     return 2;
   }
   if (text && (rank >= 0 || merge > 0)) {
@@ -602,6 +638,14 @@ int main(int argc, char **argv) {
   }
   if (regions_out_path && (getenv("BAM2BCF_HOST_PREP") || getenv("BAM2BCF_HOST_BCF") || getenv("BAM2BCF_HOST_READER"))) {
     fprintf(stderr, "%s: --meth-regions sums what the device reader's blocks leave on the device: not with BAM2BCF_HOST_READER / _HOST_BCF / _HOST_PREP\n", argv[0]);
+    return 2;
+  }
+  if (bigwig_path && (rank >= 0 || world > 1 || merge > 0)) {
+    fprintf(stderr, "%s: --meth-bigwig writes a single run's track; a sharded run (--rank / --world / --merge) has none\n", argv[0]);
+    return 2;
+  }
+  if (bigwig_path && (getenv("BAM2BCF_HOST_PREP") || getenv("BAM2BCF_HOST_BCF") || getenv("BAM2BCF_HOST_READER"))) {
+    fprintf(stderr, "%s: --meth-bigwig reduces what the device reader's blocks leave on the device: not with BAM2BCF_HOST_READER / _HOST_BCF / _HOST_PREP\n", argv[0]);
     return 2;
   }
   const char *sample = argc > 5 ? argv[5] : "SAMPLE";
@@ -724,12 +768,25 @@ int main(int argc, char **argv) {
   }
   bsc_bgzf *zw = NULL;
   bsc_csi *csi = NULL;
+  int bw_fd = -1;
+  bsc_bigwig *bw = NULL;
+  uint64_t bw_sites = 0;
   if (!sharded) {
     const char **names = calloc((size_t)n_ref + 1, sizeof *names);
     uint32_t *lens = calloc((size_t)n_ref + 1, sizeof *lens);
     for (int i = 0; i < n_ref; i++) {
       names[i] = REF_NAME(i);
       lens[i] = REF_LEN(i);
+    }
+    if (bigwig_path) { /* the track's file: the blocks' data go in as they come, the header and the indexes at the end (it keeps its own names) */
+      FILE *bf = fopen(bigwig_path, "wb");
+      if (!bf) {
+        perror(bigwig_path);
+        return 1;
+      }
+      bw_fd = dup(fileno(bf));
+      fclose(bf);
+      CHECK(bsc_bigwig_open(bw_fd, (uint32_t)n_ref, names, lens, &bwpar, &bw));
     }
     if (bgzf) { /* the header into the compressor: its members come out with the first block's */
       char *hb = NULL;
@@ -912,6 +969,30 @@ int main(int argc, char **argv) {
         CHECK(bsc_csi_add(csi, dblk.tid, ce, cn, n_bytes));
       }
       if (n_bytes && r_n) CHECK(bsc_block_meth_regions_kept(ctx, &mpar, NULL, NULL)); /* the block's cytosines into the attached regions' sums */
+      if (n_bytes && bw) { /* the block's bigWig sections and summaries, from the same arrays: a host buffer and a job of its own */
+        uint64_t b_bytes = 0, b_sites = 0, b_sec = 0, b_zoom = 0;
+        const bsc_bw_sum *sec = NULL, *zoom = NULL;
+        CHECK(bsc_block_bigwig_kept(ctx, (uint32_t)dblk.tid, &mpar, &bwpar, &b_bytes, &b_sites, &sec, &b_sec, &zoom, &b_zoom));
+        bw_sites += b_sites;
+        if (b_sec) {
+          out_job j;
+          memset(&j, 0, sizeof j);
+          j.fd = -1;
+          j.n = b_bytes;
+          j.bw = bw;
+          j.bw_tid = (uint32_t)dblk.tid;
+          j.bw_data = xrealloc(NULL, (size_t)b_bytes);
+          j.bw_sec = xrealloc(NULL, (size_t)b_sec * sizeof *sec);
+          j.bw_zoom = xrealloc(NULL, (size_t)b_zoom * sizeof *zoom);
+          j.bw_n_sec = b_sec;
+          j.bw_n_zoom = b_zoom;
+          memcpy(j.bw_sec, sec, (size_t)b_sec * sizeof *sec);
+          memcpy(j.bw_zoom, zoom, (size_t)b_zoom * sizeof *zoom);
+          CHECK(bsc_bigwig_stream_read(ctx, 0, b_bytes, j.bw_data));
+          CHECK(bsc_synchronize(ctx));
+          writer_push(&W, j);
+        }
+      }
       if (n_bytes && meth_path) { /* the block's methylation table, from the arrays the call left on the device: a buffer and a job of its own */
         uint64_t m_cap = (uint64_t)n * (mpar.contexts == BSC_METH_ALL ? 16 : 4) + 4096, m_bytes = 0, m_lines = 0;
         int (*const meth_kept)(bsc_context *, const char *, const bsc_meth_params *, uint64_t, uint64_t *, uint64_t *, uint64_t *) =
@@ -1082,6 +1163,14 @@ int main(int argc, char **argv) {
     perror(meth_path);
     return 1;
   }
+  if (bw) { /* every block's data are in: the section count, the indexes, the zoom levels, the summary and the header */
+    CHECK(bsc_bigwig_finish(bw));
+    bsc_bigwig_close(bw);
+    if (close(bw_fd)) {
+      perror(bigwig_path);
+      return 1;
+    }
+  }
   if (rout) { /* the last contig's lines */
     if (cur_tid >= 0) region_lines += regions_flush(ctx, rout, REF_NAME(cur_tid), r_regs, r_names, r_n);
     if (fclose(rout)) {
@@ -1179,6 +1268,7 @@ int main(int argc, char **argv) {
     printf("%llu blocks, %llu records written\n", (unsigned long long)n_blocks, (unsigned long long)n_records);
     if (meth_path) printf("%llu methylation table lines written\n", (unsigned long long)meth_lines);
     if (regions_out_path) printf("%llu methylation region lines written\n", (unsigned long long)region_lines);
+    if (bigwig_path) printf("%llu methylation bigWig sites written\n", (unsigned long long)bw_sites);
   }
   if (getenv("BAM2BCF_TIMING")) {
     uint64_t rc4[4] = {0, 0, 0, 0};
