@@ -70,6 +70,10 @@ $(LIBDIR)/bgzfdev.o: $(CSRC)/bgzfdev.hip
 	@mkdir -p $(LIBDIR)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
+$(LIBDIR)/zlibdev.o: $(CSRC)/zlibdev.hip
+	@mkdir -p $(LIBDIR)
+	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+
 $(LIBDIR)/dbsnpdev.o: $(CSRC)/dbsnpdev.hip $(CSRC)/dbsnpdev_core.h
 	@mkdir -p $(LIBDIR)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
@@ -146,7 +150,7 @@ $(LIBDIR)/synth_reads.o: $(CSRC)/synth_reads.c include/bscall_amd.h $(CSRC)/synt
 	@mkdir -p $(LIBDIR)
 	$(CC) $(CFLAGS) -c $< -o $@
 
-$(LIBDIR)/libbscall_amd.so: $(LIBDIR)/kernels.o $(LIBDIR)/fused.o $(LIBDIR)/accumulate.o $(LIBDIR)/sort.o $(LIBDIR)/vcfcore.o $(LIBDIR)/sitestats.o $(LIBDIR)/compact.o $(LIBDIR)/probe.o $(LIBDIR)/prepdev.o $(LIBDIR)/bcfdev.o $(LIBDIR)/vcftextdev.o $(LIBDIR)/methdev.o $(LIBDIR)/methregionsdev.o $(LIBDIR)/bigwigdev.o $(LIBDIR)/bgzfdev.o $(LIBDIR)/bamdev.o $(LIBDIR)/dbsnpdev.o $(LIBDIR)/csidev.o $(LIBDIR)/bscall_api.o $(LIBDIR)/bamstream.o $(LIBDIR)/inflate_fast.o $(LIBDIR)/synth_reads.o $(LIBDIR)/vcf_format.o $(LIBDIR)/methbed.o $(LIBDIR)/methcpg.o $(LIBDIR)/methregions.o $(LIBDIR)/bigwig.o $(LIBDIR)/dbsnp.o $(LIBDIR)/prep.o $(LIBDIR)/report.o $(LIBDIR)/bcf.o $(LIBDIR)/bamio.o $(LIBDIR)/refseq.o
+$(LIBDIR)/libbscall_amd.so: $(LIBDIR)/kernels.o $(LIBDIR)/fused.o $(LIBDIR)/accumulate.o $(LIBDIR)/sort.o $(LIBDIR)/vcfcore.o $(LIBDIR)/sitestats.o $(LIBDIR)/compact.o $(LIBDIR)/probe.o $(LIBDIR)/prepdev.o $(LIBDIR)/bcfdev.o $(LIBDIR)/vcftextdev.o $(LIBDIR)/methdev.o $(LIBDIR)/methregionsdev.o $(LIBDIR)/bigwigdev.o $(LIBDIR)/bgzfdev.o $(LIBDIR)/zlibdev.o $(LIBDIR)/bamdev.o $(LIBDIR)/dbsnpdev.o $(LIBDIR)/csidev.o $(LIBDIR)/bscall_api.o $(LIBDIR)/bamstream.o $(LIBDIR)/inflate_fast.o $(LIBDIR)/synth_reads.o $(LIBDIR)/vcf_format.o $(LIBDIR)/methbed.o $(LIBDIR)/methcpg.o $(LIBDIR)/methregions.o $(LIBDIR)/bigwig.o $(LIBDIR)/dbsnp.o $(LIBDIR)/prep.o $(LIBDIR)/report.o $(LIBDIR)/bcf.o $(LIBDIR)/bamio.o $(LIBDIR)/refseq.o
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $^ -lm -lz -lpthread
 
 oracle:
@@ -192,7 +196,15 @@ $(METHREGIONS_SAN_EXE): integration/methregions_san.c $(CSRC)/methregions.c incl
 BIGWIG_SAN_EXE ?= $(LIBDIR)/bigwig_san
 bigwig-san: $(BIGWIG_SAN_EXE)
 $(BIGWIG_SAN_EXE): integration/bigwig_san.c $(CSRC)/bigwig.c include/bscall_amd.h
-	$(CC) -std=gnu11 -O1 -g -Wall -Wextra -fsanitize=address,undefined -fno-sanitize-recover=undefined -Iinclude $< $(CSRC)/bigwig.c -lpthread -o $@
+	$(CC) -std=gnu11 -O1 -g -Wall -Wextra -fsanitize=address,undefined -fno-sanitize-recover=undefined -Iinclude $< $(CSRC)/bigwig.c -lpthread -lz -o $@
+
+# TEST ONLY: the compressed writer (bsc_bigwig_add_z, and bsc_bigwig_finish deflating the zoom blocks) as a stand-alone program under
+# AddressSanitizer + UndefinedBehaviorSanitizer, on the CPU; tests/test_bigwig_z_host.py builds its own copy and runs it:
+# $(BIGWIG_Z_SAN_EXE)  ->  "ok" and exit 0, or the case that failed
+BIGWIG_Z_SAN_EXE ?= $(LIBDIR)/bigwig_z_san
+bigwig-z-san: $(BIGWIG_Z_SAN_EXE)
+$(BIGWIG_Z_SAN_EXE): integration/bigwig_z_san.c $(CSRC)/bigwig.c include/bscall_amd.h
+	$(CC) -std=gnu11 -O1 -g -Wall -Wextra -fsanitize=address,undefined -fno-sanitize-recover=undefined -Iinclude $< $(CSRC)/bigwig.c -lpthread -lz -o $@
 
 # The library with its HOST C files under AddressSanitizer + UndefinedBehaviorSanitizer (gcc's runtimes; the device objects
 # are the ordinary ones): what tests/test_host_sanitizers.py and tools/fuzz_host_inputs.py run the readers and the host
@@ -202,7 +214,7 @@ HOST_C = bscall_api synth_reads vcf_format methbed methcpg methregions bigwig db
 san: $(LIBDIR)/libbscall_amd.so
 	@mkdir -p $(LIBDIR)/san
 	for f in $(HOST_C); do $(CC) $(SANFLAGS) -c $(CSRC)/$$f.c -o $(LIBDIR)/san/$$f.o || exit 1; done
-	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $(LIBDIR)/san/libbscall_amd_san.so $(LIBDIR)/kernels.o $(LIBDIR)/fused.o $(LIBDIR)/accumulate.o $(LIBDIR)/sort.o $(LIBDIR)/vcfcore.o $(LIBDIR)/sitestats.o $(LIBDIR)/compact.o $(LIBDIR)/probe.o $(LIBDIR)/prepdev.o $(LIBDIR)/bcfdev.o $(LIBDIR)/vcftextdev.o $(LIBDIR)/methdev.o $(LIBDIR)/methregionsdev.o $(LIBDIR)/bigwigdev.o $(LIBDIR)/bgzfdev.o $(LIBDIR)/bamdev.o $(LIBDIR)/dbsnpdev.o $(LIBDIR)/csidev.o $(addprefix $(LIBDIR)/san/,$(addsuffix .o,$(HOST_C))) -L$(dir $(shell $(CC) -print-file-name=libasan.so)) -lasan -lubsan -lm -lz -lpthread
+	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $(LIBDIR)/san/libbscall_amd_san.so $(LIBDIR)/kernels.o $(LIBDIR)/fused.o $(LIBDIR)/accumulate.o $(LIBDIR)/sort.o $(LIBDIR)/vcfcore.o $(LIBDIR)/sitestats.o $(LIBDIR)/compact.o $(LIBDIR)/probe.o $(LIBDIR)/prepdev.o $(LIBDIR)/bcfdev.o $(LIBDIR)/vcftextdev.o $(LIBDIR)/methdev.o $(LIBDIR)/methregionsdev.o $(LIBDIR)/bigwigdev.o $(LIBDIR)/bgzfdev.o $(LIBDIR)/zlibdev.o $(LIBDIR)/bamdev.o $(LIBDIR)/dbsnpdev.o $(LIBDIR)/csidev.o $(addprefix $(LIBDIR)/san/,$(addsuffix .o,$(HOST_C))) -L$(dir $(shell $(CC) -print-file-name=libasan.so)) -lasan -lubsan -lm -lz -lpthread
 
 # a plain-C host program against the C ABI: gcc only, links the shared library like bs_call would
 demo: $(LIBDIR)/demo_block $(LIBDIR)/bam2bcf
@@ -233,7 +245,7 @@ asm: $(CSRC)/kernels.hip
 	$(HIPCC) $(HIPFLAGS) -S --cuda-device-only -Rpass-analysis=kernel-resource-usage $< -o $(LIBDIR)/kernels.s
 
 clean:
-	rm -rf $(LIBDIR)/san; rm -f tests/devmath/libdevmath_probe.so tests/dbsnpdev/dbsnp_flat_host tests/csidev/csi_walk_host $(LIBDIR)/*.o $(LIBDIR)/*.so $(LIBDIR)/*.s $(LIBDIR)/demo_block $(LIBDIR)/bam2bcf $(LIBDIR)/methregions_san $(LIBDIR)/bigwig_san
+	rm -rf $(LIBDIR)/san; rm -f tests/devmath/libdevmath_probe.so tests/dbsnpdev/dbsnp_flat_host tests/csidev/csi_walk_host $(LIBDIR)/*.o $(LIBDIR)/*.so $(LIBDIR)/*.s $(LIBDIR)/demo_block $(LIBDIR)/bam2bcf $(LIBDIR)/methregions_san $(LIBDIR)/bigwig_san $(LIBDIR)/bigwig_z_san
 	$(MAKE) -C oracle clean
 
 .PHONY: all oracle demo asm clean glue-check san devmath-probe dbsnp-flat-host csi-walk-host

@@ -202,6 +202,10 @@ EXPORTS = (
     "bsc_bigwig_sites_device",
     "bsc_block_bigwig_kept",
     "bsc_bigwig_stream_read",
+    "bsc_zlib_pieces_device",
+    "bsc_block_bigwig_deflate",
+    "bsc_bigwig_zstream_read",
+    "bsc_bigwig_add_z",
 )
 
 
@@ -784,5 +788,13 @@ def load():
     L.bsc_block_bigwig_kept.argtypes = [vp, u32, C.POINTER(MethParams), C.POINTER(BwParams), pu64, pu64, C.POINTER(vp), pu64, C.POINTER(vp), pu64]
     L.bsc_bigwig_stream_read.restype = i32
     L.bsc_bigwig_stream_read.argtypes = [vp, u64, u64, vp]
+    L.bsc_zlib_pieces_device.restype = i32
+    L.bsc_zlib_pieces_device.argtypes = [vp, vp, u64, u32, vp, u64, vp, u64, vp, vp]
+    L.bsc_block_bigwig_deflate.restype = i32
+    L.bsc_block_bigwig_deflate.argtypes = [vp, pu64, C.POINTER(vp), pu64]
+    L.bsc_bigwig_zstream_read.restype = i32
+    L.bsc_bigwig_zstream_read.argtypes = [vp, u64, u64, vp]
+    L.bsc_bigwig_add_z.restype = i32
+    L.bsc_bigwig_add_z.argtypes = [vp, u32, vp, u64, vp, vp, u64, vp, u64]
     _lib = L
     return L

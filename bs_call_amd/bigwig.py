@@ -1,10 +1,13 @@
 """The methylation bigWig track (include/bscall_amd.h has the rule and the file's layout): the Python form of the rule over packed records
 (sections_of_recs), the writer of the file over the C ABI (Writer: bsc_bigwig_open / _add / _finish / _close), and a reader that follows the
 file's own offsets (read: header, chromosomes, total summary, zoom levels; intervals through the R-tree; zoom_records).  The bytes are
-UCSC-unpinned: no UCSC or pyBigWig reader has seen them; this reader is written from the same published layout."""
+UCSC-unpinned: no UCSC or pyBigWig reader has seen them; this reader is written from the same published layout.  A file whose
+uncompressBufSize is not 0 holds every section and zoom block as a zlib stream (Writer(compress=True) with add_z): the reader inflates
+them, and refuses a block that inflates to more than that size."""
 import ctypes as C
 import os
 import struct
+import zlib
 
 import numpy as np
 
@@ -106,12 +109,14 @@ def sections_recs_host(recs, chrom_id, meth_params=None, bw_params=None, room=No
 
 
 class Writer:
-    """bsc_bigwig_open / _add / _finish / _close on a file of its own.  refs: [(name, length)] in the BAM header's order."""
+    """bsc_bigwig_open / _add / _finish / _close on a file of its own.  refs: [(name, length)] in the BAM header's order.  compress: the
+    file's sections come as zlib streams through add_z (bsc_bigwig_add_z), and finish deflates the zoom blocks."""
 
-    def __init__(self, path, refs, items_per_section=1024, reduction=1024):
+    def __init__(self, path, refs, items_per_section=1024, reduction=1024, compress=False):
         from .caller import _check
 
         self._check, self._L = _check, _lib.load()
+        self.compress = bool(compress)
         self._f = open(path, "wb")
         names = (C.c_char_p * max(len(refs), 1))(*[n.encode() if isinstance(n, str) else bytes(n) for n, _ in refs])
         lens = np.array([l for _, l in refs], dtype=np.uint32)
@@ -129,6 +134,17 @@ class Writer:
         buf = np.frombuffer(data, dtype=np.uint8) if len(data) else np.zeros(1, np.uint8)
         self._check(self._L.bsc_bigwig_add(self._h, tid, buf.ctypes.data if len(data) else None, len(data), sections.ctypes.data if len(sections) else None,
                                            len(sections), zoom0.ctypes.data if len(zoom0) else None, len(zoom0)))
+
+    def add_z(self, tid, zdata, z_sizes, sections, zoom0):
+        """A block's sections as zlib streams back to back (zdata) with their lengths (z_sizes, uint32)."""
+        sections, zoom0 = np.ascontiguousarray(sections, dtype=BW_SUM), np.ascontiguousarray(zoom0, dtype=BW_SUM)
+        z_sizes = np.ascontiguousarray(z_sizes, dtype=np.uint32)
+        if len(z_sizes) != len(sections):
+            raise ValueError("one size per section")
+        buf = np.frombuffer(zdata, dtype=np.uint8) if len(zdata) else np.zeros(1, np.uint8)
+        self._check(self._L.bsc_bigwig_add_z(self._h, tid, buf.ctypes.data if len(zdata) else None, len(zdata), z_sizes.ctypes.data if len(z_sizes) else None,
+                                             sections.ctypes.data if len(sections) else None, len(sections), zoom0.ctypes.data if len(zoom0) else None,
+                                             len(zoom0)))
 
     def finish(self):
         self._check(self._L.bsc_bigwig_finish(self._h))
@@ -202,8 +218,22 @@ class BigWig:
                     pick = k
             at = struct.unpack_from("<Q", self.raw, at + 4 + pick * step + self._key)[0]
 
+    def _block(self, off, size):
+        """The raw bytes of the section or zoom block a leaf item names: as they lie in a plain file, inflated in a compressed one."""
+        blob = self.raw[off : off + size]
+        room = self.header["uncompressBufSize"]
+        if not room:
+            return blob
+        d = zlib.decompressobj()
+        out = d.decompress(blob, room + 1)
+        if len(out) > room or d.unconsumed_tail:
+            raise ValueError("a block inflates to more than uncompressBufSize = %d bytes" % room)
+        if not d.eof or d.unused_data:
+            raise ValueError("a block is not one whole zlib stream")
+        return out
+
     def _rtree_hits(self, index_at, cid, start, end):
-        """(dataOffset, dataSize) of the leaf items that overlap [start, end) on chromosome cid."""
+        """(dataOffset, dataSize) of the leaf items that overlap [start, end) on chromosome cid (cid None: of all leaf items)."""
         magic, _, n_items = struct.unpack_from("<IIQ", self.raw, index_at)
         if magic != RTREE_MAGIC:
             raise ValueError("bad R-tree")
@@ -214,7 +244,7 @@ class BigWig:
             for k in range(count):
                 o = at + 4 + k * (32 if leaf else 24)
                 c0, s0, c1, e1 = struct.unpack_from("<IIII", self.raw, o)
-                if (c0, s0) < (cid, end) and (cid, start) < (c1, e1):
+                if cid is None or ((c0, s0) < (cid, end) and (cid, start) < (c1, e1)):
                     if leaf:
                         out.append(struct.unpack_from("<QQ", self.raw, o + 16))
                     else:
@@ -229,10 +259,11 @@ class BigWig:
         end = size if end is None else end
         out = []
         for off, size_ in self._rtree_hits(self.header["fullIndexOffset"], cid, start, end):
-            c, _s, _e, _step, span, typ, _, count = struct.unpack_from("<IIIIIBBH", self.raw, off)
-            assert typ == 2 and c == cid and size_ == 24 + 8 * count
+            sec = self._block(off, size_)
+            c, _s, _e, _step, span, typ, _, count = struct.unpack_from("<IIIIIBBH", sec, 0)
+            assert typ == 2 and c == cid and len(sec) == 24 + 8 * count
             for k in range(count):
-                s, v = struct.unpack_from("<If", self.raw, off + 24 + 8 * k)
+                s, v = struct.unpack_from("<If", sec, 24 + 8 * k)
                 if start <= s < end:
                     out.append((s, s + span, v))
         return out
@@ -244,15 +275,24 @@ class BigWig:
         n = struct.unpack_from("<I", self.raw, data_at)[0]
         keys = ("chromId", "start", "end", "validCount", "minVal", "maxVal", "sumData", "sumSquares")
         if chrom is None:
-            return [dict(zip(keys, struct.unpack_from("<IIIIffff", self.raw, data_at + 4 + 32 * k))) for k in range(n)]
+            if not self.header["uncompressBufSize"]:
+                return [dict(zip(keys, struct.unpack_from("<IIIIffff", self.raw, data_at + 4 + 32 * k))) for k in range(n)]
+            out = []
+            for off, size_ in self._rtree_hits(index_at, None, 0, 0):  # (sorted by offset: the records' order)
+                blk = self._block(off, size_)
+                out.extend(dict(zip(keys, struct.unpack_from("<IIIIffff", blk, 32 * k))) for k in range(len(blk) // 32))
+            if len(out) != n:
+                raise ValueError("zoom level %d: %d records in its blocks, recordCount %d" % (level, len(out), n))
+            return out
         if chrom not in self.chroms:
             return []
         cid, size = self.chroms[chrom]
         end = size if end is None else end
         out = []
         for off, size_ in self._rtree_hits(index_at, cid, start, end):
-            for k in range(size_ // 32):
-                r = dict(zip(keys, struct.unpack_from("<IIIIffff", self.raw, off + 32 * k)))
+            blk = self._block(off, size_)
+            for k in range(len(blk) // 32):
+                r = dict(zip(keys, struct.unpack_from("<IIIIffff", blk, 32 * k)))
                 if r["chromId"] == cid and r["start"] < end and start < r["end"]:
                     out.append(r)
         return out

@@ -913,9 +913,10 @@ class SiteCaller:
         _check(self._L.bsc_bigwig_sites_device(self._h, d_core, d_aux, n, x0, chrom_id, C.byref(mp), C.byref(bp), d_out, out_cap, d_sections, sec_cap,
                                                d_zoom, zoom_cap, d_totals, stream))
 
-    def block_bigwig_kept(self, chrom_id, params=None, bw_params=None):
+    def block_bigwig_kept(self, chrom_id, params=None, bw_params=None, read_stream=True):
         """bsc_block_bigwig_kept + bsc_bigwig_stream_read: the bigWig data of the block the last *_keep call called, from the arrays it left on
-        the device.  Returns (stream bytes, sites, sections, zoom0): the two summaries as bigwig.BW_SUM arrays (copies)."""
+        the device.  Returns (stream bytes, sites, sections, zoom0): the two summaries as bigwig.BW_SUM arrays (copies).  read_stream=False:
+        the stream stays on the device (block_bigwig_deflate follows) and its length comes back in the bytes' place."""
         from .bigwig import BW_SUM
 
         mp, bp = self._meth_params(params), self._bw_params(bw_params)
@@ -925,13 +926,37 @@ class SiteCaller:
                                              C.byref(p_zoom), C.byref(nz)))
         grab = lambda p, k: np.frombuffer(C.string_at(p.value, 40 * k), dtype=BW_SUM).copy() if k else np.zeros(0, dtype=BW_SUM)
         sections, zoom0 = grab(p_sec, nsec.value), grab(p_zoom, nz.value)
-        return self.bigwig_stream_read(0, nb.value), int(ns.value), sections, zoom0
+        return (self.bigwig_stream_read(0, nb.value) if read_stream else int(nb.value)), int(ns.value), sections, zoom0
 
     def bigwig_stream_read(self, off, n):
         """bsc_bigwig_stream_read: bytes [off, off + n) of the stream block_bigwig_kept left on the device (waits)."""
         out = np.empty(max(int(n), 1), dtype=np.uint8)
         if n:
             _check(self._L.bsc_bigwig_stream_read(self._h, off, n, _ptr(out)))
+            self.synchronize()
+        return out[:n].tobytes()
+
+    # -- zlib streams of fixed-stride pieces, and of a block's bigWig sections (csrc/zlibdev.hip) -----------
+    def zlib_pieces_device(self, d_src, n_bytes, piece, d_out, out_cap, d_sizes, sizes_cap, d_totals, stream=None):
+        """bsc_zlib_pieces_device: piece k = bytes [k piece, min((k + 1) piece, n_bytes)) of d_src -> one zlib stream each, back to back in
+        d_out, their lengths (u32) in d_sizes, and d_totals: two u64 {bytes out, pieces} (asynchronous on `stream`).  An array whose room is
+        too small is not written; the needs are in d_totals."""
+        _check(self._L.bsc_zlib_pieces_device(self._h, d_src, n_bytes, piece, d_out, out_cap, d_sizes, sizes_cap, d_totals, stream))
+
+    def block_bigwig_deflate(self):
+        """bsc_block_bigwig_deflate + bsc_bigwig_zstream_read: the sections of the stream block_bigwig_kept just left on the device, one
+        zlib stream each.  Returns (the streams' bytes back to back, their sizes as a uint32 array (a copy))."""
+        nb, nsec = C.c_uint64(0), C.c_uint64(0)
+        p_sz = C.c_void_p(None)
+        _check(self._L.bsc_block_bigwig_deflate(self._h, C.byref(nb), C.byref(p_sz), C.byref(nsec)))
+        sizes = np.frombuffer(C.string_at(p_sz.value, 4 * nsec.value), dtype=np.uint32).copy() if nsec.value else np.zeros(0, dtype=np.uint32)
+        return self.bigwig_zstream_read(0, nb.value), sizes
+
+    def bigwig_zstream_read(self, off, n):
+        """bsc_bigwig_zstream_read: bytes [off, off + n) of the streams block_bigwig_deflate left on the device (waits)."""
+        out = np.empty(max(int(n), 1), dtype=np.uint8)
+        if n:
+            _check(self._L.bsc_bigwig_zstream_read(self._h, off, n, _ptr(out)))
             self.synchronize()
         return out[:n].tobytes()
 

@@ -8,12 +8,21 @@
  * of the 1001 floats, which the device copies entries of.  The writer never walks the data bytes: a section's place is arithmetic on the
  * counts, the two trees and the zoom levels are arithmetic on the summaries, all in integers until a float is stored.
  * integration/bigwig_san.c drives the writer under the address and undefined-behaviour sanitizers.
+ *
+ * A compressed writer (bsc_bigwig_add_z) takes a block's sections as zlib streams — the device made them (csrc/zlibdev.hip) — with their
+ * sizes: a section's place is the running sum of the sizes.  It deflates the zoom blocks itself at bsc_bigwig_finish (libz, compress2 at the
+ * default level) and states the largest raw block in the header; integration/bigwig_z_san.c drives it under the sanitizers.
  */
 #include <errno.h>
 #include <pthread.h>
 #include <stdlib.h>
 #include <string.h>
 #include <unistd.h>
+#include <zlib.h>
+
+/* libz is wanted by a compressed writer's bsc_bigwig_finish alone: a weak reference, so that a program of the plain writer by itself
+ * (integration/bigwig_san.c as tests/test_bigwig_host.py builds it) still links without libz; the library links it. */
+extern int compress2(Bytef *dest, uLongf *destLen, const Bytef *source, uLong sourceLen, int level) __attribute__((weak));
 
 #include "../../include/bscall_amd.h"
 
@@ -152,7 +161,8 @@ int bsc_bigwig_sections_recs(const bsc_vcf_rec *recs, size_t n, uint32_t chrom_i
 typedef struct {
   uint32_t tid;
   bsc_bw_sum s;
-  uint64_t off; /* a section's place in the file (not used by a zoom record) */
+  uint64_t off;  /* a section's place in the file (not used by a zoom record) */
+  uint64_t size; /* and its bytes there */
 } bw_rec;
 
 typedef struct { /* a leaf item of an R-tree */
@@ -179,8 +189,10 @@ struct bsc_bigwig {
   bw_rec *z0;
   uint64_t n_z0, cap_z0;
   int have_last, finished;
+  int mode; /* 0 until the first non-empty add; then BW_PLAIN or BW_Z */
   uint32_t last_tid, last_end;
 };
+enum { BW_PLAIN = 1, BW_Z = 2 };
 
 static void *buf_room(bw_buf *b, size_t k) {
   if (b->oom) return NULL;
@@ -453,10 +465,11 @@ static int grow(void **p, uint64_t *cap, uint64_t need, size_t item) {
   return 0;
 }
 
-int bsc_bigwig_add(bsc_bigwig *bw, uint32_t tid, const void *data, uint64_t n_bytes, const bsc_bw_sum *sections, uint64_t n_sections,
-                   const bsc_bw_sum *zoom0, uint64_t n_zoom0) {
-  static const char who[] = "bsc_bigwig_add";
-  if (!bw || (n_bytes && !data) || (n_sections && !sections) || (n_zoom0 && !zoom0)) return bsc_set_error(BSC_ERR_ARG, "%s: NULL argument", who);
+/* bsc_bigwig_add (z_sizes NULL: data is the plain stream) and bsc_bigwig_add_z (data is the sections' zlib streams, z_sizes their lengths) */
+static int bw_add(bsc_bigwig *bw, const char *who, uint32_t tid, const void *data, uint64_t n_bytes, const uint32_t *z_sizes, int z,
+                  const bsc_bw_sum *sections, uint64_t n_sections, const bsc_bw_sum *zoom0, uint64_t n_zoom0) {
+  if (!bw || (n_bytes && !data) || (n_sections && !sections) || (n_zoom0 && !zoom0) || (z && n_sections && !z_sizes))
+    return bsc_set_error(BSC_ERR_ARG, "%s: NULL argument", who);
   if (bw->finished) return bsc_set_error(BSC_ERR_ARG, "%s: the file is finished", who);
   if (tid >= bw->n_refs) return bsc_set_error(BSC_ERR_ARG, "%s: contig %u of %u", who, tid, bw->n_refs);
   if (bw->have_last && tid < bw->last_tid) return bsc_set_error(BSC_ERR_ARG, "%s: contig %u behind contig %u", who, tid, bw->last_tid);
@@ -465,6 +478,8 @@ int bsc_bigwig_add(bsc_bigwig *bw, uint32_t tid, const void *data, uint64_t n_by
     return BSC_OK;
   }
   if (!n_zoom0) return bsc_set_error(BSC_ERR_ARG, "%s: sections without a window", who);
+  if (bw->mode && bw->mode != (z ? BW_Z : BW_PLAIN))
+    return bsc_set_error(BSC_ERR_ARG, "%s: the file's sections are %s", who, bw->mode == BW_Z ? "compressed: bsc_bigwig_add_z adds to it" : "plain: bsc_bigwig_add adds to it");
   const uint64_t S = bw->par.items_per_section, red = bw->par.reduction;
   uint64_t sites = 0, zsites = 0;
   uint32_t end = bw->have_last && tid == bw->last_tid ? bw->last_end : 0;
@@ -477,9 +492,19 @@ int bsc_bigwig_add(bsc_bigwig *bw, uint32_t tid, const void *data, uint64_t n_by
     end = s->end;
     sites += s->count;
   }
-  if (24 * n_sections + 8 * sites != n_bytes)
+  if (!z && 24 * n_sections + 8 * sites != n_bytes)
     return bsc_set_error(BSC_ERR_ARG, "%s: %llu sections of %llu sites are not %llu bytes", who, (unsigned long long)n_sections,
                          (unsigned long long)sites, (unsigned long long)n_bytes);
+  if (z) {
+    uint64_t zsum = 0;
+    for (uint64_t k = 0; k < n_sections; k++) {
+      if (!z_sizes[k] || z_sizes[k] > 24 + 8 * (uint64_t)sections[k].count + 11)
+        return bsc_set_error(BSC_ERR_ARG, "%s: section %llu of %u sites has a stream of %u bytes", who, (unsigned long long)k, sections[k].count, z_sizes[k]);
+      zsum += z_sizes[k];
+    }
+    if (zsum != n_bytes)
+      return bsc_set_error(BSC_ERR_ARG, "%s: the streams' sizes add up to %llu bytes, not %llu", who, (unsigned long long)zsum, (unsigned long long)n_bytes);
+  }
   for (uint64_t k = 0; k < n_zoom0; k++) {
     const bsc_bw_sum *z = &zoom0[k];
     if (!z->count || z->end <= z->start || (z->end - 1u) / red != z->start / red || (k && z->start / red <= zoom0[k - 1].start / red))
@@ -492,11 +517,15 @@ int bsc_bigwig_add(bsc_bigwig *bw, uint32_t tid, const void *data, uint64_t n_by
   if (grow((void **)&bw->z0, &bw->cap_z0, bw->n_z0 + n_zoom0, sizeof *bw->z0)) return bsc_set_error(BSC_ERR_NOMEM, "%s: out of memory", who);
   const uint64_t base = bw->data_start + 8 + bw->data_bytes;
   if (write_all(bw->fd, data, n_bytes, base)) return bsc_set_error(BSC_ERR_ARG, "%s: write failed: %s", who, strerror(errno));
+  uint64_t at = base;
   for (uint64_t k = 0; k < n_sections; k++) {
-    bw->sec[bw->n_sec].tid = tid;
-    bw->sec[bw->n_sec].s = sections[k];
-    bw->sec[bw->n_sec].s._pad = 0;
-    bw->sec[bw->n_sec++].off = base + k * (24 + 8 * S);
+    bw_rec *r = &bw->sec[bw->n_sec++];
+    r->tid = tid;
+    r->s = sections[k];
+    r->s._pad = 0;
+    r->off = at;
+    r->size = z ? z_sizes[k] : 24 + 8 * (uint64_t)sections[k].count;
+    at += z ? z_sizes[k] : 24 + 8 * S;
   }
   for (uint64_t k = 0; k < n_zoom0; k++) {
     bw_rec *prev = bw->n_z0 ? &bw->z0[bw->n_z0 - 1] : NULL;
@@ -507,17 +536,30 @@ int bsc_bigwig_add(bsc_bigwig *bw, uint32_t tid, const void *data, uint64_t n_by
     bw->z0[bw->n_z0].tid = tid;
     bw->z0[bw->n_z0].s = zoom0[k];
     bw->z0[bw->n_z0].off = 0;
+    bw->z0[bw->n_z0].size = 0;
     bw->z0[bw->n_z0++].s._pad = 0;
   }
   bw->data_bytes += n_bytes;
   bw->have_last = 1;
+  bw->mode = z ? BW_Z : BW_PLAIN;
   bw->last_tid = tid;
   bw->last_end = end;
   return BSC_OK;
 }
 
-/* a zoom level's records at file offset `at`: the count, the blocks, the R-tree over the blocks; *index = the tree's offset */
-static int zoom_level_put(bw_buf *b, const bw_rec *r, uint64_t n, uint64_t at, uint64_t *index) {
+int bsc_bigwig_add(bsc_bigwig *bw, uint32_t tid, const void *data, uint64_t n_bytes, const bsc_bw_sum *sections, uint64_t n_sections,
+                   const bsc_bw_sum *zoom0, uint64_t n_zoom0) {
+  return bw_add(bw, "bsc_bigwig_add", tid, data, n_bytes, NULL, 0, sections, n_sections, zoom0, n_zoom0);
+}
+
+int bsc_bigwig_add_z(bsc_bigwig *bw, uint32_t tid, const void *zdata, uint64_t z_bytes, const uint32_t *z_sizes, const bsc_bw_sum *sections,
+                     uint64_t n_sections, const bsc_bw_sum *zoom0, uint64_t n_zoom0) {
+  return bw_add(bw, "bsc_bigwig_add_z", tid, zdata, z_bytes, z_sizes, 1, sections, n_sections, zoom0, n_zoom0);
+}
+
+/* a zoom level's records at file offset `at`: the count, the blocks — each deflated (compress2, the default level) where z —, the R-tree
+ * over the blocks; *index = the tree's offset; *max_raw: raised to the largest block's raw bytes */
+static int zoom_level_put(bw_buf *b, const bw_rec *r, uint64_t n, uint64_t at, uint64_t *index, int z, uint64_t *max_raw) {
   const uint64_t b0 = b->n;
   rt_item *it = malloc((size_t)(n ? n : 1) * sizeof *it); /* (at most one block per record) */
   if (!it) return -1;
@@ -526,8 +568,9 @@ static int zoom_level_put(bw_buf *b, const bw_rec *r, uint64_t n, uint64_t at, u
   for (uint64_t i = 0; i < n;) {
     uint64_t j = i;
     while (j < n && j - i < BW_ZBLOCK && r[j].tid == r[i].tid) j++;
-    const rt_item v = {r[i].tid, r[i].s.start, r[i].tid, r[j - 1].s.end, at + (b->n - b0), 32 * (j - i)};
-    it[n_it++] = v;
+    rt_item v = {r[i].tid, r[i].s.start, r[i].tid, r[j - 1].s.end, at + (b->n - b0), 32 * (j - i)};
+    const size_t raw_at = b->n;
+    if (v.size > *max_raw) *max_raw = v.size;
     for (; i < j; i++) {
       const bsc_bw_sum *s = &r[i].s;
       buf_u32(b, r[i].tid);
@@ -539,6 +582,21 @@ static int zoom_level_put(bw_buf *b, const bw_rec *r, uint64_t n, uint64_t at, u
       buf_f32(b, (float)((double)s->sum_m / 10.0));
       buf_f32(b, (float)((double)s->sum_m2 / 100.0));
     }
+    if (z && !b->oom) { /* the block's raw bytes, just written, give way to their stream */
+      uLongf zn = (uLongf)(v.size + v.size / 512 + 64); /* (above compressBound: at most 16 KiB in) */
+      Bytef *zb = malloc(zn);
+      if (!zb || compress2(zb, &zn, b->p + raw_at, (uLong)v.size, Z_DEFAULT_COMPRESSION) != Z_OK) {
+        free(zb);
+        free(it);
+        return -1;
+      }
+      b->n = raw_at;
+      uint8_t *q = buf_room(b, zn);
+      if (q) memcpy(q, zb, zn);
+      free(zb);
+      v.size = zn;
+    }
+    it[n_it++] = v;
   }
   *index = at + (b->n - b0);
   const int rc = rtree_put(b, it, n_it, *index, *index);
@@ -551,18 +609,21 @@ int bsc_bigwig_finish(bsc_bigwig *bw) {
   if (!bw) return bsc_set_error(BSC_ERR_ARG, "%s: NULL argument", who);
   if (bw->finished) return bsc_set_error(BSC_ERR_ARG, "%s: the file is finished", who);
   if (bw->n_z0 > 0xffffffffull) return bsc_set_error(BSC_ERR_ARG, "%s: more than 2^32 - 1 zoom records", who);
+  if (bw->mode == BW_Z && !compress2) return bsc_set_error(BSC_ERR_ARG, "%s: a compressed file needs libz, which this program does not link", who);
   bw_buf head = {0}, tail = {0};
   int rc = 0, levels = 0;
   uint64_t z_red[BW_LEVELS] = {0}, z_data[BW_LEVELS] = {0}, z_index[BW_LEVELS] = {0};
   const uint64_t index_at = bw->data_start + 8 + bw->data_bytes;
   /* the sections' index */
   rt_item *it = malloc((size_t)(bw->n_sec ? bw->n_sec : 1) * sizeof *it);
-  uint64_t covered = 0, min_m = 0, max_m = 0, sum_m = 0, sum_m2 = 0;
+  uint64_t covered = 0, min_m = 0, max_m = 0, sum_m = 0, sum_m2 = 0, max_raw = 0;
+  const int z = bw->mode == BW_Z;
   if (!it) rc = -1;
   for (uint64_t k = 0; k < bw->n_sec && !rc; k++) {
     const bw_rec *s = &bw->sec[k];
-    const rt_item v = {s->tid, s->s.start, s->tid, s->s.end, s->off, 24 + 8 * (uint64_t)s->s.count};
+    const rt_item v = {s->tid, s->s.start, s->tid, s->s.end, s->off, s->size};
     it[k] = v;
+    if (z && 24 + 8 * (uint64_t)s->s.count > max_raw) max_raw = 24 + 8 * (uint64_t)s->s.count;
     if (!k || s->s.min_m < min_m) min_m = s->s.min_m;
     if (!k || s->s.max_m > max_m) max_m = s->s.max_m;
     covered += s->s.count;
@@ -594,7 +655,7 @@ int bsc_bigwig_finish(bsc_bigwig *bw) {
     }
     z_red[l] = width < 0xffffffffull ? width : 0xffffffffull;
     z_data[l] = index_at + tail.n;
-    rc = zoom_level_put(&tail, cur, n_cur, z_data[l], &z_index[l]);
+    rc = zoom_level_put(&tail, cur, n_cur, z_data[l], &z_index[l], z, &max_raw);
     levels = l + 1;
   }
   free(own);
@@ -610,7 +671,7 @@ int bsc_bigwig_finish(bsc_bigwig *bw) {
   buf_u16(&head, 0);
   buf_u64(&head, 0);
   buf_u64(&head, 256);
-  buf_u32(&head, 0);
+  buf_u32(&head, z ? (uint32_t)max_raw : 0); /* uncompressBufSize: at most 24 + 8 * 65535 or 32 * 512 */
   buf_u64(&head, 0);
   for (int l = 0; l < BW_LEVELS; l++) {
     buf_u32(&head, l < levels ? (uint32_t)z_red[l] : 0);

@@ -93,6 +93,10 @@ int bsc_dev_launch_bigwig(const void *core, const void *aux, const void *emit, u
                           void *sites, void *wbeg, void *out, uint64_t out_cap, void *sections, uint64_t sec_cap, void *zoom, uint64_t zoom_cap,
                           void *totals, int num_cus, void *stream); /* bigwigdev.hip */
 const float *bsc_bw_values(void);                                    /* bigwig.c: (float)(m / 10.0), m = 0 .. 1000 */
+uint32_t bsc_dev_zlib_slot(uint32_t piece);                          /* zlibdev.hip: bytes of a piece's slot */
+uint32_t bsc_dev_zlib_grid(uint32_t piece, uint32_t n_pieces, int num_cus);
+int bsc_dev_launch_zlib(const void *src, uint64_t n, uint32_t piece, uint32_t n_pieces, void *slots, void *sizes, void *offs, void *scratch, uint32_t grid,
+                        void *out, uint64_t out_cap, void *sizes_out, uint64_t sizes_cap, void *totals, int num_cus, void *stream); /* zlibdev.hip */
 int bsc_dev_launch_ref_pad(const void *packed, const void *d_blk, uint32_t n_blk, void *padded, uint32_t n_pos, int num_cus, void *stream);
 int bsc_dev_launch_bin_reads_multi(const void *tpl, uint32_t nr, const void *seq, uint64_t seq_bytes, const void *d_blk, uint32_t n_blk,
                                    uint32_t n_bins, void *tflag, void *bin_cnt, void *bin_off, void *bin_cur, void *scan_tmp,
@@ -207,7 +211,20 @@ struct bsc_context {
     bsc_bw_sum *h_sec, *h_zoom;
     size_t cap_hsec, cap_hzoom;
     uint64_t bytes;
+    /* bsc_block_bigwig_deflate: whether bsc_block_bigwig_kept came before it, and with which S; the zlib streams of that block's sections,
+     * their sizes, the two totals, the host copy of the sizes, the streams' length */
+    int kept;
+    uint32_t kept_S;
+    void *d_z, *d_zsz, *d_ztot;
+    size_t cap_z, cap_zsz, cap_ztot;
+    uint32_t *h_zsz;
+    size_t cap_hzsz;
+    uint64_t z_bytes;
   } bw;
+  struct { /* bsc_zlib_pieces_device (zlibdev.hip): the pieces' slots, their sizes and prefix sums, the workgroups' token scratch */
+    void *d_slots, *d_sizes, *d_offs, *d_scratch;
+    size_t cap_slots, cap_sizes, cap_offs, cap_scratch;
+  } zl;
   /* the CSI scan (csidev.hip): runs per interval, their prefix sum, scan scratch, the entries and {entries, records, error bits} of the
    * follow-up call bsc_block_csi_kept, its host copy; and what the last encoder call left in d_bto: for which stream, how many tiles, text */
   void *d_cscn, *d_csof, *d_cstm, *d_csen, *d_cstot;
@@ -629,6 +646,14 @@ int bsc_destroy(bsc_context *ctx) {
   hipFree(ctx->bw.d_tot);
   free(ctx->bw.h_sec);
   free(ctx->bw.h_zoom);
+  hipFree(ctx->bw.d_z);
+  hipFree(ctx->bw.d_zsz);
+  hipFree(ctx->bw.d_ztot);
+  free(ctx->bw.h_zsz);
+  hipFree(ctx->zl.d_slots);
+  hipFree(ctx->zl.d_sizes);
+  hipFree(ctx->zl.d_offs);
+  hipFree(ctx->zl.d_scratch);
   hipFree(ctx->d_cscn);
   hipFree(ctx->d_csof);
   hipFree(ctx->d_cstm);
@@ -3280,11 +3305,17 @@ int bsc_block_bigwig_kept(bsc_context *ctx, uint32_t chrom_id, const bsc_meth_pa
   *sections = *zoom0 = NULL;
   if (n_sites) *n_sites = 0;
   ctx->bw.bytes = 0;
+  ctx->bw.kept = 0;
+  ctx->bw.z_bytes = 0;
   if ((rc = bsc_bigwig_params_check(who, params, bw_params))) return rc;
   if (ctx->meth_src != 1 || ctx->rec_pending || ctx->pending_sz)
     return bsc_fail(BSC_ERR_ARG, "%s: the last call left no single block's arrays on the device", who);
   const uint32_t n = ctx->again.sz, x0 = ctx->meth_x;
-  if (!n) return BSC_OK;
+  ctx->bw.kept_S = bw_params->items_per_section;
+  if (!n) {
+    ctx->bw.kept = 1;
+    return BSC_OK;
+  }
   BSC_ENTER(ctx);
   hipStream_t s = ctx->stream;
   /* room for the most a block of n positions can give: every position a site */
@@ -3316,6 +3347,7 @@ int bsc_block_bigwig_kept(bsc_context *ctx, uint32_t chrom_id, const bsc_meth_pa
   *sections = ctx->bw.h_sec;
   *zoom0 = ctx->bw.h_zoom;
   ctx->bw.bytes = tot[0];
+  ctx->bw.kept = 1;
   return BSC_OK;
 }
 
@@ -3325,6 +3357,81 @@ int bsc_bigwig_stream_read(bsc_context *ctx, uint64_t off, uint64_t n, void *dst
   if (!n) return BSC_OK;
   BSC_ENTER(ctx);
   HIP_TRY(hipMemcpyAsync(dst, (const char *)ctx->bw.d_data + off, (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+  return BSC_OK;
+}
+
+/* ---- zlib streams of fixed-stride pieces (zlibdev.hip) ------------------------------------------------------------------------------------ */
+int bsc_zlib_pieces_device(bsc_context *ctx, const void *d_src, uint64_t n_bytes, uint32_t piece, void *d_out, uint64_t out_cap, void *d_sizes,
+                           uint64_t sizes_cap, void *d_totals, void *stream) {
+  static const char who[] = "bsc_zlib_pieces_device";
+  int rc;
+  if (!ctx || !d_totals || (n_bytes && !d_src) || (out_cap && !d_out) || (sizes_cap && !d_sizes)) return bsc_fail(BSC_ERR_ARG, "%s: NULL argument", who);
+  if (piece < 1u || piece > 0xFF00u) return bsc_fail(BSC_ERR_ARG, "%s: piece is %u, not 1 .. 65280", who, piece);
+  if ((uintptr_t)d_sizes & 3u) return bsc_fail(BSC_ERR_ARG, "%s: d_sizes must be 4-byte aligned", who);
+  if ((uintptr_t)d_totals & 7u) return bsc_fail(BSC_ERR_ARG, "%s: d_totals must be 8-byte aligned", who);
+  const uint64_t np64 = (n_bytes + piece - 1) / piece;
+  if (np64 > 0x7fffffffull) return bsc_fail(BSC_ERR_ARG, "%s: %llu pieces are more than 2^31 - 1", who, (unsigned long long)np64);
+  BSC_ENTER(ctx);
+  if (!np64) { /* no byte, no piece: nothing to launch */
+    HIP_TRY(hipMemsetAsync(d_totals, 0, 2 * sizeof(unsigned long long), (hipStream_t)stream));
+    return BSC_OK;
+  }
+  const uint32_t np = (uint32_t)np64, slot = bsc_dev_zlib_slot(piece), grid = bsc_dev_zlib_grid(piece, np, ctx->num_cus);
+  if ((rc = bsc_reserve(&ctx->zl.d_slots, &ctx->zl.cap_slots, (size_t)np * slot))) return rc;
+  if ((rc = bsc_reserve(&ctx->zl.d_sizes, &ctx->zl.cap_sizes, (size_t)np * 4u))) return rc;
+  if ((rc = bsc_reserve(&ctx->zl.d_offs, &ctx->zl.cap_offs, ((size_t)np + 1u) * 8u))) return rc;
+  if ((rc = bsc_reserve(&ctx->zl.d_scratch, &ctx->zl.cap_scratch, (size_t)grid * piece * 4u))) return rc;
+  const int e = bsc_dev_launch_zlib(d_src, n_bytes, piece, np, ctx->zl.d_slots, ctx->zl.d_sizes, ctx->zl.d_offs, ctx->zl.d_scratch, grid, d_out, out_cap,
+                                    d_sizes, sizes_cap, d_totals, ctx->num_cus, stream);
+  if (e) return bsc_fail(BSC_ERR_HIP, "%s: launch failed: %s", who, hipGetErrorString((hipError_t)e));
+  return BSC_OK;
+}
+
+int bsc_block_bigwig_deflate(bsc_context *ctx, uint64_t *z_bytes, const uint32_t **z_sizes, uint64_t *n_sections) {
+  static const char who[] = "bsc_block_bigwig_deflate";
+  int rc;
+  if (!ctx || !z_bytes || !z_sizes || !n_sections) return bsc_fail(BSC_ERR_ARG, "%s: NULL argument", who);
+  *z_bytes = *n_sections = 0;
+  *z_sizes = NULL;
+  ctx->bw.z_bytes = 0;
+  if (!ctx->bw.kept) return bsc_fail(BSC_ERR_ARG, "%s: no bsc_block_bigwig_kept came before it", who);
+  const uint64_t piece = 24 + 8 * (uint64_t)ctx->bw.kept_S;
+  if (piece > 0xFF00u) return bsc_fail(BSC_ERR_ARG, "%s: a section of %u sites is %llu bytes, more than 65280 (at most 8157 sites)", who, ctx->bw.kept_S, (unsigned long long)piece);
+  const uint64_t n = ctx->bw.bytes;
+  if (!n) return BSC_OK;
+  BSC_ENTER(ctx);
+  hipStream_t s = ctx->stream;
+  const uint64_t np = (n + piece - 1) / piece, out_cap = n + 11 * np;
+  if ((rc = bsc_reserve(&ctx->bw.d_z, &ctx->bw.cap_z, (size_t)out_cap))) return rc;
+  if ((rc = bsc_reserve(&ctx->bw.d_zsz, &ctx->bw.cap_zsz, (size_t)np * 4u))) return rc;
+  if ((rc = bsc_reserve(&ctx->bw.d_ztot, &ctx->bw.cap_ztot, 2 * sizeof(unsigned long long)))) return rc;
+  if (np > ctx->bw.cap_hzsz) {
+    free(ctx->bw.h_zsz);
+    ctx->bw.cap_hzsz = 0;
+    ctx->bw.h_zsz = malloc((size_t)(np + np / 4) * 4u);
+    if (!ctx->bw.h_zsz) return bsc_fail(BSC_ERR_NOMEM, "%s: out of host memory", who);
+    ctx->bw.cap_hzsz = (size_t)(np + np / 4);
+  }
+  if ((rc = bsc_zlib_pieces_device(ctx, ctx->bw.d_data, n, (uint32_t)piece, ctx->bw.d_z, out_cap, ctx->bw.d_zsz, np, ctx->bw.d_ztot, (void *)s))) return rc;
+  unsigned long long tot[2] = {0, 0};
+  HIP_TRY(hipMemcpyAsync(tot, ctx->bw.d_ztot, sizeof tot, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipMemcpyAsync(ctx->bw.h_zsz, ctx->bw.d_zsz, (size_t)np * 4u, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  if (tot[0] > out_cap || tot[1] != np)
+    return bsc_fail(BSC_ERR_HIP, "%s: the encoder reported %llu bytes in %llu streams for %llu sections", who, tot[0], tot[1], (unsigned long long)np);
+  *z_bytes = tot[0];
+  *n_sections = np;
+  *z_sizes = ctx->bw.h_zsz;
+  ctx->bw.z_bytes = tot[0];
+  return BSC_OK;
+}
+
+int bsc_bigwig_zstream_read(bsc_context *ctx, uint64_t off, uint64_t n, void *dst) {
+  if (!ctx || (!dst && n)) return bsc_fail(BSC_ERR_ARG, "bsc_bigwig_zstream_read: NULL argument");
+  if (off + n > ctx->bw.z_bytes || off + n > ctx->bw.cap_z) return bsc_fail(BSC_ERR_ARG, "bsc_bigwig_zstream_read: beyond the streams' end");
+  if (!n) return BSC_OK;
+  BSC_ENTER(ctx);
+  HIP_TRY(hipMemcpyAsync(dst, (const char *)ctx->bw.d_z + off, (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
   return BSC_OK;
 }
 

@@ -19,7 +19,7 @@ def run(bam_path: str, reference: Dict[str, np.ndarray], bcf_path: str, sample: 
         host_prep: bool = False, host_bcf: bool = False, device_reader: bool = False, shard_rank: Optional[int] = None, shard_world: int = 1,
         reduce_device=None, text: bool = False, dbsnp_device: bool = False, meth_path: Optional[str] = None, meth_params=None, meth_merge: bool = False,
         meth_regions=None, meth_regions_path: Optional[str] = None, meth_window: Optional[int] = None, bigwig_path: Optional[str] = None,
-        bigwig_section: int = 1024, bigwig_zoom: int = 1024, **reader_kw) -> dict:
+        bigwig_section: int = 1024, bigwig_zoom: int = 1024, bigwig_compress: bool = False, **reader_kw) -> dict:
     """reference: contig name -> uint8 reference codes (0 = N, 1..4 = ACGT; position 1 first).  Returns a summary dict.
     under_conv / over_conv / min_qual (defaults 0.01 / 0.05 / 20, src/init_param.c:26-31) are the MODEL's parameters: without
     `caller` the run builds its SiteCaller from them; with one, they are taken from it and a differing explicit value is an error
@@ -55,8 +55,14 @@ def run(bam_path: str, reference: Dict[str, np.ndarray], bcf_path: str, sample: 
     bigwig_path: the methylation bigWig track of the same run (include/bscall_amd.h has the rule and the file's layout): every block's data
     sections and summaries from the arrays it left on the device (SiteCaller.block_bigwig_kept, csrc/bigwigdev.hip), the file by
     bigwig.Writer.  bigwig_section: sites a section (1 .. 65535); bigwig_zoom: the width of a level-0 zoom window.  meth_params apply; the
-    track is per cytosine whatever meth_merge says; meth_path is not needed.  The same conditions as meth_path."""
+    track is per cytosine whatever meth_merge says; meth_path is not needed.  The same conditions as meth_path.  bigwig_compress: every
+    section leaves the device as a zlib stream (SiteCaller.block_bigwig_deflate, csrc/zlibdev.hip) and the writer deflates the zoom blocks:
+    the file readers meet in practice, about half the bytes; needs bigwig_path and bigwig_section <= 8157."""
     want_bw = bigwig_path is not None
+    if bigwig_compress and not want_bw:
+        raise ValueError("bigwig_compress needs bigwig_path")
+    if bigwig_compress and int(bigwig_section) > 8157:
+        raise ValueError("bigwig_compress: a section of more than 8157 sites is more than 0xFF00 bytes")
     if want_bw and (shard_rank is not None or not device_reader or host_prep or host_bcf):
         raise ValueError("bigwig_path is a single run on the device reader (device_reader=True, no shard_rank, no host_prep / host_bcf)")
     if want_bw and not (1 <= int(bigwig_section) <= 65535 and 1 <= int(bigwig_zoom) <= 0xFFFFFFFF):
@@ -155,7 +161,7 @@ def run(bam_path: str, reference: Dict[str, np.ndarray], bcf_path: str, sample: 
             if want_bw:
                 from . import bigwig
 
-                bw_writer = bigwig.Writer(bigwig_path, refs, int(bigwig_section), int(bigwig_zoom))
+                bw_writer = bigwig.Writer(bigwig_path, refs, int(bigwig_section), int(bigwig_zoom), compress=bool(bigwig_compress))
                 bw_par = {"items_per_section": int(bigwig_section), "reduction": int(bigwig_zoom)}
 
             def regions_flush():
@@ -219,8 +225,12 @@ def run(bam_path: str, reference: Dict[str, np.ndarray], bcf_path: str, sample: 
                         if region_cur is not None:  # the block's cytosines into the attached regions' sums
                             c.block_meth_regions_kept(meth_params)
                         if want_bw:  # the block's bigWig sections and summaries, appended to the track's file
-                            data, ns, secs, zoom0 = c.block_bigwig_kept(tid, meth_params, bw_par)
-                            bw_writer.add(tid, data, secs, zoom0)
+                            data, ns, secs, zoom0 = c.block_bigwig_kept(tid, meth_params, bw_par, read_stream=not bigwig_compress)
+                            if bigwig_compress:  # ... as zlib streams: the plain stream stays on the device
+                                zdata, zsizes = c.block_bigwig_deflate()
+                                bw_writer.add_z(tid, zdata, zsizes, secs, zoom0)
+                            else:
+                                bw_writer.add(tid, data, secs, zoom0)
                             bw_sites += ns
                         if meth_path is not None:  # the same block's table, from what it left on the device
                             mb, ml, _ = c.block_meth_kept(name, meth_params, merge=meth_merge)

@@ -1270,7 +1270,7 @@ int bsc_meth_regions_reset(bsc_context *ctx);
  *   FILE      bbiFile version 4 as its published description states it, little-endian; readers follow offsets, the order is ours:
  *               0        header, 64 bytes: magic u32 = 0x888FFC26, version u16 = 4, zoomLevels u16, chromosomeTreeOffset u64,
  *                        fullDataOffset u64, fullIndexOffset u64, fieldCount u16 = 0, definedFieldCount u16 = 0, autoSqlOffset u64 = 0,
- *                        totalSummaryOffset u64, uncompressBufSize u32 = 0 (nothing is compressed), extensionOffset u64 = 0
+ *                        totalSummaryOffset u64, uncompressBufSize u32 = 0 (nothing is compressed; COMPRESSED FILE below), extensionOffset u64 = 0
  *               64       8 zoom headers of 24 bytes {reductionLevel u32 = min(reduction * 4^l, 2^32 - 1), reserved u32 = 0,
  *                        dataOffset u64, indexOffset u64}; unused ones zero
  *               256      total summary, 40 bytes {basesCovered u64 = the sites, minVal, maxVal, sumData, sumSquares f64} =
@@ -1322,8 +1322,29 @@ int bsc_meth_regions_reset(bsc_context *ctx);
  *                              its tile offsets, the methylation tables, bsc_block_csi_kept and the region accumulators are untouched;
  *                              before or after them.  BSC_ERR_ARG with the sizes should a room be too small.  Waits.
  *   bsc_bigwig_stream_read     bytes [off, off + n) of that block's stream -> dst, queued on the context's stream
- * Not built: zlib-compressed sections (the device DEFLATE encoder makes BGZF members; a zlib wrapper needs Adler-32 and a change of
- * bgzfdev.hip), a coverage track, sharded runs, the batched and host-buffer block entries.
+ * Compressed sections (csrc/zlibdev.hip: the bsc_zlib_*_kernel family; what UCSC's tools write and readers meet in practice):
+ *   ZSTREAM   of a piece of bytes: the zlib header 78 9C, ONE final DEFLATE block — dynamic Huffman codes, or stored where that would not be
+ *             smaller than the piece —, the piece's Adler-32 big-endian (RFC 1950, RFC 1951): at most the piece + 11 bytes.  A function of
+ *             the piece's bytes alone.
+ *   COMPRESSED FILE   the FILE above with every section replaced by its ZSTREAM and every zoom block by zlib's compress2 of it at the
+ *             default level (host, libz: a pyramid is a few MB once per file); a leaf item's dataOffset / dataSize are the compressed
+ *             ones; a level's leading u32 recordCount stays raw; uncompressBufSize = the largest raw size of any section or zoom block
+ *             of the file (0 with none: then nothing is compressed either).  A writer is compressed or plain from its first non-empty add.
+ *   bsc_zlib_pieces_device     piece k = bytes [k piece, min((k + 1) piece, n_bytes)) of d_src (any alignment), 1 <= piece <= 0xFF00: the
+ *                              ZSTREAMs back to back in piece order -> d_out[out_cap], their lengths -> d_sizes[sizes_cap] (u32), and
+ *                              d_totals = two device u64 {bytes out, pieces}.  The most needed: n_bytes + 11 pieces.  An array whose room
+ *                              is too small is not written at all — the needs are in d_totals.  n_bytes = 0: {0, 0}.  Asynchronous on
+ *                              `stream`; workspaces of the context (one call in flight per context).
+ *   bsc_block_bigwig_deflate   the follow-up of bsc_block_bigwig_kept of the same block: that block's stream at stride 24 + 8 S into a buffer
+ *                              of its own; *z_sizes: the context's host copy of the n_sections lengths, good until the next call.
+ *                              BSC_ERR_ARG without a bsc_block_bigwig_kept before it, or with S > 8157 (24 + 8 S > 0xFF00).  A block with
+ *                              no site: 0 / 0.  The uncompressed stream, the kept stream, the methylation tables, the CSI scan and the
+ *                              region accumulators are untouched.  Waits.
+ *   bsc_bigwig_zstream_read    bytes [off, off + n) of those streams -> dst, queued on the context's stream
+ *   bsc_bigwig_add_z           bsc_bigwig_add for a block's ZSTREAMs: every check of bsc_bigwig_add on the summaries; in place of the byte
+ *                              count, z_sizes[k] is 1 .. 24 + 8 count + 11 and their sum z_bytes.  After a non-empty bsc_bigwig_add_z a
+ *                              non-empty bsc_bigwig_add is BSC_ERR_ARG with nothing written, and the reverse.
+ * Not built: a coverage track, sharded runs, a device encoder for the zoom blocks, the batched and host-buffer block entries.
  */
 typedef struct {
   uint32_t items_per_section; /* 1 .. 65535 */
@@ -1349,6 +1370,12 @@ int bsc_bigwig_sites_device(bsc_context *ctx, const void *d_core, const void *d_
 int bsc_block_bigwig_kept(bsc_context *ctx, uint32_t chrom_id, const bsc_meth_params *params, const bsc_bw_params *bw_params, uint64_t *n_bytes,
                           uint64_t *n_sites, const bsc_bw_sum **sections, uint64_t *n_sections, const bsc_bw_sum **zoom0, uint64_t *n_zoom0);
 int bsc_bigwig_stream_read(bsc_context *ctx, uint64_t off, uint64_t n, void *dst);
+int bsc_zlib_pieces_device(bsc_context *ctx, const void *d_src, uint64_t n_bytes, uint32_t piece, void *d_out, uint64_t out_cap, void *d_sizes,
+                           uint64_t sizes_cap, void *d_totals, void *stream);
+int bsc_block_bigwig_deflate(bsc_context *ctx, uint64_t *z_bytes, const uint32_t **z_sizes, uint64_t *n_sections);
+int bsc_bigwig_zstream_read(bsc_context *ctx, uint64_t off, uint64_t n, void *dst);
+int bsc_bigwig_add_z(bsc_bigwig *bw, uint32_t tid, const void *zdata, uint64_t z_bytes, const uint32_t *z_sizes, const bsc_bw_sum *sections,
+                     uint64_t n_sections, const bsc_bw_sum *zoom0, uint64_t n_zoom0);
 /* with bsc_set_profiling: device time (HIP events on the context's stream) of the most recent raw block — bsc_block_records_raw[dev],
  * bsc_block_bcf_raw[dev][_keep] — from its first pre-processing launch to the last launch it queued, the host's wait for the prepared size included */
 int bsc_last_raw_block_ms(bsc_context *ctx, float *ms);

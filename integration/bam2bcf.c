@@ -68,6 +68,9 @@
  * output thread as one more job, which bsc_bigwig_add places in the track's own file; bsc_bigwig_finish writes the indexes, the zoom levels and
  * the header at the end.  --meth-bigwig-section n: sites a section (default 1024); --meth-bigwig-zoom n: the level-0 zoom window (default
  * 1024).  The --meth-* thresholds and --meth-all apply; the track is per cytosine even with --meth-merge; --meth is not needed.
+ * --meth-bigwig-compress: the file readers meet in practice — every section leaves the device as a zlib stream (bsc_block_bigwig_deflate,
+ * csrc/zlibdev.hip), the job carries the streams and their sizes for bsc_bigwig_add_z, and bsc_bigwig_finish deflates the zoom blocks.  Needs
+ * --meth-bigwig; sections of at most 8157 sites.
  *
  * --meth-regions regions.bed --meth-regions-out out.tsv: the per-region methylation summary — per interval of the BED file the cytosines
  * inside it added up on the device (bsc_meth_regions_attach at the contig change, where -D attaches; bsc_block_meth_regions_kept behind
@@ -138,6 +141,7 @@ typedef struct {
   void *bw_data;
   bsc_bw_sum *bw_sec, *bw_zoom;
   uint64_t bw_n_sec, bw_n_zoom;
+  uint32_t *bw_zsizes; /* --meth-bigwig-compress: bw_data holds the sections' zlib streams, these are their sizes */
 } out_job;
 typedef struct {
   bsc_context *ctx;
@@ -190,10 +194,13 @@ static void *writer_main(void *a) {
       if (bsc_detached_free(w->ctx, j.d) < 0) bad = 1;
     }
     if (j.bw) {
-      if (bsc_bigwig_add(j.bw, j.bw_tid, j.bw_data, j.n, j.bw_sec, j.bw_n_sec, j.bw_zoom, j.bw_n_zoom) < 0) {
+      const int rc = j.bw_zsizes ? bsc_bigwig_add_z(j.bw, j.bw_tid, j.bw_data, j.n, j.bw_zsizes, j.bw_sec, j.bw_n_sec, j.bw_zoom, j.bw_n_zoom)
+                                 : bsc_bigwig_add(j.bw, j.bw_tid, j.bw_data, j.n, j.bw_sec, j.bw_n_sec, j.bw_zoom, j.bw_n_zoom);
+      if (rc < 0) {
         fprintf(stderr, "bam2bcf: %s\n", bsc_last_error());
         bad = 1;
       }
+      free(j.bw_zsizes);
       free(j.bw_data);
       free(j.bw_sec);
       free(j.bw_zoom);
@@ -481,6 +488,7 @@ int main(int argc, char **argv) {
   uint32_t meth_window = 0;
   bsc_bw_params bwpar;
   bsc_bw_params_default(&bwpar);
+  int bigwig_z = 0;
   bsc_meth_params mpar;
   bsc_meth_params_default(&mpar);
   if (argc >= 2 && !strcmp(argv[argc - 1], "--meth") && (argc == 2 || strcmp(argv[argc - 2], "--meth"))) {
@@ -513,8 +521,10 @@ int main(int argc, char **argv) {
       argc -= k;
       continue;
     }
-    if (!strcmp(argv[1], "--index") || !strcmp(argv[1], "--meth-all") || !strcmp(argv[1], "--meth-pass") || !strcmp(argv[1], "--meth-merge")) { /* no value */
+    if (!strcmp(argv[1], "--index") || !strcmp(argv[1], "--meth-all") || !strcmp(argv[1], "--meth-pass") || !strcmp(argv[1], "--meth-merge") ||
+        !strcmp(argv[1], "--meth-bigwig-compress")) { /* no value */
       if (argv[1][2] == 'i') index = 1;
+      else if (argv[1][7] == 'b') bigwig_z = 1;
       else if (argv[1][7] == 'm') meth_merge = 1;
       else if (argv[1][7] == 'a') mpar.contexts = BSC_METH_ALL;
       else mpar.pass_only = 1;
@@ -573,7 +583,7 @@ int main(int argc, char **argv) {
     argc -= 2;
   }
   if (argc < 5 || world < 1 || (rank >= 0 && rank >= world)) {
-    fprintf(stderr, "usage: %s [-O u|b] [--format bcf|vcf] [--index] [-D dbsnp.idx] [--meth out.bed [--meth-merge | --meth-all] [--meth-min-cov n] [--meth-min-gq n] [--meth-pass]] [--meth-regions regions.bed | --meth-window n --meth-regions-out out.tsv] [--meth-bigwig out.bw [--meth-bigwig-section n] [--meth-bigwig-zoom n]: the methylation level as a bigWig track, per cytosine even with --meth-merge, under the --meth-* thresholds and --meth-all] [--rank r --world n | --merge n] in.bam ref.fa out.bcf report.json [sample]\n", argv[0]);
+    fprintf(stderr, "usage: %s [-O u|b] [--format bcf|vcf] [--index] [-D dbsnp.idx] [--meth out.bed [--meth-merge | --meth-all] [--meth-min-cov n] [--meth-min-gq n] [--meth-pass]] [--meth-regions regions.bed | --meth-window n --meth-regions-out out.tsv] [--meth-bigwig out.bw [--meth-bigwig-section n] [--meth-bigwig-zoom n] [--meth-bigwig-compress: zlib sections, n <= 8157]: the methylation level as a bigWig track, per cytosine even with --meth-merge, under the --meth-* thresholds and --meth-all] [--rank r --world n | --merge n] in.bam ref.fa out.bcf report.json [sample]\n", argv[0]);
     return 2;
   }
   if (text && (rank >= 0 || merge > 0)) {
@@ -638,6 +648,15 @@ int main(int argc, char **argv) {
   }
   if (regions_out_path && (getenv("BAM2BCF_HOST_PREP") || getenv("BAM2BCF_HOST_BCF") || getenv("BAM2BCF_HOST_READER"))) {
     fprintf(stderr, "%s: --meth-regions sums what the device reader's blocks leave on the device: not with BAM2BCF_HOST_READER / _HOST_BCF / _HOST_PREP\n", argv[0]);
+    return 2;
+  }
+  if (bigwig_z && !bigwig_path) {
+    fprintf(stderr, "%s: --meth-bigwig-compress needs --meth-bigwig\n", argv[0]);
+    return 2;
+  }
+  if (bigwig_z && bwpar.items_per_section > 8157u) {
+    fprintf(stderr, "%s: --meth-bigwig-compress: a section of %u sites is more than 0xFF00 bytes (--meth-bigwig-section 8157 at the most)\n", argv[0],
+            bwpar.items_per_section);
     return 2;
   }
   if (bigwig_path && (rank >= 0 || world > 1 || merge > 0)) {
@@ -981,6 +1000,18 @@ int main(int argc, char **argv) {
           j.n = b_bytes;
           j.bw = bw;
           j.bw_tid = (uint32_t)dblk.tid;
+          if (bigwig_z) { /* the sections as zlib streams: the job carries those and their sizes */
+            const uint32_t *zs = NULL;
+            uint64_t z_bytes = 0, z_sec = 0;
+            CHECK(bsc_block_bigwig_deflate(ctx, &z_bytes, &zs, &z_sec));
+            if (z_sec != b_sec) {
+              fprintf(stderr, "bam2bcf: %llu zlib streams for %llu bigWig sections\n", (unsigned long long)z_sec, (unsigned long long)b_sec);
+              return 1;
+            }
+            j.n = b_bytes = z_bytes;
+            j.bw_zsizes = xrealloc(NULL, (size_t)b_sec * sizeof *zs);
+            memcpy(j.bw_zsizes, zs, (size_t)b_sec * sizeof *zs);
+          }
           j.bw_data = xrealloc(NULL, (size_t)b_bytes);
           j.bw_sec = xrealloc(NULL, (size_t)b_sec * sizeof *sec);
           j.bw_zoom = xrealloc(NULL, (size_t)b_zoom * sizeof *zoom);
@@ -988,7 +1019,7 @@ int main(int argc, char **argv) {
           j.bw_n_zoom = b_zoom;
           memcpy(j.bw_sec, sec, (size_t)b_sec * sizeof *sec);
           memcpy(j.bw_zoom, zoom, (size_t)b_zoom * sizeof *zoom);
-          CHECK(bsc_bigwig_stream_read(ctx, 0, b_bytes, j.bw_data));
+          CHECK((bigwig_z ? bsc_bigwig_zstream_read : bsc_bigwig_stream_read)(ctx, 0, b_bytes, j.bw_data));
           CHECK(bsc_synchronize(ctx));
           writer_push(&W, j);
         }
