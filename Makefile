@@ -54,7 +54,7 @@ $(LIBDIR)/vcftextdev.o: $(CSRC)/vcftextdev.hip $(CSRC)/vcftext_emit.h $(CSRC)/fm
 	@mkdir -p $(LIBDIR)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
-$(LIBDIR)/methdev.o: $(CSRC)/methdev.hip $(CSRC)/recstream_dev.h include/bscall_amd.h
+$(LIBDIR)/methdev.o: $(CSRC)/methdev.hip $(CSRC)/recstream_dev.h $(CSRC)/methtext_dev.h include/bscall_amd.h
 	@mkdir -p $(LIBDIR)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
@@ -63,6 +63,10 @@ $(LIBDIR)/methregionsdev.o: $(CSRC)/methregionsdev.hip include/bscall_amd.h
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
 $(LIBDIR)/bigwigdev.o: $(CSRC)/bigwigdev.hip include/bscall_amd.h
+	@mkdir -p $(LIBDIR)
+	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+
+$(LIBDIR)/bigbeddev.o: $(CSRC)/bigbeddev.hip $(CSRC)/recstream_dev.h $(CSRC)/methtext_dev.h include/bscall_amd.h
 	@mkdir -p $(LIBDIR)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
@@ -106,7 +110,11 @@ $(LIBDIR)/methregions.o: $(CSRC)/methregions.c include/bscall_amd.h
 	@mkdir -p $(LIBDIR)
 	$(CC) $(CFLAGS) -c $< -o $@
 
-$(LIBDIR)/bigwig.o: $(CSRC)/bigwig.c include/bscall_amd.h
+$(LIBDIR)/bigwig.o: $(CSRC)/bigwig.c $(CSRC)/bbi_trees.h include/bscall_amd.h
+	@mkdir -p $(LIBDIR)
+	$(CC) $(CFLAGS) -c $< -o $@
+
+$(LIBDIR)/bigbed.o: $(CSRC)/bigbed.c $(CSRC)/bbi_trees.h include/bscall_amd.h
 	@mkdir -p $(LIBDIR)
 	$(CC) $(CFLAGS) -c $< -o $@
 
@@ -150,7 +158,7 @@ $(LIBDIR)/synth_reads.o: $(CSRC)/synth_reads.c include/bscall_amd.h $(CSRC)/synt
 	@mkdir -p $(LIBDIR)
 	$(CC) $(CFLAGS) -c $< -o $@
 
-$(LIBDIR)/libbscall_amd.so: $(LIBDIR)/kernels.o $(LIBDIR)/fused.o $(LIBDIR)/accumulate.o $(LIBDIR)/sort.o $(LIBDIR)/vcfcore.o $(LIBDIR)/sitestats.o $(LIBDIR)/compact.o $(LIBDIR)/probe.o $(LIBDIR)/prepdev.o $(LIBDIR)/bcfdev.o $(LIBDIR)/vcftextdev.o $(LIBDIR)/methdev.o $(LIBDIR)/methregionsdev.o $(LIBDIR)/bigwigdev.o $(LIBDIR)/bgzfdev.o $(LIBDIR)/zlibdev.o $(LIBDIR)/bamdev.o $(LIBDIR)/dbsnpdev.o $(LIBDIR)/csidev.o $(LIBDIR)/bscall_api.o $(LIBDIR)/bamstream.o $(LIBDIR)/inflate_fast.o $(LIBDIR)/synth_reads.o $(LIBDIR)/vcf_format.o $(LIBDIR)/methbed.o $(LIBDIR)/methcpg.o $(LIBDIR)/methregions.o $(LIBDIR)/bigwig.o $(LIBDIR)/dbsnp.o $(LIBDIR)/prep.o $(LIBDIR)/report.o $(LIBDIR)/bcf.o $(LIBDIR)/bamio.o $(LIBDIR)/refseq.o
+$(LIBDIR)/libbscall_amd.so: $(LIBDIR)/kernels.o $(LIBDIR)/fused.o $(LIBDIR)/accumulate.o $(LIBDIR)/sort.o $(LIBDIR)/vcfcore.o $(LIBDIR)/sitestats.o $(LIBDIR)/compact.o $(LIBDIR)/probe.o $(LIBDIR)/prepdev.o $(LIBDIR)/bcfdev.o $(LIBDIR)/vcftextdev.o $(LIBDIR)/methdev.o $(LIBDIR)/methregionsdev.o $(LIBDIR)/bigwigdev.o $(LIBDIR)/bigbeddev.o $(LIBDIR)/bgzfdev.o $(LIBDIR)/zlibdev.o $(LIBDIR)/bamdev.o $(LIBDIR)/dbsnpdev.o $(LIBDIR)/csidev.o $(LIBDIR)/bscall_api.o $(LIBDIR)/bamstream.o $(LIBDIR)/inflate_fast.o $(LIBDIR)/synth_reads.o $(LIBDIR)/vcf_format.o $(LIBDIR)/methbed.o $(LIBDIR)/methcpg.o $(LIBDIR)/methregions.o $(LIBDIR)/bigwig.o $(LIBDIR)/bigbed.o $(LIBDIR)/dbsnp.o $(LIBDIR)/prep.o $(LIBDIR)/report.o $(LIBDIR)/bcf.o $(LIBDIR)/bamio.o $(LIBDIR)/refseq.o
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $^ -lm -lz -lpthread
 
 oracle:
@@ -195,7 +203,7 @@ $(METHREGIONS_SAN_EXE): integration/methregions_san.c $(CSRC)/methregions.c incl
 # tests/test_bigwig_host.py builds its own copy and runs it: $(BIGWIG_SAN_EXE)  ->  "ok" and exit 0, or the case that failed
 BIGWIG_SAN_EXE ?= $(LIBDIR)/bigwig_san
 bigwig-san: $(BIGWIG_SAN_EXE)
-$(BIGWIG_SAN_EXE): integration/bigwig_san.c $(CSRC)/bigwig.c include/bscall_amd.h
+$(BIGWIG_SAN_EXE): integration/bigwig_san.c $(CSRC)/bigwig.c $(CSRC)/bbi_trees.h include/bscall_amd.h
 	$(CC) -std=gnu11 -O1 -g -Wall -Wextra -fsanitize=address,undefined -fno-sanitize-recover=undefined -Iinclude $< $(CSRC)/bigwig.c -lpthread -lz -o $@
 
 # TEST ONLY: the compressed writer (bsc_bigwig_add_z, and bsc_bigwig_finish deflating the zoom blocks) as a stand-alone program under
@@ -203,18 +211,26 @@ $(BIGWIG_SAN_EXE): integration/bigwig_san.c $(CSRC)/bigwig.c include/bscall_amd.
 # $(BIGWIG_Z_SAN_EXE)  ->  "ok" and exit 0, or the case that failed
 BIGWIG_Z_SAN_EXE ?= $(LIBDIR)/bigwig_z_san
 bigwig-z-san: $(BIGWIG_Z_SAN_EXE)
-$(BIGWIG_Z_SAN_EXE): integration/bigwig_z_san.c $(CSRC)/bigwig.c include/bscall_amd.h
+$(BIGWIG_Z_SAN_EXE): integration/bigwig_z_san.c $(CSRC)/bigwig.c $(CSRC)/bbi_trees.h include/bscall_amd.h
 	$(CC) -std=gnu11 -O1 -g -Wall -Wextra -fsanitize=address,undefined -fno-sanitize-recover=undefined -Iinclude $< $(CSRC)/bigwig.c -lpthread -lz -o $@
+
+# TEST ONLY: the host form of the bigBed items (csrc/bigbed.c over csrc/methbed.c: the shortest and the longest item, rooms one short, block and
+# window borders) as a stand-alone program under AddressSanitizer + UndefinedBehaviorSanitizer, on the CPU; tests/test_bigbed_host.py builds
+# its own copy and runs it: $(BIGBED_SAN_EXE)  ->  "ok" and exit 0, or the case that failed
+BIGBED_SAN_EXE ?= $(LIBDIR)/bigbed_san
+bigbed-san: $(BIGBED_SAN_EXE)
+$(BIGBED_SAN_EXE): integration/bigbed_san.c $(CSRC)/bigbed.c $(CSRC)/bbi_trees.h $(CSRC)/methbed.c include/bscall_amd.h
+	$(CC) -std=gnu11 -O1 -g -Wall -Wextra -fsanitize=address,undefined -fno-sanitize-recover=undefined -Iinclude $< $(CSRC)/bigbed.c $(CSRC)/methbed.c -lz -o $@
 
 # The library with its HOST C files under AddressSanitizer + UndefinedBehaviorSanitizer (gcc's runtimes; the device objects
 # are the ordinary ones): what tests/test_host_sanitizers.py and tools/fuzz_host_inputs.py run the readers and the host
 # logic under, on the CPU.  Load it with LD_PRELOAD=<libasan.so>:<libubsan.so> BSCALL_AMD_LIB=$(LIBDIR)/san/libbscall_amd_san.so.
 SANFLAGS = -O1 -g -fPIC -Wall -ffp-contract=off -std=gnu11 -I$(ROCM)/include -D__HIP_PLATFORM_AMD__ -fsanitize=address,undefined -fno-sanitize-recover=undefined -fno-omit-frame-pointer
-HOST_C = bscall_api synth_reads vcf_format methbed methcpg methregions bigwig dbsnp prep report bcf bamio bamstream inflate_fast refseq
+HOST_C = bscall_api synth_reads vcf_format methbed methcpg methregions bigwig bigbed dbsnp prep report bcf bamio bamstream inflate_fast refseq
 san: $(LIBDIR)/libbscall_amd.so
 	@mkdir -p $(LIBDIR)/san
 	for f in $(HOST_C); do $(CC) $(SANFLAGS) -c $(CSRC)/$$f.c -o $(LIBDIR)/san/$$f.o || exit 1; done
-	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $(LIBDIR)/san/libbscall_amd_san.so $(LIBDIR)/kernels.o $(LIBDIR)/fused.o $(LIBDIR)/accumulate.o $(LIBDIR)/sort.o $(LIBDIR)/vcfcore.o $(LIBDIR)/sitestats.o $(LIBDIR)/compact.o $(LIBDIR)/probe.o $(LIBDIR)/prepdev.o $(LIBDIR)/bcfdev.o $(LIBDIR)/vcftextdev.o $(LIBDIR)/methdev.o $(LIBDIR)/methregionsdev.o $(LIBDIR)/bigwigdev.o $(LIBDIR)/bgzfdev.o $(LIBDIR)/zlibdev.o $(LIBDIR)/bamdev.o $(LIBDIR)/dbsnpdev.o $(LIBDIR)/csidev.o $(addprefix $(LIBDIR)/san/,$(addsuffix .o,$(HOST_C))) -L$(dir $(shell $(CC) -print-file-name=libasan.so)) -lasan -lubsan -lm -lz -lpthread
+	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $(LIBDIR)/san/libbscall_amd_san.so $(LIBDIR)/kernels.o $(LIBDIR)/fused.o $(LIBDIR)/accumulate.o $(LIBDIR)/sort.o $(LIBDIR)/vcfcore.o $(LIBDIR)/sitestats.o $(LIBDIR)/compact.o $(LIBDIR)/probe.o $(LIBDIR)/prepdev.o $(LIBDIR)/bcfdev.o $(LIBDIR)/vcftextdev.o $(LIBDIR)/methdev.o $(LIBDIR)/methregionsdev.o $(LIBDIR)/bigwigdev.o $(LIBDIR)/bigbeddev.o $(LIBDIR)/bgzfdev.o $(LIBDIR)/zlibdev.o $(LIBDIR)/bamdev.o $(LIBDIR)/dbsnpdev.o $(LIBDIR)/csidev.o $(addprefix $(LIBDIR)/san/,$(addsuffix .o,$(HOST_C))) -L$(dir $(shell $(CC) -print-file-name=libasan.so)) -lasan -lubsan -lm -lz -lpthread
 
 # a plain-C host program against the C ABI: gcc only, links the shared library like bs_call would
 demo: $(LIBDIR)/demo_block $(LIBDIR)/bam2bcf
@@ -245,7 +261,7 @@ asm: $(CSRC)/kernels.hip
 	$(HIPCC) $(HIPFLAGS) -S --cuda-device-only -Rpass-analysis=kernel-resource-usage $< -o $(LIBDIR)/kernels.s
 
 clean:
-	rm -rf $(LIBDIR)/san; rm -f tests/devmath/libdevmath_probe.so tests/dbsnpdev/dbsnp_flat_host tests/csidev/csi_walk_host $(LIBDIR)/*.o $(LIBDIR)/*.so $(LIBDIR)/*.s $(LIBDIR)/demo_block $(LIBDIR)/bam2bcf $(LIBDIR)/methregions_san $(LIBDIR)/bigwig_san $(LIBDIR)/bigwig_z_san
+	rm -rf $(LIBDIR)/san; rm -f tests/devmath/libdevmath_probe.so tests/dbsnpdev/dbsnp_flat_host tests/csidev/csi_walk_host $(LIBDIR)/*.o $(LIBDIR)/*.so $(LIBDIR)/*.s $(LIBDIR)/demo_block $(LIBDIR)/bam2bcf $(LIBDIR)/methregions_san $(LIBDIR)/bigwig_san $(LIBDIR)/bigwig_z_san $(LIBDIR)/bigbed_san
 	$(MAKE) -C oracle clean
 
 .PHONY: all oracle demo asm clean glue-check san devmath-probe dbsnp-flat-host csi-walk-host

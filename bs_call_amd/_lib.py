@@ -206,6 +206,19 @@ EXPORTS = (
     "bsc_block_bigwig_deflate",
     "bsc_bigwig_zstream_read",
     "bsc_bigwig_add_z",
+    "bsc_bb_params_default",
+    "bsc_bigbed_blocks_recs",
+    "bsc_bigbed_sites_device",
+    "bsc_zlib_ranges_device",
+    "bsc_block_bigbed_kept",
+    "bsc_bigbed_stream_read",
+    "bsc_block_bigbed_deflate",
+    "bsc_bigbed_zstream_read",
+    "bsc_bigbed_open",
+    "bsc_bigbed_add",
+    "bsc_bigbed_add_z",
+    "bsc_bigbed_finish",
+    "bsc_bigbed_close",
 )
 
 
@@ -235,6 +248,15 @@ class BwParams(C.Structure):
 
     def __init__(self, items_per_section=1024, reduction=1024):
         super().__init__(int(items_per_section), int(reduction))
+
+
+class BbParams(C.Structure):
+    """bsc_bb_params; the defaults are bsc_bb_params_default's."""
+
+    _fields_ = [("items_per_block", C.c_uint32), ("reduction", C.c_uint32)]
+
+    def __init__(self, items_per_block=512, reduction=1024):
+        super().__init__(int(items_per_block), int(reduction))
 
 
 class MethBed(C.Structure):
@@ -796,5 +818,31 @@ def load():
     L.bsc_bigwig_zstream_read.argtypes = [vp, u64, u64, vp]
     L.bsc_bigwig_add_z.restype = i32
     L.bsc_bigwig_add_z.argtypes = [vp, u32, vp, u64, vp, vp, u64, vp, u64]
+    L.bsc_bb_params_default.restype = None
+    L.bsc_bb_params_default.argtypes = [C.POINTER(BbParams)]
+    L.bsc_bigbed_blocks_recs.restype = i32
+    L.bsc_bigbed_blocks_recs.argtypes = [vp, C.c_size_t, u32, C.POINTER(MethParams), C.POINTER(BbParams), vp, u64, pu64, vp, pu64, vp, pu64]
+    L.bsc_bigbed_sites_device.restype = i32
+    L.bsc_bigbed_sites_device.argtypes = [vp, vp, vp, u32, u32, u32, C.POINTER(MethParams), C.POINTER(BbParams), vp, u64, vp, u64, vp, u64, vp, vp]
+    L.bsc_zlib_ranges_device.restype = i32
+    L.bsc_zlib_ranges_device.argtypes = [vp, vp, vp, u32, u32, vp, u64, vp, u64, vp, vp]
+    L.bsc_block_bigbed_kept.restype = i32
+    L.bsc_block_bigbed_kept.argtypes = [vp, u32, C.POINTER(MethParams), C.POINTER(BbParams), pu64, pu64, C.POINTER(vp), pu64, C.POINTER(vp), pu64]
+    L.bsc_bigbed_stream_read.restype = i32
+    L.bsc_bigbed_stream_read.argtypes = [vp, u64, u64, vp]
+    L.bsc_block_bigbed_deflate.restype = i32
+    L.bsc_block_bigbed_deflate.argtypes = [vp, pu64, C.POINTER(vp), pu64]
+    L.bsc_bigbed_zstream_read.restype = i32
+    L.bsc_bigbed_zstream_read.argtypes = [vp, u64, u64, vp]
+    L.bsc_bigbed_open.restype = i32
+    L.bsc_bigbed_open.argtypes = [C.c_int, u32, C.POINTER(C.c_char_p), vp, C.POINTER(BbParams), C.POINTER(vp)]
+    L.bsc_bigbed_add.restype = i32
+    L.bsc_bigbed_add.argtypes = [vp, u32, vp, u64, vp, u64, vp, u64]
+    L.bsc_bigbed_add_z.restype = i32
+    L.bsc_bigbed_add_z.argtypes = [vp, u32, vp, u64, vp, u64, vp, u64, vp, u64]
+    L.bsc_bigbed_finish.restype = i32
+    L.bsc_bigbed_finish.argtypes = [vp]
+    L.bsc_bigbed_close.restype = None
+    L.bsc_bigbed_close.argtypes = [vp]
     _lib = L
     return L

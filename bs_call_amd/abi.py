@@ -106,3 +106,6 @@ MISMS_MISMS, MISMS_INS, MISMS_DEL, MISMS_SOFT = 0, 1, 2, 3
 PREP_PARAMS = np.dtype([("left_trim", "<i4", (2,)), ("right_trim", "<i4", (2,)), ("min_qual", "<i4")])
 PREP_STATS = np.dtype([("base_none", "<u8"), ("base_trim", "<u8"), ("base_clip", "<u8"), ("base_overlap", "<u8"), ("base_lowqual", "<u8"),
                        ("reads", "<u8"), ("read_bases", "<u8")])
+# bsc_bb_sum (include/bscall_amd.h): a bigBed block (off: its byte offset in the call's stream) or a level-0 zoom window (off = 0), 24 B
+BB_SUM = np.dtype([("start", "<u4"), ("end", "<u4"), ("count", "<u4"), ("_pad", "<u4"), ("off", "<u8")])
+BB_ITEM_MAX, BB_ITEM_MIN = 100, 46  # BSC_BB_ITEM_MAX, BSC_BB_ITEM_MIN

@@ -166,14 +166,16 @@ class BigWig:
     """A file read back by its own offsets.  header: the 64-byte header's fields; chroms: name -> (chromId, size), found by walking the B+
     tree; summary: the total summary; zooms: [(reductionLevel, dataOffset, indexOffset)]."""
 
+    FILE_MAGIC = MAGIC  # (bigbed.BigBed reads the same container under its own magic)
+
     def __init__(self, raw):
         self.raw = raw
         h = struct.unpack_from("<IHHQQQHHQQIQ", raw, 0)
         keys = ("magic", "version", "zoomLevels", "chromosomeTreeOffset", "fullDataOffset", "fullIndexOffset", "fieldCount", "definedFieldCount",
                 "autoSqlOffset", "totalSummaryOffset", "uncompressBufSize", "extensionOffset")
         self.header = dict(zip(keys, h))
-        if self.header["magic"] != MAGIC or struct.unpack_from("<I", raw, len(raw) - 4)[0] != MAGIC:
-            raise ValueError("not a bigWig file")
+        if self.header["magic"] != self.FILE_MAGIC or struct.unpack_from("<I", raw, len(raw) - 4)[0] != self.FILE_MAGIC:
+            raise ValueError("not a %s file" % type(self).__name__)
         self.zooms = []
         for l in range(self.header["zoomLevels"]):
             red, _, d, i = struct.unpack_from("<IIQQ", raw, 64 + 24 * l)

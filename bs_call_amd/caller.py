@@ -960,6 +960,62 @@ class SiteCaller:
             self.synchronize()
         return out[:n].tobytes()
 
+    # -- the bedMethyl table as bigBed items (csrc/bigbeddev.hip), zlib streams of ranges (csrc/zlibdev.hip) --
+    def bigbed_sites_device(self, d_core, d_aux, n, x0, chrom_id, d_out, out_cap, d_blocks, blk_cap, d_zoom, zoom_cap, d_totals, params=None,
+                            bb_params=None, stream=None):
+        """bsc_bigbed_sites_device: the per-position arrays of reads_chain_device (entry i = position x0 + i) -> the call's stream of bigBed
+        items in d_out (16-byte aligned), the blocks' and the level-0 windows' 24-byte summaries (bigbed.BB_SUM), and d_totals: four u64
+        {bytes, sites, blocks, windows} (asynchronous on `stream`).  An array whose room is too small is not written; the needs are in
+        d_totals."""
+        mp = self._meth_params(params)
+        bp = bb_params if isinstance(bb_params, _lib.BbParams) else _lib.BbParams(**(bb_params or {}))
+        _check(self._L.bsc_bigbed_sites_device(self._h, d_core, d_aux, n, x0, chrom_id, C.byref(mp), C.byref(bp), d_out, out_cap, d_blocks, blk_cap,
+                                               d_zoom, zoom_cap, d_totals, stream))
+
+    def block_bigbed_kept(self, chrom_id, params=None, bb_params=None, read_stream=True):
+        """bsc_block_bigbed_kept + bsc_bigbed_stream_read: the bigBed items of the block the last *_keep call called, from the arrays it left
+        on the device.  Returns (stream bytes, sites, blocks, zoom0): the two summaries as bigbed.BB_SUM arrays (copies).  read_stream=False:
+        the stream stays on the device (block_bigbed_deflate follows) and its length comes back in the bytes' place."""
+        from .bigbed import BB_SUM
+
+        mp = self._meth_params(params)
+        bp = bb_params if isinstance(bb_params, _lib.BbParams) else _lib.BbParams(**(bb_params or {}))
+        nb, ns, nblk, nz = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        p_blk, p_zoom = C.c_void_p(None), C.c_void_p(None)
+        _check(self._L.bsc_block_bigbed_kept(self._h, chrom_id, C.byref(mp), C.byref(bp), C.byref(nb), C.byref(ns), C.byref(p_blk), C.byref(nblk),
+                                             C.byref(p_zoom), C.byref(nz)))
+        grab = lambda p, k: np.frombuffer(C.string_at(p.value, 24 * k), dtype=BB_SUM).copy() if k else np.zeros(0, dtype=BB_SUM)
+        blocks, zoom0 = grab(p_blk, nblk.value), grab(p_zoom, nz.value)
+        return (self.bigbed_stream_read(0, nb.value) if read_stream else int(nb.value)), int(ns.value), blocks, zoom0
+
+    def bigbed_stream_read(self, off, n):
+        """bsc_bigbed_stream_read: bytes [off, off + n) of the stream block_bigbed_kept left on the device (waits)."""
+        out = np.empty(max(int(n), 1), dtype=np.uint8)
+        if n:
+            _check(self._L.bsc_bigbed_stream_read(self._h, off, n, _ptr(out)))
+            self.synchronize()
+        return out[:n].tobytes()
+
+    def block_bigbed_deflate(self):
+        """bsc_block_bigbed_deflate + bsc_bigbed_zstream_read: the blocks of the stream block_bigbed_kept just left on the device, one zlib
+        stream each.  Returns (the streams' bytes back to back, their sizes as a uint32 array (a copy))."""
+        nb, nblk = C.c_uint64(0), C.c_uint64(0)
+        p_sz = C.c_void_p(None)
+        _check(self._L.bsc_block_bigbed_deflate(self._h, C.byref(nb), C.byref(p_sz), C.byref(nblk)))
+        sizes = np.frombuffer(C.string_at(p_sz.value, 4 * nblk.value), dtype=np.uint32).copy() if nblk.value else np.zeros(0, dtype=np.uint32)
+        out = np.empty(max(int(nb.value), 1), dtype=np.uint8)
+        if nb.value:
+            _check(self._L.bsc_bigbed_zstream_read(self._h, 0, nb.value, _ptr(out)))
+            self.synchronize()
+        return out[: nb.value].tobytes(), sizes
+
+    def zlib_ranges_device(self, d_src, d_offs, n_pieces, max_piece, d_out, out_cap, d_sizes, sizes_cap, d_totals, stream=None):
+        """bsc_zlib_ranges_device: piece k = bytes [offs[k], offs[k + 1]) of d_src (d_offs: n_pieces + 1 ascending device u64, every length
+        1 .. max_piece) -> one zlib stream each, back to back in d_out, their lengths (u32) in d_sizes, and d_totals: three u64 {bytes
+        out, pieces, bad ranges}.  Waits for the count of bad ranges: a BscError when it is not 0.  An array whose room is too small is not
+        written; the needs are in d_totals."""
+        _check(self._L.bsc_zlib_ranges_device(self._h, d_src, d_offs, n_pieces, max_piece, d_out, out_cap, d_sizes, sizes_cap, d_totals, stream))
+
     def block_meth_kept(self, contig, params=None, cap=None, merge=False):
         """bsc_block_meth_kept + bsc_meth_stream_read: the bedMethyl table of the block the last *_keep call called (block_vcf_rawdev,
         block_bcf_rawdev(keep=True)), from the arrays that block left on the device.  params: a _lib.MethParams, a dict of its fields, or

@@ -93,6 +93,13 @@ int bsc_dev_launch_bigwig(const void *core, const void *aux, const void *emit, u
                           void *sites, void *wbeg, void *out, uint64_t out_cap, void *sections, uint64_t sec_cap, void *zoom, uint64_t zoom_cap,
                           void *totals, int num_cus, void *stream); /* bigwigdev.hip */
 const float *bsc_bw_values(void);                                    /* bigwig.c: (float)(m / 10.0), m = 0 .. 1000 */
+int bsc_dev_launch_zlib_ranges(const void *src, const void *range_offs, uint32_t max_piece, uint32_t n_pieces, void *slots, void *sizes, void *offs,
+                               void *scratch, uint32_t grid, void *out, uint64_t out_cap, void *sizes_out, uint64_t sizes_cap, void *totals, int num_cus,
+                               void *stream); /* zlibdev.hip */
+int bsc_dev_launch_bigbed(const void *core, const void *aux, const void *emit, uint64_t n, uint32_t x0, uint32_t chrom_id, const bsc_meth_params *par,
+                          const bsc_bb_params *bbp, void *item_len, void *cnt, void *off, void *tbytes, void *boff, void *hcnt, void *hoff, void *scan_tmp,
+                          size_t scan_tmp_bytes, void *sites, void *wbeg, void *out, uint64_t out_cap, void *blocks, uint64_t blk_cap, void *zoom,
+                          uint64_t zoom_cap, void *totals, int num_cus, void *stream); /* bigbeddev.hip */
 uint32_t bsc_dev_zlib_slot(uint32_t piece);                          /* zlibdev.hip: bytes of a piece's slot */
 uint32_t bsc_dev_zlib_grid(uint32_t piece, uint32_t n_pieces, int num_cus);
 int bsc_dev_launch_zlib(const void *src, uint64_t n, uint32_t piece, uint32_t n_pieces, void *slots, void *sizes, void *offs, void *scratch, uint32_t grid,
@@ -221,6 +228,26 @@ struct bsc_context {
     size_t cap_hzsz;
     uint64_t z_bytes;
   } bw;
+  struct { /* the bigBed items (bigbeddev.hip): the workspaces of a call — item lengths, sites and bytes per tile and window heads per tile with
+            * their prefix sums, scan scratch, the compact starts, the windows' first ranks */
+    void *d_len, *d_cnt, *d_off, *d_tb, *d_boff, *d_hcnt, *d_hoff, *d_tmp, *d_sites, *d_wbeg;
+    size_t cap_len, cap_cnt, cap_off, cap_tb, cap_boff, cap_hcnt, cap_hoff, cap_tmp, cap_sites, cap_wbeg;
+    /* bsc_block_bigbed_kept: the block's stream, its block and window summaries, the four totals, the host copies, the stream's length; whether
+     * it came, with which B and how many blocks.  bsc_block_bigbed_deflate: the blocks' offsets, their zlib streams, the sizes, the three totals */
+    void *d_data, *d_blk, *d_zoom, *d_tot;
+    size_t cap_data, cap_blk, cap_zoom, cap_tot;
+    bsc_bb_sum *h_blk, *h_zoom;
+    size_t cap_hblk, cap_hzoom;
+    uint64_t bytes, kept_blocks;
+    int kept;
+    uint32_t kept_B;
+    void *d_zoffs, *d_z, *d_zsz, *d_ztot;
+    size_t cap_zoffs, cap_z, cap_zsz, cap_ztot;
+    uint64_t *h_zoffs;
+    uint32_t *h_zsz;
+    size_t cap_hzoffs, cap_hzsz;
+    uint64_t z_bytes;
+  } bb;
   struct { /* bsc_zlib_pieces_device (zlibdev.hip): the pieces' slots, their sizes and prefix sums, the workgroups' token scratch */
     void *d_slots, *d_sizes, *d_offs, *d_scratch;
     size_t cap_slots, cap_sizes, cap_offs, cap_scratch;
@@ -650,6 +677,28 @@ int bsc_destroy(bsc_context *ctx) {
   hipFree(ctx->bw.d_zsz);
   hipFree(ctx->bw.d_ztot);
   free(ctx->bw.h_zsz);
+  hipFree(ctx->bb.d_len);
+  hipFree(ctx->bb.d_cnt);
+  hipFree(ctx->bb.d_off);
+  hipFree(ctx->bb.d_tb);
+  hipFree(ctx->bb.d_boff);
+  hipFree(ctx->bb.d_hcnt);
+  hipFree(ctx->bb.d_hoff);
+  hipFree(ctx->bb.d_tmp);
+  hipFree(ctx->bb.d_sites);
+  hipFree(ctx->bb.d_wbeg);
+  hipFree(ctx->bb.d_data);
+  hipFree(ctx->bb.d_blk);
+  hipFree(ctx->bb.d_zoom);
+  hipFree(ctx->bb.d_tot);
+  hipFree(ctx->bb.d_zoffs);
+  hipFree(ctx->bb.d_z);
+  hipFree(ctx->bb.d_zsz);
+  hipFree(ctx->bb.d_ztot);
+  free(ctx->bb.h_blk);
+  free(ctx->bb.h_zoom);
+  free(ctx->bb.h_zoffs);
+  free(ctx->bb.h_zsz);
   hipFree(ctx->zl.d_slots);
   hipFree(ctx->zl.d_sizes);
   hipFree(ctx->zl.d_offs);
@@ -3387,6 +3436,44 @@ int bsc_zlib_pieces_device(bsc_context *ctx, const void *d_src, uint64_t n_bytes
   return BSC_OK;
 }
 
+/* zlib streams of ranges of varying length (zlibdev.hip: the same body, base and length from the offsets) */
+/* the checks and the launches, no wait: d_totals[2] is the caller's to read */
+static int bsc_zlib_ranges_queue(bsc_context *ctx, const char *who, const void *d_src, const void *d_offs, uint32_t n_pieces, uint32_t max_piece, void *d_out,
+                                 uint64_t out_cap, void *d_sizes, uint64_t sizes_cap, void *d_totals, void *stream) {
+  int rc;
+  if (!ctx || !d_totals || (n_pieces && (!d_src || !d_offs)) || (out_cap && !d_out) || (sizes_cap && !d_sizes)) return bsc_fail(BSC_ERR_ARG, "%s: NULL argument", who);
+  if (max_piece < 1u || max_piece > 0xFF00u) return bsc_fail(BSC_ERR_ARG, "%s: max_piece is %u, not 1 .. 65280", who, max_piece);
+  if ((uintptr_t)d_sizes & 3u) return bsc_fail(BSC_ERR_ARG, "%s: d_sizes must be 4-byte aligned", who);
+  if (((uintptr_t)d_totals | (uintptr_t)d_offs) & 7u) return bsc_fail(BSC_ERR_ARG, "%s: d_offs and d_totals must be 8-byte aligned", who);
+  if (n_pieces > 0x7fffffffu) return bsc_fail(BSC_ERR_ARG, "%s: %u pieces are more than 2^31 - 1", who, n_pieces);
+  BSC_ENTER(ctx);
+  if (!n_pieces) { /* no piece: nothing to launch */
+    HIP_TRY(hipMemsetAsync(d_totals, 0, 3 * sizeof(unsigned long long), (hipStream_t)stream));
+    return BSC_OK;
+  }
+  const uint32_t slot = bsc_dev_zlib_slot(max_piece), grid = bsc_dev_zlib_grid(max_piece, n_pieces, ctx->num_cus);
+  if ((rc = bsc_reserve(&ctx->zl.d_slots, &ctx->zl.cap_slots, (size_t)n_pieces * slot))) return rc;
+  if ((rc = bsc_reserve(&ctx->zl.d_sizes, &ctx->zl.cap_sizes, (size_t)n_pieces * 4u))) return rc;
+  if ((rc = bsc_reserve(&ctx->zl.d_offs, &ctx->zl.cap_offs, ((size_t)n_pieces + 1u) * 8u))) return rc;
+  if ((rc = bsc_reserve(&ctx->zl.d_scratch, &ctx->zl.cap_scratch, (size_t)grid * max_piece * 4u))) return rc;
+  const int e = bsc_dev_launch_zlib_ranges(d_src, d_offs, max_piece, n_pieces, ctx->zl.d_slots, ctx->zl.d_sizes, ctx->zl.d_offs, ctx->zl.d_scratch, grid,
+                                           d_out, out_cap, d_sizes, sizes_cap, d_totals, ctx->num_cus, stream);
+  if (e) return bsc_fail(BSC_ERR_HIP, "%s: launch failed: %s", who, hipGetErrorString((hipError_t)e));
+  return BSC_OK;
+}
+
+int bsc_zlib_ranges_device(bsc_context *ctx, const void *d_src, const void *d_offs, uint32_t n_pieces, uint32_t max_piece, void *d_out,
+                           uint64_t out_cap, void *d_sizes, uint64_t sizes_cap, void *d_totals, void *stream) {
+  static const char who[] = "bsc_zlib_ranges_device";
+  const int rc = bsc_zlib_ranges_queue(ctx, who, d_src, d_offs, n_pieces, max_piece, d_out, out_cap, d_sizes, sizes_cap, d_totals, stream);
+  if (rc || !n_pieces) return rc;
+  unsigned long long bad = 0; /* the one wait of this entry: a range the kernel had to clamp makes the call an error */
+  HIP_TRY(hipMemcpyAsync(&bad, (const unsigned long long *)d_totals + 2, sizeof bad, hipMemcpyDeviceToHost, (hipStream_t)stream));
+  HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+  if (bad) return bsc_fail(BSC_ERR_ARG, "%s: %llu ranges have no byte or more than max_piece = %u", who, bad, max_piece);
+  return BSC_OK;
+}
+
 int bsc_block_bigwig_deflate(bsc_context *ctx, uint64_t *z_bytes, const uint32_t **z_sizes, uint64_t *n_sections) {
   static const char who[] = "bsc_block_bigwig_deflate";
   int rc;
@@ -3432,6 +3519,190 @@ int bsc_bigwig_zstream_read(bsc_context *ctx, uint64_t off, uint64_t n, void *ds
   if (!n) return BSC_OK;
   BSC_ENTER(ctx);
   HIP_TRY(hipMemcpyAsync(dst, (const char *)ctx->bw.d_z + off, (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+  return BSC_OK;
+}
+
+/* ---- the bedMethyl table as bigBed items (bigbeddev.hip): include/bscall_amd.h has the rule, csrc/bigbed.c the host form ----------------------- */
+static int bsc_bigbed_params_check(const char *who, const bsc_meth_params *par, const bsc_bb_params *bbp) {
+  if (!par || !bbp) return bsc_fail(BSC_ERR_ARG, "%s: NULL argument", who);
+  if (par->contexts != BSC_METH_CPG && par->contexts != BSC_METH_ALL)
+    return bsc_fail(BSC_ERR_ARG, "%s: contexts is %d, not BSC_METH_CPG or BSC_METH_ALL", who, (int)par->contexts);
+  if (bbp->items_per_block < 1u || bbp->items_per_block > 65535u || bbp->reduction < 1u)
+    return bsc_fail(BSC_ERR_ARG, "%s: items_per_block is 1 .. 65535, reduction 1 or more", who);
+  return BSC_OK;
+}
+
+/* the kernels over d_core[n] / d_aux[n] (entry i = position x0 + i, n >= 1) on stream s, in the context's workspaces */
+static int bsc_bigbed_run(bsc_context *ctx, const char *who, const void *d_core, const void *d_aux, const void *d_emit, uint32_t n, uint32_t x0,
+                          uint32_t chrom_id, const bsc_meth_params *params, const bsc_bb_params *bb_params, void *d_out, uint64_t out_cap, void *d_blocks,
+                          uint64_t blk_cap, void *d_zoom, uint64_t zoom_cap, void *d_totals, hipStream_t stream) {
+  int rc;
+  const uint32_t n_tiles = (uint32_t)(((uint64_t)n + 63u) / 64u);
+  const size_t tiles8 = ((size_t)n_tiles + 1u) * 8u;
+  size_t scan_bytes = 0;
+  if (bsc_dev_scan_tmp_bytes_u64(n_tiles + 1u, &scan_bytes)) return bsc_fail(BSC_ERR_HIP, "%s: scan size query failed", who);
+  if ((rc = bsc_reserve(&ctx->bb.d_len, &ctx->bb.cap_len, (size_t)n))) return rc;
+  if ((rc = bsc_reserve(&ctx->bb.d_cnt, &ctx->bb.cap_cnt, tiles8))) return rc;
+  if ((rc = bsc_reserve(&ctx->bb.d_off, &ctx->bb.cap_off, tiles8))) return rc;
+  if ((rc = bsc_reserve(&ctx->bb.d_tb, &ctx->bb.cap_tb, tiles8))) return rc;
+  if ((rc = bsc_reserve(&ctx->bb.d_boff, &ctx->bb.cap_boff, tiles8))) return rc;
+  if ((rc = bsc_reserve(&ctx->bb.d_hcnt, &ctx->bb.cap_hcnt, tiles8))) return rc;
+  if ((rc = bsc_reserve(&ctx->bb.d_hoff, &ctx->bb.cap_hoff, tiles8))) return rc;
+  if ((rc = bsc_reserve(&ctx->bb.d_tmp, &ctx->bb.cap_tmp, scan_bytes ? scan_bytes : 1))) return rc;
+  if ((rc = bsc_reserve(&ctx->bb.d_sites, &ctx->bb.cap_sites, (size_t)n * 4u))) return rc;
+  if ((rc = bsc_reserve(&ctx->bb.d_wbeg, &ctx->bb.cap_wbeg, ((size_t)n + 1u) * 4u))) return rc;
+  const int e = bsc_dev_launch_bigbed(d_core, d_aux, d_emit, n, x0, chrom_id, params, bb_params, ctx->bb.d_len, ctx->bb.d_cnt, ctx->bb.d_off, ctx->bb.d_tb,
+                                      ctx->bb.d_boff, ctx->bb.d_hcnt, ctx->bb.d_hoff, ctx->bb.d_tmp, scan_bytes, ctx->bb.d_sites, ctx->bb.d_wbeg, d_out,
+                                      out_cap, d_blocks, blk_cap, d_zoom, zoom_cap, d_totals, ctx->num_cus, (void *)stream);
+  if (e) return bsc_fail(BSC_ERR_HIP, "%s: launch failed: %s", who, hipGetErrorString((hipError_t)e));
+  return BSC_OK;
+}
+
+int bsc_bigbed_sites_device(bsc_context *ctx, const void *d_core, const void *d_aux, uint32_t n, uint32_t x0, uint32_t chrom_id,
+                            const bsc_meth_params *params, const bsc_bb_params *bb_params, void *d_out, uint64_t out_cap, void *d_blocks,
+                            uint64_t blk_cap, void *d_zoom, uint64_t zoom_cap, void *d_totals, void *stream) {
+  static const char who[] = "bsc_bigbed_sites_device";
+  int rc;
+  if (!ctx || !d_totals || (n && (!d_core || !d_aux)) || (out_cap && !d_out) || (blk_cap && !d_blocks) || (zoom_cap && !d_zoom))
+    return bsc_fail(BSC_ERR_ARG, "%s: NULL argument", who);
+  if ((rc = bsc_bigbed_params_check(who, params, bb_params))) return rc;
+  if (((uintptr_t)d_core | (uintptr_t)d_aux | (uintptr_t)d_out) & 15u) return bsc_fail(BSC_ERR_ARG, "%s: the arrays and d_out must be 16-byte aligned", who);
+  if (((uintptr_t)d_blocks | (uintptr_t)d_zoom | (uintptr_t)d_totals) & 7u) return bsc_fail(BSC_ERR_ARG, "%s: the summaries and d_totals must be 8-byte aligned", who);
+  if (x0 < 1u) return bsc_fail(BSC_ERR_ARG, "%s: positions are 1-based (x0 = 0)", who);
+  if (n && (uint64_t)x0 + n - 1u > 0xffffffffull) return bsc_fail(BSC_ERR_ARG, "%s: x0 + n - 1 = %llu is beyond 2^32 - 1", who, (unsigned long long)x0 + n - 1u);
+  BSC_ENTER(ctx);
+  if (!n) { /* no position, no site: nothing to launch */
+    HIP_TRY(hipMemsetAsync(d_totals, 0, 4 * sizeof(unsigned long long), (hipStream_t)stream));
+    return BSC_OK;
+  }
+  return bsc_bigbed_run(ctx, who, d_core, d_aux, NULL, n, x0, chrom_id, params, bb_params, d_out, out_cap, d_blocks, blk_cap, d_zoom, zoom_cap, d_totals,
+                        (hipStream_t)stream);
+}
+
+static int bsc_host_room_bytes(void **p, size_t *cap, size_t need, const char *who) {
+  if (need <= *cap) return BSC_OK;
+  free(*p);
+  *cap = 0;
+  *p = malloc(need + need / 4);
+  if (!*p) return bsc_fail(BSC_ERR_NOMEM, "%s: out of host memory", who);
+  *cap = need + need / 4;
+  return BSC_OK;
+}
+
+int bsc_block_bigbed_kept(bsc_context *ctx, uint32_t chrom_id, const bsc_meth_params *params, const bsc_bb_params *bb_params, uint64_t *n_bytes,
+                          uint64_t *n_sites, const bsc_bb_sum **blocks, uint64_t *n_blocks, const bsc_bb_sum **zoom0, uint64_t *n_zoom0) {
+  static const char who[] = "bsc_block_bigbed_kept";
+  int rc;
+  if (!ctx || !n_bytes || !blocks || !n_blocks || !zoom0 || !n_zoom0) return bsc_fail(BSC_ERR_ARG, "%s: NULL argument", who);
+  *n_bytes = *n_blocks = *n_zoom0 = 0;
+  *blocks = *zoom0 = NULL;
+  if (n_sites) *n_sites = 0;
+  ctx->bb.bytes = 0;
+  ctx->bb.kept = 0;
+  ctx->bb.kept_blocks = 0;
+  ctx->bb.z_bytes = 0;
+  if ((rc = bsc_bigbed_params_check(who, params, bb_params))) return rc;
+  if (ctx->meth_src != 1 || ctx->rec_pending || ctx->pending_sz)
+    return bsc_fail(BSC_ERR_ARG, "%s: the last call left no single block's arrays on the device", who);
+  const uint32_t n = ctx->again.sz, x0 = ctx->meth_x;
+  ctx->bb.kept_B = bb_params->items_per_block;
+  if (!n) {
+    ctx->bb.kept = 1;
+    return BSC_OK;
+  }
+  BSC_ENTER(ctx);
+  hipStream_t s = ctx->stream;
+  /* room for the most a block of n positions can give: every position a site with the longest item */
+  const uint64_t B = bb_params->items_per_block, red = bb_params->reduction;
+  const uint64_t blk_cap = ((uint64_t)n + B - 1) / B, out_cap = (uint64_t)BSC_BB_ITEM_MAX * n;
+  const uint64_t span = ((uint64_t)n + red - 1) / red + 1, zoom_cap = span < n ? span : n;
+  if ((rc = bsc_reserve(&ctx->bb.d_data, &ctx->bb.cap_data, (size_t)out_cap))) return rc;
+  if ((rc = bsc_reserve(&ctx->bb.d_blk, &ctx->bb.cap_blk, (size_t)blk_cap * sizeof(bsc_bb_sum)))) return rc;
+  if ((rc = bsc_reserve(&ctx->bb.d_zoom, &ctx->bb.cap_zoom, (size_t)zoom_cap * sizeof(bsc_bb_sum)))) return rc;
+  if ((rc = bsc_reserve(&ctx->bb.d_tot, &ctx->bb.cap_tot, 4 * sizeof(unsigned long long)))) return rc;
+  if ((rc = bsc_bigbed_run(ctx, who, ctx->d_vout, ctx->d_out, ctx->again.emit, n, x0, chrom_id, params, bb_params, ctx->bb.d_data, out_cap, ctx->bb.d_blk,
+                           blk_cap, ctx->bb.d_zoom, zoom_cap, ctx->bb.d_tot, s)))
+    return rc;
+  unsigned long long tot[4] = {0, 0, 0, 0};
+  HIP_TRY(hipMemcpyAsync(tot, ctx->bb.d_tot, sizeof tot, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  *n_bytes = tot[0];
+  if (n_sites) *n_sites = tot[1];
+  *n_blocks = tot[2];
+  *n_zoom0 = tot[3];
+  if (tot[0] > out_cap || tot[2] > blk_cap || tot[3] > zoom_cap)
+    return bsc_fail(BSC_ERR_ARG, "%s: the block's %llu bytes, %llu blocks, %llu windows are beyond the room of %llu, %llu, %llu", who, tot[0], tot[2],
+                    tot[3], (unsigned long long)out_cap, (unsigned long long)blk_cap, (unsigned long long)zoom_cap);
+  if ((rc = bsc_host_room_bytes((void **)&ctx->bb.h_blk, &ctx->bb.cap_hblk, (size_t)tot[2] * sizeof(bsc_bb_sum), who))) return rc;
+  if ((rc = bsc_host_room_bytes((void **)&ctx->bb.h_zoom, &ctx->bb.cap_hzoom, (size_t)tot[3] * sizeof(bsc_bb_sum), who))) return rc;
+  if (tot[2]) HIP_TRY(hipMemcpyAsync(ctx->bb.h_blk, ctx->bb.d_blk, (size_t)tot[2] * sizeof(bsc_bb_sum), hipMemcpyDeviceToHost, s));
+  if (tot[3]) HIP_TRY(hipMemcpyAsync(ctx->bb.h_zoom, ctx->bb.d_zoom, (size_t)tot[3] * sizeof(bsc_bb_sum), hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  *blocks = ctx->bb.h_blk;
+  *zoom0 = ctx->bb.h_zoom;
+  ctx->bb.bytes = tot[0];
+  ctx->bb.kept_blocks = tot[2];
+  ctx->bb.kept = 1;
+  return BSC_OK;
+}
+
+int bsc_bigbed_stream_read(bsc_context *ctx, uint64_t off, uint64_t n, void *dst) {
+  if (!ctx || (!dst && n)) return bsc_fail(BSC_ERR_ARG, "bsc_bigbed_stream_read: NULL argument");
+  if (off + n > ctx->bb.bytes || off + n > ctx->bb.cap_data) return bsc_fail(BSC_ERR_ARG, "bsc_bigbed_stream_read: beyond the stream's end");
+  if (!n) return BSC_OK;
+  BSC_ENTER(ctx);
+  HIP_TRY(hipMemcpyAsync(dst, (const char *)ctx->bb.d_data + off, (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+  return BSC_OK;
+}
+
+int bsc_block_bigbed_deflate(bsc_context *ctx, uint64_t *z_bytes, const uint32_t **z_sizes, uint64_t *n_blocks) {
+  static const char who[] = "bsc_block_bigbed_deflate";
+  int rc;
+  if (!ctx || !z_bytes || !z_sizes || !n_blocks) return bsc_fail(BSC_ERR_ARG, "%s: NULL argument", who);
+  *z_bytes = *n_blocks = 0;
+  *z_sizes = NULL;
+  ctx->bb.z_bytes = 0;
+  if (!ctx->bb.kept) return bsc_fail(BSC_ERR_ARG, "%s: no bsc_block_bigbed_kept came before it", who);
+  if (ctx->bb.kept_B > BSC_BB_Z_ITEMS_MAX)
+    return bsc_fail(BSC_ERR_ARG, "%s: a block of %u items may be %llu bytes, more than 65280 (at most %u items)", who, ctx->bb.kept_B,
+                    (unsigned long long)ctx->bb.kept_B * BSC_BB_ITEM_MAX, BSC_BB_Z_ITEMS_MAX);
+  const uint64_t n = ctx->bb.bytes, np = ctx->bb.kept_blocks;
+  if (!n) return BSC_OK;
+  BSC_ENTER(ctx);
+  hipStream_t s = ctx->stream;
+  const uint64_t out_cap = n + 11 * np;
+  if ((rc = bsc_reserve(&ctx->bb.d_z, &ctx->bb.cap_z, (size_t)out_cap))) return rc;
+  if ((rc = bsc_reserve(&ctx->bb.d_zsz, &ctx->bb.cap_zsz, (size_t)np * 4u))) return rc;
+  if ((rc = bsc_reserve(&ctx->bb.d_zoffs, &ctx->bb.cap_zoffs, ((size_t)np + 1u) * 8u))) return rc;
+  if ((rc = bsc_reserve(&ctx->bb.d_ztot, &ctx->bb.cap_ztot, 3 * sizeof(unsigned long long)))) return rc;
+  if ((rc = bsc_host_room_bytes((void **)&ctx->bb.h_zsz, &ctx->bb.cap_hzsz, (size_t)np * 4u, who))) return rc;
+  if ((rc = bsc_host_room_bytes((void **)&ctx->bb.h_zoffs, &ctx->bb.cap_hzoffs, ((size_t)np + 1u) * 8u, who))) return rc;
+  for (uint64_t k = 0; k < np; k++) ctx->bb.h_zoffs[k] = ctx->bb.h_blk[k].off; /* that call's blocks[].off, and the stream's end behind them */
+  ctx->bb.h_zoffs[np] = n;
+  HIP_TRY(hipMemcpyAsync(ctx->bb.d_zoffs, ctx->bb.h_zoffs, ((size_t)np + 1u) * 8u, hipMemcpyHostToDevice, s));
+  if ((rc = bsc_zlib_ranges_queue(ctx, who, ctx->bb.d_data, ctx->bb.d_zoffs, (uint32_t)np, ctx->bb.kept_B * BSC_BB_ITEM_MAX, ctx->bb.d_z, out_cap, ctx->bb.d_zsz,
+                                  np, ctx->bb.d_ztot, (void *)s)))
+    return rc; /* (queued only: the one wait is below, with the copy of the three totals) */
+  unsigned long long tot[3] = {0, 0, 0};
+  HIP_TRY(hipMemcpyAsync(tot, ctx->bb.d_ztot, sizeof tot, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipMemcpyAsync(ctx->bb.h_zsz, ctx->bb.d_zsz, (size_t)np * 4u, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  if (tot[0] > out_cap || tot[1] != np || tot[2])
+    return bsc_fail(BSC_ERR_HIP, "%s: the encoder reported %llu bytes in %llu streams for %llu blocks, %llu of them out of range", who, tot[0], tot[1],
+                    (unsigned long long)np, tot[2]);
+  *z_bytes = tot[0];
+  *n_blocks = np;
+  *z_sizes = ctx->bb.h_zsz;
+  ctx->bb.z_bytes = tot[0];
+  return BSC_OK;
+}
+
+int bsc_bigbed_zstream_read(bsc_context *ctx, uint64_t off, uint64_t n, void *dst) {
+  if (!ctx || (!dst && n)) return bsc_fail(BSC_ERR_ARG, "bsc_bigbed_zstream_read: NULL argument");
+  if (off + n > ctx->bb.z_bytes || off + n > ctx->bb.cap_z) return bsc_fail(BSC_ERR_ARG, "bsc_bigbed_zstream_read: beyond the streams' end");
+  if (!n) return BSC_OK;
+  BSC_ENTER(ctx);
+  HIP_TRY(hipMemcpyAsync(dst, (const char *)ctx->bb.d_z + off, (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
   return BSC_OK;
 }
 

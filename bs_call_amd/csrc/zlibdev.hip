@@ -19,6 +19,11 @@
  * The image goes to a slot of round16(piece + 11) + 16 bytes with its size; bsc_zlib_scan_kernel sums the sizes and leaves the totals;
  * bsc_zlib_gather_kernel packs the slots end to end and copies the sizes — each only if its room holds all of it.  A stream is a function
  * of its piece's bytes alone.  (The helpers from the tables to the two writers are bgzfdev.hip's, restated here so that file stays as it is.)
+ *
+ * Pieces of varying length (the bigBed blocks: bsc_zlib_ranges_device): the same body, bsc_zlib_deflate_ranges_small_kernel / _large_kernel,
+ * with a piece's base and length taken from n_pieces + 1 ascending offsets instead of a stride; slots and scratch are sized for the longest
+ * piece the caller allows.  A range of no byte reads nothing and gets size 0, a longer one is cut at that length, and both are counted: no
+ * offset, whatever it holds, makes a workgroup touch memory outside its buffers or outside the range it names.
  */
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -280,9 +285,10 @@ __device__ __forceinline__ void put_u32be(uint8_t *b, uint32_t v) {
  * src[0 .. n): piece k = [k piece, min((k + 1) piece, n)); slots[n_pieces][slot]; sizes[n_pieces]; scratch[gridDim.x][piece] u32.
  * PIECE_MAX: the longest piece of this instance (piece <= PIECE_MAX).  Workgroups loop over the pieces.
  */
-template <uint32_t PIECE_MAX>
+template <uint32_t PIECE_MAX, bool RANGES = false>
 __device__ __forceinline__ void zlib_deflate_body(const uint8_t *__restrict__ src, uint64_t n, uint32_t piece, uint32_t n_pieces, uint8_t *__restrict__ slots,
-                                                  uint32_t slot, uint32_t *__restrict__ sizes, uint32_t *__restrict__ scratch_all) {
+                                                  uint32_t slot, uint32_t *__restrict__ sizes, uint32_t *__restrict__ scratch_all,
+                                                  const unsigned long long *__restrict__ range_offs = nullptr, unsigned long long *bad = nullptr) {
   constexpr uint32_t WORDS = ZL_WORDS(PIECE_MAX) < 160u ? 160u : ZL_WORDS(PIECE_MAX);
   __shared__ __attribute__((aligned(16))) uint32_t s_buf[WORDS]; /* the piece's bytes, then its image */
   __shared__ uint32_t s_head[1u << ZL_HBITS];
@@ -300,8 +306,22 @@ __device__ __forceinline__ void zlib_deflate_body(const uint8_t *__restrict__ sr
   uint8_t *s_bytes = (uint8_t *)s_buf;
 
   for (uint32_t m = blockIdx.x; m < n_pieces; m += gridDim.x) {
-    const uint64_t base = (uint64_t)m * piece;
-    const uint32_t len = (uint32_t)(n - base < piece ? n - base : piece);
+    uint64_t base;
+    uint32_t len;
+    if (RANGES) { /* piece m = [offs[m], offs[m + 1]): its length clamped to what the buffers of this launch are sized for */
+      const unsigned long long o0 = range_offs[m], o1 = range_offs[m + 1u];
+      const bool none = o1 <= o0, over = !none && o1 - o0 > piece;
+      if ((none || over) && tid == 0) atomicAdd(bad, 1ull); /* an integer count: no order can change it */
+      if (none) { /* (block-uniform) nothing of the source is read, nothing but the size is written */
+        if (tid == 0) sizes[m] = 0u;
+        continue;
+      }
+      base = o0;
+      len = over ? piece : (uint32_t)(o1 - o0);
+    } else {
+      base = (uint64_t)m * piece;
+      len = (uint32_t)(n - base < piece ? n - base : piece);
+    }
     __syncthreads(); /* the previous piece's image is out */
     load_piece(src + base, len, s_buf, 0);
     for (uint32_t w = ((len + 3u) >> 2) + tid; w < WORDS; w += ZL_LANES) s_buf[w] = 0;
@@ -571,6 +591,22 @@ extern "C" __global__ __launch_bounds__(256) void bsc_zlib_deflate_large_kernel(
   zlib_deflate_body<ZL_MAX_PIECE>(src, n, piece, n_pieces, slots, slot, sizes, scratch_all);
 }
 
+/* the same body over ranges: piece m = src[offs[m], offs[m + 1]), 1 .. piece bytes each (piece: the longest the caller allows, what slots and
+ * scratch are sized for).  A range of no byte, or whose end lies before its start, gives size 0 and reads nothing; a longer one is cut at
+ * `piece` bytes; *bad counts both. */
+extern "C" __global__ __launch_bounds__(256) void bsc_zlib_deflate_ranges_small_kernel(const uint8_t *__restrict__ src, const unsigned long long *__restrict__ offs,
+                                                                                      uint32_t piece, uint32_t n_pieces, uint8_t *__restrict__ slots,
+                                                                                      uint32_t slot, uint32_t *__restrict__ sizes,
+                                                                                      uint32_t *__restrict__ scratch_all, unsigned long long *bad) {
+  zlib_deflate_body<ZL_SMALL_PIECE, true>(src, 0ull, piece, n_pieces, slots, slot, sizes, scratch_all, offs, bad);
+}
+extern "C" __global__ __launch_bounds__(256) void bsc_zlib_deflate_ranges_large_kernel(const uint8_t *__restrict__ src, const unsigned long long *__restrict__ offs,
+                                                                                      uint32_t piece, uint32_t n_pieces, uint8_t *__restrict__ slots,
+                                                                                      uint32_t slot, uint32_t *__restrict__ sizes,
+                                                                                      uint32_t *__restrict__ scratch_all, unsigned long long *bad) {
+  zlib_deflate_body<ZL_MAX_PIECE, true>(src, 0ull, piece, n_pieces, slots, slot, sizes, scratch_all, offs, bad);
+}
+
 /* offs[i] = sizes[0] + ... + sizes[i - 1], offs[n] = the total; totals = {the total, n}; one workgroup */
 extern "C" __global__ __launch_bounds__(256) void bsc_zlib_scan_kernel(const uint32_t *__restrict__ sizes, unsigned long long *__restrict__ offs, uint32_t n,
                                                                       unsigned long long *__restrict__ totals) {
@@ -635,11 +671,24 @@ extern "C" uint32_t bsc_dev_zlib_grid(uint32_t piece, uint32_t n_pieces, int num
 }
 
 /* n_pieces >= 1.  scratch: grid * piece u32; slots: n_pieces * bsc_dev_zlib_slot(piece); sizes: n_pieces u32; offs: n_pieces + 1 u64 */
-extern "C" int bsc_dev_launch_zlib(const void *src, uint64_t n, uint32_t piece, uint32_t n_pieces, void *slots, void *sizes, void *offs, void *scratch,
-                                   uint32_t grid, void *out, uint64_t out_cap, void *sizes_out, uint64_t sizes_cap, void *totals, int num_cus, void *stream) {
+/* range_offs: NULL — the fixed-stride pieces of src[0 .. n) —, or n_pieces + 1 ascending device u64 — piece m = src[range_offs[m],
+ * range_offs[m + 1]), `piece` the longest allowed; then totals has a third word, the count of bad ranges, zeroed here. */
+static int zlib_launch(const void *src, uint64_t n, const void *range_offs, uint32_t piece, uint32_t n_pieces, void *slots, void *sizes, void *offs,
+                       void *scratch, uint32_t grid, void *out, uint64_t out_cap, void *sizes_out, uint64_t sizes_cap, void *totals, int num_cus,
+                       void *stream) {
   hipStream_t s = (hipStream_t)stream;
   const uint32_t slot = bsc_dev_zlib_slot(piece);
-  if (piece <= ZL_SMALL_PIECE)
+  if (range_offs) {
+    unsigned long long *bad = (unsigned long long *)totals + 2;
+    const hipError_t e = hipMemsetAsync(bad, 0, sizeof *bad, s);
+    if (e != hipSuccess) return (int)e;
+    if (piece <= ZL_SMALL_PIECE)
+      hipLaunchKernelGGL(bsc_zlib_deflate_ranges_small_kernel, dim3(grid), dim3(ZL_LANES), 0, s, (const uint8_t *)src, (const unsigned long long *)range_offs,
+                         piece, n_pieces, (uint8_t *)slots, slot, (uint32_t *)sizes, (uint32_t *)scratch, bad);
+    else
+      hipLaunchKernelGGL(bsc_zlib_deflate_ranges_large_kernel, dim3(grid), dim3(ZL_LANES), 0, s, (const uint8_t *)src, (const unsigned long long *)range_offs,
+                         piece, n_pieces, (uint8_t *)slots, slot, (uint32_t *)sizes, (uint32_t *)scratch, bad);
+  } else if (piece <= ZL_SMALL_PIECE)
     hipLaunchKernelGGL(bsc_zlib_deflate_small_kernel, dim3(grid), dim3(ZL_LANES), 0, s, (const uint8_t *)src, n, piece, n_pieces, (uint8_t *)slots, slot,
                        (uint32_t *)sizes, (uint32_t *)scratch);
   else
@@ -653,4 +702,17 @@ extern "C" int bsc_dev_launch_zlib(const void *src, uint64_t n, uint32_t piece, 
   hipLaunchKernelGGL(bsc_zlib_gather_kernel, dim3(gg), dim3(ZL_LANES), 0, s, (const uint8_t *)slots, slot, (const unsigned long long *)offs,
                      (const uint32_t *)sizes, n_pieces, (uint8_t *)out, out_cap, (uint32_t *)sizes_out, sizes_cap);
   return (int)hipGetLastError();
+}
+
+extern "C" int bsc_dev_launch_zlib(const void *src, uint64_t n, uint32_t piece, uint32_t n_pieces, void *slots, void *sizes, void *offs, void *scratch,
+                                   uint32_t grid, void *out, uint64_t out_cap, void *sizes_out, uint64_t sizes_cap, void *totals, int num_cus, void *stream) {
+  return zlib_launch(src, n, NULL, piece, n_pieces, slots, sizes, offs, scratch, grid, out, out_cap, sizes_out, sizes_cap, totals, num_cus, stream);
+}
+
+/* as bsc_dev_launch_zlib with piece = max_piece for the workspaces; range_offs: n_pieces + 1 device u64; totals: three u64 */
+extern "C" int bsc_dev_launch_zlib_ranges(const void *src, const void *range_offs, uint32_t max_piece, uint32_t n_pieces, void *slots, void *sizes, void *offs,
+                                          void *scratch, uint32_t grid, void *out, uint64_t out_cap, void *sizes_out, uint64_t sizes_cap, void *totals,
+                                          int num_cus, void *stream) {
+  if (!range_offs) return (int)hipErrorInvalidValue;
+  return zlib_launch(src, 0ull, range_offs, max_piece, n_pieces, slots, sizes, offs, scratch, grid, out, out_cap, sizes_out, sizes_cap, totals, num_cus, stream);
 }

@@ -19,7 +19,8 @@ def run(bam_path: str, reference: Dict[str, np.ndarray], bcf_path: str, sample: 
         host_prep: bool = False, host_bcf: bool = False, device_reader: bool = False, shard_rank: Optional[int] = None, shard_world: int = 1,
         reduce_device=None, text: bool = False, dbsnp_device: bool = False, meth_path: Optional[str] = None, meth_params=None, meth_merge: bool = False,
         meth_regions=None, meth_regions_path: Optional[str] = None, meth_window: Optional[int] = None, bigwig_path: Optional[str] = None,
-        bigwig_section: int = 1024, bigwig_zoom: int = 1024, bigwig_compress: bool = False, **reader_kw) -> dict:
+        bigwig_section: int = 1024, bigwig_zoom: int = 1024, bigwig_compress: bool = False, bigbed_path: Optional[str] = None, bigbed_items: int = 512,
+        bigbed_zoom: int = 1024, bigbed_compress: bool = False, **reader_kw) -> dict:
     """reference: contig name -> uint8 reference codes (0 = N, 1..4 = ACGT; position 1 first).  Returns a summary dict.
     under_conv / over_conv / min_qual (defaults 0.01 / 0.05 / 20, src/init_param.c:26-31) are the MODEL's parameters: without
     `caller` the run builds its SiteCaller from them; with one, they are taken from it and a differing explicit value is an error
@@ -57,7 +58,22 @@ def run(bam_path: str, reference: Dict[str, np.ndarray], bcf_path: str, sample: 
     bigwig.Writer.  bigwig_section: sites a section (1 .. 65535); bigwig_zoom: the width of a level-0 zoom window.  meth_params apply; the
     track is per cytosine whatever meth_merge says; meth_path is not needed.  The same conditions as meth_path.  bigwig_compress: every
     section leaves the device as a zlib stream (SiteCaller.block_bigwig_deflate, csrc/zlibdev.hip) and the writer deflates the zoom blocks:
-    the file readers meet in practice, about half the bytes; needs bigwig_path and bigwig_section <= 8157."""
+    the file readers meet in practice, about half the bytes; needs bigwig_path and bigwig_section <= 8157.
+
+    bigbed_path: the per-cytosine table of the same run as a bigBed file (include/bscall_amd.h has the rule and the file's layout): every
+    block's items and summaries from the arrays it left on the device (SiteCaller.block_bigbed_kept, csrc/bigbeddev.hip), the file by
+    bigbed.Writer.  bigbed_items: sites a block (1 .. 65535); bigbed_zoom: the width of a level-0 zoom window.  meth_params apply; the same
+    conditions as bigwig_path.  bigbed_compress: every block leaves the device as a zlib stream (SiteCaller.block_bigbed_deflate); needs
+    bigbed_path and bigbed_items <= bigbed.Z_ITEMS_MAX."""
+    want_bb = bigbed_path is not None
+    if bigbed_compress and not want_bb:
+        raise ValueError("bigbed_compress needs bigbed_path")
+    if bigbed_compress and int(bigbed_items) > 0xFF00 // 100:
+        raise ValueError("bigbed_compress: a block of more than %d sites may be more than 0xFF00 bytes" % (0xFF00 // 100))
+    if want_bb and (shard_rank is not None or not device_reader or host_prep or host_bcf):
+        raise ValueError("bigbed_path is a single run on the device reader (device_reader=True, no shard_rank, no host_prep / host_bcf)")
+    if want_bb and not (1 <= int(bigbed_items) <= 65535 and 1 <= int(bigbed_zoom) <= 0xFFFFFFFF):
+        raise ValueError("bigbed_items is 1 .. 65535 sites, bigbed_zoom 1 or more bases")
     want_bw = bigwig_path is not None
     if bigwig_compress and not want_bw:
         raise ValueError("bigwig_compress needs bigwig_path")
@@ -106,7 +122,8 @@ def run(bam_path: str, reference: Dict[str, np.ndarray], bcf_path: str, sample: 
     on_device = dbsnp_device and dbsnp is not None
     if text and (shard_rank is not None or not device_reader or host_prep or host_bcf):
         raise ValueError("text=True is a single run on the device reader (device_reader=True, no shard_rank, no host_prep / host_bcf)")
-    bw_writer = None
+    bw_writer = bb_writer = None
+    bb_sites = 0
     own = caller is None
     if own:
         under_conv = 0.01 if under_conv is None else under_conv
@@ -164,6 +181,12 @@ def run(bam_path: str, reference: Dict[str, np.ndarray], bcf_path: str, sample: 
                 bw_writer = bigwig.Writer(bigwig_path, refs, int(bigwig_section), int(bigwig_zoom), compress=bool(bigwig_compress))
                 bw_par = {"items_per_section": int(bigwig_section), "reduction": int(bigwig_zoom)}
 
+            if want_bb:
+                from . import bigbed
+
+                bb_writer = bigbed.Writer(bigbed_path, refs, int(bigbed_items), int(bigbed_zoom), compress=bool(bigbed_compress))
+                bb_par = {"items_per_block": int(bigbed_items), "reduction": int(bigbed_zoom)}
+
             def regions_flush():
                 nonlocal region_cur
                 if region_cur is not None:
@@ -173,7 +196,7 @@ def run(bam_path: str, reference: Dict[str, np.ndarray], bcf_path: str, sample: 
                 region_cur = None
 
             def block_blobs():
-                nonlocal n_blocks, n_records, base_filter, passed, meth_lines, region_cur, bw_sites
+                nonlocal n_blocks, n_records, base_filter, passed, meth_lines, region_cur, bw_sites, bb_sites
                 before, cur_tid = c.site_totals(), -1
                 for item in (rd.device_blocks() if device_reader else rd.blocks()):
                     if device_reader:
@@ -221,7 +244,7 @@ def run(bam_path: str, reference: Dict[str, np.ndarray], bcf_path: str, sample: 
                         else:
                             blob, n_rec, st = c.block_bcf_rawdev(dblk, ref, tid, names=names, left_trim=left_trim, right_trim=right_trim, min_qual=min_qual,
                                                                  reg_stop=len(codes), dbsnp=flags, with_stats=True, profile=prof,
-                                                                 keep=meth_path is not None or want_regions or want_bw)
+                                                                 keep=meth_path is not None or want_regions or want_bw or want_bb)
                         if region_cur is not None:  # the block's cytosines into the attached regions' sums
                             c.block_meth_regions_kept(meth_params)
                         if want_bw:  # the block's bigWig sections and summaries, appended to the track's file
@@ -232,6 +255,14 @@ def run(bam_path: str, reference: Dict[str, np.ndarray], bcf_path: str, sample: 
                             else:
                                 bw_writer.add(tid, data, secs, zoom0)
                             bw_sites += ns
+                        if want_bb:  # the block's bigBed items and summaries, appended to the bigBed's file
+                            data, ns, blks, zoom0 = c.block_bigbed_kept(tid, meth_params, bb_par, read_stream=not bigbed_compress)
+                            if bigbed_compress:  # ... as zlib streams: the plain stream stays on the device
+                                zdata, zsizes = c.block_bigbed_deflate()
+                                bb_writer.add_z(tid, zdata, zsizes, data, blks, zoom0)
+                            else:
+                                bb_writer.add(tid, data, blks, zoom0)
+                            bb_sites += ns
                         if meth_path is not None:  # the same block's table, from what it left on the device
                             mb, ml, _ = c.block_meth_kept(name, meth_params, merge=meth_merge)
                             meth_blobs.append(mb)
@@ -276,6 +307,8 @@ def run(bam_path: str, reference: Dict[str, np.ndarray], bcf_path: str, sample: 
                 vcf.write_vcf_blobs(meth_path, "", meth_blobs, compressed)
             if want_bw:
                 bw_writer.finish()
+            if want_bb:
+                bb_writer.finish()
             if want_regions:
                 regions_flush()
                 with open(meth_regions_path, "wb") as f:
@@ -348,12 +381,16 @@ def run(bam_path: str, reference: Dict[str, np.ndarray], bcf_path: str, sample: 
             summary["meth_lines"] = meth_lines
         if want_bw:
             summary["bigwig_sites"] = bw_sites
+        if want_bb:
+            summary["bigbed_items"] = bb_sites
         if want_regions:
             summary["meth_region_lines"] = sum(b.count(b"\n") for b in region_out)
         return summary
     finally:
         if bw_writer is not None:
             bw_writer.close()
+        if bb_writer is not None:
+            bb_writer.close()
         if own:
             c.close()
         else:  # a supplied caller goes back as it came

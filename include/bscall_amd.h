@@ -1376,6 +1376,147 @@ int bsc_block_bigwig_deflate(bsc_context *ctx, uint64_t *z_bytes, const uint32_t
 int bsc_bigwig_zstream_read(bsc_context *ctx, uint64_t off, uint64_t n, void *dst);
 int bsc_bigwig_add_z(bsc_bigwig *bw, uint32_t tid, const void *zdata, uint64_t z_bytes, const uint32_t *z_sizes, const bsc_bw_sum *sections,
                      uint64_t n_sections, const bsc_bw_sum *zoom0, uint64_t n_zoom0);
+/*
+ * The bedMethyl table as bigBed items (csrc/bigbeddev.hip: the bsc_bigbed_*_kernel family; csrc/bigbed.c holds the host form, which is their
+ * checker): what a genome browser fetches by region — counts, GQ and FILTER per site — in place of the text table, made from the
+ * per-position arrays a block call left in HBM.  Integers only, no atomics, no result that depends on an order.  The rule, from which the
+ * host form, the tests' Python form and the kernels are each written:
+ *   SITE      a record that gives a line under the per-cytosine rule of bsc_meth_format_rec with the given bsc_meth_params (contexts —
+ *             BSC_METH_ALL included —, min_cov, min_phred, pass_only: exactly as written there).  Sites come in record order, their
+ *             starts strictly increasing.
+ *   ITEM      the site's bedMethyl line without its first three columns:
+ *               chromId u32, chromStart u32 = pos - 1, chromEnd u32 = pos, little-endian                  (12 bytes)
+ *               the line's bytes from the first byte of column 4 (the name) to the last byte of column 15, tabs included
+ *               one NUL in the place of the '\n'
+ *             so contig "\t" start "\t" end "\t" + the text + "\n" is the table's line, byte for byte.
+ *             BSC_BB_ITEM_MAX = 100: 12 + name 3 + score 4 + strand 1 + thickStart 10 + thickEnd 10 + itemRgb 9 + coverage 10 + pct 2 + a 10 +
+ *             b 10 + GQ 3 + FILTER 4 + 11 tabs + NUL — the table's longest line (the contig's name + 111) less the name, less "\t" 10 "\t"
+ *             10 "\t", plus 12; pct 100 has a shorter itemRgb and b.  Attained by pos = 2^32 - 1, a CHG / CHH / CHN site, a = b = 4 * 10^9,
+ *             phred >= 100 (under BSC_METH_CPG the longest is 99).  BSC_BB_ITEM_MIN = 46: 12 + "CG" + nine one-byte columns
+ *             (score, strand, thickStart, thickEnd, coverage, pct, a, b, GQ) + itemRgb "0,255,0" 7 + FILTER 4 + 11 tabs + NUL.  Attained
+ *             by pos <= 9, a = 0, b = 1 .. 9, phred <= 9.
+ *   PARAMS    bsc_bb_params {items_per_block B: 1 .. 65535, default 512;  reduction: >= 1, default 1024}.
+ *   STREAM    of a block call: the items of the call's sites back to back, in order; bigBed blocks carry no header.  Block k holds the
+ *             sites of rank [k B, (k + 1) B); only the last block is short.  A block never spans two block calls or two contigs.
+ *   PER CALL  one 24-byte struct, bsc_bb_sum {start u32, end u32, count u32, _pad u32 = 0, off u64}, for two arrays:
+ *             blocks[n_blocks]: start = the block's first site's start, end = its last site's start + 1, count, off = the block's byte
+ *             offset in the stream;  zoom0[n_windows]: the same {start, end, count} for the windows w = start / reduction that hold a
+ *             site, ascending, off = 0.  d_totals = four u64 {n_bytes, n_sites, n_blocks, n_windows}.
+ *   FILE      bbiFile version 4 in the layout of the bigWig file above, with these
+ *             differences: magic 0x8789F2EB in the header and at the end; fieldCount = 15, definedFieldCount = 9; autoSqlOffset names
+ *             the NUL-terminated text below, placed behind the total summary; fullDataOffset names a u64 that is the number of ITEMS;
+ *             the R-tree has itemsPerSlot = B and one leaf item per block, bounds {tid, start, tid, end}, dataOffset / dataSize the
+ *             block's bytes.  Sites are one base wide and never overlap, so the depth is 1 wherever it is not 0: the total summary is
+ *             {basesCovered = sites, minVal = 1, maxVal = 1, sumData = sites, sumSquares = sites} (all zero with no site), a zoom record
+ *             {chromId, chromStart, chromEnd, validCount = count, 1.0f, 1.0f, (float)count, (float)count}.  The pyramid's levels follow
+ *             the bigWig rule unchanged (windows of reduction * 4^l, counts add, level l iff level l - 1 has more than 256 records, at
+ *             most 8 levels, 512 records a zoom block, a zoom block never spans contigs).  uncompressBufSize = 0 in a plain file, the
+ *             largest raw size of any data or zoom block in a compressed one, where every data block is its ZSTREAM and every zoom
+ *             block compress2's at the default level: a raw block must fit a piece, B * BSC_BB_ITEM_MAX <= 0xFF00
+ *             (B <= BSC_BB_Z_ITEMS_MAX = 652).  The bytes are UCSC-unpinned, as the bigWig's are.  The autoSql text, lines ending "\n":
+ *               table bedMethyl
+ *               "Methylation level per cytosine"
+ *               (
+ *               string chrom; "Reference sequence"
+ *               uint chromStart; "Start, 0-based"
+ *               uint chromEnd; "End"
+ *               string name; "Context: CG, CHG, CHH or CHN"
+ *               uint score; "Coverage, capped at 1000"
+ *               char[1] strand; "+ or -"
+ *               uint thickStart; "Start"
+ *               uint thickEnd; "End"
+ *               uint reserved; "Colour by level (itemRgb)"
+ *               bigint coverage; "Informative reads: non-converted + converted"
+ *               uint percent; "Methylation level, percent, rounded half up"
+ *               uint nonConverted; "Non-converted reads"
+ *               uint converted; "Converted reads"
+ *               uint gq; "Phred-scaled genotype quality"
+ *               string filter; "FILTER of the call"
+ *               )
+ * Host (csrc/bigbed.c):
+ *   bsc_bb_params_default      {512, 1024}
+ *   bsc_bigbed_blocks_recs     the host form over packed records recs[0 .. n), plain C over bsc_meth_format_rec: the stream -> out[cap],
+ *                              the summaries -> blocks[] and zoom0[].  *n_blocks and *n_zoom0 hold the ROOM of the two arrays on entry and
+ *                              the counts on return.  Where any of the three rooms is too small: BSC_ERR_ARG, the three needs reported and
+ *                              nothing written.
+ *   bsc_bigbed_open            a writer on a descriptor it may pwrite to (not closed here); names / lens: the BAM header's contigs
+ *   bsc_bigbed_add             a call's stream appended (pwrite) and its entries kept.  BSC_ERR_ARG — nothing written — for a tid lower than
+ *                              the last or not in the header, a start below the previous end on the same tid, a block other than the last
+ *                              whose count is not B, blocks[0].off not 0 or offsets that do not ascend, a block whose bytes (to the next
+ *                              offset; the last block's to n_bytes) lie outside count * [BSC_BB_ITEM_MIN, BSC_BB_ITEM_MAX], windows that do
+ *                              not hold the blocks' sites.  A window two adds share on one contig merges: the counts add.
+ *   bsc_bigbed_add_z           bsc_bigbed_add for a call's ZSTREAMs: every check of bsc_bigbed_add, with raw_bytes — the plain stream's
+ *                              length, which the twin bsc_bigwig_add_z can work out from the counts and this one cannot — in n_bytes'
+ *                              place; z_sizes[k] is 1 .. the block's raw bytes + 11 and their sum z_bytes; B <= BSC_BB_Z_ITEMS_MAX.  After a
+ *                              non-empty bsc_bigbed_add_z a non-empty bsc_bigbed_add is BSC_ERR_ARG with nothing written, and the reverse.
+ *   bsc_bigbed_finish          item count, R-tree, zoom levels (deflated with compress2 in a compressed file), total summary, autoSql text,
+ *                              header, the closing magic; every write checked (BSC_ERR_ARG with errno's text).  Once.
+ *   bsc_bigbed_close           frees the writer (an unfinished file stays without a header: not a bigBed)
+ *                              The chromosome tree, the R-tree and the byte buffer are csrc/bbi_trees.h, which csrc/bigwig.c includes too.
+ * Device:
+ *   bsc_bigbed_sites_device    from d_core[n] / d_aux[n], entry i = position x0 + i (x0 >= 1, x0 + n - 1 < 2^32; the contract of
+ *                              bsc_bigwig_sites_device): the stream -> d_out[out_cap] (16-byte aligned), the summaries ->
+ *                              d_blocks[blk_cap], d_zoom[zoom_cap] (8-byte aligned), and d_totals.  An array whose room is too small is
+ *                              not written at all — the needs are in d_totals, and nothing partial is to be trusted.  Asynchronous on
+ *                              `stream`; workspaces of the context (one call in flight per context).
+ *   bsc_block_bigbed_kept      the follow-up of the _keep block calls: preconditions and refusals of bsc_block_bigwig_kept; from the
+ *                              arrays that block left in HBM, by the chain's emit byte per position, with the block's own x, into buffers
+ *                              of its own (room for the most the block can give: its BSC_ERR_ARG for a room too small is unreachable).
+ *                              *blocks / *zoom0: the context's host copies, good until the next call.  The kept stream, its tile offsets,
+ *                              the methylation tables, bsc_block_csi_kept, the region accumulators and the bigWig buffers are untouched;
+ *                              before or after them.  Waits.
+ *   bsc_bigbed_stream_read     bytes [off, off + n) of that block's stream -> dst, queued on the context's stream
+ * Compressed blocks (csrc/zlibdev.hip):
+ *   bsc_zlib_ranges_device     piece k = bytes [offs[k], offs[k + 1]) of d_src (any alignment), d_offs = n_pieces + 1 ascending device
+ *                              u64, every length 1 .. max_piece <= 0xFF00: the ZSTREAMs back to back in piece order -> d_out[out_cap],
+ *                              their lengths -> d_sizes[sizes_cap] (u32), d_totals = THREE device u64 {bytes out, pieces, ranges whose
+ *                              length was 0 or above max_piece}.  A stream is a function of its bytes alone: equal-length ranges give
+ *                              bsc_zlib_pieces_device's bytes.  A bad range is clamped in the kernel (its workgroup touches no memory
+ *                              outside its buffers; what comes out is then not to be trusted) and counted; the entry waits for the
+ *                              count and reports BSC_ERR_ARG when it is not 0.  The most needed: the ranges' bytes + 11 n_pieces.  An
+ *                              array whose room is too small is not written at all.  Workspaces of the context.
+ *   bsc_block_bigbed_deflate   the follow-up of bsc_block_bigbed_kept of the same block: that call's blocks, by its blocks[].off, one ZSTREAM each
+ *                              into a buffer of its own; *z_sizes: the context's host copy of the n_blocks lengths, good until the next call.
+ *                              BSC_ERR_ARG without a bsc_block_bigbed_kept before it, or with B > BSC_BB_Z_ITEMS_MAX.  A block with no site:
+ *                              0 / 0.  The uncompressed stream and everything bsc_block_bigbed_kept leaves alone are untouched.  Waits.
+ *   bsc_bigbed_zstream_read    bytes [off, off + n) of those streams -> dst, queued on the context's stream
+ * bam2bcf --meth-bigbed out.bb [--meth-bigbed-items n] [--meth-bigbed-zoom n] [--meth-bigbed-compress] and pipeline.run(bigbed_path=) drive
+ * all of it; bs_call_amd/bigbed.py reads the file back by its offsets alone.
+ * Not built: the combined-strand (--meth-merge) lines as items, sharded runs, a device encoder for the zoom blocks, the batched and
+ * host-buffer block entries.
+ */
+#define BSC_BB_ITEM_MAX 100u
+#define BSC_BB_ITEM_MIN 46u
+#define BSC_BB_Z_ITEMS_MAX (0xFF00u / BSC_BB_ITEM_MAX) /* the most items a block of a compressed file may hold */
+typedef struct {
+  uint32_t items_per_block; /* 1 .. 65535 */
+  uint32_t reduction;       /* >= 1: the width of a level-0 zoom window */
+} bsc_bb_params;
+typedef struct {
+  uint32_t start, end, count, _pad;
+  uint64_t off;
+} bsc_bb_sum;
+typedef struct bsc_bigbed bsc_bigbed;
+void bsc_bb_params_default(bsc_bb_params *p);
+int bsc_bigbed_blocks_recs(const bsc_vcf_rec *recs, size_t n, uint32_t chrom_id, const bsc_meth_params *params, const bsc_bb_params *bb_params,
+                           void *out, uint64_t cap, uint64_t *n_bytes, bsc_bb_sum *blocks, uint64_t *n_blocks, bsc_bb_sum *zoom0, uint64_t *n_zoom0);
+int bsc_bigbed_open(int fd, uint32_t n_refs, const char *const *names, const uint32_t *lens, const bsc_bb_params *bb_params, bsc_bigbed **bb);
+int bsc_bigbed_add(bsc_bigbed *bb, uint32_t tid, const void *data, uint64_t n_bytes, const bsc_bb_sum *blocks, uint64_t n_blocks,
+                   const bsc_bb_sum *zoom0, uint64_t n_zoom0);
+int bsc_bigbed_add_z(bsc_bigbed *bb, uint32_t tid, const void *zdata, uint64_t z_bytes, const uint32_t *z_sizes, uint64_t raw_bytes,
+                     const bsc_bb_sum *blocks, uint64_t n_blocks, const bsc_bb_sum *zoom0, uint64_t n_zoom0);
+int bsc_bigbed_finish(bsc_bigbed *bb);
+void bsc_bigbed_close(bsc_bigbed *bb);
+int bsc_bigbed_sites_device(bsc_context *ctx, const void *d_core, const void *d_aux, uint32_t n, uint32_t x0, uint32_t chrom_id,
+                            const bsc_meth_params *params, const bsc_bb_params *bb_params, void *d_out, uint64_t out_cap, void *d_blocks,
+                            uint64_t blk_cap, void *d_zoom, uint64_t zoom_cap, void *d_totals, void *stream);
+int bsc_block_bigbed_kept(bsc_context *ctx, uint32_t chrom_id, const bsc_meth_params *params, const bsc_bb_params *bb_params, uint64_t *n_bytes,
+                          uint64_t *n_sites, const bsc_bb_sum **blocks, uint64_t *n_blocks, const bsc_bb_sum **zoom0, uint64_t *n_zoom0);
+int bsc_bigbed_stream_read(bsc_context *ctx, uint64_t off, uint64_t n, void *dst);
+int bsc_zlib_ranges_device(bsc_context *ctx, const void *d_src, const void *d_offs, uint32_t n_pieces, uint32_t max_piece, void *d_out,
+                           uint64_t out_cap, void *d_sizes, uint64_t sizes_cap, void *d_totals, void *stream);
+int bsc_block_bigbed_deflate(bsc_context *ctx, uint64_t *z_bytes, const uint32_t **z_sizes, uint64_t *n_blocks);
+int bsc_bigbed_zstream_read(bsc_context *ctx, uint64_t off, uint64_t n, void *dst);
 /* with bsc_set_profiling: device time (HIP events on the context's stream) of the most recent raw block — bsc_block_records_raw[dev],
  * bsc_block_bcf_raw[dev][_keep] — from its first pre-processing launch to the last launch it queued, the host's wait for the prepared size included */
 int bsc_last_raw_block_ms(bsc_context *ctx, float *ms);

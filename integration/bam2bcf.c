@@ -68,6 +68,12 @@
  * output thread as one more job, which bsc_bigwig_add places in the track's own file; bsc_bigwig_finish writes the indexes, the zoom levels and
  * the header at the end.  --meth-bigwig-section n: sites a section (default 1024); --meth-bigwig-zoom n: the level-0 zoom window (default
  * 1024).  The --meth-* thresholds and --meth-all apply; the track is per cytosine even with --meth-merge; --meth is not needed.
+ * --meth-bigbed out.bb: the per-cytosine table as a bigBed file (include/bscall_amd.h has the rule and the file's layout): every block's items,
+ * block and window summaries on the device (bsc_block_bigbed_kept, csrc/bigbeddev.hip), handed to the output thread as one more job for
+ * bsc_bigbed_add; bsc_bigbed_finish writes the indexes, the zoom levels and the header at the end.  --meth-bigbed-items n: sites a block
+ * (default 512); --meth-bigbed-zoom n: the level-0 zoom window (default 1024); the --meth-all / --meth-min-cov / --meth-min-gq / --meth-pass
+ * thresholds apply.  --meth-bigbed-compress: every block leaves the device as a zlib stream (bsc_block_bigbed_deflate) for bsc_bigbed_add_z;
+ * needs --meth-bigbed and at most BSC_BB_Z_ITEMS_MAX sites a block.  Refused like --meth-bigwig in a sharded run and on the BAM2BCF_HOST_* paths.
  * --meth-bigwig-compress: the file readers meet in practice — every section leaves the device as a zlib stream (bsc_block_bigwig_deflate,
  * csrc/zlibdev.hip), the job carries the streams and their sizes for bsc_bigwig_add_z, and bsc_bigwig_finish deflates the zoom blocks.  Needs
  * --meth-bigwig; sections of at most 8157 sites.
@@ -142,6 +148,12 @@ typedef struct {
   bsc_bw_sum *bw_sec, *bw_zoom;
   uint64_t bw_n_sec, bw_n_zoom;
   uint32_t *bw_zsizes; /* --meth-bigwig-compress: bw_data holds the sections' zlib streams, these are their sizes */
+  /* --meth-bigbed: the same for bsc_bigbed_add / _add_z — the block's items (or their zlib streams: bb_zsizes, bb_raw the plain length) */
+  bsc_bigbed *bb;
+  void *bb_data;
+  bsc_bb_sum *bb_blk, *bb_zoom;
+  uint64_t bb_n_blk, bb_n_zoom, bb_raw;
+  uint32_t *bb_zsizes;
 } out_job;
 typedef struct {
   bsc_context *ctx;
@@ -204,6 +216,18 @@ static void *writer_main(void *a) {
       free(j.bw_data);
       free(j.bw_sec);
       free(j.bw_zoom);
+    }
+    if (j.bb) {
+      const int rc = j.bb_zsizes ? bsc_bigbed_add_z(j.bb, j.bw_tid, j.bb_data, j.n, j.bb_zsizes, j.bb_raw, j.bb_blk, j.bb_n_blk, j.bb_zoom, j.bb_n_zoom)
+                                 : bsc_bigbed_add(j.bb, j.bw_tid, j.bb_data, j.n, j.bb_blk, j.bb_n_blk, j.bb_zoom, j.bb_n_zoom);
+      if (rc < 0) {
+        fprintf(stderr, "bam2bcf: %s\n", bsc_last_error());
+        bad = 1;
+      }
+      free(j.bb_zsizes);
+      free(j.bb_data);
+      free(j.bb_blk);
+      free(j.bb_zoom);
     }
     if (j.close_fd && j.fd >= 0) close(j.fd);
     pthread_mutex_lock(&w->mu);
@@ -489,6 +513,10 @@ int main(int argc, char **argv) {
   bsc_bw_params bwpar;
   bsc_bw_params_default(&bwpar);
   int bigwig_z = 0;
+  const char *bigbed_path = NULL;
+  bsc_bb_params bbpar;
+  bsc_bb_params_default(&bbpar);
+  int bigbed_z = 0;
   bsc_meth_params mpar;
   bsc_meth_params_default(&mpar);
   if (argc >= 2 && !strcmp(argv[argc - 1], "--meth") && (argc == 2 || strcmp(argv[argc - 2], "--meth"))) {
@@ -521,6 +549,13 @@ int main(int argc, char **argv) {
       argc -= k;
       continue;
     }
+    if (!strcmp(argv[1], "--meth-bigbed-compress")) { /* no value */
+      bigbed_z = 1;
+      argv[1] = argv[0];
+      argv += 1;
+      argc -= 1;
+      continue;
+    }
     if (!strcmp(argv[1], "--index") || !strcmp(argv[1], "--meth-all") || !strcmp(argv[1], "--meth-pass") || !strcmp(argv[1], "--meth-merge") ||
         !strcmp(argv[1], "--meth-bigwig-compress")) { /* no value */
       if (argv[1][2] == 'i') index = 1;
@@ -549,6 +584,18 @@ int main(int argc, char **argv) {
       meth_window = (uint32_t)v;
     }
     else if (!strcmp(argv[1], "--meth-bigwig")) bigwig_path = argv[2];
+    else if (!strcmp(argv[1], "--meth-bigbed")) bigbed_path = argv[2];
+    else if (!strcmp(argv[1], "--meth-bigbed-items") || !strcmp(argv[1], "--meth-bigbed-zoom")) {
+      char *end = NULL;
+      const int items = argv[1][14] == 'i';
+      const unsigned long v = strtoul(argv[2], &end, 10);
+      if (!argv[2][0] || *end || argv[2][0] == '-' || v < 1 || v > (items ? 65535ul : 0xfffffffful)) {
+        fprintf(stderr, "%s: %s takes a count of %s, not '%s'\n", argv[0], argv[1], items ? "sites, 1 .. 65535" : "bases, 1 or more", argv[2]);
+        return 2;
+      }
+      if (items) bbpar.items_per_block = (uint32_t)v;
+      else bbpar.reduction = (uint32_t)v;
+    }
     else if (!strcmp(argv[1], "--meth-bigwig-section") || !strcmp(argv[1], "--meth-bigwig-zoom")) {
       char *end = NULL;
       const int sec = argv[1][14] == 's';
@@ -583,7 +630,7 @@ int main(int argc, char **argv) {
     argc -= 2;
   }
   if (argc < 5 || world < 1 || (rank >= 0 && rank >= world)) {
-    fprintf(stderr, "usage: %s [-O u|b] [--format bcf|vcf] [--index] [-D dbsnp.idx] [--meth out.bed [--meth-merge | --meth-all] [--meth-min-cov n] [--meth-min-gq n] [--meth-pass]] [--meth-regions regions.bed | --meth-window n --meth-regions-out out.tsv] [--meth-bigwig out.bw [--meth-bigwig-section n] [--meth-bigwig-zoom n] [--meth-bigwig-compress: zlib sections, n <= 8157]: the methylation level as a bigWig track, per cytosine even with --meth-merge, under the --meth-* thresholds and --meth-all] [--rank r --world n | --merge n] in.bam ref.fa out.bcf report.json [sample]\n", argv[0]);
+    fprintf(stderr, "usage: %s [-O u|b] [--format bcf|vcf] [--index] [-D dbsnp.idx] [--meth out.bed [--meth-merge | --meth-all] [--meth-min-cov n] [--meth-min-gq n] [--meth-pass]] [--meth-regions regions.bed | --meth-window n --meth-regions-out out.tsv] [--meth-bigwig out.bw [--meth-bigwig-section n] [--meth-bigwig-zoom n] [--meth-bigwig-compress: zlib sections, n <= 8157]: the methylation level as a bigWig track, per cytosine even with --meth-merge, under the --meth-* thresholds and --meth-all] [--meth-bigbed out.bb [--meth-bigbed-items n] [--meth-bigbed-zoom n] [--meth-bigbed-compress: zlib blocks, n <= 652]] [--rank r --world n | --merge n] in.bam ref.fa out.bcf report.json [sample]\n", argv[0]);
     return 2;
   }
   if (text && (rank >= 0 || merge > 0)) {
@@ -648,6 +695,23 @@ int main(int argc, char **argv) {
   }
   if (regions_out_path && (getenv("BAM2BCF_HOST_PREP") || getenv("BAM2BCF_HOST_BCF") || getenv("BAM2BCF_HOST_READER"))) {
     fprintf(stderr, "%s: --meth-regions sums what the device reader's blocks leave on the device: not with BAM2BCF_HOST_READER / _HOST_BCF / _HOST_PREP\n", argv[0]);
+    return 2;
+  }
+  if (bigbed_z && !bigbed_path) {
+    fprintf(stderr, "%s: --meth-bigbed-compress needs --meth-bigbed\n", argv[0]);
+    return 2;
+  }
+  if (bigbed_z && bbpar.items_per_block > BSC_BB_Z_ITEMS_MAX) {
+    fprintf(stderr, "%s: --meth-bigbed-compress: a block of %u sites may be more than 0xFF00 bytes (--meth-bigbed-items %u at the most)\n", argv[0],
+            bbpar.items_per_block, BSC_BB_Z_ITEMS_MAX);
+    return 2;
+  }
+  if (bigbed_path && (rank >= 0 || world > 1 || merge > 0)) {
+    fprintf(stderr, "%s: --meth-bigbed writes a single run's file; a sharded run (--rank / --world / --merge) has none\n", argv[0]);
+    return 2;
+  }
+  if (bigbed_path && (getenv("BAM2BCF_HOST_PREP") || getenv("BAM2BCF_HOST_BCF") || getenv("BAM2BCF_HOST_READER"))) {
+    fprintf(stderr, "%s: --meth-bigbed encodes what the device reader's blocks leave on the device: not with BAM2BCF_HOST_READER / _HOST_BCF / _HOST_PREP\n", argv[0]);
     return 2;
   }
   if (bigwig_z && !bigwig_path) {
@@ -790,6 +854,9 @@ int main(int argc, char **argv) {
   int bw_fd = -1;
   bsc_bigwig *bw = NULL;
   uint64_t bw_sites = 0;
+  int bb_fd = -1;
+  bsc_bigbed *bb = NULL;
+  uint64_t bb_sites = 0;
   if (!sharded) {
     const char **names = calloc((size_t)n_ref + 1, sizeof *names);
     uint32_t *lens = calloc((size_t)n_ref + 1, sizeof *lens);
@@ -806,6 +873,16 @@ int main(int argc, char **argv) {
       bw_fd = dup(fileno(bf));
       fclose(bf);
       CHECK(bsc_bigwig_open(bw_fd, (uint32_t)n_ref, names, lens, &bwpar, &bw));
+    }
+    if (bigbed_path) { /* the bigBed's file, as the track's */
+      FILE *bf = fopen(bigbed_path, "wb");
+      if (!bf) {
+        perror(bigbed_path);
+        return 1;
+      }
+      bb_fd = dup(fileno(bf));
+      fclose(bf);
+      CHECK(bsc_bigbed_open(bb_fd, (uint32_t)n_ref, names, lens, &bbpar, &bb));
     }
     if (bgzf) { /* the header into the compressor: its members come out with the first block's */
       char *hb = NULL;
@@ -1024,6 +1101,42 @@ int main(int argc, char **argv) {
           writer_push(&W, j);
         }
       }
+      if (n_bytes && bb) { /* the block's bigBed items and summaries, from the same arrays: a host buffer and a job of its own */
+        uint64_t b_bytes = 0, b_sites = 0, b_blk = 0, b_zoom = 0;
+        const bsc_bb_sum *blk = NULL, *zoom = NULL;
+        CHECK(bsc_block_bigbed_kept(ctx, (uint32_t)dblk.tid, &mpar, &bbpar, &b_bytes, &b_sites, &blk, &b_blk, &zoom, &b_zoom));
+        bb_sites += b_sites;
+        if (b_blk) {
+          out_job j;
+          memset(&j, 0, sizeof j);
+          j.fd = -1;
+          j.n = j.bb_raw = b_bytes;
+          j.bb = bb;
+          j.bw_tid = (uint32_t)dblk.tid;
+          j.bb_blk = xrealloc(NULL, (size_t)b_blk * sizeof *blk); /* copied before the next call: the host copies are good until then */
+          j.bb_zoom = xrealloc(NULL, (size_t)b_zoom * sizeof *zoom);
+          j.bb_n_blk = b_blk;
+          j.bb_n_zoom = b_zoom;
+          memcpy(j.bb_blk, blk, (size_t)b_blk * sizeof *blk);
+          memcpy(j.bb_zoom, zoom, (size_t)b_zoom * sizeof *zoom);
+          if (bigbed_z) { /* the blocks as zlib streams: the job carries those and their sizes */
+            const uint32_t *zs = NULL;
+            uint64_t z_bytes = 0, z_blk = 0;
+            CHECK(bsc_block_bigbed_deflate(ctx, &z_bytes, &zs, &z_blk));
+            if (z_blk != b_blk) {
+              fprintf(stderr, "bam2bcf: %llu zlib streams for %llu bigBed blocks\n", (unsigned long long)z_blk, (unsigned long long)b_blk);
+              return 1;
+            }
+            j.n = b_bytes = z_bytes;
+            j.bb_zsizes = xrealloc(NULL, (size_t)b_blk * sizeof *zs);
+            memcpy(j.bb_zsizes, zs, (size_t)b_blk * sizeof *zs);
+          }
+          j.bb_data = xrealloc(NULL, (size_t)b_bytes);
+          CHECK((bigbed_z ? bsc_bigbed_zstream_read : bsc_bigbed_stream_read)(ctx, 0, b_bytes, j.bb_data));
+          CHECK(bsc_synchronize(ctx));
+          writer_push(&W, j);
+        }
+      }
       if (n_bytes && meth_path) { /* the block's methylation table, from the arrays the call left on the device: a buffer and a job of its own */
         uint64_t m_cap = (uint64_t)n * (mpar.contexts == BSC_METH_ALL ? 16 : 4) + 4096, m_bytes = 0, m_lines = 0;
         int (*const meth_kept)(bsc_context *, const char *, const bsc_meth_params *, uint64_t, uint64_t *, uint64_t *, uint64_t *) =
@@ -1202,6 +1315,14 @@ int main(int argc, char **argv) {
       return 1;
     }
   }
+  if (bb) { /* every block's items are in: the item count, the indexes, the zoom levels, the summary and the header */
+    CHECK(bsc_bigbed_finish(bb));
+    bsc_bigbed_close(bb);
+    if (close(bb_fd)) {
+      perror(bigbed_path);
+      return 1;
+    }
+  }
   if (rout) { /* the last contig's lines */
     if (cur_tid >= 0) region_lines += regions_flush(ctx, rout, REF_NAME(cur_tid), r_regs, r_names, r_n);
     if (fclose(rout)) {
@@ -1300,6 +1421,7 @@ int main(int argc, char **argv) {
     if (meth_path) printf("%llu methylation table lines written\n", (unsigned long long)meth_lines);
     if (regions_out_path) printf("%llu methylation region lines written\n", (unsigned long long)region_lines);
     if (bigwig_path) printf("%llu methylation bigWig sites written\n", (unsigned long long)bw_sites);
+    if (bigbed_path) printf("%llu bedMethyl bigBed items written\n", (unsigned long long)bb_sites);
   }
   if (getenv("BAM2BCF_TIMING")) {
     uint64_t rc4[4] = {0, 0, 0, 0};
