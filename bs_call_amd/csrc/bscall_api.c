@@ -549,6 +549,18 @@ int bsc_create(const bsc_params *params, bsc_context **out) {
       if (v >= 64 && v < BSC_MAX_LAUNCH) ctx->max_launch = v;
     }
   }
+  {
+    /* BSC_NUM_CUS: every launcher caps its grid at a multiple of ctx->num_cus and lets the waves stride over the rest, and the workspaces
+     * sized from the grid (the chain's per-wave lists and scratch, the BGZF scratch) follow the same field.  The tests lower it so that
+     * the second and later rounds of those loops run at shapes a CPU reference can follow.  It never raises the count: a value outside
+     * [1, the device's CUs] (empty, 0, not a number, too large) leaves the device's own. */
+    const char *nc = getenv("BSC_NUM_CUS");
+    if (nc && *nc) {
+      char *end = NULL;
+      const long v = strtol(nc, &end, 10);
+      if (end != nc && *end == '\0' && v >= 1 && v <= (long)prop.multiProcessorCount) ctx->num_cus = (int)v;
+    }
+  }
   bsc_build_tables(ctx);
   int rc = BSC_OK;
   if (bsc_build_phred_table(&ctx->host_tables)) { /* cannot happen with a monotone log; never a silently wrong QUAL */

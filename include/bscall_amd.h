@@ -132,6 +132,8 @@ void bsc_params_default(bsc_params *p);
  * src/genotype_model.c:10-21; src/call_genotypes.c:124-138) and the lfact_store / gt_het tables of
  * init_param() (src/init_param.c:16,52-55).  Builds the tables on the host with libm exactly as the
  * reference does, uploads them verbatim, creates the context's HIP stream and workspaces.
+ * BSC_NUM_CUS in the environment, an integer in [1, the device's CU count], lowers the CU count that this context's grids and the
+ * workspaces sized from them follow (for tests of the grid-stride rounds; any other value is ignored, and it never raises the count).
  */
 int bsc_create(const bsc_params *params, bsc_context **out);
 
@@ -581,7 +583,7 @@ int bsc_set_reads_fused(bsc_context *ctx, int fused);
 /* Test hook (tests/test_gpu_reads_chain.py): on != 0 makes the summaries' allocation of the two-kernel form fail for real — an absurd
  * request the runtime refuses — so that the quiet fall-back to the one-kernel form can be exercised.  Off in every new context; nothing
  * in the environment switches it (the switches that are read from the environment — BSC_NO_H2D_TURNS, BSC_NO_EMIT_BYTES,
- * BSC_STAGE_TIMING, BSC_MAX_LAUNCH_SITES: A/B measurements — are read ONCE, by bsc_create). */
+ * BSC_STAGE_TIMING, BSC_MAX_LAUNCH_SITES, BSC_NUM_CUS: A/B measurements and tests — are read ONCE, by bsc_create). */
 int bsc_debug_fail_summary_alloc(bsc_context *ctx, int on);
 /* Window sizes for a caller that cuts a resident contig into windows of its own choosing (the reference's blocks are data
  * dependent, src/process_template.c:24-28; SURVEY.md 8d fixes 4 Mi).  bsc_chain_window_size: the largest window <= limit in
