@@ -126,6 +126,15 @@ EXPORTS = (
     "bsc_csi_add",
     "bsc_csi_finish",
     "bsc_csi_close",
+    "bsc_bed_scan_device",
+    "bsc_bed_entries_host",
+    "bsc_block_meth_index_kept",
+    "bsc_tbx_open",
+    "bsc_tbx_open_detached",
+    "bsc_tbx_members",
+    "bsc_tbx_add",
+    "bsc_tbx_finish",
+    "bsc_tbx_close",
     "bsc_debug_fail_summary_alloc",
     "bsc_last_kernel_ms",
     "bsc_kernel_ms_history",
@@ -617,6 +626,24 @@ def load():
     L.bsc_csi_finish.argtypes = [vp, vp, u64]
     L.bsc_csi_close.restype = None
     L.bsc_csi_close.argtypes = [vp]
+    L.bsc_bed_scan_device.restype = i32
+    L.bsc_bed_scan_device.argtypes = [vp, vp, u64, vp, u32, i32, vp, u64, vp, vp]
+    L.bsc_bed_entries_host.restype = i32
+    L.bsc_bed_entries_host.argtypes = [vp, u64, vp, u32, i32, vp, u64, vp]
+    L.bsc_block_meth_index_kept.restype = i32
+    L.bsc_block_meth_index_kept.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(u64), C.POINTER(u64)]
+    L.bsc_tbx_open.restype = i32
+    L.bsc_tbx_open.argtypes = [vp, i32, i32, i32, C.POINTER(C.c_char_p), C.POINTER(u32), C.POINTER(vp)]
+    L.bsc_tbx_open_detached.restype = i32
+    L.bsc_tbx_open_detached.argtypes = [i32, i32, i32, C.POINTER(C.c_char_p), C.POINTER(u32), u64, C.POINTER(vp)]
+    L.bsc_tbx_members.restype = i32
+    L.bsc_tbx_members.argtypes = [vp, vp, u64]
+    L.bsc_tbx_add.restype = i32
+    L.bsc_tbx_add.argtypes = [vp, i32, vp, u64, u64]
+    L.bsc_tbx_finish.restype = C.c_long
+    L.bsc_tbx_finish.argtypes = [vp, vp, u64]
+    L.bsc_tbx_close.restype = None
+    L.bsc_tbx_close.argtypes = [vp]
     L.bsc_block_bcf_again.restype = i32
     L.bsc_block_bcf_again.argtypes = [vp, vp, u64, C.POINTER(u64), C.POINTER(u64)]
     L.bsc_debug_fail_summary_alloc.restype = i32

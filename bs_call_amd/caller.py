@@ -148,6 +148,73 @@ class CsiIndex:
         self.close()
 
 
+TBX_TBI, TBX_CSI = 0, 1
+BED_ENTRY = np.dtype([("win_beg", "<u4"), ("win_last", "<u4"), ("n_lines", "<u4"), ("zero", "<u4"), ("u_beg", "<u8")])  # bsc_bed_entry
+
+
+def bed_entries_host(stream, sync=None, min_shift=14, cap_entries=None):
+    """bsc_bed_entries_host, the host form of the BED index scan: (entries BED_ENTRY[], entries there are, lines, error bits) of a table's
+    bytes; sync: the interval offsets (n_sync + 1 of them) or None for one interval."""
+    L = _lib.load()
+    data = np.frombuffer(bytes(stream), dtype=np.uint8)
+    sy = None if sync is None else np.ascontiguousarray(sync, dtype=np.uint64)
+    if cap_entries is None:
+        cap_entries = len(data) // 6 + (0 if sy is None else len(sy)) + 2
+    ent = np.zeros(max(1, cap_entries), dtype=BED_ENTRY)
+    tot = np.zeros(3, dtype=np.uint64)
+    _check(L.bsc_bed_entries_host(_ptr(data) if len(data) else None, len(data), None if sy is None else _ptr(sy), 0 if sy is None else max(len(sy) - 1, 0),
+                                  int(min_shift), _ptr(ent) if cap_entries else None, int(cap_entries), _ptr(tot)))
+    return ent[: min(int(tot[0]), cap_entries)].copy(), int(tot[0]), int(tot[1]), int(tot[2])
+
+
+class TabixIndex:
+    """A tabix (.tbi) or CSI (.csi) index made beside a compressed methylation table (bsc_tbx_*).  writer: the DeviceBgzf that writes the
+    table — or None with header_bytes: the table is compressed elsewhere with members cut every 0xFF00 bytes, and members() hands their
+    compressed sizes over.  add() the entries of a block BEFORE its table is written; finish() after the writer's close() returns the
+    index file's bytes.  kind: TBX_TBI (min_shift 14) or TBX_CSI."""
+
+    def __init__(self, writer, kind, contigs, min_shift=14, header_bytes=0):
+        self._L = _lib.load()
+        names = (C.c_char_p * max(1, len(contigs)))(*[c[0].encode() if isinstance(c[0], str) else bytes(c[0]) for c in contigs])
+        lens = (C.c_uint32 * max(1, len(contigs)))(*[int(c[1]) for c in contigs])
+        h = C.c_void_p()
+        if writer is None:
+            _check(self._L.bsc_tbx_open_detached(kind, min_shift, len(contigs), names, lens, int(header_bytes), C.byref(h)))
+        else:
+            _check(self._L.bsc_tbx_open(writer._h, kind, min_shift, len(contigs), names, lens, C.byref(h)))
+        self._h = h
+        self.kind, self.min_shift = kind, min_shift
+
+    def add(self, tid, entries, n_bytes):
+        e = np.ascontiguousarray(entries, dtype=BED_ENTRY)
+        _check(self._L.bsc_tbx_add(self._h, int(tid), _ptr(e) if len(e) else None, len(e), int(n_bytes)))
+
+    def members(self, sizes):
+        a = np.ascontiguousarray(sizes, dtype=np.uint64)
+        _check(self._L.bsc_tbx_members(self._h, _ptr(a) if len(a) else None, len(a)))
+
+    def finish(self):
+        need = self._L.bsc_tbx_finish(self._h, None, 0)
+        if need < 0:
+            _check(int(need))
+        out = np.empty(need, np.uint8)
+        got = self._L.bsc_tbx_finish(self._h, _ptr(out), need)
+        if got < 0:
+            _check(int(got))
+        return out[:got].tobytes()
+
+    def close(self):
+        if self._h is not None:
+            self._L.bsc_tbx_close(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
 class SiteCaller:
     def __init__(self, under_conv=0.01, over_conv=0.05, ref_bias=2.0, min_qual=20, device=-1):
         self._L = _lib.load()
@@ -207,6 +274,34 @@ class SiteCaller:
             return np.zeros(0, CSI_ENTRY), int(r.value)
         buf = (C.c_uint8 * (16 * n.value)).from_address(p.value)
         return np.frombuffer(buf, dtype=CSI_ENTRY).copy(), int(r.value)
+
+    def bed_scan_device(self, d_stream, n_bytes, d_sync, n_sync, min_shift, cap_entries=None, stream=None):
+        """bsc_bed_scan_device over a methylation table in HBM (pointers as integers; d_sync 0 / None: one interval): (entries BED_ENTRY[],
+        entries there are, lines, error bits).  cap_entries None: room for every interval and line."""
+        import torch
+
+        if cap_entries is None:
+            cap_entries = int(n_sync if d_sync else 1) + int(n_bytes) // 6 + 2
+        ent = torch.zeros(max(1, cap_entries) * 3, dtype=torch.int64, device="cuda")
+        tot = torch.zeros(3, dtype=torch.int64, device="cuda")
+        st = C.c_void_p(torch.cuda.current_stream().cuda_stream) if stream is None else stream
+        _check(self._L.bsc_bed_scan_device(self._h, C.c_void_p(int(d_stream) if d_stream else None), int(n_bytes),
+                                           C.c_void_p(int(d_sync)) if d_sync else None, int(n_sync), int(min_shift), C.c_void_p(ent.data_ptr()),
+                                           int(cap_entries), C.c_void_p(tot.data_ptr()), st))
+        torch.cuda.synchronize()
+        t = [int(v) for v in tot.cpu().numpy().view(np.uint64)]
+        n = min(t[0], cap_entries)
+        return ent.cpu().numpy().view(BED_ENTRY)[:n].copy(), t[0], t[1], t[2]
+
+    def block_meth_index_kept(self, min_shift=14):
+        """bsc_block_meth_index_kept: (entries BED_ENTRY[], lines) of the table the last bsc_block_meth_kept / _cpg_kept call left on the
+        device — block_meth_kept(...) reads the table back without detaching it, so this may follow it."""
+        p, n, r = C.c_void_p(), C.c_uint64(), C.c_uint64()
+        _check(self._L.bsc_block_meth_index_kept(self._h, int(min_shift), C.byref(p), C.byref(n), C.byref(r)))
+        if not n.value:
+            return np.zeros(0, BED_ENTRY), int(r.value)
+        buf = (C.c_uint8 * (24 * n.value)).from_address(p.value)
+        return np.frombuffer(buf, dtype=BED_ENTRY).copy(), int(r.value)
 
     def bgzf_compress(self, data, pieces=None):
         """BGZF bytes of `data` (bytes-like), written whole or in the given piece lengths, with the end-of-file marker."""

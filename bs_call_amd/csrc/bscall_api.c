@@ -22,6 +22,7 @@
 #include "bsmath_tables.h"
 #include "synth.h"
 #include "dbsnpdev_core.h"
+#include "tabix_int.h"
 
 /* launchers implemented in kernels.hip */
 int bsc_dev_launch_call(const void *cts, const void *ref, uint64_t n, void *out, uint32_t out_dw, void *skip,
@@ -112,6 +113,8 @@ int bsc_dev_launch_bgzf(const void *src, uint64_t n, uint32_t n_members, void *s
                         void *stream); /* bgzfdev.hip */
 int bsc_dev_launch_csi_scan(int format, const void *s, uint64_t n_bytes, const void *sync, uint32_t n_sync, int min_shift, void *cnt, void *off,
                             void *scan_tmp, size_t scan_tmp_bytes, void *entries, uint64_t cap, void *totals, int num_cus, void *stream); /* csidev.hip */
+int bsc_dev_launch_bed_scan(const void *s, uint64_t n_bytes, const void *sync, uint32_t n_sync, int min_shift, void *cnt, void *off, void *scan_tmp,
+                            size_t scan_tmp_bytes, void *entries, uint64_t cap, void *totals, int num_cus, void *stream); /* beddev.hip */
 int bsc_dev_launch_bgzf_gather(const void *slots, const void *offs, const void *sizes, uint32_t n_members, void *out, void *stream);
 int bsc_dev_launch_dbsnp_flags(const bsc_dbsnp_flat *f, uint32_t x0, uint32_t n, void *d_out, int num_cus, void *stream); /* dbsnpdev.hip */
 int bsc_dev_launch_dbsnp_names(const bsc_dbsnp_flat *f, uint32_t e0, uint32_t n_names, void *d_pos, void *d_off, void *d_bytes, int num_cus,
@@ -261,6 +264,15 @@ struct bsc_context {
   const void *bto_for;
   uint32_t bto_tiles;
   int bto_text;
+  /* the BED index scan (beddev.hip) of the follow-up call bsc_block_meth_index_kept: the entries and {entries, lines, error bits}, the host
+   * copy; and what the last table call left in d_mto: for which table (d_meth), how many tiles, the lines it reported */
+  void *d_bden, *d_bdtot;
+  size_t cap_bden, cap_bdtot;
+  bsc_bed_entry *h_bden;
+  size_t cap_hbden;
+  const void *mto_for;
+  uint32_t mto_tiles;
+  uint64_t mto_lines;
   struct { /* streams handed to the caller (bsc_bcf_stream_detach) come back here (bsc_detached_free) and are taken again by the next block:
             * no hipMalloc / hipFree — a device-wide wait — in the steady state of a run that writes behind the calling */
     void *p[4];
@@ -721,6 +733,9 @@ int bsc_destroy(bsc_context *ctx) {
   hipFree(ctx->d_csen);
   hipFree(ctx->d_cstot);
   free(ctx->h_csen);
+  hipFree(ctx->d_bden);
+  hipFree(ctx->d_bdtot);
+  free(ctx->h_bden);
   hipFree(ctx->d_emit);
   for (int i = 0; i < 2; i++)
     if (ctx->ev_raw[i]) hipEventDestroy(ctx->ev_raw[i]);
@@ -3039,6 +3054,7 @@ static int bsc_meth_encode(bsc_context *ctx, const char *who, const void *d_recs
   hipStream_t s = (hipStream_t)stream;
   const uint32_t n_tiles = (uint32_t)((max_recs + 63u) / 64u);
   size_t scan_bytes = 0;
+  ctx->mto_for = NULL; /* d_mto is about to change: the tile offsets of no kept table, until bsc_meth_kept says otherwise */
   if (bsc_dev_scan_tmp_bytes_u64(n_tiles + 1u, &scan_bytes)) return bsc_fail(BSC_ERR_HIP, "%s: scan size query failed", who);
   if ((rc = bsc_reserve(&ctx->d_mtb, &ctx->cap_mtb, ((size_t)n_tiles + 1u) * 8u))) return rc;
   if ((rc = bsc_reserve(&ctx->d_mto, &ctx->cap_mto, ((size_t)n_tiles + 1u) * 8u))) return rc;
@@ -3104,6 +3120,9 @@ static int bsc_meth_kept(bsc_context *ctx, const char *who, int cpg, const char 
   for (int k = 0; sums && k < n_sums; k++) sums[k] = tot[2 + k];
   if (tot[0] > dev_cap) return bsc_fail(BSC_ERR_ARG, "%s: the block's table has %llu bytes, dev_cap is %llu", who, tot[0], (unsigned long long)dev_cap);
   ctx->meth_bytes = tot[0];
+  ctx->mto_for = ctx->d_meth; /* d_mto: this table's tile offsets, until the next table call (bsc_block_meth_index_kept) */
+  ctx->mto_tiles = (uint32_t)(((uint64_t)ctx->again.sz + 63u) / 64u);
+  ctx->mto_lines = tot[1];
   return BSC_OK;
 }
 
@@ -4374,6 +4393,7 @@ struct bsc_bgzf {
   uint64_t *msize;    /* the compressed size of every member completed so far, in stream order (bsc_csi_*) */
   uint64_t n_msize, cap_msize;
   struct bsc_csi *csi; /* the index that is being made beside this file: it inherits msize at bsc_bgzf_close */
+  bsc_tbx *tbx;        /* the same for a table's index (tabix.c): it takes a copy of msize at bsc_bgzf_close */
   struct bsc_bgzf *next_open;
 };
 static const uint8_t bsc_bgzf_eof[28] = {0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 0x42, 0x43, 2, 0, 0x1b, 0, 3, 0, 0, 0, 0, 0, 0, 0, 0, 0};
@@ -4620,6 +4640,8 @@ int bsc_bgzf_close(bsc_bgzf *z, void **d_out, uint64_t *n_bytes) {
     else z->n_pend += sizeof bsc_bgzf_eof;
   }
   if (!rc) rc = bsc_bgzf_hand_over(z, d_out, n_bytes);
+  if (z->tbx) bsc_tbx_writer_closed_(z->tbx, rc, z->msize, z->n_msize, z->n_logical);
+  z->tbx = NULL;
   bsc_csi_writer_closed(z, rc);
   pthread_mutex_lock(&bsc_bgzf_mu);
   for (struct bsc_bgzf **q = &bsc_bgzf_open_list; *q; q = &(*q)->next_open)
@@ -4713,6 +4735,87 @@ int bsc_block_csi_kept(bsc_context *ctx, int min_shift, const bsc_csi_entry **en
   *entries = ctx->h_csen;
   *n_entries = tot[0];
   if (n_records) *n_records = tot[1];
+  return BSC_OK;
+}
+
+/* ---- the index of a compressed methylation table (beddev.hip makes a block's entries; tabix.c is the writer) ---------------------------------- */
+int bsc_bed_scan_device(bsc_context *ctx, const void *d_stream, uint64_t n_bytes, const void *d_sync, uint32_t n_sync, int min_shift, void *d_entries,
+                        uint64_t cap_entries, void *d_totals, void *stream) {
+  if (!ctx || !d_totals || (!d_stream && n_bytes) || (!d_entries && cap_entries)) return bsc_fail(BSC_ERR_ARG, "bsc_bed_scan_device: NULL argument");
+  if (min_shift < 0 || min_shift > 31) return bsc_fail(BSC_ERR_ARG, "bsc_bed_scan_device: min_shift %d is not 0 .. 31", min_shift);
+  if (!d_sync) n_sync = 1;
+  if (n_sync >= 0x7fffffffu) return bsc_fail(BSC_ERR_ARG, "bsc_bed_scan_device: too many intervals");
+  if (!n_sync && n_bytes) return bsc_fail(BSC_ERR_ARG, "bsc_bed_scan_device: no interval for %llu bytes", (unsigned long long)n_bytes);
+  BSC_ENTER(ctx);
+  hipStream_t s = (hipStream_t)stream;
+  HIP_TRY(hipMemsetAsync(d_totals, 0, 3 * sizeof(unsigned long long), s));
+  if (!n_sync) return BSC_OK;
+  size_t scan_bytes = 0;
+  int rc;
+  if (bsc_dev_scan_tmp_bytes_u64(n_sync + 1u, &scan_bytes)) return bsc_fail(BSC_ERR_HIP, "bsc_bed_scan_device: scan size query failed");
+  if ((rc = bsc_reserve(&ctx->d_cscn, &ctx->cap_cscn, ((size_t)n_sync + 1u) * 8u))) return rc; /* (the CSI scan's workspaces: one scan in flight) */
+  if ((rc = bsc_reserve(&ctx->d_csof, &ctx->cap_csof, ((size_t)n_sync + 1u) * 8u))) return rc;
+  if ((rc = bsc_reserve(&ctx->d_cstm, &ctx->cap_cstm, scan_bytes ? scan_bytes : 1))) return rc;
+  const int e = bsc_dev_launch_bed_scan(d_stream, n_bytes, d_sync, n_sync, min_shift, ctx->d_cscn, ctx->d_csof, ctx->d_cstm, scan_bytes, d_entries, cap_entries,
+                                        d_totals, ctx->num_cus, stream);
+  if (e) return bsc_fail(BSC_ERR_HIP, "BED index scan launch failed: %s", hipGetErrorString((hipError_t)e));
+  return BSC_OK;
+}
+
+int bsc_block_meth_index_kept(bsc_context *ctx, int min_shift, const bsc_bed_entry **entries, uint64_t *n_entries, uint64_t *n_lines) {
+  if (!ctx || !entries || !n_entries) return bsc_fail(BSC_ERR_ARG, "bsc_block_meth_index_kept: NULL argument");
+  *entries = NULL;
+  *n_entries = 0;
+  if (n_lines) *n_lines = 0;
+  if (!ctx->d_meth || !ctx->mto_for || ctx->mto_for != ctx->d_meth)
+    return bsc_fail(BSC_ERR_ARG, "bsc_block_meth_index_kept: the last call left no table on the device (none made, or detached)");
+  if (min_shift < 0 || min_shift > 31) return bsc_fail(BSC_ERR_ARG, "bsc_block_meth_index_kept: min_shift %d is not 0 .. 31", min_shift);
+  if (n_lines) *n_lines = ctx->mto_lines;
+  if (!ctx->meth_bytes) return BSC_OK;
+  BSC_ENTER(ctx);
+  /* every tile that holds a line gives one entry, and at most two more wherever a window border lies inside one (the lines before it, a
+   * line across it, the lines behind it): a tile spans 64 positions */
+  const uint32_t n_sync = ctx->mto_tiles;
+  const uint64_t cap = (uint64_t)n_sync + 2u * (((uint64_t)n_sync * 64u) >> min_shift) + 4u;
+  int rc;
+  if ((rc = bsc_reserve(&ctx->d_bden, &ctx->cap_bden, (size_t)cap * sizeof(bsc_bed_entry)))) return rc;
+  if ((rc = bsc_reserve(&ctx->d_bdtot, &ctx->cap_bdtot, 3 * sizeof(unsigned long long)))) return rc;
+  if ((rc = bsc_bed_scan_device(ctx, ctx->d_meth, ctx->meth_bytes, ctx->d_mto, n_sync, min_shift, ctx->d_bden, cap, ctx->d_bdtot, ctx->stream))) return rc;
+  unsigned long long tot[3] = {0, 0, 0};
+  HIP_TRY(hipMemcpyAsync(tot, ctx->d_bdtot, sizeof tot, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  if (tot[2]) return bsc_fail(BSC_ERR_ARG, "bsc_block_meth_index_kept: the table is not whole lines in position order (error bits %llu)", tot[2]);
+  if (tot[1] != ctx->mto_lines)
+    return bsc_fail(BSC_ERR_ARG, "bsc_block_meth_index_kept: %llu lines walked, the table call reported %llu", tot[1], (unsigned long long)ctx->mto_lines);
+  if (tot[0] > cap) return bsc_fail(BSC_ERR_RANGE, "bsc_block_meth_index_kept: %llu entries, room for %llu", tot[0], (unsigned long long)cap);
+  if (tot[0] > ctx->cap_hbden) {
+    free(ctx->h_bden);
+    ctx->cap_hbden = 0;
+    ctx->h_bden = malloc((size_t)(tot[0] + tot[0] / 4) * sizeof(bsc_bed_entry));
+    if (!ctx->h_bden) return bsc_fail(BSC_ERR_NOMEM, "bsc_block_meth_index_kept: out of host memory");
+    ctx->cap_hbden = (size_t)(tot[0] + tot[0] / 4);
+  }
+  if (tot[0]) {
+    HIP_TRY(hipMemcpyAsync(ctx->h_bden, ctx->d_bden, (size_t)tot[0] * sizeof(bsc_bed_entry), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+  }
+  *entries = ctx->h_bden;
+  *n_entries = tot[0];
+  return BSC_OK;
+}
+
+static uint64_t bsc_tbx_writer_logical(void *w) { return ((bsc_bgzf *)w)->n_logical; }
+static void bsc_tbx_writer_unbind(void *w) {
+  if (bsc_bgzf_is_open((bsc_bgzf *)w)) ((bsc_bgzf *)w)->tbx = NULL;
+}
+int bsc_tbx_open(bsc_bgzf *z, int kind, int min_shift, int n_refs, const char *const *names, const uint32_t *lens, bsc_tbx **out) {
+  if (out) *out = NULL;
+  if (!bsc_bgzf_is_open(z)) return bsc_fail(BSC_ERR_ARG, "bsc_tbx_open: not an open BGZF writer (NULL, or closed)");
+  if (z->tbx) return bsc_fail(BSC_ERR_ARG, "bsc_tbx_open: the writer has an index already");
+  const int rc = bsc_tbx_make_("bsc_tbx_open", kind, min_shift, n_refs, names, lens, out);
+  if (rc) return rc;
+  bsc_tbx_bind_(*out, z, bsc_tbx_writer_logical, bsc_tbx_writer_unbind);
+  z->tbx = *out;
   return BSC_OK;
 }
 

@@ -196,3 +196,143 @@ def read_bed(path):
     if data[:2] == b"\x1f\x8b":
         data = gzip.decompress(data)
     return parse_bed(data)
+
+
+# ---- region queries through the table's index: what bam2bcf --meth-index / bsc_tbx_* / pipeline.run(meth_index=...) write beside a BGZF table --
+def _inflate_all(blob):
+    import zlib
+
+    out, at = [], 0
+    while at < len(blob):
+        bsize = int.from_bytes(blob[at + 16 : at + 18], "little") + 1
+        out.append(zlib.decompress(blob[at + 18 : at + bsize - 8], -15))
+        at += bsize
+    return b"".join(out)
+
+
+def read_index(path):
+    """A .tbi or .csi file of a table parsed: {"kind": "tbi" | "csi", "min_shift", "depth", "names", "refs": [{"bins": {bin: [(vbeg, vend)]},
+    "loff": {bin: loffset} (csi), "ioff": [..] (tbi), "n_lines"}]} — the pseudo-bin is taken out of "bins" and gives "n_lines"."""
+    import struct
+
+    with open(path, "rb") as f:
+        b = _inflate_all(f.read())
+    kind = {b"TBI\x01": "tbi", b"CSI\x01": "csi"}.get(b[:4])
+    if kind is None:
+        raise ValueError("%s: neither a tabix nor a CSI index" % path)
+    if kind == "tbi":
+        n_ref, fmt, cs, cb, ce, meta, skip, l_nm = struct.unpack_from("<8i", b, 4)
+        min_shift, depth, at = 14, 5, 36
+    else:
+        min_shift, depth, l_aux = struct.unpack_from("<3i", b, 4)
+        if l_aux < 28:
+            raise ValueError("%s: a CSI index without the tabix block is not a table's" % path)
+        fmt, cs, cb, ce, meta, skip, l_nm = struct.unpack_from("<7i", b, 16)
+        (n_ref,) = struct.unpack_from("<i", b, 16 + l_aux)
+        at = 44
+    if (fmt, cs, cb, ce) != (0x10000, 1, 2, 3):
+        raise ValueError("%s: not the index of a BED table (format %#x, columns %d %d %d)" % (path, fmt, cs, cb, ce))
+    names = [n.decode() for n in b[at : at + l_nm].split(b"\0")[:-1]]
+    at += l_nm + (4 if kind == "csi" else 0)
+    pseudo = ((1 << (3 * (depth + 1))) - 1) // 7 + 1
+    refs = []
+    for _ in range(n_ref):
+        (n_bin,) = struct.unpack_from("<i", b, at)
+        at += 4
+        r = {"bins": {}, "loff": {}, "ioff": [], "n_lines": 0}
+        for _ in range(n_bin):
+            (k,) = struct.unpack_from("<I", b, at)
+            at += 4
+            if kind == "csi":
+                (r["loff"][k],) = struct.unpack_from("<Q", b, at)
+                at += 8
+            (n_chunk,) = struct.unpack_from("<i", b, at)
+            at += 4
+            ch = [struct.unpack_from("<QQ", b, at + 16 * i) for i in range(n_chunk)]
+            at += 16 * n_chunk
+            if k == pseudo:
+                r["n_lines"] = ch[1][0]
+                r["loff"].pop(k, None)
+            else:
+                r["bins"][k] = ch
+        if kind == "tbi":
+            (n_intv,) = struct.unpack_from("<i", b, at)
+            r["ioff"] = list(struct.unpack_from("<%dQ" % n_intv, b, at + 4))
+            at += 4 + 8 * n_intv
+        refs.append(r)
+    if at + 8 != len(b):
+        raise ValueError("%s: %d bytes behind the last contig, not n_no_coor alone" % (path, len(b) - at))
+    return {"kind": kind, "min_shift": min_shift, "depth": depth, "names": names, "refs": refs}
+
+
+def reg2bins(beg, end, min_shift=14, depth=5):
+    """The bins of every level that overlap [beg, end) (0-based, half open), ascending."""
+    if end <= beg:
+        return []
+    out, first = [], 0
+    for level in range(depth + 1):
+        s = min_shift + 3 * (depth - level)
+        out += range(first + (beg >> s), first + ((end - 1) >> s) + 1)
+        first += 1 << (3 * level)
+    return out
+
+
+def index_chunks(index, tid, beg, end):
+    """The chunks [(vbeg, vend)] a query of [beg, end) on contig number tid has to read, sorted, overlapping and touching ones joined; what
+    ends at or before the linear index's offset of beg's window (tbi) cannot hold a line of the range and is left out."""
+    r = index["refs"][tid]
+    lo = 0
+    if index["kind"] == "tbi":
+        w = beg >> index["min_shift"]
+        if w >= len(r["ioff"]):
+            return []
+        lo = r["ioff"][w]
+    ch = sorted(c for k in reg2bins(beg, end, index["min_shift"], index["depth"]) for c in r["bins"].get(k, ()) if c[1] > lo)
+    out = []
+    for a, b in ch:
+        if out and a <= out[-1][1]:
+            out[-1][1] = max(out[-1][1], b)
+        else:
+            out.append([a, b])
+    return [tuple(c) for c in out]
+
+
+def _read_chunk(f, vbeg, vend):
+    import zlib
+
+    out, at = [], vbeg >> 16
+    while at < (vend >> 16) or (at == (vend >> 16) and (vend & 0xFFFF)):
+        f.seek(at)
+        head = f.read(18)
+        bsize = int.from_bytes(head[16:18], "little") + 1
+        data = zlib.decompress(f.read(bsize - 18)[:-8], -15)
+        a = (vbeg & 0xFFFF) if at == (vbeg >> 16) else 0
+        out.append(data[a : (vend & 0xFFFF)] if at == (vend >> 16) else data[a:])
+        at += bsize
+    return b"".join(out)
+
+
+def fetch(table_path, contig, beg, end, index_path=None):
+    """The lines (bytes, each with its newline) of `contig` (name or number) that overlap [beg, end) (0-based, half open), in file order, read
+    from the BGZF table through its index (default: table_path + ".tbi", else + ".csi"): only the chunks the index names are inflated."""
+    import os
+
+    if index_path is None:
+        index_path = table_path + ".tbi" if os.path.exists(table_path + ".tbi") else table_path + ".csi"
+    ix = index_path if isinstance(index_path, dict) else read_index(index_path)
+    if isinstance(contig, str):
+        if contig not in ix["names"]:
+            return []
+        tid = ix["names"].index(contig)
+    else:
+        tid = int(contig)
+    if not 0 <= tid < len(ix["refs"]) or end <= beg:
+        return []
+    name, out = ix["names"][tid].encode(), []
+    with open(table_path, "rb") as f:
+        for vbeg, vend in index_chunks(ix, tid, int(beg), int(end)):
+            for ln in _read_chunk(f, vbeg, vend).split(b"\n")[:-1]:
+                c = ln.split(b"\t", 3)
+                if c[0] == name and int(c[1]) < end and int(c[2]) > beg:
+                    out.append(ln + b"\n")
+    return out

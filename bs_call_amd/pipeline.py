@@ -20,7 +20,7 @@ def run(bam_path: str, reference: Dict[str, np.ndarray], bcf_path: str, sample: 
         reduce_device=None, text: bool = False, dbsnp_device: bool = False, meth_path: Optional[str] = None, meth_params=None, meth_merge: bool = False,
         meth_regions=None, meth_regions_path: Optional[str] = None, meth_window: Optional[int] = None, bigwig_path: Optional[str] = None,
         bigwig_section: int = 1024, bigwig_zoom: int = 1024, bigwig_compress: bool = False, bigbed_path: Optional[str] = None, bigbed_items: int = 512,
-        bigbed_zoom: int = 1024, bigbed_compress: bool = False, **reader_kw) -> dict:
+        bigbed_zoom: int = 1024, bigbed_compress: bool = False, meth_index: Optional[str] = None, **reader_kw) -> dict:
     """reference: contig name -> uint8 reference codes (0 = N, 1..4 = ACGT; position 1 first).  Returns a summary dict.
     under_conv / over_conv / min_qual (defaults 0.01 / 0.05 / 20, src/init_param.c:26-31) are the MODEL's parameters: without
     `caller` the run builds its SiteCaller from them; with one, they are taken from it and a differing explicit value is an error
@@ -46,6 +46,10 @@ def run(bam_path: str, reference: Dict[str, np.ndarray], bcf_path: str, sample: 
     device_reader and is refused where text=True is; the main file and the report are those of the run without it.  meth_merge: the table
     is the combined-strand one, a line per CpG dinucleotide with both strands' counts added (bsc_block_meth_cpg_kept); needs meth_path and
     CpG-only meth_params.
+    meth_index: "tbi" or "csi" — the index of the compressed table, written to meth_path + ".tbi" / ".csi" (include/bscall_amd.h has the
+    rule): every block's table is scanned on the device where it lies (SiteCaller.block_meth_index_kept, csrc/beddev.hip), the entries
+    go to a detached TabixIndex, and the sizes of the members this process compressed on the host close it.  Needs meth_path and
+    compressed=True.
     meth_regions / meth_window with meth_regions_path: the per-region methylation summary of the same run (include/bscall_amd.h has the rule
     and the ten columns), summed on the device: a contig's regions are attached at the contig change, every block adds its cytosines
     (SiteCaller.block_meth_regions_kept, csrc/methregionsdev.hip), the sums are read at the next contig change and at the end.
@@ -113,6 +117,10 @@ def run(bam_path: str, reference: Dict[str, np.ndarray], bcf_path: str, sample: 
         raise ValueError("meth_merge=True combines the strands of the table meth_path names: it needs meth_path")
     if meth_merge and meth_params is not None and (meth_params.contexts if hasattr(meth_params, "contexts") else meth_params.get("contexts", 0)) != 0:
         raise ValueError("meth_merge=True is the CpG table: only a CpG has a partner strand (meth_params.contexts must be BSC_METH_CPG)")
+    if meth_index is not None and meth_index not in ("tbi", "csi"):
+        raise ValueError("meth_index is 'tbi' or 'csi', not %r" % (meth_index,))
+    if meth_index is not None and (meth_path is None or not compressed):
+        raise ValueError("meth_index indexes the compressed table meth_path names: it needs meth_path and compressed=True")
     if meth_path is not None and (shard_rank is not None or not device_reader or host_prep or host_bcf):
         raise ValueError("meth_path is a single run on the device reader (device_reader=True, no shard_rank, no host_prep / host_bcf)")
     if dbsnp_device and not device_reader:
@@ -143,6 +151,7 @@ def run(bam_path: str, reference: Dict[str, np.ndarray], bcf_path: str, sample: 
         per_contig = []
         n_blocks = n_records = 0
         meth_blobs, meth_lines = [], 0
+        meth_entries = []  # meth_index: (contig number, BED_ENTRY[], bytes of the block's table)
         bw_sites = 0
         region_out, region_cur = [], None  # the summary's lines, contig by contig; (name, regions, names) of the contig attached
         c.reset_site_stats()
@@ -267,6 +276,8 @@ def run(bam_path: str, reference: Dict[str, np.ndarray], bcf_path: str, sample: 
                             mb, ml, _ = c.block_meth_kept(name, meth_params, merge=meth_merge)
                             meth_blobs.append(mb)
                             meth_lines += ml
+                            if meth_index is not None and mb:  # while the table is still the context's: the scan by the encoder's tile offsets
+                                meth_entries.append((tid, c.block_meth_index_kept(14)[0], len(mb)))
                         recs = None
                     elif host_prep:  # round 4's split: the process thread's per-template work here, then the block
                         tpl, pseq, st = prepare_templates(raw, seq, ms, left_trim, right_trim, min_qual, profile=prof, x=x, ref=ref)
@@ -305,6 +316,21 @@ def run(bam_path: str, reference: Dict[str, np.ndarray], bcf_path: str, sample: 
                 vcf.write_bcf(bcf_path, header, block_blobs(), compressed)  # blocks go to the writer as they are formed
             if meth_path is not None:
                 vcf.write_vcf_blobs(meth_path, "", meth_blobs, compressed)
+                if meth_index is not None:
+                    from .caller import TBX_CSI, TBX_TBI, TabixIndex
+
+                    with open(meth_path, "rb") as f:
+                        zb = f.read()
+                    sizes, at = [], 0
+                    while at < len(zb):  # the members' sizes, from their own BSIZE fields; the last one is the end-of-file marker
+                        sizes.append(int.from_bytes(zb[at + 16 : at + 18], "little") + 1)
+                        at += sizes[-1]
+                    with TabixIndex(None, TBX_TBI if meth_index == "tbi" else TBX_CSI, refs, 14, 0) as ix:
+                        for tid_, ent, nb in meth_entries:
+                            ix.add(tid_, ent, nb)
+                        ix.members(sizes[:-1])
+                        with open(meth_path + "." + meth_index, "wb") as f:
+                            f.write(ix.finish())
             if want_bw:
                 bw_writer.finish()
             if want_bb:

@@ -1017,6 +1017,72 @@ int bsc_csi_members(bsc_csi *ix, const uint64_t *sizes, uint64_t n_members);
 int bsc_csi_add(bsc_csi *ix, int32_t tid, const bsc_csi_entry *entries, uint64_t n, uint64_t n_bytes);
 long bsc_csi_finish(bsc_csi *ix, void *buf, uint64_t cap);
 void bsc_csi_close(bsc_csi *ix);
+
+/*
+ * A tabix (.tbi) or CSI (.csi) index of a BGZF-compressed methylation table (bam2bcf --meth, --meth-merge), made WHILE the table is written:
+ * the line-level work runs on the device (csrc/beddev.hip, csrc/bedidx_core.h), the host never walks the table.  No reading tool was at
+ * hand when this was written (no tabix, no pysam): the bytes are pinned by the rule below, from which the kernel, the host form
+ * (bsc_bed_entries_host), the writer (csrc/tabix.c) and an independent Python builder (tests/tabix_ref.py) are each written.
+ *
+ * Line     the bytes up to and including '\n': chrom '\t' start '\t' end '\t' ...; start and end plain decimal of 1 .. 10 digits, 0-based
+ *          half open, 0 <= start < end <= 2^32.  A stream is one contig's lines with start non-descending.  With s = min_shift (0 .. 31):
+ *          wb = start >> s, wl = (end - 1) >> s.  A BED line is an interval: a combined-strand CpG line covers two bases, and one whose
+ *          start is 2^s - 1 (mod 2^s) lies in two windows.
+ * Entry    (what the device makes) a run: a maximal sequence of consecutive lines inside one interval of the stream that share (wb, wl).
+ *          bsc_bed_entry {win_beg, win_last, n_lines, zero, u_beg}: 24 bytes, u_beg the offset of the run's first line in the block's stream.
+ *          Entries come out in stream order whatever the launch geometry; a run that continues across an interval border comes out as
+ *          adjacent entries with equal (win_beg, win_last); an empty interval gives none.
+ * bsc_bed_scan_device   the twin of bsc_csi_scan_device, with its d_sync contract (NULL: one interval, walked by one lane).  d_totals: three
+ *          device u64 {entries there are — also beyond cap_entries: nothing is written beyond it —, lines walked, error bits: a line that
+ *          leaves its interval (1), a start below the one before it inside an interval (2), a line without two tab-separated decimal
+ *          columns after the first, or end <= start, or end > 2^32, or more than 10 digits (4), interval offsets that descend or lie beyond
+ *          the stream (8); the walk of that interval stops at the first error}.  Asynchronous on `stream`; uses workspaces of the context.
+ * bsc_bed_entries_host  the same on the host, from the same statements (csrc/bedidx_core.h): the kernel's checker.  totals: three u64.
+ * bsc_block_meth_index_kept   the follow-up of bsc_block_meth_kept / bsc_block_meth_cpg_kept, BEFORE bsc_meth_stream_detach: scans the
+ *          context's table by the encoder's own tile offsets on the context's stream, waits, and returns the entries in memory of the
+ *          context (valid until the next call of this function on it); *n_lines = what the table call returned.  No table on the context
+ *          (none made, or detached), or error bits: BSC_ERR_ARG.  Nothing else the context keeps changes.
+ * Bin      with depth D: k the smallest k >= 0 with wb >> 3k == wl >> 3k; bin = ((1 << 3 (D - k)) - 1) / 7 + (wb >> 3k).  k > D, or
+ *          wl >= 1 << 3 D: refused.
+ * Chunks   an entry's extent is [base + u_beg, base + u_next): base the logical length of the file before the block, u_next the next
+ *          entry's u_beg or the block's n_bytes.  Per bin, in file order: an extent that begins exactly where the bin's last chunk ends
+ *          extends it, anything else opens a new chunk — parent bins may hold several, and so may a leaf bin that a straddling line
+ *          interrupts.  A chunk is (voff(begin), voff(end)), voff the arithmetic of bsc_csi_* on members cut every 0xFF00 logical bytes.
+ * Linear   n_intv = 1 + the largest wl of the contig's lines (0 for a contig without lines); ioff[w] = voff of the first line with
+ *          wb <= w <= wl; a window no line overlaps takes the value of the next window that has one.
+ * Pseudo-bin   ((1 << 3 (D + 1)) - 1) / 7 + 1 (37450 at D = 5): chunks (voff of the contig's first line, voff behind its last), (lines, 0).
+ * .tbi     "TBI\1", n_ref, format 0x10000, col_seq 1, col_beg 2, col_end 3, meta '#', skip 0, l_nm, the NUL-terminated names of ALL header
+ *          contigs in order; per contig n_bin, the bins ascending {bin u32, n_chunk i32, chunks}, the pseudo-bin last where the contig has
+ *          lines, then n_intv and ioff[]; then n_no_coor (u64) 0.  min_shift is 14 and D is 5; a contig longer than 2^29 is refused at
+ *          open with a message that names csi.
+ * .csi     "CSI\1", min_shift, depth (the rule of bsc_csi_open), l_aux = 28 + l_nm, aux = the same seven ints and the names, n_ref; per
+ *          contig n_bin, the bins {bin, loffset u64, n_chunk, chunks}: loffset = ioff[first window of the bin] under the linear rule at
+ *          min_shift, 0 for the pseudo-bin; then n_no_coor 0.
+ * Both files are BGZF as the .csi of a BCF is: one stored member per 0xFF00 bytes and the end-of-file marker.
+ *   bsc_tbx_open / _open_detached / _members / _finish / _close   as their bsc_csi_* namesakes; kind: BSC_TBX_TBI (min_shift must be 14) or
+ *          BSC_TBX_CSI (1 .. 31); z: the TABLE's writer.
+ *   bsc_tbx_add   the entries of the block of contig tid whose n_bytes-long table is written NEXT.  A descending tid; within a contig a
+ *          win_beg below the last one; a u_beg that does not ascend from 0 or reaches n_bytes; an entry without lines; win_last < win_beg;
+ *          a bin out of range: BSC_ERR_ARG, and the index stays as it was.
+ */
+#define BSC_TBX_TBI 0
+#define BSC_TBX_CSI 1
+typedef struct {
+  uint32_t win_beg, win_last, n_lines, zero;
+  uint64_t u_beg;
+} bsc_bed_entry;
+typedef struct bsc_tbx bsc_tbx;
+int bsc_bed_scan_device(bsc_context *ctx, const void *d_stream, uint64_t n_bytes, const void *d_sync, uint32_t n_sync, int min_shift, void *d_entries,
+                        uint64_t cap_entries, void *d_totals, void *stream);
+int bsc_bed_entries_host(const void *stream, uint64_t n_bytes, const uint64_t *sync, uint32_t n_sync, int min_shift, bsc_bed_entry *entries,
+                         uint64_t cap_entries, uint64_t totals[3]);
+int bsc_block_meth_index_kept(bsc_context *ctx, int min_shift, const bsc_bed_entry **entries, uint64_t *n_entries, uint64_t *n_lines);
+int bsc_tbx_open(bsc_bgzf *z, int kind, int min_shift, int n_refs, const char *const *names, const uint32_t *lens, bsc_tbx **out);
+int bsc_tbx_open_detached(int kind, int min_shift, int n_refs, const char *const *names, const uint32_t *lens, uint64_t header_bytes, bsc_tbx **out);
+int bsc_tbx_members(bsc_tbx *ix, const uint64_t *sizes, uint64_t n_members);
+int bsc_tbx_add(bsc_tbx *ix, int32_t tid, const bsc_bed_entry *entries, uint64_t n, uint64_t n_bytes);
+long bsc_tbx_finish(bsc_tbx *ix, void *buf, uint64_t cap);
+void bsc_tbx_close(bsc_tbx *ix);
 /* bsc_block_bcf_rawdev with the stream left on the device (room: dev_cap bytes; BSC_ERR_ARG and the length needed in *n_bytes when it does
  * not fit), and bytes [off, off + n) of that stream -> dst, queued on the context's stream (bsc_synchronize before dst is read): a contig-sized
  * block's stream is gigabytes — read in pieces through a small page-locked buffer it costs no page-locking of its own */

@@ -63,6 +63,11 @@
  * BCF / VCF, the .csi and the report are those of the run without it.  A single run on the device reader only.  --meth-merge: the table
  * is the combined-strand one — a line per CpG dinucleotide, both strands' counts added (bsc_block_meth_cpg_kept); not with --meth-all.
  *
+ * --meth-bgzf: the table leaves the device as BGZF whatever -O says (with -O b it does anyway).  --meth-index tbi|csi: out.bed.gz.tbi /
+ * out.bed.gz.csi beside the compressed table, made while the table is written — the block's table is scanned where it lies, by the
+ * encoder's own tile offsets (bsc_block_meth_index_kept, csrc/beddev.hip: the runs of lines per 16 384-base window, a line across a border
+ * apart), noted at the table writer's logical length (bsc_tbx_add) and turned into virtual offsets once the table is closed
+ * (bsc_tbx_finish).  The table's bytes are those of the run without it.  Needs --meth and -O b or --meth-bgzf; a single run on the device reader.
  * --meth-bigwig out.bw: the methylation level per cytosine as a bigWig track (include/bscall_amd.h has the rule and the file's layout): every
  * block's data sections and summaries on the device (bsc_block_bigwig_kept, csrc/bigwigdev.hip), read into a host buffer and handed to the
  * output thread as one more job, which bsc_bigwig_add places in the track's own file; bsc_bigwig_finish writes the indexes, the zoom levels and
@@ -517,6 +522,8 @@ int main(int argc, char **argv) {
   bsc_bb_params bbpar;
   bsc_bb_params_default(&bbpar);
   int bigbed_z = 0;
+  int meth_bgzf = 0;
+  const char *meth_index = NULL; /* --meth-index tbi | csi */
   bsc_meth_params mpar;
   bsc_meth_params_default(&mpar);
   if (argc >= 2 && !strcmp(argv[argc - 1], "--meth") && (argc == 2 || strcmp(argv[argc - 2], "--meth"))) {
@@ -549,8 +556,9 @@ int main(int argc, char **argv) {
       argc -= k;
       continue;
     }
-    if (!strcmp(argv[1], "--meth-bigbed-compress")) { /* no value */
-      bigbed_z = 1;
+    if (!strcmp(argv[1], "--meth-bigbed-compress") || !strcmp(argv[1], "--meth-bgzf")) { /* no value */
+      if (argv[1][8] == 'g') meth_bgzf = 1;
+      else bigbed_z = 1;
       argv[1] = argv[0];
       argv += 1;
       argc -= 1;
@@ -572,6 +580,13 @@ int main(int argc, char **argv) {
     else if (!strcmp(argv[1], "--world")) world = atoi(argv[2]);
     else if (!strcmp(argv[1], "--merge")) merge = atoi(argv[2]);
     else if (!strcmp(argv[1], "--meth")) meth_path = argv[2];
+    else if (!strcmp(argv[1], "--meth-index")) {
+      if (strcmp(argv[2], "tbi") && strcmp(argv[2], "csi")) {
+        fprintf(stderr, "%s: --meth-index takes tbi or csi, not '%s'\n", argv[0], argv[2]);
+        return 2;
+      }
+      meth_index = argv[2];
+    }
     else if (!strcmp(argv[1], "--meth-regions")) regions_path = argv[2];
     else if (!strcmp(argv[1], "--meth-regions-out")) regions_out_path = argv[2];
     else if (!strcmp(argv[1], "--meth-window")) {
@@ -630,7 +645,7 @@ int main(int argc, char **argv) {
     argc -= 2;
   }
   if (argc < 5 || world < 1 || (rank >= 0 && rank >= world)) {
-    fprintf(stderr, "usage: %s [-O u|b] [--format bcf|vcf] [--index] [-D dbsnp.idx] [--meth out.bed [--meth-merge | --meth-all] [--meth-min-cov n] [--meth-min-gq n] [--meth-pass]] [--meth-regions regions.bed | --meth-window n --meth-regions-out out.tsv] [--meth-bigwig out.bw [--meth-bigwig-section n] [--meth-bigwig-zoom n] [--meth-bigwig-compress: zlib sections, n <= 8157]: the methylation level as a bigWig track, per cytosine even with --meth-merge, under the --meth-* thresholds and --meth-all] [--meth-bigbed out.bb [--meth-bigbed-items n] [--meth-bigbed-zoom n] [--meth-bigbed-compress: zlib blocks, n <= 652]] [--rank r --world n | --merge n] in.bam ref.fa out.bcf report.json [sample]\n", argv[0]);
+    fprintf(stderr, "usage: %s [-O u|b] [--format bcf|vcf] [--index] [-D dbsnp.idx] [--meth out.bed [--meth-bgzf] [--meth-index tbi|csi] [--meth-merge | --meth-all] [--meth-min-cov n] [--meth-min-gq n] [--meth-pass]] [--meth-regions regions.bed | --meth-window n --meth-regions-out out.tsv] [--meth-bigwig out.bw [--meth-bigwig-section n] [--meth-bigwig-zoom n] [--meth-bigwig-compress: zlib sections, n <= 8157]: the methylation level as a bigWig track, per cytosine even with --meth-merge, under the --meth-* thresholds and --meth-all] [--meth-bigbed out.bb [--meth-bigbed-items n] [--meth-bigbed-zoom n] [--meth-bigbed-compress: zlib blocks, n <= 652]] [--rank r --world n | --merge n] in.bam ref.fa out.bcf report.json [sample]\n", argv[0]);
     return 2;
   }
   if (text && (rank >= 0 || merge > 0)) {
@@ -675,6 +690,18 @@ int main(int argc, char **argv) {
   }
   if (meth_path && (getenv("BAM2BCF_HOST_PREP") || getenv("BAM2BCF_HOST_BCF") || getenv("BAM2BCF_HOST_READER"))) {
     fprintf(stderr, "%s: --meth encodes what the device reader's blocks leave on the device: not with BAM2BCF_HOST_READER / _HOST_BCF / _HOST_PREP\n", argv[0]);
+    return 2;
+  }
+  if (meth_bgzf && !meth_path) {
+    fprintf(stderr, "%s: --meth-bgzf compresses the table --meth writes: it needs --meth out.bed.gz\n", argv[0]);
+    return 2;
+  }
+  if (meth_index && !meth_path) {
+    fprintf(stderr, "%s: --meth-index indexes the table --meth writes: it needs --meth out.bed.gz\n", argv[0]);
+    return 2;
+  }
+  if (meth_index && !bgzf && !meth_bgzf) {
+    fprintf(stderr, "%s: --meth-index indexes a compressed table: it needs -O b or --meth-bgzf\n", argv[0]);
     return 2;
   }
   if (regions_path && meth_window) {
@@ -847,8 +874,9 @@ int main(int argc, char **argv) {
     }
     meth_fd = dup(fileno(mf));
     fclose(mf);
-    if (bgzf) CHECK(bsc_bgzf_open(ctx, &zm));
+    if (bgzf || meth_bgzf) CHECK(bsc_bgzf_open(ctx, &zm));
   }
+  bsc_tbx *tbx = NULL;
   bsc_bgzf *zw = NULL;
   bsc_csi *csi = NULL;
   int bw_fd = -1;
@@ -884,6 +912,8 @@ int main(int argc, char **argv) {
       fclose(bf);
       CHECK(bsc_bigbed_open(bb_fd, (uint32_t)n_ref, names, lens, &bbpar, &bb));
     }
+    if (meth_index) /* the table has no header: its index begins with the first block (it keeps its own copy of the names) */
+      CHECK(bsc_tbx_open(zm, meth_index[0] == 't' ? BSC_TBX_TBI : BSC_TBX_CSI, 14, n_ref, names, lens, &tbx));
     if (bgzf) { /* the header into the compressor: its members come out with the first block's */
       char *hb = NULL;
       size_t hn = 0;
@@ -1145,6 +1175,13 @@ int main(int argc, char **argv) {
         if (mrc == BSC_ERR_ARG && m_bytes > m_cap) mrc = meth_kept(ctx, REF_NAME(dblk.tid), &mpar, m_bytes, &m_bytes, &m_lines, NULL);
         CHECK(mrc);
         meth_lines += m_lines;
+        if (m_bytes && tbx) { /* the index's entries of this block, while the encoder's tile offsets are still the table's: noted at the
+                               * writer's logical length, before the table goes into the compressor */
+          const bsc_bed_entry *be = NULL;
+          uint64_t bn = 0;
+          CHECK(bsc_block_meth_index_kept(ctx, 14, &be, &bn, NULL));
+          CHECK(bsc_tbx_add(tbx, dblk.tid, be, bn, m_bytes));
+        }
         if (m_bytes) {
           void *d_m = NULL;
           uint64_t n_m = 0;
@@ -1289,6 +1326,23 @@ int main(int argc, char **argv) {
       writer_push(&W, j);
     }
     meth_at += n_z;
+    if (tbx) { /* the members' sizes are all there: the index's virtual offsets, and the .tbi / .csi file beside the table */
+      const long need = bsc_tbx_finish(tbx, NULL, 0);
+      CHECK(need);
+      uint8_t *ib = xrealloc(NULL, (size_t)need);
+      CHECK(bsc_tbx_finish(tbx, ib, (uint64_t)need));
+      char *ip = xrealloc(NULL, strlen(meth_path) + 8);
+      sprintf(ip, "%s.%s", meth_path, meth_index);
+      FILE *fi = fopen(ip, "wb");
+      if (!fi || fwrite(ib, 1, (size_t)need, fi) != (size_t)need || fclose(fi)) {
+        perror(ip);
+        return 1;
+      }
+      free(ip);
+      free(ib);
+      bsc_tbx_close(tbx);
+      tbx = NULL;
+    }
   }
   if (W.started) { /* the output thread writes what it still holds, then goes */
     pthread_mutex_lock(&W.mu);
