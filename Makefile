@@ -62,7 +62,11 @@ $(LIBDIR)/methregionsdev.o: $(CSRC)/methregionsdev.hip include/bscall_amd.h
 	@mkdir -p $(LIBDIR)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
-$(LIBDIR)/bigwigdev.o: $(CSRC)/bigwigdev.hip include/bscall_amd.h
+$(LIBDIR)/bigwigdev.o: $(CSRC)/bigwigdev.hip $(CSRC)/bigwig_dev.h include/bscall_amd.h
+	@mkdir -p $(LIBDIR)
+	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+
+$(LIBDIR)/bwcovdev.o: $(CSRC)/bwcovdev.hip $(CSRC)/bigwig_dev.h include/bscall_amd.h
 	@mkdir -p $(LIBDIR)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
@@ -166,7 +170,7 @@ $(LIBDIR)/synth_reads.o: $(CSRC)/synth_reads.c include/bscall_amd.h $(CSRC)/synt
 	@mkdir -p $(LIBDIR)
 	$(CC) $(CFLAGS) -c $< -o $@
 
-$(LIBDIR)/libbscall_amd.so: $(LIBDIR)/kernels.o $(LIBDIR)/fused.o $(LIBDIR)/accumulate.o $(LIBDIR)/sort.o $(LIBDIR)/vcfcore.o $(LIBDIR)/sitestats.o $(LIBDIR)/compact.o $(LIBDIR)/probe.o $(LIBDIR)/prepdev.o $(LIBDIR)/bcfdev.o $(LIBDIR)/vcftextdev.o $(LIBDIR)/methdev.o $(LIBDIR)/methregionsdev.o $(LIBDIR)/bigwigdev.o $(LIBDIR)/bigbeddev.o $(LIBDIR)/bgzfdev.o $(LIBDIR)/zlibdev.o $(LIBDIR)/bamdev.o $(LIBDIR)/dbsnpdev.o $(LIBDIR)/csidev.o $(LIBDIR)/beddev.o $(LIBDIR)/bscall_api.o $(LIBDIR)/bamstream.o $(LIBDIR)/inflate_fast.o $(LIBDIR)/synth_reads.o $(LIBDIR)/vcf_format.o $(LIBDIR)/methbed.o $(LIBDIR)/methcpg.o $(LIBDIR)/methregions.o $(LIBDIR)/bigwig.o $(LIBDIR)/bigbed.o $(LIBDIR)/tabix.o $(LIBDIR)/dbsnp.o $(LIBDIR)/prep.o $(LIBDIR)/report.o $(LIBDIR)/bcf.o $(LIBDIR)/bamio.o $(LIBDIR)/refseq.o
+$(LIBDIR)/libbscall_amd.so: $(LIBDIR)/kernels.o $(LIBDIR)/fused.o $(LIBDIR)/accumulate.o $(LIBDIR)/sort.o $(LIBDIR)/vcfcore.o $(LIBDIR)/sitestats.o $(LIBDIR)/compact.o $(LIBDIR)/probe.o $(LIBDIR)/prepdev.o $(LIBDIR)/bcfdev.o $(LIBDIR)/vcftextdev.o $(LIBDIR)/methdev.o $(LIBDIR)/methregionsdev.o $(LIBDIR)/bigwigdev.o $(LIBDIR)/bwcovdev.o $(LIBDIR)/bigbeddev.o $(LIBDIR)/bgzfdev.o $(LIBDIR)/zlibdev.o $(LIBDIR)/bamdev.o $(LIBDIR)/dbsnpdev.o $(LIBDIR)/csidev.o $(LIBDIR)/beddev.o $(LIBDIR)/bscall_api.o $(LIBDIR)/bamstream.o $(LIBDIR)/inflate_fast.o $(LIBDIR)/synth_reads.o $(LIBDIR)/vcf_format.o $(LIBDIR)/methbed.o $(LIBDIR)/methcpg.o $(LIBDIR)/methregions.o $(LIBDIR)/bigwig.o $(LIBDIR)/bigbed.o $(LIBDIR)/tabix.o $(LIBDIR)/dbsnp.o $(LIBDIR)/prep.o $(LIBDIR)/report.o $(LIBDIR)/bcf.o $(LIBDIR)/bamio.o $(LIBDIR)/refseq.o
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $^ -lm -lz -lpthread
 
 oracle:
@@ -222,6 +226,15 @@ bigwig-z-san: $(BIGWIG_Z_SAN_EXE)
 $(BIGWIG_Z_SAN_EXE): integration/bigwig_z_san.c $(CSRC)/bigwig.c $(CSRC)/bbi_trees.h include/bscall_amd.h
 	$(CC) -std=gnu11 -O1 -g -Wall -Wextra -fsanitize=address,undefined -fno-sanitize-recover=undefined -Iinclude $< $(CSRC)/bigwig.c -lpthread -lz -o $@
 
+# TEST ONLY: the coverage track on the host (csrc/bigwig.c: bsc_bigwig_cov_sections_recs with its rooms, a coverage writer over crafted entries,
+# plain and compressed, sums of squares beyond 2^64, the integer-to-float roundings, every refusal) as a stand-alone program under
+# AddressSanitizer + UndefinedBehaviorSanitizer, on the CPU; tests/test_bigwig_cov_host.py builds its own copy and runs it:
+# $(BIGWIG_COV_SAN_EXE)  ->  "ok" and exit 0, or the case that failed
+BIGWIG_COV_SAN_EXE ?= $(LIBDIR)/bigwig_cov_san
+bigwig-cov-san: $(BIGWIG_COV_SAN_EXE)
+$(BIGWIG_COV_SAN_EXE): integration/bigwig_cov_san.c $(CSRC)/bigwig.c $(CSRC)/bbi_trees.h include/bscall_amd.h
+	$(CC) -std=gnu11 -O1 -g -Wall -Wextra -fsanitize=address,undefined -fno-sanitize-recover=undefined -Iinclude $< $(CSRC)/bigwig.c -lpthread -lz -o $@
+
 # TEST ONLY: the host form of the bigBed items (csrc/bigbed.c over csrc/methbed.c: the shortest and the longest item, rooms one short, block and
 # window borders) as a stand-alone program under AddressSanitizer + UndefinedBehaviorSanitizer, on the CPU; tests/test_bigbed_host.py builds
 # its own copy and runs it: $(BIGBED_SAN_EXE)  ->  "ok" and exit 0, or the case that failed
@@ -246,7 +259,7 @@ HOST_C = bscall_api synth_reads vcf_format methbed methcpg methregions bigwig bi
 san: $(LIBDIR)/libbscall_amd.so
 	@mkdir -p $(LIBDIR)/san
 	for f in $(HOST_C); do $(CC) $(SANFLAGS) -c $(CSRC)/$$f.c -o $(LIBDIR)/san/$$f.o || exit 1; done
-	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $(LIBDIR)/san/libbscall_amd_san.so $(LIBDIR)/kernels.o $(LIBDIR)/fused.o $(LIBDIR)/accumulate.o $(LIBDIR)/sort.o $(LIBDIR)/vcfcore.o $(LIBDIR)/sitestats.o $(LIBDIR)/compact.o $(LIBDIR)/probe.o $(LIBDIR)/prepdev.o $(LIBDIR)/bcfdev.o $(LIBDIR)/vcftextdev.o $(LIBDIR)/methdev.o $(LIBDIR)/methregionsdev.o $(LIBDIR)/bigwigdev.o $(LIBDIR)/bigbeddev.o $(LIBDIR)/bgzfdev.o $(LIBDIR)/zlibdev.o $(LIBDIR)/bamdev.o $(LIBDIR)/dbsnpdev.o $(LIBDIR)/csidev.o $(LIBDIR)/beddev.o $(addprefix $(LIBDIR)/san/,$(addsuffix .o,$(HOST_C))) -L$(dir $(shell $(CC) -print-file-name=libasan.so)) -lasan -lubsan -lm -lz -lpthread
+	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $(LIBDIR)/san/libbscall_amd_san.so $(LIBDIR)/kernels.o $(LIBDIR)/fused.o $(LIBDIR)/accumulate.o $(LIBDIR)/sort.o $(LIBDIR)/vcfcore.o $(LIBDIR)/sitestats.o $(LIBDIR)/compact.o $(LIBDIR)/probe.o $(LIBDIR)/prepdev.o $(LIBDIR)/bcfdev.o $(LIBDIR)/vcftextdev.o $(LIBDIR)/methdev.o $(LIBDIR)/methregionsdev.o $(LIBDIR)/bigwigdev.o $(LIBDIR)/bwcovdev.o $(LIBDIR)/bigbeddev.o $(LIBDIR)/bgzfdev.o $(LIBDIR)/zlibdev.o $(LIBDIR)/bamdev.o $(LIBDIR)/dbsnpdev.o $(LIBDIR)/csidev.o $(LIBDIR)/beddev.o $(addprefix $(LIBDIR)/san/,$(addsuffix .o,$(HOST_C))) -L$(dir $(shell $(CC) -print-file-name=libasan.so)) -lasan -lubsan -lm -lz -lpthread
 
 # a plain-C host program against the C ABI: gcc only, links the shared library like bs_call would
 demo: $(LIBDIR)/demo_block $(LIBDIR)/bam2bcf
@@ -277,7 +290,7 @@ asm: $(CSRC)/kernels.hip
 	$(HIPCC) $(HIPFLAGS) -S --cuda-device-only -Rpass-analysis=kernel-resource-usage $< -o $(LIBDIR)/kernels.s
 
 clean:
-	rm -rf $(LIBDIR)/san; rm -f tests/devmath/libdevmath_probe.so tests/dbsnpdev/dbsnp_flat_host tests/csidev/csi_walk_host $(LIBDIR)/*.o $(LIBDIR)/*.so $(LIBDIR)/*.s $(LIBDIR)/demo_block $(LIBDIR)/bam2bcf $(LIBDIR)/methregions_san $(LIBDIR)/bigwig_san $(LIBDIR)/bigwig_z_san $(LIBDIR)/bigbed_san $(LIBDIR)/tabix_san
+	rm -rf $(LIBDIR)/san; rm -f tests/devmath/libdevmath_probe.so tests/dbsnpdev/dbsnp_flat_host tests/csidev/csi_walk_host $(LIBDIR)/*.o $(LIBDIR)/*.so $(LIBDIR)/*.s $(LIBDIR)/demo_block $(LIBDIR)/bam2bcf $(LIBDIR)/methregions_san $(LIBDIR)/bigwig_san $(LIBDIR)/bigwig_z_san $(LIBDIR)/bigwig_cov_san $(LIBDIR)/bigbed_san $(LIBDIR)/tabix_san
 	$(MAKE) -C oracle clean
 
-.PHONY: all oracle demo asm clean glue-check san devmath-probe dbsnp-flat-host csi-walk-host tabix-san
+.PHONY: all oracle demo asm clean glue-check san devmath-probe dbsnp-flat-host csi-walk-host tabix-san bigwig-cov-san

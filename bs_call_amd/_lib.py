@@ -215,6 +215,13 @@ EXPORTS = (
     "bsc_block_bigwig_deflate",
     "bsc_bigwig_zstream_read",
     "bsc_bigwig_add_z",
+    "bsc_bigwig_cov_sections_recs",
+    "bsc_bigwig_open_track",
+    "bsc_bigwig_tracks_device",
+    "bsc_block_bigwig_tracks_kept",
+    "bsc_bigwig_cov_stream_read",
+    "bsc_block_bigwig_cov_deflate",
+    "bsc_bigwig_cov_zstream_read",
     "bsc_bb_params_default",
     "bsc_bigbed_blocks_recs",
     "bsc_bigbed_sites_device",
@@ -257,6 +264,16 @@ class BwParams(C.Structure):
 
     def __init__(self, items_per_section=1024, reduction=1024):
         super().__init__(int(items_per_section), int(reduction))
+
+
+BW_LEVEL, BW_COVERAGE = 1, 2  # BSC_BW_LEVEL, BSC_BW_COVERAGE: the bits of a track mask
+
+
+class BwTrackOut(C.Structure):
+    """bsc_bw_track_out: where one track of bsc_bigwig_tracks_device goes."""
+
+    _fields_ = [("d_out", C.c_void_p), ("out_cap", C.c_uint64), ("d_sections", C.c_void_p), ("sec_cap", C.c_uint64), ("d_zoom", C.c_void_p),
+                ("zoom_cap", C.c_uint64)]
 
 
 class BbParams(C.Structure):
@@ -845,6 +862,22 @@ def load():
     L.bsc_bigwig_zstream_read.argtypes = [vp, u64, u64, vp]
     L.bsc_bigwig_add_z.restype = i32
     L.bsc_bigwig_add_z.argtypes = [vp, u32, vp, u64, vp, vp, u64, vp, u64]
+    L.bsc_bigwig_cov_sections_recs.restype = i32
+    L.bsc_bigwig_cov_sections_recs.argtypes = [vp, C.c_size_t, u32, C.POINTER(MethParams), C.POINTER(BwParams), vp, u64, pu64, vp, pu64, vp, pu64]
+    L.bsc_bigwig_open_track.restype = i32
+    L.bsc_bigwig_open_track.argtypes = [C.c_int, u32, C.POINTER(C.c_char_p), vp, C.POINTER(BwParams), u32, C.POINTER(vp)]
+    L.bsc_bigwig_tracks_device.restype = i32
+    L.bsc_bigwig_tracks_device.argtypes = [vp, vp, vp, u32, u32, u32, C.POINTER(MethParams), C.POINTER(BwParams), u32, C.POINTER(BwTrackOut),
+                                           C.POINTER(BwTrackOut), vp, vp]
+    L.bsc_block_bigwig_tracks_kept.restype = i32
+    L.bsc_block_bigwig_tracks_kept.argtypes = [vp, u32, C.POINTER(MethParams), C.POINTER(BwParams), u32, pu64, pu64, pu64, pu64, C.POINTER(vp), C.POINTER(vp),
+                                               C.POINTER(vp), C.POINTER(vp)]
+    L.bsc_bigwig_cov_stream_read.restype = i32
+    L.bsc_bigwig_cov_stream_read.argtypes = [vp, u64, u64, vp]
+    L.bsc_block_bigwig_cov_deflate.restype = i32
+    L.bsc_block_bigwig_cov_deflate.argtypes = [vp, pu64, C.POINTER(vp), pu64]
+    L.bsc_bigwig_cov_zstream_read.restype = i32
+    L.bsc_bigwig_cov_zstream_read.argtypes = [vp, u64, u64, vp]
     L.bsc_bb_params_default.restype = None
     L.bsc_bb_params_default.argtypes = [C.POINTER(BbParams)]
     L.bsc_bigbed_blocks_recs.restype = i32

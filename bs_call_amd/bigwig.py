@@ -1,5 +1,5 @@
-"""The methylation bigWig track (include/bscall_amd.h has the rule and the file's layout): the Python form of the rule over packed records
-(sections_of_recs), the writer of the file over the C ABI (Writer: bsc_bigwig_open / _add / _finish / _close), and a reader that follows the
+"""The methylation bigWig track and the coverage track beside it (include/bscall_amd.h has the rules and the file's layout; track="level" or
+"coverage" throughout): the Python form of the rule over packed records (sections_of_recs), the writer of the file over the C ABI (Writer: bsc_bigwig_open / _add / _finish / _close), and a reader that follows the
 file's own offsets (read: header, chromosomes, total summary, zoom levels; intervals through the R-tree; zoom_records).  The bytes are
 UCSC-unpinned: no UCSC or pyBigWig reader has seen them; this reader is written from the same published layout.  A file whose
 uncompressBufSize is not 0 holds every section and zoom block as a zlib stream (Writer(compress=True) with add_z): the reader inflates
@@ -32,9 +32,35 @@ def value_bytes(m):
     return struct.pack("<f", m / 10.0)
 
 
-def site_of_rec(rec, meth_params=None):
+TRACKS = {"level": _lib.BW_LEVEL, "coverage": _lib.BW_COVERAGE}
+
+
+def int_float_bits(v, mant, bias):
+    """The bits of the non-negative integer v as a binary float of `mant` significand bits, rounded once, to nearest, ties to even, in
+    integer arithmetic (v below the format's range)."""
+    if not v:
+        return 0
+    top = v.bit_length() - 1
+    if top < mant:
+        q = v << (mant - 1 - top)
+    else:
+        sh = top - (mant - 1)
+        q, rem, half = v >> sh, v & ((1 << sh) - 1), 1 << (sh - 1)
+        if rem > half or (rem == half and q & 1):
+            q += 1
+        if q >> mant:
+            q, top = q >> 1, top + 1
+    return ((top + bias) << (mant - 1)) | (q & ((1 << (mant - 1)) - 1))
+
+
+def cov_value_bytes(c):
+    """The four bytes written for a coverage c (0 .. 2^32 - 1): the unsigned integer as binary32, rounded once to nearest even."""
+    return struct.pack("<I", int_float_bits(int(c), 24, 127))
+
+
+def site_of_rec(rec, meth_params=None, track="level"):
     """None, or (start, m) of the site a packed record (a VCF_REC element) gives: the per-cytosine rule, start = pos - 1,
-    m = (2000 a + (a + b)) / (2 (a + b))."""
+    m = (2000 a + (a + b)) / (2 (a + b)); track="coverage": (start, c), c = min(a + b, 2^32 - 1)."""
     p = _as_dict(meth_params, _METH)
     c = rec["core"]
     gt, cg = int(c["gt"]), bytes(c["cg"])
@@ -46,22 +72,28 @@ def site_of_rec(rec, meth_params=None):
     a, b = (cnt[5], cnt[7]) if gt == 4 else (cnt[6], cnt[4])
     if a + b < max(1, p["min_cov"]) or int(c["phred"]) < p["min_phred"] or (p["pass_only"] and int(c["flt"])):
         return None
+    if TRACKS[track] == _lib.BW_COVERAGE:
+        return ((int(c["pos"]) - 1) & 0xFFFFFFFF, min(a + b, 0xFFFFFFFF))
     return ((int(c["pos"]) - 1) & 0xFFFFFFFF, (2000 * a + (a + b)) // (2 * (a + b)))
 
 
 def summary_of(sites):
-    """The bsc_bw_sum of a run of (start, m) sites, as a tuple in BW_SUM's field order."""
+    """The bsc_bw_sum of a run of (start, m) sites — or (start, c) sites: the sum of squares is 96 bits, its top 32 in _pad —, as a tuple in
+    BW_SUM's field order."""
     ms = [m for _, m in sites]
-    return (sites[0][0], sites[-1][0] + 1, len(sites), min(ms), max(ms), 0, sum(ms), sum(m * m for m in ms))
+    sq = sum(m * m for m in ms)
+    return (sites[0][0], sites[-1][0] + 1, len(sites), min(ms), max(ms), sq >> 64, sum(ms), sq & 0xFFFFFFFFFFFFFFFF)
 
 
-def sections_of_sites(sites, chrom_id, items_per_section=1024, reduction=1024):
-    """A block's (start, m) sites in order -> (the data stream's bytes, sections, zoom0): the two summaries as BW_SUM arrays."""
+def sections_of_sites(sites, chrom_id, items_per_section=1024, reduction=1024, track="level"):
+    """A block's (start, m) sites in order -> (the data stream's bytes, sections, zoom0): the two summaries as BW_SUM arrays.
+    track="coverage": (start, c) sites."""
     S, out, secs, zoom = int(items_per_section), [], [], []
+    vb = cov_value_bytes if TRACKS[track] == _lib.BW_COVERAGE else value_bytes
     for k in range(0, len(sites), S):
         part = sites[k : k + S]
         out.append(struct.pack("<IIIIIBBH", chrom_id, part[0][0], part[-1][0] + 1, 0, 1, 2, 0, len(part)))
-        out.extend(struct.pack("<I", s) + value_bytes(m) for s, m in part)
+        out.extend(struct.pack("<I", s) + vb(m) for s, m in part)
         secs.append(summary_of(part))
     run = []
     for s, m in sites:
@@ -74,25 +106,26 @@ def sections_of_sites(sites, chrom_id, items_per_section=1024, reduction=1024):
     return b"".join(out), np.array(secs, dtype=BW_SUM).reshape(-1), np.array(zoom, dtype=BW_SUM).reshape(-1)
 
 
-def sections_of_recs(recs, chrom_id, meth_params=None, items_per_section=1024, reduction=1024):
+def sections_of_recs(recs, chrom_id, meth_params=None, items_per_section=1024, reduction=1024, track="level"):
     """The Python form of the rule over packed records (a VCF_REC array): (bytes, sections, zoom0)."""
-    sites = [s for s in (site_of_rec(r, meth_params) for r in recs) if s is not None]
-    return sections_of_sites(sites, chrom_id, items_per_section, reduction)
+    sites = [s for s in (site_of_rec(r, meth_params, track) for r in recs) if s is not None]
+    return sections_of_sites(sites, chrom_id, items_per_section, reduction, track)
 
 
-def sections_recs_host(recs, chrom_id, meth_params=None, bw_params=None, room=None):
-    """bsc_bigwig_sections_recs, the C host form: (bytes, sections, zoom0).  room: (bytes, sections, windows) to offer instead of asking first;
-    a BscError where it is too small."""
+def sections_recs_host(recs, chrom_id, meth_params=None, bw_params=None, room=None, track="level"):
+    """bsc_bigwig_sections_recs (track="coverage": bsc_bigwig_cov_sections_recs), the C host form: (bytes, sections, zoom0).  room: (bytes,
+    sections, windows) to offer instead of asking first; a BscError where it is too small."""
     from .caller import _check
 
     L = _lib.load()
+    host_form = L.bsc_bigwig_cov_sections_recs if TRACKS[track] == _lib.BW_COVERAGE else L.bsc_bigwig_sections_recs
     recs = np.ascontiguousarray(recs)
     mp = meth_params if isinstance(meth_params, _lib.MethParams) else _lib.MethParams(**(meth_params or {}))
     bp = bw_params if isinstance(bw_params, _lib.BwParams) else _lib.BwParams(**(bw_params or {}))
     nb, ns, nz = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
     ptr = recs.ctypes.data if len(recs) else None
     if room is None:
-        rc = L.bsc_bigwig_sections_recs(ptr, len(recs), chrom_id, C.byref(mp), C.byref(bp), None, 0, C.byref(nb), None, C.byref(ns), None, C.byref(nz))
+        rc = host_form(ptr, len(recs), chrom_id, C.byref(mp), C.byref(bp), None, 0, C.byref(nb), None, C.byref(ns), None, C.byref(nz))
         if rc == 0:  # nothing at all
             return b"", np.zeros(0, dtype=BW_SUM), np.zeros(0, dtype=BW_SUM)
         if rc != -1 or not nb.value:
@@ -102,28 +135,32 @@ def sections_recs_host(recs, chrom_id, meth_params=None, bw_params=None, room=No
     out[room[0] :] = 0xA5
     sec, zoom = np.zeros(room[1] + 1, dtype=BW_SUM), np.zeros(room[2] + 1, dtype=BW_SUM)
     ns.value, nz.value = room[1], room[2]
-    _check(L.bsc_bigwig_sections_recs(ptr, len(recs), chrom_id, C.byref(mp), C.byref(bp), out.ctypes.data, room[0], C.byref(nb), sec.ctypes.data,
-                                      C.byref(ns), zoom.ctypes.data, C.byref(nz)))
+    _check(host_form(ptr, len(recs), chrom_id, C.byref(mp), C.byref(bp), out.ctypes.data, room[0], C.byref(nb), sec.ctypes.data, C.byref(ns),
+                     zoom.ctypes.data, C.byref(nz)))
     assert (out[room[0] :] == 0xA5).all()
     return out[: nb.value].tobytes(), sec[: ns.value].copy(), zoom[: nz.value].copy()
 
 
 class Writer:
     """bsc_bigwig_open / _add / _finish / _close on a file of its own.  refs: [(name, length)] in the BAM header's order.  compress: the
-    file's sections come as zlib streams through add_z (bsc_bigwig_add_z), and finish deflates the zoom blocks."""
+    file's sections come as zlib streams through add_z (bsc_bigwig_add_z), and finish deflates the zoom blocks.  track="coverage": a coverage
+    writer (bsc_bigwig_open_track)."""
 
-    def __init__(self, path, refs, items_per_section=1024, reduction=1024, compress=False):
+    def __init__(self, path, refs, items_per_section=1024, reduction=1024, compress=False, track="level"):
         from .caller import _check
 
         self._check, self._L = _check, _lib.load()
         self.compress = bool(compress)
+        if track not in TRACKS:
+            raise ValueError("track is 'level' or 'coverage'")
         self._f = open(path, "wb")
         names = (C.c_char_p * max(len(refs), 1))(*[n.encode() if isinstance(n, str) else bytes(n) for n, _ in refs])
         lens = np.array([l for _, l in refs], dtype=np.uint32)
         bp = _lib.BwParams(items_per_section, reduction)
         self._h = C.c_void_p(None)
         try:
-            _check(self._L.bsc_bigwig_open(self._f.fileno(), len(refs), names, lens.ctypes.data if len(refs) else None, C.byref(bp), C.byref(self._h)))
+            _check(self._L.bsc_bigwig_open_track(self._f.fileno(), len(refs), names, lens.ctypes.data if len(refs) else None, C.byref(bp), TRACKS[track],
+                                                 C.byref(self._h)))
         except Exception:
             self._f.close()
             os.remove(path)

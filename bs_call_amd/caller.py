@@ -1055,6 +1055,62 @@ class SiteCaller:
             self.synchronize()
         return out[:n].tobytes()
 
+    # -- the coverage track, alone or with the level track in one sweep (csrc/bwcovdev.hip) -----------------
+    def bigwig_tracks_device(self, d_core, d_aux, n, x0, chrom_id, tracks, level_out, cov_out, d_totals, params=None, bw_params=None, stream=None):
+        """bsc_bigwig_tracks_device: bigwig_sites_device for a mask of tracks (1 level, 2 coverage, 3 both) in one sweep.  level_out / cov_out:
+        (d_out, out_cap, d_sections, sec_cap, d_zoom, zoom_cap) or a _lib.BwTrackOut per requested track, None for the other; d_totals: six
+        u64 {bytes, sites, sections, windows, sum of m, sum of m * m}, the last two 0 without the level track."""
+        mp, bp = self._meth_params(params), self._bw_params(bw_params)
+        desc = lambda o: None if o is None else C.byref(o if isinstance(o, _lib.BwTrackOut) else _lib.BwTrackOut(*o))
+        _check(self._L.bsc_bigwig_tracks_device(self._h, d_core, d_aux, n, x0, chrom_id, C.byref(mp), C.byref(bp), tracks, desc(level_out), desc(cov_out),
+                                                d_totals, stream))
+
+    def block_bigwig_tracks_kept(self, chrom_id, tracks, params=None, bw_params=None, read_stream=True):
+        """bsc_block_bigwig_tracks_kept (+ the stream reads): the bigWig data of the block the last *_keep call called, for a mask of tracks
+        in one sweep.  Returns (sites, level, coverage): per requested track (stream bytes, sections, zoom0) — the summaries as
+        bigwig.BW_SUM arrays (copies) —, None for the other.  read_stream=False: the streams stay on the device (block_bigwig_deflate /
+        block_bigwig_cov_deflate follow) and their length comes back in the bytes' place."""
+        from .bigwig import BW_SUM
+
+        mp, bp = self._meth_params(params), self._bw_params(bw_params)
+        nb, ns, nsec, nz = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        ptr = [C.c_void_p(None) for _ in range(4)]
+        _check(self._L.bsc_block_bigwig_tracks_kept(self._h, chrom_id, C.byref(mp), C.byref(bp), tracks, C.byref(nb), C.byref(ns), C.byref(nsec), C.byref(nz),
+                                                    *[C.byref(p) for p in ptr]))
+        grab = lambda p, k: np.frombuffer(C.string_at(p.value, 40 * k), dtype=BW_SUM).copy() if k else np.zeros(0, dtype=BW_SUM)
+        out = []
+        for t, read in ((0, self.bigwig_stream_read), (1, self.bigwig_cov_stream_read)):
+            if not tracks & (1 << t):
+                out.append(None)
+                continue
+            sections, zoom0 = grab(ptr[2 * t], nsec.value), grab(ptr[2 * t + 1], nz.value)
+            out.append((read(0, nb.value) if read_stream else int(nb.value), sections, zoom0))
+        return int(ns.value), out[0], out[1]
+
+    def bigwig_cov_stream_read(self, off, n):
+        """bsc_bigwig_cov_stream_read: bytes [off, off + n) of the coverage stream block_bigwig_tracks_kept left on the device (waits)."""
+        out = np.empty(max(int(n), 1), dtype=np.uint8)
+        if n:
+            _check(self._L.bsc_bigwig_cov_stream_read(self._h, off, n, _ptr(out)))
+            self.synchronize()
+        return out[:n].tobytes()
+
+    def block_bigwig_cov_deflate(self):
+        """bsc_block_bigwig_cov_deflate + bsc_bigwig_cov_zstream_read: block_bigwig_deflate for the coverage stream."""
+        nb, nsec = C.c_uint64(0), C.c_uint64(0)
+        p_sz = C.c_void_p(None)
+        _check(self._L.bsc_block_bigwig_cov_deflate(self._h, C.byref(nb), C.byref(p_sz), C.byref(nsec)))
+        sizes = np.frombuffer(C.string_at(p_sz.value, 4 * nsec.value), dtype=np.uint32).copy() if nsec.value else np.zeros(0, dtype=np.uint32)
+        return self.bigwig_cov_zstream_read(0, nb.value), sizes
+
+    def bigwig_cov_zstream_read(self, off, n):
+        """bsc_bigwig_cov_zstream_read: bytes [off, off + n) of the streams block_bigwig_cov_deflate left on the device (waits)."""
+        out = np.empty(max(int(n), 1), dtype=np.uint8)
+        if n:
+            _check(self._L.bsc_bigwig_cov_zstream_read(self._h, off, n, _ptr(out)))
+            self.synchronize()
+        return out[:n].tobytes()
+
     # -- the bedMethyl table as bigBed items (csrc/bigbeddev.hip), zlib streams of ranges (csrc/zlibdev.hip) --
     def bigbed_sites_device(self, d_core, d_aux, n, x0, chrom_id, d_out, out_cap, d_blocks, blk_cap, d_zoom, zoom_cap, d_totals, params=None,
                             bb_params=None, stream=None):

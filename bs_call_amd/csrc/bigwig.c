@@ -12,6 +12,12 @@
  * A compressed writer (bsc_bigwig_add_z) takes a block's sections as zlib streams — the device made them (csrc/zlibdev.hip) — with their
  * sizes: a section's place is the running sum of the sizes.  It deflates the zoom blocks itself at bsc_bigwig_finish (libz, compress2 at the
  * default level) and states the largest raw block in the header; integration/bigwig_z_san.c drives it under the sanitizers.
+ *
+ * The coverage track (bsc_bigwig_cov_sections_recs, bsc_bigwig_open_track with BSC_BW_COVERAGE) shares all of it: the host form differs in
+ * the site's integer (c = min(a + b, 2^32 - 1)) and its float ((float)c, one rounding), a summary's sum of squares is 96 bits (_pad holds
+ * the top 32; sum_merge carries), the writer's merged sums are unsigned __int128, and a coverage file's floats come from the exact integers
+ * by bw_round_bits — integer arithmetic, rounded once.  The level writer's bytes are what they were.  integration/bigwig_cov_san.c drives
+ * the coverage code under the sanitizers; bsc_bigwig_cov_sections_recs is the checker of csrc/bwcovdev.hip.
  */
 #include <errno.h>
 #include <pthread.h>
@@ -81,16 +87,17 @@ static void sum_merge(bsc_bw_sum *s, const bsc_bw_sum *t) {
   s->count += t->count;
   s->sum_m += t->sum_m;
   s->sum_m2 += t->sum_m2;
+  s->_pad += t->_pad + (s->sum_m2 < t->sum_m2); /* a coverage summary's 96-bit sum of squares: the carry (a level summary's never carries) */
   if (t->min_m < s->min_m) s->min_m = t->min_m;
   if (t->max_m > s->max_m) s->max_m = t->max_m;
   if (t->start < s->start) s->start = t->start;
   if (t->end > s->end) s->end = t->end;
 }
 
-int bsc_bigwig_sections_recs(const bsc_vcf_rec *recs, size_t n, uint32_t chrom_id, const bsc_meth_params *params, const bsc_bw_params *bw_params,
-                             void *out, uint64_t cap, uint64_t *n_bytes, bsc_bw_sum *sections, uint64_t *n_sections, bsc_bw_sum *zoom0,
-                             uint64_t *n_zoom0) {
-  static const char who[] = "bsc_bigwig_sections_recs";
+/* the host form of one track (BSC_BW_LEVEL or BSC_BW_COVERAGE) */
+static int bw_sections_recs(const char *who, uint32_t track, const bsc_vcf_rec *recs, size_t n, uint32_t chrom_id, const bsc_meth_params *params,
+                            const bsc_bw_params *bw_params, void *out, uint64_t cap, uint64_t *n_bytes, bsc_bw_sum *sections, uint64_t *n_sections,
+                            bsc_bw_sum *zoom0, uint64_t *n_zoom0) {
   if (!params || !bw_params || !n_bytes || !n_sections || !n_zoom0 || (n && !recs) || (cap && !out) || (*n_sections && !sections) ||
       (*n_zoom0 && !zoom0))
     return bsc_set_error(BSC_ERR_ARG, "%s: NULL argument", who);
@@ -121,7 +128,9 @@ int bsc_bigwig_sections_recs(const bsc_vcf_rec *recs, size_t n, uint32_t chrom_i
   for (size_t i = 0; i < n; i++) {
     if (!bw_site(&recs[i], params, &a, &b)) continue;
     const uint32_t start = recs[i].core.pos - 1u;
-    const uint32_t m = (uint32_t)((2000 * a + (a + b)) / (2 * (a + b)));
+    /* the site's integer: m, or c = min(a + b, 2^32 - 1); its float: entry m of the table, or the one conversion of c */
+    const uint32_t m = track == BSC_BW_COVERAGE ? (a + b > 0xffffffffull ? 0xffffffffu : (uint32_t)(a + b)) : (uint32_t)((2000 * a + (a + b)) / (2 * (a + b)));
+    const float value = track == BSC_BW_COVERAGE ? (float)m : val[m];
     const uint64_t k = rank / S, in = rank % S;
     uint8_t *sec = (uint8_t *)out + k * (24 + 8 * S);
     bsc_bw_sum one;
@@ -142,7 +151,7 @@ int bsc_bigwig_sections_recs(const bsc_vcf_rec *recs, size_t n, uint32_t chrom_i
     }
     put32(sec + 8, start + 1u); /* (the last site's stays) */
     put32(sec + 24 + 8 * in, start);
-    memcpy(sec + 24 + 8 * in + 4, &val[m], 4);
+    memcpy(sec + 24 + 8 * in + 4, &value, 4);
     const uint64_t w = start / red;
     if (!rank || w != last_w) zoom0[nw++] = one; else sum_merge(&zoom0[nw - 1], &one);
     last_w = w;
@@ -151,13 +160,78 @@ int bsc_bigwig_sections_recs(const bsc_vcf_rec *recs, size_t n, uint32_t chrom_i
   return BSC_OK;
 }
 
+int bsc_bigwig_sections_recs(const bsc_vcf_rec *recs, size_t n, uint32_t chrom_id, const bsc_meth_params *params, const bsc_bw_params *bw_params,
+                             void *out, uint64_t cap, uint64_t *n_bytes, bsc_bw_sum *sections, uint64_t *n_sections, bsc_bw_sum *zoom0,
+                             uint64_t *n_zoom0) {
+  return bw_sections_recs("bsc_bigwig_sections_recs", BSC_BW_LEVEL, recs, n, chrom_id, params, bw_params, out, cap, n_bytes, sections, n_sections, zoom0,
+                          n_zoom0);
+}
+
+int bsc_bigwig_cov_sections_recs(const bsc_vcf_rec *recs, size_t n, uint32_t chrom_id, const bsc_meth_params *params, const bsc_bw_params *bw_params,
+                                 void *out, uint64_t cap, uint64_t *n_bytes, bsc_bw_sum *sections, uint64_t *n_sections, bsc_bw_sum *zoom0,
+                                 uint64_t *n_zoom0) {
+  return bw_sections_recs("bsc_bigwig_cov_sections_recs", BSC_BW_COVERAGE, recs, n, chrom_id, params, bw_params, out, cap, n_bytes, sections, n_sections,
+                          zoom0, n_zoom0);
+}
+
+/* ---- an exact integer to a float, rounded once -----------------------------------------------------------------------------------------
+ * v as the float of `mant` significand bits (24: binary32, 53: binary64) and exponent bias `bias`, to nearest, ties to even, in integer
+ * arithmetic: no intermediate type, so a sum of 96 bits is rounded once (a conversion through a double rounds twice).  Returns the
+ * float's bits; a value that rounds beyond the format's range gives infinity, as the conversion does. */
+typedef unsigned __int128 u128;
+static uint64_t bw_round_bits(u128 v, int mant, int bias, int exp_max) {
+  if (!v) return 0;
+  int top = 127;
+  while (!(v >> top)) top--;
+  uint64_t q;
+  if (top < mant) {
+    q = (uint64_t)v << (mant - 1 - top); /* exact */
+  } else {
+    const int sh = top - (mant - 1);
+    const u128 rem = v & (((u128)1 << sh) - 1), half = (u128)1 << (sh - 1);
+    q = (uint64_t)(v >> sh);
+    if (rem > half || (rem == half && (q & 1))) q++;
+    if (q >> mant) { /* rounded up to the next power of two */
+      q >>= 1;
+      top++;
+    }
+  }
+  const uint64_t e = (uint64_t)(top + bias);
+  if (e >= (uint64_t)exp_max) return (uint64_t)exp_max << (mant - 1); /* infinity */
+  return (e << (mant - 1)) | (q & (((uint64_t)1 << (mant - 1)) - 1));
+}
+static float bw_f32_of(u128 v) {
+  const uint32_t bits = (uint32_t)bw_round_bits(v, 24, 127, 255);
+  float f;
+  memcpy(&f, &bits, 4);
+  return f;
+}
+static double bw_f64_of(u128 v) {
+  const uint64_t bits = bw_round_bits(v, 53, 1023, 2047);
+  double d;
+  memcpy(&d, &bits, 8);
+  return d;
+}
+static u128 bw_sum2_of(const bsc_bw_sum *s) { return ((u128)s->_pad << 64) | s->sum_m2; }
+
 /* ---- the writer ------------------------------------------------------------------------------------------------------------------------- */
 typedef struct {
   uint32_t tid;
   bsc_bw_sum s;
   uint64_t off;  /* a section's place in the file (not used by a zoom record) */
   uint64_t size; /* and its bytes there */
+  u128 wide_m, wide_m2; /* a coverage writer's zoom record: the sums of c and of c * c as merged, held wide enough that nothing wraps */
 } bw_rec;
+
+static void rec_wide_set(bw_rec *r) {
+  r->wide_m = r->s.sum_m;
+  r->wide_m2 = bw_sum2_of(&r->s);
+}
+static void rec_merge(bw_rec *r, const bw_rec *t) {
+  sum_merge(&r->s, &t->s);
+  r->wide_m += t->wide_m;
+  r->wide_m2 += t->wide_m2;
+}
 
 struct bsc_bigwig {
   int fd;
@@ -173,18 +247,21 @@ struct bsc_bigwig {
   uint64_t n_z0, cap_z0;
   int have_last, finished;
   int mode; /* 0 until the first non-empty add; then BW_PLAIN or BW_Z */
+  uint32_t track; /* BSC_BW_LEVEL or BSC_BW_COVERAGE: what the summaries' integers are, and how they become floats */
   uint32_t last_tid, last_end;
 };
 enum { BW_PLAIN = 1, BW_Z = 2 };
 
-int bsc_bigwig_open(int fd, uint32_t n_refs, const char *const *names, const uint32_t *lens, const bsc_bw_params *bw_params, bsc_bigwig **out) {
-  static const char who[] = "bsc_bigwig_open";
+static int bw_open(const char *who, int fd, uint32_t n_refs, const char *const *names, const uint32_t *lens, const bsc_bw_params *bw_params, uint32_t track,
+                   bsc_bigwig **out) {
   if (out) *out = NULL;
   if (!out || fd < 0 || (n_refs && (!names || !lens))) return bsc_set_error(BSC_ERR_ARG, "%s: NULL argument", who);
+  if (track != BSC_BW_LEVEL && track != BSC_BW_COVERAGE) return bsc_set_error(BSC_ERR_ARG, "%s: track is %u, not BSC_BW_LEVEL or BSC_BW_COVERAGE", who, track);
   if (!bw_params_ok(bw_params)) return bsc_set_error(BSC_ERR_ARG, "%s: items_per_section is 1 .. 65535, reduction 1 or more", who);
   bsc_bigwig *bw = calloc(1, sizeof *bw);
   if (!bw) return bsc_set_error(BSC_ERR_NOMEM, "%s: out of memory", who);
   bw->fd = fd;
+  bw->track = track;
   bw->par = *bw_params;
   bw->names = calloc(n_refs ? n_refs : 1, sizeof *bw->names);
   bw->lens = calloc(n_refs ? n_refs : 1, sizeof *bw->lens);
@@ -216,6 +293,15 @@ int bsc_bigwig_open(int fd, uint32_t n_refs, const char *const *names, const uin
   bw->data_start = 296 + chrom_tree_bytes(n_refs, bw->key_size);
   *out = bw;
   return BSC_OK;
+}
+
+int bsc_bigwig_open(int fd, uint32_t n_refs, const char *const *names, const uint32_t *lens, const bsc_bw_params *bw_params, bsc_bigwig **out) {
+  return bw_open("bsc_bigwig_open", fd, n_refs, names, lens, bw_params, BSC_BW_LEVEL, out);
+}
+
+int bsc_bigwig_open_track(int fd, uint32_t n_refs, const char *const *names, const uint32_t *lens, const bsc_bw_params *bw_params, uint32_t track,
+                          bsc_bigwig **out) {
+  return bw_open("bsc_bigwig_open_track", fd, n_refs, names, lens, bw_params, track, out);
 }
 
 void bsc_bigwig_close(bsc_bigwig *bw) {
@@ -285,7 +371,8 @@ static int bw_add(bsc_bigwig *bw, const char *who, uint32_t tid, const void *dat
     bw_rec *r = &bw->sec[bw->n_sec++];
     r->tid = tid;
     r->s = sections[k];
-    r->s._pad = 0;
+    if (bw->track == BSC_BW_LEVEL) r->s._pad = 0;
+    rec_wide_set(r);
     r->off = at;
     r->size = z ? z_sizes[k] : 24 + 8 * (uint64_t)sections[k].count;
     at += z ? z_sizes[k] : 24 + 8 * S;
@@ -293,14 +380,21 @@ static int bw_add(bsc_bigwig *bw, const char *who, uint32_t tid, const void *dat
   for (uint64_t k = 0; k < n_zoom0; k++) {
     bw_rec *prev = bw->n_z0 ? &bw->z0[bw->n_z0 - 1] : NULL;
     if (!k && prev && prev->tid == tid && prev->s.start / red == zoom0[0].start / red) { /* a window two blocks share */
-      sum_merge(&prev->s, &zoom0[0]);
+      bw_rec first;
+      first.s = zoom0[0];
+      if (bw->track == BSC_BW_LEVEL) first.s._pad = 0;
+      rec_wide_set(&first);
+      rec_merge(prev, &first);
+      if (bw->track == BSC_BW_LEVEL) prev->s._pad = 0;
       continue;
     }
     bw->z0[bw->n_z0].tid = tid;
     bw->z0[bw->n_z0].s = zoom0[k];
     bw->z0[bw->n_z0].off = 0;
     bw->z0[bw->n_z0].size = 0;
-    bw->z0[bw->n_z0++].s._pad = 0;
+    if (bw->track == BSC_BW_LEVEL) bw->z0[bw->n_z0].s._pad = 0;
+    rec_wide_set(&bw->z0[bw->n_z0]);
+    bw->n_z0++;
   }
   bw->data_bytes += n_bytes;
   bw->have_last = 1;
@@ -322,7 +416,7 @@ int bsc_bigwig_add_z(bsc_bigwig *bw, uint32_t tid, const void *zdata, uint64_t z
 
 /* a zoom level's records at file offset `at`: the count, the blocks — each deflated (compress2, the default level) where z —, the R-tree
  * over the blocks; *index = the tree's offset; *max_raw: raised to the largest block's raw bytes */
-static int zoom_level_put(bw_buf *b, const bw_rec *r, uint64_t n, uint64_t at, uint64_t *index, int z, uint64_t *max_raw) {
+static int zoom_level_put(bw_buf *b, const bw_rec *r, uint64_t n, uint64_t at, uint64_t *index, int z, uint64_t *max_raw, uint32_t track) {
   const uint64_t b0 = b->n;
   rt_item *it = malloc((size_t)(n ? n : 1) * sizeof *it); /* (at most one block per record) */
   if (!it) return -1;
@@ -340,6 +434,13 @@ static int zoom_level_put(bw_buf *b, const bw_rec *r, uint64_t n, uint64_t at, u
       buf_u32(b, s->start);
       buf_u32(b, s->end);
       buf_u32(b, s->count);
+      if (track == BSC_BW_COVERAGE) { /* each from the exact integer, once */
+        buf_f32(b, bw_f32_of(s->min_m));
+        buf_f32(b, bw_f32_of(s->max_m));
+        buf_f32(b, bw_f32_of(r[i].wide_m));
+        buf_f32(b, bw_f32_of(r[i].wide_m2));
+        continue;
+      }
       buf_f32(b, (float)((double)s->min_m / 10.0));
       buf_f32(b, (float)((double)s->max_m / 10.0));
       buf_f32(b, (float)((double)s->sum_m / 10.0));
@@ -380,6 +481,7 @@ int bsc_bigwig_finish(bsc_bigwig *bw) {
   /* the sections' index */
   rt_item *it = malloc((size_t)(bw->n_sec ? bw->n_sec : 1) * sizeof *it);
   uint64_t covered = 0, min_m = 0, max_m = 0, sum_m = 0, sum_m2 = 0, max_raw = 0;
+  u128 wide_m = 0, wide_m2 = 0; /* a coverage file's totals: nothing wraps */
   const int z = bw->mode == BW_Z;
   if (!it) rc = -1;
   for (uint64_t k = 0; k < bw->n_sec && !rc; k++) {
@@ -392,6 +494,8 @@ int bsc_bigwig_finish(bsc_bigwig *bw) {
     covered += s->s.count;
     sum_m += s->s.sum_m;
     sum_m2 += s->s.sum_m2;
+    wide_m += s->s.sum_m;
+    wide_m2 += bw_sum2_of(&s->s);
   }
   if (!rc) rc = rtree_put(&tail, it, bw->n_sec, index_at, index_at, 1);
   free(it);
@@ -409,7 +513,7 @@ int bsc_bigwig_finish(bsc_bigwig *bw) {
       }
       uint64_t m = 0;
       for (uint64_t i = 0; i < n_cur; i++) {
-        if (m && next[m - 1].tid == cur[i].tid && next[m - 1].s.start / width == cur[i].s.start / width) sum_merge(&next[m - 1].s, &cur[i].s);
+        if (m && next[m - 1].tid == cur[i].tid && next[m - 1].s.start / width == cur[i].s.start / width) rec_merge(&next[m - 1], &cur[i]);
         else next[m++] = cur[i];
       }
       free(own);
@@ -418,7 +522,7 @@ int bsc_bigwig_finish(bsc_bigwig *bw) {
     }
     z_red[l] = width < 0xffffffffull ? width : 0xffffffffull;
     z_data[l] = index_at + tail.n;
-    rc = zoom_level_put(&tail, cur, n_cur, z_data[l], &z_index[l], z, &max_raw);
+    rc = zoom_level_put(&tail, cur, n_cur, z_data[l], &z_index[l], z, &max_raw, bw->track);
     levels = l + 1;
   }
   free(own);
@@ -443,10 +547,17 @@ int bsc_bigwig_finish(bsc_bigwig *bw) {
     buf_u64(&head, l < levels ? z_index[l] : 0);
   }
   buf_u64(&head, covered);
-  buf_f64(&head, (double)min_m / 10.0);
-  buf_f64(&head, (double)max_m / 10.0);
-  buf_f64(&head, (double)sum_m / 10.0);
-  buf_f64(&head, (double)sum_m2 / 100.0);
+  if (bw->track == BSC_BW_COVERAGE) {
+    buf_f64(&head, bw_f64_of(min_m));
+    buf_f64(&head, bw_f64_of(max_m));
+    buf_f64(&head, bw_f64_of(wide_m));
+    buf_f64(&head, bw_f64_of(wide_m2));
+  } else {
+    buf_f64(&head, (double)min_m / 10.0);
+    buf_f64(&head, (double)max_m / 10.0);
+    buf_f64(&head, (double)sum_m / 10.0);
+    buf_f64(&head, (double)sum_m2 / 100.0);
+  }
   if (!rc) rc = chrom_tree_put(&head, bw->n_refs, bw->key_size, bw->names, bw->lens, 296);
   buf_u64(&head, bw->n_sec);
   if (!rc && (head.oom || tail.oom)) rc = -1;

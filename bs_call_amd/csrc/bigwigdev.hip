@@ -19,66 +19,9 @@
  *                              which no order can change.
  *
  * Positions increase with the index, so the compact sites are sorted by start: a section is a range of ranks, a window too.
- * rank / S and start / reduction go through a 64-bit multiply-high with ceil(2^64 / d), exact for a 32-bit dividend and any divisor of
- * 2 .. 2^32 - 1 (d = 1: the dividend itself) — the compiler's expansion of a division by a variable goes through a floating-point
- * reciprocal; m is found by bisection over 0 .. 1000 for the same reason.
+ * The divisions, m and the site predicate are csrc/bigwig_dev.h.
  */
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-
-#include "../../include/bscall_amd.h"
-
-static_assert(sizeof(bsc_vcf_rec) == 128 && sizeof(bsc_vcf_core) == 64, "bsc_vcf_rec is 128 bytes, its core the first 64");
-static_assert(sizeof(bsc_bw_sum) == 40, "a summary is 40 bytes");
-
-#define BW_WAVES 4u
-
-struct bw_args {
-  const uint8_t *core, *aux; /* 64 bytes per position each */
-  const uint8_t *emit;       /* the chain's byte per position, or NULL */
-  uint64_t n;                /* positions */
-  int32_t all_contexts;
-  uint32_t min_cov, min_phred;
-  int32_t pass_only;
-  uint32_t x0, chrom_id;
-  uint32_t S, red;
-  uint64_t S_magic, red_magic; /* ceil(2^64 / d), d >= 2 */
-};
-
-/* v / d, v < 2^32 */
-__device__ __forceinline__ uint32_t bw_div(uint32_t v, uint32_t d, uint64_t magic) {
-  return d == 1u ? v : (uint32_t)__umul64hi((uint64_t)v, magic);
-}
-
-/* (2000 a + n) / (2 n), n = a + b > 0: the largest q of 0 .. 1000 with 2 n q <= 2000 a + n */
-__device__ __forceinline__ unsigned bw_m(uint64_t a, uint64_t n) {
-  const uint64_t num = 2000ull * a + n, den = 2ull * n;
-  unsigned lo = 0u, hi = 1000u;
-  while (lo < hi) {
-    const unsigned mid = (lo + hi + 1u) >> 1;
-    if (den * mid <= num) lo = mid; else hi = mid - 1u;
-  }
-  return lo;
-}
-
-/* entry i < n: is it a site, and its a and b (the per-cytosine rule, restated from the header) */
-__device__ __forceinline__ bool bw_site_of(const bw_args &g, uint64_t i, uint32_t &a, uint32_t &b) {
-  if (g.emit && !g.emit[i]) return false;
-  const uint4 v0 = *reinterpret_cast<const uint4 *>(g.core + i * 64u);
-  const unsigned emit = v0.y & 0xffu, gt = (v0.y >> 8) & 0xffu, flt = v0.z & 0xffu, phred = (v0.z >> 8) & 0xffu, cg = v0.z >> 24;
-  if (!emit || (gt != 4u && gt != 7u)) return false;
-  if (cg != 'C' && !(g.all_contexts && cg == 'H')) return false;
-  if (phred < g.min_phred || (g.pass_only && flt)) return false;
-  const uint4 c1 = reinterpret_cast<const uint4 *>(g.aux + i * 64u)[1]; /* counts[4 .. 7] */
-  const bool minus = gt == 7u;
-  a = minus ? c1.z : c1.y; /* counts[6] : counts[5] */
-  b = minus ? c1.x : c1.w; /* counts[4] : counts[7] */
-  return (uint64_t)a + b >= (uint64_t)(g.min_cov > 1u ? g.min_cov : 1u);
-}
-
-__device__ __forceinline__ unsigned bw_lanes_below(unsigned long long mask, unsigned lane) {
-  return (unsigned)__popcll(mask & ((1ull << lane) - 1ull));
-}
+#include "bigwig_dev.h" /* bw_args, bw_div, bw_m, bw_site_of, bw_lanes_below, bw_window: shared with bwcovdev.hip */
 
 /* cnt: [n_tiles + 1] */
 extern "C" __global__ __launch_bounds__(256) void bsc_bigwig_tile_kernel(bw_args g, uint32_t n_tiles, unsigned long long *__restrict__ cnt) {
@@ -134,9 +77,6 @@ extern "C" __global__ __launch_bounds__(256) void bsc_bigwig_write_kernel(bw_arg
     if (in == g.S - 1u || (uint64_t)rank == n_sites - 1u) reinterpret_cast<uint32_t *>(sec)[2] = start + 1u;
   }
 }
-
-/* the window of a start */
-__device__ __forceinline__ uint32_t bw_window(const bw_args &g, uint32_t start) { return bw_div(start, g.red, g.red_magic); }
 
 /* hcnt: [n_tiles + 1]: window heads per 64 compact sites (n_sites <= n: n_tiles tiles cover them) */
 extern "C" __global__ __launch_bounds__(256) void bsc_bigwig_heads_kernel(bw_args g, uint32_t n_tiles, const unsigned long long *__restrict__ off,
@@ -240,7 +180,22 @@ extern "C" __global__ __launch_bounds__(256) void bsc_bigwig_reduce_kernel(bw_ar
 
 extern "C" int bsc_dev_scan_u64(const void *in, void *out, uint32_t n, void *tmp, size_t tmp_bytes, void *stream); /* sort.hip */
 
-static uint64_t bw_magic(uint32_t d) { return d < 2u ? 0ull : 0xffffffffffffffffull / d + 1ull; } /* ceil(2^64 / d) */
+/* the three kernels the coverage launch (bwcovdev.hip) reuses as they are, launched from this file (a kernel is launched where it is compiled) */
+extern "C" int bsc_dev_bigwig_tile(const bw_args *g, uint32_t n_tiles, void *cnt, unsigned grid, void *stream) {
+  hipLaunchKernelGGL(bsc_bigwig_tile_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, *g, n_tiles, (unsigned long long *)cnt);
+  return (int)hipGetLastError();
+}
+extern "C" int bsc_dev_bigwig_heads(const bw_args *g, uint32_t n_tiles, const void *off, const void *sites, void *hcnt, unsigned grid, void *stream) {
+  hipLaunchKernelGGL(bsc_bigwig_heads_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, *g, n_tiles, (const unsigned long long *)off,
+                     (const uint2 *)sites, (unsigned long long *)hcnt);
+  return (int)hipGetLastError();
+}
+extern "C" int bsc_dev_bigwig_windows(const bw_args *g, uint32_t n_tiles, const void *off, const void *hoff, const void *sites, void *wbeg, void *totals,
+                                      unsigned grid, void *stream) {
+  hipLaunchKernelGGL(bsc_bigwig_windows_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, *g, n_tiles, (const unsigned long long *)off,
+                     (const unsigned long long *)hoff, (const uint2 *)sites, (uint32_t *)wbeg, (unsigned long long *)totals);
+  return (int)hipGetLastError();
+}
 
 /*
  * core[n] / aux[n]: the per-position arrays, entry i = position x0 + i; emit: the chain's byte per position or NULL.  cnt / off / hcnt /

@@ -93,6 +93,10 @@ int bsc_dev_launch_bigwig(const void *core, const void *aux, const void *emit, u
                           const bsc_bw_params *bwp, const void *val, void *cnt, void *off, void *hcnt, void *hoff, void *scan_tmp, size_t scan_tmp_bytes,
                           void *sites, void *wbeg, void *out, uint64_t out_cap, void *sections, uint64_t sec_cap, void *zoom, uint64_t zoom_cap,
                           void *totals, int num_cus, void *stream); /* bigwigdev.hip */
+int bsc_dev_launch_bigwig_tracks(const void *core, const void *aux, const void *emit, uint64_t n, uint32_t x0, uint32_t chrom_id,
+                                 const bsc_meth_params *par, const bsc_bw_params *bwp, uint32_t tracks, const void *val, void *cnt, void *off, void *hcnt,
+                                 void *hoff, void *scan_tmp, size_t scan_tmp_bytes, void *sites, void *cov, void *wbeg, const bsc_bw_track_out *level,
+                                 const bsc_bw_track_out *coverage, void *totals, int num_cus, void *stream); /* bwcovdev.hip */
 const float *bsc_bw_values(void);                                    /* bigwig.c: (float)(m / 10.0), m = 0 .. 1000 */
 int bsc_dev_launch_zlib_ranges(const void *src, const void *range_offs, uint32_t max_piece, uint32_t n_pieces, void *slots, void *sizes, void *offs,
                                void *scratch, uint32_t grid, void *out, uint64_t out_cap, void *sizes_out, uint64_t sizes_cap, void *totals, int num_cus,
@@ -124,6 +128,24 @@ int bsc_dev_launch_dbsnp_names(const bsc_dbsnp_flat *f, uint32_t e0, uint32_t n_
 #define BSC_LN10 (2.30258509299404568402) /* the reference's LOG10 literal (include/bs_call.h:36) */
 #define BSC_HOST_CHUNK (4u << 20)         /* sites per host->device round trip (4 Mi sites = 1.2 GiB of records) */
 #define BSC_MAX_LAUNCH (1ull << 31)       /* sites per launch: site indices in the het list are 32-bit */
+
+/* one bigWig track's data of a block (the level track's or the coverage track's): the stream, the section and window summaries, their host
+ * copies, the stream's length; whether a block call filled them, and with which S; for the deflate behind it the sections' zlib streams,
+ * their sizes, the two totals, the host copy of the sizes, the streams' length */
+struct bsc_bw_block {
+  void *d_data, *d_sec, *d_zoom;
+  size_t cap_data, cap_sec, cap_zoom;
+  bsc_bw_sum *h_sec, *h_zoom;
+  size_t cap_hsec, cap_hzoom;
+  uint64_t bytes;
+  int kept;
+  uint32_t kept_S;
+  void *d_z, *d_zsz, *d_ztot;
+  size_t cap_z, cap_zsz, cap_ztot;
+  uint32_t *h_zsz;
+  size_t cap_hzsz;
+  uint64_t z_bytes;
+};
 
 struct bsc_context {
   bsc_params params;
@@ -210,26 +232,17 @@ struct bsc_context {
     size_t cap_pl, cap_sc, cap_tmp;
     hipStream_t last;
   } mr;
-  struct { /* the bigWig track (bigwigdev.hip): the 1001 floats; the workspaces of a call — sites per tile and window heads per tile with their
+  struct { /* the bigWig tracks (bigwigdev.hip, bwcovdev.hip): the 1001 floats; the workspaces of a call — sites per tile and window heads per tile with their
             * prefix sums, scan scratch, the compact {start, m} sites, the windows' first ranks; bsc_block_bigwig_kept: the block's stream, its
             * section and window summaries, the six totals, the host copies of the summaries, the stream's length */
     void *d_val;
     void *d_cnt, *d_off, *d_hcnt, *d_hoff, *d_tmp, *d_sites, *d_wbeg;
     size_t cap_cnt, cap_off, cap_hcnt, cap_hoff, cap_tmp, cap_sites, cap_wbeg;
-    void *d_data, *d_sec, *d_zoom, *d_tot;
-    size_t cap_data, cap_sec, cap_zoom, cap_tot;
-    bsc_bw_sum *h_sec, *h_zoom;
-    size_t cap_hsec, cap_hzoom;
-    uint64_t bytes;
-    /* bsc_block_bigwig_deflate: whether bsc_block_bigwig_kept came before it, and with which S; the zlib streams of that block's sections,
-     * their sizes, the two totals, the host copy of the sizes, the streams' length */
-    int kept;
-    uint32_t kept_S;
-    void *d_z, *d_zsz, *d_ztot;
-    size_t cap_z, cap_zsz, cap_ztot;
-    uint32_t *h_zsz;
-    size_t cap_hzsz;
-    uint64_t z_bytes;
+    void *d_cov; /* the compact coverage values c beside d_sites (bwcovdev.hip) */
+    size_t cap_cov;
+    void *d_tot;
+    size_t cap_tot;
+    struct bsc_bw_block lv, cv; /* the level track's block (bsc_block_bigwig_kept, or bit 0 of bsc_block_bigwig_tracks_kept) and the coverage's */
   } bw;
   struct { /* the bigBed items (bigbeddev.hip): the workspaces of a call — item lengths, sites and bytes per tile and window heads per tile with
             * their prefix sums, scan scratch, the compact starts, the windows' first ranks */
@@ -691,16 +704,19 @@ int bsc_destroy(bsc_context *ctx) {
   hipFree(ctx->bw.d_tmp);
   hipFree(ctx->bw.d_sites);
   hipFree(ctx->bw.d_wbeg);
-  hipFree(ctx->bw.d_data);
-  hipFree(ctx->bw.d_sec);
-  hipFree(ctx->bw.d_zoom);
+  hipFree(ctx->bw.d_cov);
   hipFree(ctx->bw.d_tot);
-  free(ctx->bw.h_sec);
-  free(ctx->bw.h_zoom);
-  hipFree(ctx->bw.d_z);
-  hipFree(ctx->bw.d_zsz);
-  hipFree(ctx->bw.d_ztot);
-  free(ctx->bw.h_zsz);
+  for (struct bsc_bw_block *b = &ctx->bw.lv; b; b = b == &ctx->bw.lv ? &ctx->bw.cv : NULL) {
+    hipFree(b->d_data);
+    hipFree(b->d_sec);
+    hipFree(b->d_zoom);
+    free(b->h_sec);
+    free(b->h_zoom);
+    hipFree(b->d_z);
+    hipFree(b->d_zsz);
+    hipFree(b->d_ztot);
+    free(b->h_zsz);
+  }
   hipFree(ctx->bb.d_len);
   hipFree(ctx->bb.d_cnt);
   hipFree(ctx->bb.d_off);
@@ -3318,14 +3334,12 @@ static int bsc_bigwig_params_check(const char *who, const bsc_meth_params *par, 
   return BSC_OK;
 }
 
-/* the kernels over d_core[n] / d_aux[n] (entry i = position x0 + i, n >= 1) on stream s, in the context's workspaces */
-static int bsc_bigwig_run(bsc_context *ctx, const char *who, const void *d_core, const void *d_aux, const void *d_emit, uint32_t n, uint32_t x0,
-                          uint32_t chrom_id, const bsc_meth_params *par, const bsc_bw_params *bwp, void *d_out, uint64_t out_cap, void *d_sections,
-                          uint64_t sec_cap, void *d_zoom, uint64_t zoom_cap, void *d_totals, hipStream_t s) {
+/* the workspaces of a call over n positions; *scan_bytes: the scans' scratch */
+static int bsc_bigwig_reserve(bsc_context *ctx, const char *who, uint32_t n, int coverage, size_t *scan_bytes) {
   const uint32_t n_tiles = (uint32_t)(((uint64_t)n + 63u) / 64u);
-  size_t scan_bytes = 0;
   int rc;
-  if (bsc_dev_scan_tmp_bytes_u64(n_tiles + 1u, &scan_bytes)) return bsc_fail(BSC_ERR_HIP, "%s: scan size query failed", who);
+  *scan_bytes = 0;
+  if (bsc_dev_scan_tmp_bytes_u64(n_tiles + 1u, scan_bytes)) return bsc_fail(BSC_ERR_HIP, "%s: scan size query failed", who);
   if (!ctx->bw.d_val) { /* the table of the 1001 floats, uploaded verbatim (the host's copy is static) */
     HIP_TRY(hipMalloc(&ctx->bw.d_val, 1001 * sizeof(float)));
     HIP_TRY(hipMemcpy(ctx->bw.d_val, bsc_bw_values(), 1001 * sizeof(float), hipMemcpyHostToDevice));
@@ -3334,12 +3348,37 @@ static int bsc_bigwig_run(bsc_context *ctx, const char *who, const void *d_core,
   if ((rc = bsc_reserve(&ctx->bw.d_off, &ctx->bw.cap_off, ((size_t)n_tiles + 1u) * 8u))) return rc;
   if ((rc = bsc_reserve(&ctx->bw.d_hcnt, &ctx->bw.cap_hcnt, ((size_t)n_tiles + 1u) * 8u))) return rc;
   if ((rc = bsc_reserve(&ctx->bw.d_hoff, &ctx->bw.cap_hoff, ((size_t)n_tiles + 1u) * 8u))) return rc;
-  if ((rc = bsc_reserve(&ctx->bw.d_tmp, &ctx->bw.cap_tmp, scan_bytes ? scan_bytes : 1))) return rc;
+  if ((rc = bsc_reserve(&ctx->bw.d_tmp, &ctx->bw.cap_tmp, *scan_bytes ? *scan_bytes : 1))) return rc;
   if ((rc = bsc_reserve(&ctx->bw.d_sites, &ctx->bw.cap_sites, (size_t)n * 8u))) return rc;
   if ((rc = bsc_reserve(&ctx->bw.d_wbeg, &ctx->bw.cap_wbeg, ((size_t)n + 1u) * 4u))) return rc;
+  if (coverage && (rc = bsc_reserve(&ctx->bw.d_cov, &ctx->bw.cap_cov, (size_t)n * 4u))) return rc;
+  return BSC_OK;
+}
+
+/* the kernels over d_core[n] / d_aux[n] (entry i = position x0 + i, n >= 1) on stream s, in the context's workspaces */
+static int bsc_bigwig_run(bsc_context *ctx, const char *who, const void *d_core, const void *d_aux, const void *d_emit, uint32_t n, uint32_t x0,
+                          uint32_t chrom_id, const bsc_meth_params *par, const bsc_bw_params *bwp, void *d_out, uint64_t out_cap, void *d_sections,
+                          uint64_t sec_cap, void *d_zoom, uint64_t zoom_cap, void *d_totals, hipStream_t s) {
+  size_t scan_bytes = 0;
+  int rc;
+  if ((rc = bsc_bigwig_reserve(ctx, who, n, 0, &scan_bytes))) return rc;
   const int e = bsc_dev_launch_bigwig(d_core, d_aux, d_emit, n, x0, chrom_id, par, bwp, ctx->bw.d_val, ctx->bw.d_cnt, ctx->bw.d_off, ctx->bw.d_hcnt,
                                       ctx->bw.d_hoff, ctx->bw.d_tmp, scan_bytes, ctx->bw.d_sites, ctx->bw.d_wbeg, d_out, out_cap, d_sections, sec_cap,
                                       d_zoom, zoom_cap, d_totals, ctx->num_cus, (void *)s);
+  if (e) return bsc_fail(BSC_ERR_HIP, "%s: launch failed: %s", who, hipGetErrorString((hipError_t)e));
+  return BSC_OK;
+}
+
+/* the same for a mask of tracks, in one sweep (bwcovdev.hip) */
+static int bsc_bigwig_tracks_run(bsc_context *ctx, const char *who, const void *d_core, const void *d_aux, const void *d_emit, uint32_t n, uint32_t x0,
+                                 uint32_t chrom_id, const bsc_meth_params *par, const bsc_bw_params *bwp, uint32_t tracks, const bsc_bw_track_out *level,
+                                 const bsc_bw_track_out *coverage, void *d_totals, hipStream_t s) {
+  size_t scan_bytes = 0;
+  int rc;
+  if ((rc = bsc_bigwig_reserve(ctx, who, n, (tracks & BSC_BW_COVERAGE) != 0, &scan_bytes))) return rc;
+  const int e = bsc_dev_launch_bigwig_tracks(d_core, d_aux, d_emit, n, x0, chrom_id, par, bwp, tracks, ctx->bw.d_val, ctx->bw.d_cnt, ctx->bw.d_off,
+                                             ctx->bw.d_hcnt, ctx->bw.d_hoff, ctx->bw.d_tmp, scan_bytes, ctx->bw.d_sites, ctx->bw.d_cov, ctx->bw.d_wbeg, level,
+                                             coverage, d_totals, ctx->num_cus, (void *)s);
   if (e) return bsc_fail(BSC_ERR_HIP, "%s: launch failed: %s", who, hipGetErrorString((hipError_t)e));
   return BSC_OK;
 }
@@ -3366,6 +3405,34 @@ int bsc_bigwig_sites_device(bsc_context *ctx, const void *d_core, const void *d_
                         d_totals, (hipStream_t)stream);
 }
 
+int bsc_bigwig_tracks_device(bsc_context *ctx, const void *d_core, const void *d_aux, uint32_t n, uint32_t x0, uint32_t chrom_id,
+                             const bsc_meth_params *params, const bsc_bw_params *bw_params, uint32_t tracks, const bsc_bw_track_out *level_out,
+                             const bsc_bw_track_out *cov_out, void *d_totals, void *stream) {
+  static const char who[] = "bsc_bigwig_tracks_device";
+  int rc;
+  if (!ctx || !d_totals || (n && (!d_core || !d_aux))) return bsc_fail(BSC_ERR_ARG, "%s: NULL argument", who);
+  if (tracks < 1u || tracks > 3u) return bsc_fail(BSC_ERR_ARG, "%s: tracks is %u, not 1 (level), 2 (coverage) or 3", who, tracks);
+  if (((tracks & BSC_BW_LEVEL) && !level_out) || ((tracks & BSC_BW_COVERAGE) && !cov_out))
+    return bsc_fail(BSC_ERR_ARG, "%s: a track of the mask has no descriptor", who);
+  if ((rc = bsc_bigwig_params_check(who, params, bw_params))) return rc;
+  if (((uintptr_t)d_core | (uintptr_t)d_aux) & 15u) return bsc_fail(BSC_ERR_ARG, "%s: the arrays must be 16-byte aligned", who);
+  if ((uintptr_t)d_totals & 7u) return bsc_fail(BSC_ERR_ARG, "%s: the outputs must be 8-byte aligned", who);
+  for (int t = 0; t < 2; t++) {
+    const bsc_bw_track_out *o = t ? cov_out : level_out;
+    if (!(tracks & (1u << t))) continue;
+    if ((o->out_cap && !o->d_out) || (o->sec_cap && !o->d_sections) || (o->zoom_cap && !o->d_zoom)) return bsc_fail(BSC_ERR_ARG, "%s: NULL argument", who);
+    if (((uintptr_t)o->d_out | (uintptr_t)o->d_sections | (uintptr_t)o->d_zoom) & 7u) return bsc_fail(BSC_ERR_ARG, "%s: the outputs must be 8-byte aligned", who);
+  }
+  if (x0 < 1u) return bsc_fail(BSC_ERR_ARG, "%s: positions are 1-based (x0 = 0)", who);
+  if (n && (uint64_t)x0 + n - 1u > 0xffffffffull) return bsc_fail(BSC_ERR_ARG, "%s: x0 + n - 1 = %llu is beyond 2^32 - 1", who, (unsigned long long)x0 + n - 1u);
+  BSC_ENTER(ctx);
+  if (!n) { /* no position, no site: nothing to launch */
+    HIP_TRY(hipMemsetAsync(d_totals, 0, 6 * sizeof(unsigned long long), (hipStream_t)stream));
+    return BSC_OK;
+  }
+  return bsc_bigwig_tracks_run(ctx, who, d_core, d_aux, NULL, n, x0, chrom_id, params, bw_params, tracks, level_out, cov_out, d_totals, (hipStream_t)stream);
+}
+
 static int bsc_host_room(bsc_bw_sum **p, size_t *cap, uint64_t need) {
   if (need <= *cap) return BSC_OK;
   free(*p);
@@ -3376,24 +3443,37 @@ static int bsc_host_room(bsc_bw_sum **p, size_t *cap, uint64_t need) {
   return BSC_OK;
 }
 
-int bsc_block_bigwig_kept(bsc_context *ctx, uint32_t chrom_id, const bsc_meth_params *params, const bsc_bw_params *bw_params, uint64_t *n_bytes,
-                          uint64_t *n_sites, const bsc_bw_sum **sections, uint64_t *n_sections, const bsc_bw_sum **zoom0, uint64_t *n_zoom0) {
-  static const char who[] = "bsc_block_bigwig_kept";
+static void bsc_bw_block_forget(struct bsc_bw_block *b) {
+  b->bytes = 0;
+  b->kept = 0;
+  b->z_bytes = 0;
+}
+
+/* bsc_block_bigwig_kept (tracks 0: the level track by the kernels of bigwigdev.hip alone) and bsc_block_bigwig_tracks_kept (tracks 1 .. 3: by
+ * bwcovdev.hip's sweep); sec[t] / zoom[t]: where track t's host copies are reported, or NULL */
+static int bsc_block_bigwig_do(bsc_context *ctx, const char *who, uint32_t chrom_id, const bsc_meth_params *params, const bsc_bw_params *bw_params,
+                               uint32_t tracks, uint64_t *n_bytes, uint64_t *n_sites, uint64_t *n_sections, uint64_t *n_zoom0, const bsc_bw_sum **sec[2],
+                               const bsc_bw_sum **zoom[2]) {
   int rc;
-  if (!ctx || !n_bytes || !sections || !n_sections || !zoom0 || !n_zoom0) return bsc_fail(BSC_ERR_ARG, "%s: NULL argument", who);
   *n_bytes = *n_sections = *n_zoom0 = 0;
-  *sections = *zoom0 = NULL;
+  for (int t = 0; t < 2; t++) {
+    if (sec[t]) *sec[t] = NULL;
+    if (zoom[t]) *zoom[t] = NULL;
+  }
   if (n_sites) *n_sites = 0;
-  ctx->bw.bytes = 0;
-  ctx->bw.kept = 0;
-  ctx->bw.z_bytes = 0;
+  bsc_bw_block_forget(&ctx->bw.lv);
+  bsc_bw_block_forget(&ctx->bw.cv);
   if ((rc = bsc_bigwig_params_check(who, params, bw_params))) return rc;
   if (ctx->meth_src != 1 || ctx->rec_pending || ctx->pending_sz)
     return bsc_fail(BSC_ERR_ARG, "%s: the last call left no single block's arrays on the device", who);
   const uint32_t n = ctx->again.sz, x0 = ctx->meth_x;
-  ctx->bw.kept_S = bw_params->items_per_section;
+  const uint32_t mask = tracks ? tracks : BSC_BW_LEVEL;
+  struct bsc_bw_block *const blk[2] = {&ctx->bw.lv, &ctx->bw.cv};
+  for (int t = 0; t < 2; t++)
+    if (mask & (1u << t)) blk[t]->kept_S = bw_params->items_per_section;
   if (!n) {
-    ctx->bw.kept = 1;
+    for (int t = 0; t < 2; t++)
+      if (mask & (1u << t)) blk[t]->kept = 1;
     return BSC_OK;
   }
   BSC_ENTER(ctx);
@@ -3402,13 +3482,27 @@ int bsc_block_bigwig_kept(bsc_context *ctx, uint32_t chrom_id, const bsc_meth_pa
   const uint64_t S = bw_params->items_per_section, red = bw_params->reduction;
   const uint64_t sec_cap = ((uint64_t)n + S - 1) / S, out_cap = 24 * sec_cap + 8 * (uint64_t)n;
   const uint64_t span = ((uint64_t)n + red - 1) / red + 1, zoom_cap = span < n ? span : n;
-  if ((rc = bsc_reserve(&ctx->bw.d_data, &ctx->bw.cap_data, (size_t)out_cap))) return rc;
-  if ((rc = bsc_reserve(&ctx->bw.d_sec, &ctx->bw.cap_sec, (size_t)sec_cap * sizeof(bsc_bw_sum)))) return rc;
-  if ((rc = bsc_reserve(&ctx->bw.d_zoom, &ctx->bw.cap_zoom, (size_t)zoom_cap * sizeof(bsc_bw_sum)))) return rc;
+  bsc_bw_track_out o[2] = {{0}};
+  for (int t = 0; t < 2; t++) {
+    struct bsc_bw_block *b = blk[t];
+    if (!(mask & (1u << t))) continue;
+    if ((rc = bsc_reserve(&b->d_data, &b->cap_data, (size_t)out_cap))) return rc;
+    if ((rc = bsc_reserve(&b->d_sec, &b->cap_sec, (size_t)sec_cap * sizeof(bsc_bw_sum)))) return rc;
+    if ((rc = bsc_reserve(&b->d_zoom, &b->cap_zoom, (size_t)zoom_cap * sizeof(bsc_bw_sum)))) return rc;
+    o[t].d_out = b->d_data;
+    o[t].out_cap = out_cap;
+    o[t].d_sections = b->d_sec;
+    o[t].sec_cap = sec_cap;
+    o[t].d_zoom = b->d_zoom;
+    o[t].zoom_cap = zoom_cap;
+  }
   if ((rc = bsc_reserve(&ctx->bw.d_tot, &ctx->bw.cap_tot, 6 * sizeof(unsigned long long)))) return rc;
-  if ((rc = bsc_bigwig_run(ctx, who, ctx->d_vout, ctx->d_out, ctx->again.emit, n, x0, chrom_id, params, bw_params, ctx->bw.d_data, out_cap, ctx->bw.d_sec,
-                           sec_cap, ctx->bw.d_zoom, zoom_cap, ctx->bw.d_tot, s)))
-    return rc;
+  if (!tracks)
+    rc = bsc_bigwig_run(ctx, who, ctx->d_vout, ctx->d_out, ctx->again.emit, n, x0, chrom_id, params, bw_params, o[0].d_out, out_cap, o[0].d_sections, sec_cap,
+                        o[0].d_zoom, zoom_cap, ctx->bw.d_tot, s);
+  else
+    rc = bsc_bigwig_tracks_run(ctx, who, ctx->d_vout, ctx->d_out, ctx->again.emit, n, x0, chrom_id, params, bw_params, tracks, &o[0], &o[1], ctx->bw.d_tot, s);
+  if (rc) return rc;
   unsigned long long tot[6] = {0, 0, 0, 0, 0, 0};
   HIP_TRY(hipMemcpyAsync(tot, ctx->bw.d_tot, sizeof tot, hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
@@ -3419,25 +3513,61 @@ int bsc_block_bigwig_kept(bsc_context *ctx, uint32_t chrom_id, const bsc_meth_pa
   if (tot[0] > out_cap || tot[2] > sec_cap || tot[3] > zoom_cap)
     return bsc_fail(BSC_ERR_ARG, "%s: the block's %llu bytes, %llu sections, %llu windows are beyond the room of %llu, %llu, %llu", who, tot[0], tot[2],
                     tot[3], (unsigned long long)out_cap, (unsigned long long)sec_cap, (unsigned long long)zoom_cap);
-  if ((rc = bsc_host_room(&ctx->bw.h_sec, &ctx->bw.cap_hsec, tot[2]))) return rc;
-  if ((rc = bsc_host_room(&ctx->bw.h_zoom, &ctx->bw.cap_hzoom, tot[3]))) return rc;
-  if (tot[2]) HIP_TRY(hipMemcpyAsync(ctx->bw.h_sec, ctx->bw.d_sec, (size_t)tot[2] * sizeof(bsc_bw_sum), hipMemcpyDeviceToHost, s));
-  if (tot[3]) HIP_TRY(hipMemcpyAsync(ctx->bw.h_zoom, ctx->bw.d_zoom, (size_t)tot[3] * sizeof(bsc_bw_sum), hipMemcpyDeviceToHost, s));
+  for (int t = 0; t < 2; t++) {
+    struct bsc_bw_block *b = blk[t];
+    if (!(mask & (1u << t))) continue;
+    if ((rc = bsc_host_room(&b->h_sec, &b->cap_hsec, tot[2]))) return rc;
+    if ((rc = bsc_host_room(&b->h_zoom, &b->cap_hzoom, tot[3]))) return rc;
+    if (tot[2]) HIP_TRY(hipMemcpyAsync(b->h_sec, b->d_sec, (size_t)tot[2] * sizeof(bsc_bw_sum), hipMemcpyDeviceToHost, s));
+    if (tot[3]) HIP_TRY(hipMemcpyAsync(b->h_zoom, b->d_zoom, (size_t)tot[3] * sizeof(bsc_bw_sum), hipMemcpyDeviceToHost, s));
+  }
   HIP_TRY(hipStreamSynchronize(s));
-  *sections = ctx->bw.h_sec;
-  *zoom0 = ctx->bw.h_zoom;
-  ctx->bw.bytes = tot[0];
-  ctx->bw.kept = 1;
+  for (int t = 0; t < 2; t++) {
+    struct bsc_bw_block *b = blk[t];
+    if (!(mask & (1u << t))) continue;
+    if (sec[t]) *sec[t] = b->h_sec;
+    if (zoom[t]) *zoom[t] = b->h_zoom;
+    b->bytes = tot[0];
+    b->kept = 1;
+  }
+  return BSC_OK;
+}
+
+int bsc_block_bigwig_kept(bsc_context *ctx, uint32_t chrom_id, const bsc_meth_params *params, const bsc_bw_params *bw_params, uint64_t *n_bytes,
+                          uint64_t *n_sites, const bsc_bw_sum **sections, uint64_t *n_sections, const bsc_bw_sum **zoom0, uint64_t *n_zoom0) {
+  static const char who[] = "bsc_block_bigwig_kept";
+  if (!ctx || !n_bytes || !sections || !n_sections || !zoom0 || !n_zoom0) return bsc_fail(BSC_ERR_ARG, "%s: NULL argument", who);
+  const bsc_bw_sum **sec[2] = {sections, NULL}, **zoom[2] = {zoom0, NULL};
+  return bsc_block_bigwig_do(ctx, who, chrom_id, params, bw_params, 0, n_bytes, n_sites, n_sections, n_zoom0, sec, zoom);
+}
+
+int bsc_block_bigwig_tracks_kept(bsc_context *ctx, uint32_t chrom_id, const bsc_meth_params *params, const bsc_bw_params *bw_params, uint32_t tracks,
+                                 uint64_t *n_bytes, uint64_t *n_sites, uint64_t *n_sections, uint64_t *n_zoom0, const bsc_bw_sum **level_sections,
+                                 const bsc_bw_sum **level_zoom0, const bsc_bw_sum **cov_sections, const bsc_bw_sum **cov_zoom0) {
+  static const char who[] = "bsc_block_bigwig_tracks_kept";
+  if (!ctx || !n_bytes || !n_sections || !n_zoom0) return bsc_fail(BSC_ERR_ARG, "%s: NULL argument", who);
+  if (tracks < 1u || tracks > 3u) return bsc_fail(BSC_ERR_ARG, "%s: tracks is %u, not 1 (level), 2 (coverage) or 3", who, tracks);
+  if (((tracks & BSC_BW_LEVEL) && (!level_sections || !level_zoom0)) || ((tracks & BSC_BW_COVERAGE) && (!cov_sections || !cov_zoom0)))
+    return bsc_fail(BSC_ERR_ARG, "%s: a track of the mask has nowhere to report its summaries", who);
+  const bsc_bw_sum **sec[2] = {level_sections, cov_sections}, **zoom[2] = {level_zoom0, cov_zoom0};
+  return bsc_block_bigwig_do(ctx, who, chrom_id, params, bw_params, tracks, n_bytes, n_sites, n_sections, n_zoom0, sec, zoom);
+}
+
+static int bsc_bw_stream_read(bsc_context *ctx, const char *who, const struct bsc_bw_block *b, uint64_t off, uint64_t n, void *dst) {
+  if (!ctx || (!dst && n)) return bsc_fail(BSC_ERR_ARG, "%s: NULL argument", who);
+  if (off + n > b->bytes || off + n > b->cap_data) return bsc_fail(BSC_ERR_ARG, "%s: beyond the stream's end", who);
+  if (!n) return BSC_OK;
+  BSC_ENTER(ctx);
+  HIP_TRY(hipMemcpyAsync(dst, (const char *)b->d_data + off, (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
   return BSC_OK;
 }
 
 int bsc_bigwig_stream_read(bsc_context *ctx, uint64_t off, uint64_t n, void *dst) {
-  if (!ctx || (!dst && n)) return bsc_fail(BSC_ERR_ARG, "bsc_bigwig_stream_read: NULL argument");
-  if (off + n > ctx->bw.bytes || off + n > ctx->bw.cap_data) return bsc_fail(BSC_ERR_ARG, "bsc_bigwig_stream_read: beyond the stream's end");
-  if (!n) return BSC_OK;
-  BSC_ENTER(ctx);
-  HIP_TRY(hipMemcpyAsync(dst, (const char *)ctx->bw.d_data + off, (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
-  return BSC_OK;
+  return bsc_bw_stream_read(ctx, "bsc_bigwig_stream_read", ctx ? &ctx->bw.lv : NULL, off, n, dst);
+}
+
+int bsc_bigwig_cov_stream_read(bsc_context *ctx, uint64_t off, uint64_t n, void *dst) {
+  return bsc_bw_stream_read(ctx, "bsc_bigwig_cov_stream_read", ctx ? &ctx->bw.cv : NULL, off, n, dst);
 }
 
 /* ---- zlib streams of fixed-stride pieces (zlibdev.hip) ------------------------------------------------------------------------------------ */
@@ -3505,52 +3635,69 @@ int bsc_zlib_ranges_device(bsc_context *ctx, const void *d_src, const void *d_of
   return BSC_OK;
 }
 
-int bsc_block_bigwig_deflate(bsc_context *ctx, uint64_t *z_bytes, const uint32_t **z_sizes, uint64_t *n_sections) {
-  static const char who[] = "bsc_block_bigwig_deflate";
+static int bsc_bw_block_deflate(bsc_context *ctx, const char *who, const char *before, struct bsc_bw_block *b, uint64_t *z_bytes, const uint32_t **z_sizes,
+                                uint64_t *n_sections) {
   int rc;
   if (!ctx || !z_bytes || !z_sizes || !n_sections) return bsc_fail(BSC_ERR_ARG, "%s: NULL argument", who);
   *z_bytes = *n_sections = 0;
   *z_sizes = NULL;
-  ctx->bw.z_bytes = 0;
-  if (!ctx->bw.kept) return bsc_fail(BSC_ERR_ARG, "%s: no bsc_block_bigwig_kept came before it", who);
-  const uint64_t piece = 24 + 8 * (uint64_t)ctx->bw.kept_S;
-  if (piece > 0xFF00u) return bsc_fail(BSC_ERR_ARG, "%s: a section of %u sites is %llu bytes, more than 65280 (at most 8157 sites)", who, ctx->bw.kept_S, (unsigned long long)piece);
-  const uint64_t n = ctx->bw.bytes;
+  b->z_bytes = 0;
+  if (!b->kept) return bsc_fail(BSC_ERR_ARG, "%s: no %s came before it", who, before);
+  const uint64_t piece = 24 + 8 * (uint64_t)b->kept_S;
+  if (piece > 0xFF00u) return bsc_fail(BSC_ERR_ARG, "%s: a section of %u sites is %llu bytes, more than 65280 (at most 8157 sites)", who, b->kept_S, (unsigned long long)piece);
+  const uint64_t n = b->bytes;
   if (!n) return BSC_OK;
   BSC_ENTER(ctx);
   hipStream_t s = ctx->stream;
   const uint64_t np = (n + piece - 1) / piece, out_cap = n + 11 * np;
-  if ((rc = bsc_reserve(&ctx->bw.d_z, &ctx->bw.cap_z, (size_t)out_cap))) return rc;
-  if ((rc = bsc_reserve(&ctx->bw.d_zsz, &ctx->bw.cap_zsz, (size_t)np * 4u))) return rc;
-  if ((rc = bsc_reserve(&ctx->bw.d_ztot, &ctx->bw.cap_ztot, 2 * sizeof(unsigned long long)))) return rc;
-  if (np > ctx->bw.cap_hzsz) {
-    free(ctx->bw.h_zsz);
-    ctx->bw.cap_hzsz = 0;
-    ctx->bw.h_zsz = malloc((size_t)(np + np / 4) * 4u);
-    if (!ctx->bw.h_zsz) return bsc_fail(BSC_ERR_NOMEM, "%s: out of host memory", who);
-    ctx->bw.cap_hzsz = (size_t)(np + np / 4);
+  if ((rc = bsc_reserve(&b->d_z, &b->cap_z, (size_t)out_cap))) return rc;
+  if ((rc = bsc_reserve(&b->d_zsz, &b->cap_zsz, (size_t)np * 4u))) return rc;
+  if ((rc = bsc_reserve(&b->d_ztot, &b->cap_ztot, 2 * sizeof(unsigned long long)))) return rc;
+  if (np > b->cap_hzsz) {
+    free(b->h_zsz);
+    b->cap_hzsz = 0;
+    b->h_zsz = malloc((size_t)(np + np / 4) * 4u);
+    if (!b->h_zsz) return bsc_fail(BSC_ERR_NOMEM, "%s: out of host memory", who);
+    b->cap_hzsz = (size_t)(np + np / 4);
   }
-  if ((rc = bsc_zlib_pieces_device(ctx, ctx->bw.d_data, n, (uint32_t)piece, ctx->bw.d_z, out_cap, ctx->bw.d_zsz, np, ctx->bw.d_ztot, (void *)s))) return rc;
+  if ((rc = bsc_zlib_pieces_device(ctx, b->d_data, n, (uint32_t)piece, b->d_z, out_cap, b->d_zsz, np, b->d_ztot, (void *)s))) return rc;
   unsigned long long tot[2] = {0, 0};
-  HIP_TRY(hipMemcpyAsync(tot, ctx->bw.d_ztot, sizeof tot, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipMemcpyAsync(ctx->bw.h_zsz, ctx->bw.d_zsz, (size_t)np * 4u, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipMemcpyAsync(tot, b->d_ztot, sizeof tot, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipMemcpyAsync(b->h_zsz, b->d_zsz, (size_t)np * 4u, hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
   if (tot[0] > out_cap || tot[1] != np)
     return bsc_fail(BSC_ERR_HIP, "%s: the encoder reported %llu bytes in %llu streams for %llu sections", who, tot[0], tot[1], (unsigned long long)np);
   *z_bytes = tot[0];
   *n_sections = np;
-  *z_sizes = ctx->bw.h_zsz;
-  ctx->bw.z_bytes = tot[0];
+  *z_sizes = b->h_zsz;
+  b->z_bytes = tot[0];
+  return BSC_OK;
+}
+
+int bsc_block_bigwig_deflate(bsc_context *ctx, uint64_t *z_bytes, const uint32_t **z_sizes, uint64_t *n_sections) {
+  return bsc_bw_block_deflate(ctx, "bsc_block_bigwig_deflate", "bsc_block_bigwig_kept", ctx ? &ctx->bw.lv : NULL, z_bytes, z_sizes, n_sections);
+}
+
+int bsc_block_bigwig_cov_deflate(bsc_context *ctx, uint64_t *z_bytes, const uint32_t **z_sizes, uint64_t *n_sections) {
+  return bsc_bw_block_deflate(ctx, "bsc_block_bigwig_cov_deflate", "bsc_block_bigwig_tracks_kept with the coverage track", ctx ? &ctx->bw.cv : NULL, z_bytes,
+                              z_sizes, n_sections);
+}
+
+static int bsc_bw_zstream_read(bsc_context *ctx, const char *who, const struct bsc_bw_block *b, uint64_t off, uint64_t n, void *dst) {
+  if (!ctx || (!dst && n)) return bsc_fail(BSC_ERR_ARG, "%s: NULL argument", who);
+  if (off + n > b->z_bytes || off + n > b->cap_z) return bsc_fail(BSC_ERR_ARG, "%s: beyond the streams' end", who);
+  if (!n) return BSC_OK;
+  BSC_ENTER(ctx);
+  HIP_TRY(hipMemcpyAsync(dst, (const char *)b->d_z + off, (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
   return BSC_OK;
 }
 
 int bsc_bigwig_zstream_read(bsc_context *ctx, uint64_t off, uint64_t n, void *dst) {
-  if (!ctx || (!dst && n)) return bsc_fail(BSC_ERR_ARG, "bsc_bigwig_zstream_read: NULL argument");
-  if (off + n > ctx->bw.z_bytes || off + n > ctx->bw.cap_z) return bsc_fail(BSC_ERR_ARG, "bsc_bigwig_zstream_read: beyond the streams' end");
-  if (!n) return BSC_OK;
-  BSC_ENTER(ctx);
-  HIP_TRY(hipMemcpyAsync(dst, (const char *)ctx->bw.d_z + off, (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
-  return BSC_OK;
+  return bsc_bw_zstream_read(ctx, "bsc_bigwig_zstream_read", ctx ? &ctx->bw.lv : NULL, off, n, dst);
+}
+
+int bsc_bigwig_cov_zstream_read(bsc_context *ctx, uint64_t off, uint64_t n, void *dst) {
+  return bsc_bw_zstream_read(ctx, "bsc_bigwig_cov_zstream_read", ctx ? &ctx->bw.cv : NULL, off, n, dst);
 }
 
 /* ---- the bedMethyl table as bigBed items (bigbeddev.hip): include/bscall_amd.h has the rule, csrc/bigbed.c the host form ----------------------- */

@@ -8,7 +8,7 @@ from typing import Dict, Optional
 
 import numpy as np
 
-from . import report, vcf
+from . import _lib, report, vcf
 from .bam import BamReader, block_reference
 from .caller import ReadProfile, SiteCaller, gc_bins, prepare_templates
 
@@ -19,6 +19,7 @@ def run(bam_path: str, reference: Dict[str, np.ndarray], bcf_path: str, sample: 
         host_prep: bool = False, host_bcf: bool = False, device_reader: bool = False, shard_rank: Optional[int] = None, shard_world: int = 1,
         reduce_device=None, text: bool = False, dbsnp_device: bool = False, meth_path: Optional[str] = None, meth_params=None, meth_merge: bool = False,
         meth_regions=None, meth_regions_path: Optional[str] = None, meth_window: Optional[int] = None, bigwig_path: Optional[str] = None,
+        cov_bigwig_path: Optional[str] = None,
         bigwig_section: int = 1024, bigwig_zoom: int = 1024, bigwig_compress: bool = False, bigbed_path: Optional[str] = None, bigbed_items: int = 512,
         bigbed_zoom: int = 1024, bigbed_compress: bool = False, meth_index: Optional[str] = None, **reader_kw) -> dict:
     """reference: contig name -> uint8 reference codes (0 = N, 1..4 = ACGT; position 1 first).  Returns a summary dict.
@@ -62,7 +63,10 @@ def run(bam_path: str, reference: Dict[str, np.ndarray], bcf_path: str, sample: 
     bigwig.Writer.  bigwig_section: sites a section (1 .. 65535); bigwig_zoom: the width of a level-0 zoom window.  meth_params apply; the
     track is per cytosine whatever meth_merge says; meth_path is not needed.  The same conditions as meth_path.  bigwig_compress: every
     section leaves the device as a zlib stream (SiteCaller.block_bigwig_deflate, csrc/zlibdev.hip) and the writer deflates the zoom blocks:
-    the file readers meet in practice, about half the bytes; needs bigwig_path and bigwig_section <= 8157.
+    the file readers meet in practice, about half the bytes; needs bigwig_path or cov_bigwig_path and bigwig_section <= 8157.
+    cov_bigwig_path: the coverage track of the same sites (the depth a + b; the coverage rule of include/bscall_amd.h), alone or beside
+    bigwig_path — then ONE SiteCaller.block_bigwig_tracks_kept call (csrc/bwcovdev.hip, mask 3) reduces the block for both files.  It
+    honours bigwig_section, bigwig_zoom and bigwig_compress; the same conditions as bigwig_path.
 
     bigbed_path: the per-cytosine table of the same run as a bigBed file (include/bscall_amd.h has the rule and the file's layout): every
     block's items and summaries from the arrays it left on the device (SiteCaller.block_bigbed_kept, csrc/bigbeddev.hip), the file by
@@ -78,14 +82,16 @@ def run(bam_path: str, reference: Dict[str, np.ndarray], bcf_path: str, sample: 
         raise ValueError("bigbed_path is a single run on the device reader (device_reader=True, no shard_rank, no host_prep / host_bcf)")
     if want_bb and not (1 <= int(bigbed_items) <= 65535 and 1 <= int(bigbed_zoom) <= 0xFFFFFFFF):
         raise ValueError("bigbed_items is 1 .. 65535 sites, bigbed_zoom 1 or more bases")
-    want_bw = bigwig_path is not None
-    if bigwig_compress and not want_bw:
+    want_bw, want_cov = bigwig_path is not None, cov_bigwig_path is not None
+    if bigwig_compress and not (want_bw or want_cov):
         raise ValueError("bigwig_compress needs bigwig_path")
     if bigwig_compress and int(bigwig_section) > 8157:
         raise ValueError("bigwig_compress: a section of more than 8157 sites is more than 0xFF00 bytes")
     if want_bw and (shard_rank is not None or not device_reader or host_prep or host_bcf):
         raise ValueError("bigwig_path is a single run on the device reader (device_reader=True, no shard_rank, no host_prep / host_bcf)")
-    if want_bw and not (1 <= int(bigwig_section) <= 65535 and 1 <= int(bigwig_zoom) <= 0xFFFFFFFF):
+    if want_cov and (shard_rank is not None or not device_reader or host_prep or host_bcf):
+        raise ValueError("cov_bigwig_path is a single run on the device reader (device_reader=True, no shard_rank, no host_prep / host_bcf)")
+    if (want_bw or want_cov) and not (1 <= int(bigwig_section) <= 65535 and 1 <= int(bigwig_zoom) <= 0xFFFFFFFF):
         raise ValueError("bigwig_section is 1 .. 65535 sites, bigwig_zoom 1 or more bases")
     want_regions = meth_regions is not None or meth_window is not None
     if meth_regions is not None and meth_window is not None:
@@ -130,7 +136,7 @@ def run(bam_path: str, reference: Dict[str, np.ndarray], bcf_path: str, sample: 
     on_device = dbsnp_device and dbsnp is not None
     if text and (shard_rank is not None or not device_reader or host_prep or host_bcf):
         raise ValueError("text=True is a single run on the device reader (device_reader=True, no shard_rank, no host_prep / host_bcf)")
-    bw_writer = bb_writer = None
+    bw_writer = cov_writer = bb_writer = None
     bb_sites = 0
     own = caller is None
     if own:
@@ -152,7 +158,7 @@ def run(bam_path: str, reference: Dict[str, np.ndarray], bcf_path: str, sample: 
         n_blocks = n_records = 0
         meth_blobs, meth_lines = [], 0
         meth_entries = []  # meth_index: (contig number, BED_ENTRY[], bytes of the block's table)
-        bw_sites = 0
+        bw_sites = cov_sites = 0
         region_out, region_cur = [], None  # the summary's lines, contig by contig; (name, regions, names) of the contig attached
         c.reset_site_stats()
         sharded = shard_rank is not None
@@ -184,11 +190,14 @@ def run(bam_path: str, reference: Dict[str, np.ndarray], bcf_path: str, sample: 
                                      mapq_thresh=reader_kw.get("mapq_thresh", 20), min_qual=min_qual, date=date,
                                      dbsnp_header=None if dbsnp is None else dbsnp.header, benchmark_mode=benchmark_mode)
 
-            if want_bw:
+            if want_bw or want_cov:
                 from . import bigwig
 
-                bw_writer = bigwig.Writer(bigwig_path, refs, int(bigwig_section), int(bigwig_zoom), compress=bool(bigwig_compress))
                 bw_par = {"items_per_section": int(bigwig_section), "reduction": int(bigwig_zoom)}
+                if want_bw:
+                    bw_writer = bigwig.Writer(bigwig_path, refs, int(bigwig_section), int(bigwig_zoom), compress=bool(bigwig_compress))
+                if want_cov:
+                    cov_writer = bigwig.Writer(cov_bigwig_path, refs, int(bigwig_section), int(bigwig_zoom), compress=bool(bigwig_compress), track="coverage")
 
             if want_bb:
                 from . import bigbed
@@ -205,7 +214,7 @@ def run(bam_path: str, reference: Dict[str, np.ndarray], bcf_path: str, sample: 
                 region_cur = None
 
             def block_blobs():
-                nonlocal n_blocks, n_records, base_filter, passed, meth_lines, region_cur, bw_sites, bb_sites
+                nonlocal n_blocks, n_records, base_filter, passed, meth_lines, region_cur, bw_sites, cov_sites, bb_sites
                 before, cur_tid = c.site_totals(), -1
                 for item in (rd.device_blocks() if device_reader else rd.blocks()):
                     if device_reader:
@@ -253,10 +262,23 @@ def run(bam_path: str, reference: Dict[str, np.ndarray], bcf_path: str, sample: 
                         else:
                             blob, n_rec, st = c.block_bcf_rawdev(dblk, ref, tid, names=names, left_trim=left_trim, right_trim=right_trim, min_qual=min_qual,
                                                                  reg_stop=len(codes), dbsnp=flags, with_stats=True, profile=prof,
-                                                                 keep=meth_path is not None or want_regions or want_bw or want_bb)
+                                                                 keep=meth_path is not None or want_regions or want_bw or want_cov or want_bb)
                         if region_cur is not None:  # the block's cytosines into the attached regions' sums
                             c.block_meth_regions_kept(meth_params)
-                        if want_bw:  # the block's bigWig sections and summaries, appended to the track's file
+                        if want_cov:  # the coverage track, and the level track with it, from ONE sweep over the block's arrays
+                            ns, lv, cv = c.block_bigwig_tracks_kept(tid, (_lib.BW_LEVEL if want_bw else 0) | _lib.BW_COVERAGE, meth_params, bw_par,
+                                                                    read_stream=not bigwig_compress)
+                            for w, got, deflate in ((bw_writer, lv, c.block_bigwig_deflate), (cov_writer, cv, c.block_bigwig_cov_deflate)):
+                                if got is None:
+                                    continue
+                                if bigwig_compress:
+                                    zdata, zsizes = deflate()
+                                    w.add_z(tid, zdata, zsizes, got[1], got[2])
+                                else:
+                                    w.add(tid, *got)
+                            cov_sites += ns
+                            bw_sites += ns if want_bw else 0
+                        elif want_bw:  # the block's bigWig sections and summaries, appended to the track's file
                             data, ns, secs, zoom0 = c.block_bigwig_kept(tid, meth_params, bw_par, read_stream=not bigwig_compress)
                             if bigwig_compress:  # ... as zlib streams: the plain stream stays on the device
                                 zdata, zsizes = c.block_bigwig_deflate()
@@ -333,6 +355,8 @@ def run(bam_path: str, reference: Dict[str, np.ndarray], bcf_path: str, sample: 
                             f.write(ix.finish())
             if want_bw:
                 bw_writer.finish()
+            if want_cov:
+                cov_writer.finish()
             if want_bb:
                 bb_writer.finish()
             if want_regions:
@@ -407,6 +431,8 @@ def run(bam_path: str, reference: Dict[str, np.ndarray], bcf_path: str, sample: 
             summary["meth_lines"] = meth_lines
         if want_bw:
             summary["bigwig_sites"] = bw_sites
+        if want_cov:
+            summary["cov_bigwig_sites"] = cov_sites
         if want_bb:
             summary["bigbed_items"] = bb_sites
         if want_regions:
@@ -415,6 +441,8 @@ def run(bam_path: str, reference: Dict[str, np.ndarray], bcf_path: str, sample: 
     finally:
         if bw_writer is not None:
             bw_writer.close()
+        if cov_writer is not None:
+            cov_writer.close()
         if bb_writer is not None:
             bb_writer.close()
         if own:

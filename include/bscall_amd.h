@@ -1412,16 +1412,70 @@ int bsc_meth_regions_reset(bsc_context *ctx);
  *   bsc_bigwig_add_z           bsc_bigwig_add for a block's ZSTREAMs: every check of bsc_bigwig_add on the summaries; in place of the byte
  *                              count, z_sizes[k] is 1 .. 24 + 8 count + 11 and their sum z_bytes.  After a non-empty bsc_bigwig_add_z a
  *                              non-empty bsc_bigwig_add is BSC_ERR_ARG with nothing written, and the reverse.
- * Not built: a coverage track, sharded runs, a device encoder for the zoom blocks, the batched and host-buffer block entries.
+ * The coverage track (csrc/bwcovdev.hip: bsc_bwcov_write_kernel / bsc_bwcov_reduce_kernel over the mask of tracks, beside the tile, heads
+ * and windows kernels of bigwigdev.hip; csrc/bigwig.c holds the host form and the writer): the depth a + b a level is read with, as a second
+ * bigWig of the same sites.  The rule, from which the kernels, the host form and the Python forms are each written:
+ *   TRACK     BSC_BW_LEVEL (bit 0): the track above, unchanged.  BSC_BW_COVERAGE (bit 1).  A track mask is 1, 2 or 3.
+ *   SITE      exactly the SITE above: the same bsc_meth_params, the same a and b, the same emit-byte gate; a + b >= max(1, min_cov) is tested
+ *             on the 64-bit sum, before any saturation.  Both tracks of one call therefore have the same sites, section boundaries, start /
+ *             end / count, window set and n_bytes.
+ *   COVERAGE VALUE   c = min(a + b, 2^32 - 1), a + b in 64 bits (counts already saturate at 2^32 - 1).  The float written is the conversion
+ *             of the unsigned integer c to binary32, rounded once, to nearest, ties to even: C's (float)(uint32_t)c in the default rounding
+ *             mode.  The device uses the hardware's u32 -> f32 conversion and does no other floating-point arithmetic here.
+ *   SUMMARY   bsc_bw_sum, the same 40 bytes.  In a coverage summary min_m = min c, max_m = max c, sum_m = the sum of c (< 2^64 for
+ *             count < 2^32: exact), sum_m2 = bits 0 .. 63 of the sum of c * c and _pad = its bits 64 .. 95 (the sum is < 2^96: exact).  In a
+ *             level summary _pad stays 0.  Two coverage summaries merge as level summaries do, the 96-bit add carrying from sum_m2 into _pad.
+ *   STREAM    the level STREAM with the coverage float in each item's value word: varStep type 2, 24 + 8 S bytes a section.
+ *   PYRAMID   the level PYRAMID; on the host the merged sums are held in unsigned __int128, so nothing wraps.
+ *   FILE / COMPRESSED FILE   the same layout and magic.  Every number is rounded ONCE from the exact integer, to nearest, ties to even
+ *             (integer arithmetic on the host: no intermediate type).  Total summary: basesCovered = the sites; minVal, maxVal, sumData,
+ *             sumSquares = min c, max c, the sum of c, the sum of c * c, each converted to f64.  A zoom record's minVal, maxVal, sumData,
+ *             sumSquares are each converted to f32 directly from the integer, not through a double.  The level file's / 10.0 and / 100.0
+ *             forms stay exactly as they are.
+ *   bsc_bigwig_cov_sections_recs   the host form of the coverage track over packed records: the signature and the room rule of
+ *                              bsc_bigwig_sections_recs; the kernels' checker.
+ *   bsc_bigwig_open_track      bsc_bigwig_open with the writer's track, BSC_BW_LEVEL or BSC_BW_COVERAGE (anything else: BSC_ERR_ARG);
+ *                              bsc_bigwig_open is this with BSC_BW_LEVEL.  A coverage writer's bsc_bigwig_add, _add_z, _finish and _close
+ *                              apply the same checks and refusals; it keeps its entries' _pad (a level writer sets it to 0) and writes the
+ *                              values and sums of the coverage FILE rule.  The level writer's bytes do not change.
+ *   bsc_bigwig_tracks_device   bsc_bigwig_sites_device for a mask of tracks, in one sweep: its preconditions, alignment rules and refusals;
+ *                              level_out / cov_out: a bsc_bw_track_out {d_out, out_cap, d_sections, sec_cap, d_zoom, zoom_cap} per requested
+ *                              track, NULL for one not in `tracks` (a track asked for with NULL, or a mask other than 1, 2, 3: BSC_ERR_ARG).
+ *                              d_totals = six device u64 {n_bytes, n_sites, n_sections, n_windows, sum of m, sum of m * m}, the last two 0
+ *                              without bit 0 (a coverage track's totals are the sums of its section summaries: the host adds them).  An
+ *                              array whose room is too small is not written at all and every other array is complete.  n = 0: six zeros.
+ *   bsc_block_bigwig_tracks_kept   the twin of bsc_block_bigwig_kept for a mask of tracks: its preconditions, refusals and wait; the counts
+ *                              once, the host copies of the sections and of zoom0 per requested track (NULL for the other; the pointer
+ *                              arguments of a track not asked for may be NULL).  With bit 0 it fills the level buffers bsc_block_bigwig_kept
+ *                              fills: bsc_bigwig_stream_read, bsc_block_bigwig_deflate and bsc_bigwig_zstream_read follow as they follow
+ *                              that call; without bit 0 those are refused until the next level call.  The coverage stream lives in buffers
+ *                              of its own (bsc_block_bigwig_kept leaves none: the three calls below are refused behind it).  The kept
+ *                              stream, its tile offsets, the methylation tables, bsc_block_csi_kept, the region accumulators, the bigBed
+ *                              data and the tabix scan are untouched.
+ *   bsc_bigwig_cov_stream_read / bsc_block_bigwig_cov_deflate / bsc_bigwig_cov_zstream_read   bsc_bigwig_stream_read,
+ *                              bsc_block_bigwig_deflate and bsc_bigwig_zstream_read for the coverage stream of the last
+ *                              bsc_block_bigwig_tracks_kept with bit 1: bsc_zlib_pieces_device at stride 24 + 8 S, S <= 8157.
+ * Not built: sharded runs, a device encoder for the zoom blocks, the batched and host-buffer block entries, a track of the combined-strand
+ * CpGs, a per-base depth over every position (the kept arrays hold records only where the chain emitted one).
  */
 typedef struct {
   uint32_t items_per_section; /* 1 .. 65535 */
   uint32_t reduction;         /* >= 1: the width of a level-0 zoom window */
 } bsc_bw_params;
 typedef struct {
-  uint32_t start, end, count, min_m, max_m, _pad;
+  uint32_t start, end, count, min_m, max_m, _pad; /* _pad: 0 in a level summary; bits 64 .. 95 of the sum of c * c in a coverage summary */
   uint64_t sum_m, sum_m2;
 } bsc_bw_sum;
+#define BSC_BW_LEVEL 1u    /* track bits */
+#define BSC_BW_COVERAGE 2u
+typedef struct { /* where one track of bsc_bigwig_tracks_device goes: the rooms of bsc_bigwig_sites_device */
+  void *d_out;
+  uint64_t out_cap;
+  void *d_sections;
+  uint64_t sec_cap;
+  void *d_zoom;
+  uint64_t zoom_cap;
+} bsc_bw_track_out;
 typedef struct bsc_bigwig bsc_bigwig;
 void bsc_bw_params_default(bsc_bw_params *p);
 int bsc_bigwig_sections_recs(const bsc_vcf_rec *recs, size_t n, uint32_t chrom_id, const bsc_meth_params *params, const bsc_bw_params *bw_params,
@@ -1444,6 +1498,20 @@ int bsc_block_bigwig_deflate(bsc_context *ctx, uint64_t *z_bytes, const uint32_t
 int bsc_bigwig_zstream_read(bsc_context *ctx, uint64_t off, uint64_t n, void *dst);
 int bsc_bigwig_add_z(bsc_bigwig *bw, uint32_t tid, const void *zdata, uint64_t z_bytes, const uint32_t *z_sizes, const bsc_bw_sum *sections,
                      uint64_t n_sections, const bsc_bw_sum *zoom0, uint64_t n_zoom0);
+int bsc_bigwig_cov_sections_recs(const bsc_vcf_rec *recs, size_t n, uint32_t chrom_id, const bsc_meth_params *params, const bsc_bw_params *bw_params,
+                                 void *out, uint64_t cap, uint64_t *n_bytes, bsc_bw_sum *sections, uint64_t *n_sections, bsc_bw_sum *zoom0,
+                                 uint64_t *n_zoom0);
+int bsc_bigwig_open_track(int fd, uint32_t n_refs, const char *const *names, const uint32_t *lens, const bsc_bw_params *bw_params, uint32_t track,
+                          bsc_bigwig **bw);
+int bsc_bigwig_tracks_device(bsc_context *ctx, const void *d_core, const void *d_aux, uint32_t n, uint32_t x0, uint32_t chrom_id,
+                             const bsc_meth_params *params, const bsc_bw_params *bw_params, uint32_t tracks, const bsc_bw_track_out *level_out,
+                             const bsc_bw_track_out *cov_out, void *d_totals, void *stream);
+int bsc_block_bigwig_tracks_kept(bsc_context *ctx, uint32_t chrom_id, const bsc_meth_params *params, const bsc_bw_params *bw_params, uint32_t tracks,
+                                 uint64_t *n_bytes, uint64_t *n_sites, uint64_t *n_sections, uint64_t *n_zoom0, const bsc_bw_sum **level_sections,
+                                 const bsc_bw_sum **level_zoom0, const bsc_bw_sum **cov_sections, const bsc_bw_sum **cov_zoom0);
+int bsc_bigwig_cov_stream_read(bsc_context *ctx, uint64_t off, uint64_t n, void *dst);
+int bsc_block_bigwig_cov_deflate(bsc_context *ctx, uint64_t *z_bytes, const uint32_t **z_sizes, uint64_t *n_sections);
+int bsc_bigwig_cov_zstream_read(bsc_context *ctx, uint64_t off, uint64_t n, void *dst);
 /*
  * The bedMethyl table as bigBed items (csrc/bigbeddev.hip: the bsc_bigbed_*_kernel family; csrc/bigbed.c holds the host form, which is their
  * checker): what a genome browser fetches by region — counts, GQ and FILTER per site — in place of the text table, made from the

@@ -81,7 +81,12 @@
  * needs --meth-bigbed and at most BSC_BB_Z_ITEMS_MAX sites a block.  Refused like --meth-bigwig in a sharded run and on the BAM2BCF_HOST_* paths.
  * --meth-bigwig-compress: the file readers meet in practice — every section leaves the device as a zlib stream (bsc_block_bigwig_deflate,
  * csrc/zlibdev.hip), the job carries the streams and their sizes for bsc_bigwig_add_z, and bsc_bigwig_finish deflates the zoom blocks.  Needs
- * --meth-bigwig; sections of at most 8157 sites.
+ * --meth-bigwig or --cov-bigwig; sections of at most 8157 sites.
+ * --cov-bigwig cov.bw: the depth a + b of the same sites as a second bigWig track (the coverage rule of include/bscall_amd.h), alone or beside
+ * --meth-bigwig.  With both, ONE bsc_block_bigwig_tracks_kept call (csrc/bwcovdev.hip, mask 3) reduces the block for the two files: the
+ * per-position arrays are read once.  --meth-bigwig-section, --meth-bigwig-zoom and --meth-bigwig-compress apply to both files (the
+ * coverage sections through bsc_block_bigwig_cov_deflate); each file is a job of its own for the output thread.  Refused where --meth-bigwig is.
+ * Without --cov-bigwig the program makes the calls it made before the switch existed.
  *
  * --meth-regions regions.bed --meth-regions-out out.tsv: the per-region methylation summary — per interval of the BED file the cytosines
  * inside it added up on the device (bsc_meth_regions_attach at the contig change, where -D attaches; bsc_block_meth_regions_kept behind
@@ -513,7 +518,7 @@ static uint64_t regions_flush(bsc_context *ctx, FILE *f, const char *contig, con
 
 int main(int argc, char **argv) {
   int rank = -1, world = 1, merge = 0, bgzf = 0, text = 0, index = 0, meth_merge = 0;
-  const char *dbsnp_path = NULL, *meth_path = NULL, *regions_path = NULL, *regions_out_path = NULL, *bigwig_path = NULL;
+  const char *dbsnp_path = NULL, *meth_path = NULL, *regions_path = NULL, *regions_out_path = NULL, *bigwig_path = NULL, *cov_path = NULL;
   uint32_t meth_window = 0;
   bsc_bw_params bwpar;
   bsc_bw_params_default(&bwpar);
@@ -599,6 +604,7 @@ int main(int argc, char **argv) {
       meth_window = (uint32_t)v;
     }
     else if (!strcmp(argv[1], "--meth-bigwig")) bigwig_path = argv[2];
+    else if (!strcmp(argv[1], "--cov-bigwig")) cov_path = argv[2];
     else if (!strcmp(argv[1], "--meth-bigbed")) bigbed_path = argv[2];
     else if (!strcmp(argv[1], "--meth-bigbed-items") || !strcmp(argv[1], "--meth-bigbed-zoom")) {
       char *end = NULL;
@@ -645,7 +651,7 @@ int main(int argc, char **argv) {
     argc -= 2;
   }
   if (argc < 5 || world < 1 || (rank >= 0 && rank >= world)) {
-    fprintf(stderr, "usage: %s [-O u|b] [--format bcf|vcf] [--index] [-D dbsnp.idx] [--meth out.bed [--meth-bgzf] [--meth-index tbi|csi] [--meth-merge | --meth-all] [--meth-min-cov n] [--meth-min-gq n] [--meth-pass]] [--meth-regions regions.bed | --meth-window n --meth-regions-out out.tsv] [--meth-bigwig out.bw [--meth-bigwig-section n] [--meth-bigwig-zoom n] [--meth-bigwig-compress: zlib sections, n <= 8157]: the methylation level as a bigWig track, per cytosine even with --meth-merge, under the --meth-* thresholds and --meth-all] [--meth-bigbed out.bb [--meth-bigbed-items n] [--meth-bigbed-zoom n] [--meth-bigbed-compress: zlib blocks, n <= 652]] [--rank r --world n | --merge n] in.bam ref.fa out.bcf report.json [sample]\n", argv[0]);
+    fprintf(stderr, "usage: %s [-O u|b] [--format bcf|vcf] [--index] [-D dbsnp.idx] [--meth out.bed [--meth-bgzf] [--meth-index tbi|csi] [--meth-merge | --meth-all] [--meth-min-cov n] [--meth-min-gq n] [--meth-pass]] [--meth-regions regions.bed | --meth-window n --meth-regions-out out.tsv] [--meth-bigwig out.bw [--meth-bigwig-section n] [--meth-bigwig-zoom n] [--meth-bigwig-compress: zlib sections, n <= 8157]: the methylation level as a bigWig track, per cytosine even with --meth-merge, under the --meth-* thresholds and --meth-all] [--cov-bigwig cov.bw: the depth of the same sites as a bigWig track, under the same --meth-bigwig-* switches] [--meth-bigbed out.bb [--meth-bigbed-items n] [--meth-bigbed-zoom n] [--meth-bigbed-compress: zlib blocks, n <= 652]] [--rank r --world n | --merge n] in.bam ref.fa out.bcf report.json [sample]\n", argv[0]);
     return 2;
   }
   if (text && (rank >= 0 || merge > 0)) {
@@ -741,7 +747,7 @@ int main(int argc, char **argv) {
     fprintf(stderr, "%s: --meth-bigbed encodes what the device reader's blocks leave on the device: not with BAM2BCF_HOST_READER / _HOST_BCF / _HOST_PREP\n", argv[0]);
     return 2;
   }
-  if (bigwig_z && !bigwig_path) {
+  if (bigwig_z && !bigwig_path && !cov_path) {
     fprintf(stderr, "%s: --meth-bigwig-compress needs --meth-bigwig\n", argv[0]);
     return 2;
   }
@@ -756,6 +762,14 @@ int main(int argc, char **argv) {
   }
   if (bigwig_path && (getenv("BAM2BCF_HOST_PREP") || getenv("BAM2BCF_HOST_BCF") || getenv("BAM2BCF_HOST_READER"))) {
     fprintf(stderr, "%s: --meth-bigwig reduces what the device reader's blocks leave on the device: not with BAM2BCF_HOST_READER / _HOST_BCF / _HOST_PREP\n", argv[0]);
+    return 2;
+  }
+  if (cov_path && (rank >= 0 || world > 1 || merge > 0)) {
+    fprintf(stderr, "%s: --cov-bigwig writes a single run's track; a sharded run (--rank / --world / --merge) has none\n", argv[0]);
+    return 2;
+  }
+  if (cov_path && (getenv("BAM2BCF_HOST_PREP") || getenv("BAM2BCF_HOST_BCF") || getenv("BAM2BCF_HOST_READER"))) {
+    fprintf(stderr, "%s: --cov-bigwig reduces what the device reader's blocks leave on the device: not with BAM2BCF_HOST_READER / _HOST_BCF / _HOST_PREP\n", argv[0]);
     return 2;
   }
   const char *sample = argc > 5 ? argv[5] : "SAMPLE";
@@ -882,6 +896,9 @@ int main(int argc, char **argv) {
   int bw_fd = -1;
   bsc_bigwig *bw = NULL;
   uint64_t bw_sites = 0;
+  int cw_fd = -1; /* --cov-bigwig: the coverage track's file and writer */
+  bsc_bigwig *cw = NULL;
+  uint64_t cw_sites = 0;
   int bb_fd = -1;
   bsc_bigbed *bb = NULL;
   uint64_t bb_sites = 0;
@@ -901,6 +918,16 @@ int main(int argc, char **argv) {
       bw_fd = dup(fileno(bf));
       fclose(bf);
       CHECK(bsc_bigwig_open(bw_fd, (uint32_t)n_ref, names, lens, &bwpar, &bw));
+    }
+    if (cov_path) { /* the coverage track's file, as the level track's */
+      FILE *bf = fopen(cov_path, "wb");
+      if (!bf) {
+        perror(cov_path);
+        return 1;
+      }
+      cw_fd = dup(fileno(bf));
+      fclose(bf);
+      CHECK(bsc_bigwig_open_track(cw_fd, (uint32_t)n_ref, names, lens, &bwpar, BSC_BW_COVERAGE, &cw));
     }
     if (bigbed_path) { /* the bigBed's file, as the track's */
       FILE *bf = fopen(bigbed_path, "wb");
@@ -1095,22 +1122,30 @@ int main(int argc, char **argv) {
         CHECK(bsc_csi_add(csi, dblk.tid, ce, cn, n_bytes));
       }
       if (n_bytes && r_n) CHECK(bsc_block_meth_regions_kept(ctx, &mpar, NULL, NULL)); /* the block's cytosines into the attached regions' sums */
-      if (n_bytes && bw) { /* the block's bigWig sections and summaries, from the same arrays: a host buffer and a job of its own */
-        uint64_t b_bytes = 0, b_sites = 0, b_sec = 0, b_zoom = 0;
-        const bsc_bw_sum *sec = NULL, *zoom = NULL;
-        CHECK(bsc_block_bigwig_kept(ctx, (uint32_t)dblk.tid, &mpar, &bwpar, &b_bytes, &b_sites, &sec, &b_sec, &zoom, &b_zoom));
-        bw_sites += b_sites;
-        if (b_sec) {
+      if (n_bytes && (bw || cw)) { /* the block's bigWig sections and summaries, from the same arrays: a host buffer and a job of its own per
+                                    * track.  With --cov-bigwig ONE call reduces the block for every track asked for. */
+        uint64_t b_raw = 0, b_sites = 0, b_sec = 0, b_zoom = 0;
+        const bsc_bw_sum *sec[2] = {NULL, NULL}, *zoom[2] = {NULL, NULL};
+        if (cw)
+          CHECK(bsc_block_bigwig_tracks_kept(ctx, (uint32_t)dblk.tid, &mpar, &bwpar, (bw ? BSC_BW_LEVEL : 0u) | BSC_BW_COVERAGE, &b_raw, &b_sites, &b_sec,
+                                             &b_zoom, bw ? &sec[0] : NULL, bw ? &zoom[0] : NULL, &sec[1], &zoom[1]));
+        else
+          CHECK(bsc_block_bigwig_kept(ctx, (uint32_t)dblk.tid, &mpar, &bwpar, &b_raw, &b_sites, &sec[0], &b_sec, &zoom[0], &b_zoom));
+        if (bw) bw_sites += b_sites;
+        if (cw) cw_sites += b_sites;
+        for (int t = 0; t < 2 && b_sec; t++) {
+          if (!(t ? cw : bw)) continue;
+          uint64_t b_bytes = b_raw;
           out_job j;
           memset(&j, 0, sizeof j);
           j.fd = -1;
           j.n = b_bytes;
-          j.bw = bw;
+          j.bw = t ? cw : bw;
           j.bw_tid = (uint32_t)dblk.tid;
           if (bigwig_z) { /* the sections as zlib streams: the job carries those and their sizes */
             const uint32_t *zs = NULL;
             uint64_t z_bytes = 0, z_sec = 0;
-            CHECK(bsc_block_bigwig_deflate(ctx, &z_bytes, &zs, &z_sec));
+            CHECK((t ? bsc_block_bigwig_cov_deflate : bsc_block_bigwig_deflate)(ctx, &z_bytes, &zs, &z_sec));
             if (z_sec != b_sec) {
               fprintf(stderr, "bam2bcf: %llu zlib streams for %llu bigWig sections\n", (unsigned long long)z_sec, (unsigned long long)b_sec);
               return 1;
@@ -1120,13 +1155,14 @@ int main(int argc, char **argv) {
             memcpy(j.bw_zsizes, zs, (size_t)b_sec * sizeof *zs);
           }
           j.bw_data = xrealloc(NULL, (size_t)b_bytes);
-          j.bw_sec = xrealloc(NULL, (size_t)b_sec * sizeof *sec);
-          j.bw_zoom = xrealloc(NULL, (size_t)b_zoom * sizeof *zoom);
+          j.bw_sec = xrealloc(NULL, (size_t)b_sec * sizeof **sec);
+          j.bw_zoom = xrealloc(NULL, (size_t)b_zoom * sizeof **zoom);
           j.bw_n_sec = b_sec;
           j.bw_n_zoom = b_zoom;
-          memcpy(j.bw_sec, sec, (size_t)b_sec * sizeof *sec);
-          memcpy(j.bw_zoom, zoom, (size_t)b_zoom * sizeof *zoom);
-          CHECK((bigwig_z ? bsc_bigwig_zstream_read : bsc_bigwig_stream_read)(ctx, 0, b_bytes, j.bw_data));
+          memcpy(j.bw_sec, sec[t], (size_t)b_sec * sizeof **sec);
+          memcpy(j.bw_zoom, zoom[t], (size_t)b_zoom * sizeof **zoom);
+          CHECK((t ? (bigwig_z ? bsc_bigwig_cov_zstream_read : bsc_bigwig_cov_stream_read) : (bigwig_z ? bsc_bigwig_zstream_read : bsc_bigwig_stream_read))(
+              ctx, 0, b_bytes, j.bw_data));
           CHECK(bsc_synchronize(ctx));
           writer_push(&W, j);
         }
@@ -1369,6 +1405,14 @@ int main(int argc, char **argv) {
       return 1;
     }
   }
+  if (cw) { /* the coverage track's, likewise */
+    CHECK(bsc_bigwig_finish(cw));
+    bsc_bigwig_close(cw);
+    if (close(cw_fd)) {
+      perror(cov_path);
+      return 1;
+    }
+  }
   if (bb) { /* every block's items are in: the item count, the indexes, the zoom levels, the summary and the header */
     CHECK(bsc_bigbed_finish(bb));
     bsc_bigbed_close(bb);
@@ -1475,6 +1519,7 @@ int main(int argc, char **argv) {
     if (meth_path) printf("%llu methylation table lines written\n", (unsigned long long)meth_lines);
     if (regions_out_path) printf("%llu methylation region lines written\n", (unsigned long long)region_lines);
     if (bigwig_path) printf("%llu methylation bigWig sites written\n", (unsigned long long)bw_sites);
+    if (cov_path) printf("%llu coverage bigWig sites written\n", (unsigned long long)cw_sites);
     if (bigbed_path) printf("%llu bedMethyl bigBed items written\n", (unsigned long long)bb_sites);
   }
   if (getenv("BAM2BCF_TIMING")) {
