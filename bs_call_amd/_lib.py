@@ -235,6 +235,13 @@ EXPORTS = (
     "bsc_bigbed_add_z",
     "bsc_bigbed_finish",
     "bsc_bigbed_close",
+    "bsc_var_params_default",
+    "bsc_variants_select_recs",
+    "bsc_variants_sites_device",
+    "bsc_block_variants_kept",
+    "bsc_variants_stream_read",
+    "bsc_variants_stream_detach",
+    "bsc_block_variants_csi_kept",
 )
 
 
@@ -255,6 +262,15 @@ class MethParams(C.Structure):
 
     def __init__(self, contexts=0, min_cov=1, min_phred=0, pass_only=0):
         super().__init__(int(contexts), int(min_cov), int(min_phred), int(pass_only))
+
+
+class VarParams(C.Structure):
+    """bsc_var_params; the defaults are bsc_var_params_default's."""
+
+    _fields_ = [("min_phred", C.c_uint32), ("pass_only", C.c_int32), ("known_only", C.c_int32), ("reserved", C.c_uint32)]
+
+    def __init__(self, min_phred=0, pass_only=0, known_only=0, reserved=0):
+        super().__init__(int(min_phred), int(pass_only), int(known_only), int(reserved))
 
 
 class BwParams(C.Structure):
@@ -810,6 +826,20 @@ def load():
     L.bsc_meth_stream_detach.restype = i32
     L.bsc_meth_stream_detach.argtypes = [vp, C.POINTER(vp), C.POINTER(u64)]
     L.bsc_meth_cpg_format_recs.restype = C.c_long
+    L.bsc_var_params_default.restype = None
+    L.bsc_var_params_default.argtypes = [C.POINTER(VarParams)]
+    L.bsc_variants_select_recs.restype = i32
+    L.bsc_variants_select_recs.argtypes = [vp, C.c_size_t, C.POINTER(VarParams), vp, u64, C.POINTER(u64), C.POINTER(u64)]
+    L.bsc_variants_sites_device.restype = i32
+    L.bsc_variants_sites_device.argtypes = [vp, vp, vp, vp, u32, C.POINTER(VarParams), vp, u64, vp, vp, vp]
+    L.bsc_block_variants_kept.restype = i32
+    L.bsc_block_variants_kept.argtypes = [vp, C.POINTER(VarParams), u64, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)]
+    L.bsc_variants_stream_read.restype = i32
+    L.bsc_variants_stream_read.argtypes = [vp, u64, u64, vp]
+    L.bsc_variants_stream_detach.restype = i32
+    L.bsc_variants_stream_detach.argtypes = [vp, C.POINTER(vp), C.POINTER(u64)]
+    L.bsc_block_variants_csi_kept.restype = i32
+    L.bsc_block_variants_csi_kept.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(u64), C.POINTER(u64)]
     L.bsc_meth_cpg_format_recs.argtypes = [vp, C.c_size_t, C.c_char_p, C.POINTER(MethParams), vp, C.c_size_t, C.POINTER(u64)]
     L.bsc_meth_cpg_block_device.restype = i32
     L.bsc_meth_cpg_block_device.argtypes = [vp, vp, vp, u64, C.c_char_p, C.POINTER(MethParams), vp, u64, vp, vp]

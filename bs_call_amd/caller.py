@@ -1188,6 +1188,54 @@ class SiteCaller:
             self.synchronize()
         return out[: nb.value].tobytes(), int(nl.value), tuple(int(v) for v in sums)
 
+    # -- the variant-only call set (csrc/variantsdev.hip) --------------------------------------------------
+    @staticmethod
+    def _var_params(params):
+        if params is None:
+            return _lib.VarParams()
+        if isinstance(params, _lib.VarParams):
+            return params
+        return _lib.VarParams(**params)
+
+    def variants_sites_device(self, d_core, d_aux, d_emit, n, d_recs, max_recs, d_n_recs, d_totals, params=None, stream=None):
+        """bsc_variants_sites_device: the per-position arrays of reads_chain_device (d_core, d_aux; d_emit the chain's byte per position or
+        None) -> the selected records, packed, in d_recs[<= max_recs], their count (a device u64) in d_n_recs and the ten totals in
+        d_totals (asynchronous on `stream`)."""
+        vp_ = self._var_params(params)
+        _check(self._L.bsc_variants_sites_device(self._h, d_core, d_aux, d_emit, n, C.byref(vp_), d_recs, max_recs, d_n_recs, d_totals, stream))
+
+    def block_variants_kept(self, params=None, cap=None):
+        """bsc_block_variants_kept + bsc_variants_stream_read: the variant-only stream of the block the last *_keep call called — the
+        selected records as that call's encoder writes them (BCF2 records or VCF lines).  params: a _lib.VarParams, a dict of its fields,
+        or None (every variant).  Returns (bytes, records, totals[10]).  cap: the room on the device (default: asked for and given on a
+        second call)."""
+        vp_ = self._var_params(params)
+        nb, nr, tot = C.c_uint64(0), C.c_uint64(0), (C.c_uint64 * 10)()
+        room = 1 << 16 if cap is None else int(cap)
+        rc = self._L.bsc_block_variants_kept(self._h, C.byref(vp_), room, C.byref(nb), C.byref(nr), tot)
+        if rc == -1 and nb.value > room and cap is None:
+            room = int(nb.value)
+            rc = self._L.bsc_block_variants_kept(self._h, C.byref(vp_), room, C.byref(nb), C.byref(nr), tot)
+        _check(rc)
+        return self.variants_stream_read(0, nb.value), int(nr.value), tuple(int(v) for v in tot)
+
+    def variants_stream_read(self, off, n):
+        """bsc_variants_stream_read: bytes [off, off + n) of the variant stream the last block_variants_kept left on the device."""
+        out = np.empty(max(int(n), 1), dtype=np.uint8)
+        _check(self._L.bsc_variants_stream_read(self._h, int(off), int(n), _ptr(out)))
+        if n:
+            self.synchronize()
+        return out[: int(n)].tobytes()
+
+    def block_variants_csi_kept(self, min_shift=14):
+        """bsc_block_variants_csi_kept: (entries CSI_ENTRY[], records) of the variant stream the last block_variants_kept left on the device."""
+        p, n, r = C.c_void_p(), C.c_uint64(), C.c_uint64()
+        _check(self._L.bsc_block_variants_csi_kept(self._h, int(min_shift), C.byref(p), C.byref(n), C.byref(r)))
+        if not n.value:
+            return np.zeros(0, CSI_ENTRY), int(r.value)
+        buf = (C.c_uint8 * (16 * n.value)).from_address(p.value)
+        return np.frombuffer(buf, dtype=CSI_ENTRY).copy(), int(r.value)
+
     def blocks_records(self, blocks, ref, out=None, all_positions=False, reg_start=1, reg_stop=0xFFFFFFFF, dbsnp=None, with_stats=False,
                        submit_only=False):
         """Several blocks in one launch sequence (bsc_blocks_records): blocks = [(templates, seq, x, y), ...] in genome order;

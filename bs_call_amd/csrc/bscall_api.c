@@ -115,6 +115,10 @@ int bsc_dev_launch_bin_reads_multi(const void *tpl, uint32_t nr, const void *seq
                                    size_t scan_tmp_bytes, void *rd, void *counters, void *stream);
 int bsc_dev_launch_bgzf(const void *src, uint64_t n, uint32_t n_members, void *slots, void *sizes, void *offs, void *scratch, uint32_t grid,
                         void *stream); /* bgzfdev.hip */
+int bsc_dev_launch_var_select(const void *core, const void *aux, const void *emit, uint32_t n, const bsc_var_params *p, void *tile_cnt, void *tile_off,
+                              void *tile_mask, void *scan_tmp, size_t scan_tmp_bytes, void *totals, int num_cus, void *stream); /* variantsdev.hip */
+int bsc_dev_launch_var_pack(const void *core, const void *aux, uint32_t n, const void *tile_off, const void *tile_mask, void *out, uint64_t out_cap,
+                            void *total, int num_cus, void *stream);
 int bsc_dev_launch_csi_scan(int format, const void *s, uint64_t n_bytes, const void *sync, uint32_t n_sync, int min_shift, void *cnt, void *off,
                             void *scan_tmp, size_t scan_tmp_bytes, void *entries, uint64_t cap, void *totals, int num_cus, void *stream); /* csidev.hip */
 int bsc_dev_launch_bed_scan(const void *s, uint64_t n_bytes, const void *sync, uint32_t n_sync, int min_shift, void *cnt, void *off, void *scan_tmp,
@@ -286,6 +290,19 @@ struct bsc_context {
   const void *mto_for;
   uint32_t mto_tiles;
   uint64_t mto_lines;
+  struct { /* the variant-only call set (variantsdev.hip): the workspaces of a call — selected records per tile, their prefix sum, the tiles' ballots,
+            * scan scratch; bsc_block_variants_kept: the packed records, {count, ten totals, the encoder's three}, the encoder's tile bytes, tile
+            * offsets, scan scratch and line lengths — its own, so that d_bto stays the kept stream's —, the stream and its length; for which
+            * stream d_bto holds the offsets, how many tiles, text; bsc_block_variants_csi_kept: the entries, their totals, the host copy */
+    void *d_cnt, *d_off, *d_mask, *d_tmp, *d_recs, *d_tot, *d_btb, *d_bto, *d_bscn, *d_vtl, *d_out, *d_csen, *d_cstot;
+    size_t cap_cnt, cap_off, cap_mask, cap_tmp, cap_recs, cap_tot, cap_btb, cap_bto, cap_bscn, cap_vtl, cap_out, cap_csen, cap_cstot;
+    uint64_t bytes;
+    const void *bto_for;
+    uint32_t bto_tiles;
+    int bto_text;
+    bsc_csi_entry *h_csen;
+    size_t cap_hcsen;
+  } var;
   struct { /* streams handed to the caller (bsc_bcf_stream_detach) come back here (bsc_detached_free) and are taken again by the next block:
             * no hipMalloc / hipFree — a device-wide wait — in the steady state of a run that writes behind the calling */
     void *p[4];
@@ -689,6 +706,20 @@ int bsc_destroy(bsc_context *ctx) {
   hipFree(ctx->d_mll);
   hipFree(ctx->d_meth);
   hipFree(ctx->d_mtot);
+  hipFree(ctx->var.d_cnt);
+  hipFree(ctx->var.d_off);
+  hipFree(ctx->var.d_mask);
+  hipFree(ctx->var.d_tmp);
+  hipFree(ctx->var.d_recs);
+  hipFree(ctx->var.d_tot);
+  hipFree(ctx->var.d_btb);
+  hipFree(ctx->var.d_bto);
+  hipFree(ctx->var.d_bscn);
+  hipFree(ctx->var.d_vtl);
+  hipFree(ctx->var.d_out);
+  hipFree(ctx->var.d_csen);
+  hipFree(ctx->var.d_cstot);
+  free(ctx->var.h_csen);
   hipFree(ctx->mr.d_reg);
   hipFree(ctx->mr.d_acc);
   free(ctx->mr.h_start);
@@ -4880,6 +4911,200 @@ int bsc_block_csi_kept(bsc_context *ctx, int min_shift, const bsc_csi_entry **en
     HIP_TRY(hipStreamSynchronize(ctx->stream));
   }
   *entries = ctx->h_csen;
+  *n_entries = tot[0];
+  if (n_records) *n_records = tot[1];
+  return BSC_OK;
+}
+
+/* ---- the variant-only call set (variantsdev.hip): include/bscall_amd.h has the rule, csrc/variants.c the host form ------------------------------ */
+static int bsc_var_params_check(const char *who, const bsc_var_params *p) {
+  if (!p) return bsc_fail(BSC_ERR_ARG, "%s: NULL argument", who);
+  if (p->reserved != 0) return bsc_fail(BSC_ERR_ARG, "%s: reserved is %u, not 0", who, p->reserved);
+  return BSC_OK;
+}
+
+/* the select pass and the scan over d_core[n] / d_aux[n] on stream s, in the context's workspaces; d_totals: ten u64, zeroed here */
+static int bsc_var_select_run(bsc_context *ctx, const char *who, const void *d_core, const void *d_aux, const void *d_emit, uint32_t n,
+                              const bsc_var_params *p, void *d_totals, hipStream_t s) {
+  HIP_TRY(hipMemsetAsync(d_totals, 0, BSC_VAR_N_TOTALS * sizeof(unsigned long long), s));
+  if (!n) return BSC_OK;
+  const uint32_t n_tiles = (uint32_t)(((uint64_t)n + 63u) / 64u);
+  size_t scan_bytes = 0;
+  int rc;
+  if (bsc_dev_scan_tmp_bytes(n_tiles, &scan_bytes)) return bsc_fail(BSC_ERR_HIP, "%s: scan size query failed", who);
+  if ((rc = bsc_reserve(&ctx->var.d_cnt, &ctx->var.cap_cnt, (size_t)n_tiles * 4u))) return rc;
+  if ((rc = bsc_reserve(&ctx->var.d_off, &ctx->var.cap_off, (size_t)n_tiles * 4u))) return rc;
+  if ((rc = bsc_reserve(&ctx->var.d_mask, &ctx->var.cap_mask, (size_t)n_tiles * 8u))) return rc;
+  if ((rc = bsc_reserve(&ctx->var.d_tmp, &ctx->var.cap_tmp, scan_bytes ? scan_bytes : 1))) return rc;
+  const int e = bsc_dev_launch_var_select(d_core, d_aux, d_emit, n, p, ctx->var.d_cnt, ctx->var.d_off, ctx->var.d_mask, ctx->var.d_tmp, scan_bytes, d_totals,
+                                          ctx->num_cus, (void *)s);
+  if (e) return bsc_fail(BSC_ERR_HIP, "%s: select launch failed: %s", who, hipGetErrorString((hipError_t)e));
+  return BSC_OK;
+}
+
+int bsc_variants_sites_device(bsc_context *ctx, const void *d_core, const void *d_aux, const void *d_emit, uint32_t n, const bsc_var_params *p,
+                              void *d_recs, uint64_t max_recs, void *d_n_recs, void *d_totals, void *stream) {
+  static const char who[] = "bsc_variants_sites_device";
+  int rc;
+  if (!ctx || !d_n_recs || !d_totals || (n && (!d_core || !d_aux)) || (max_recs && !d_recs)) return bsc_fail(BSC_ERR_ARG, "%s: NULL argument", who);
+  if ((rc = bsc_var_params_check(who, p))) return rc;
+  if ((((uintptr_t)d_core | (uintptr_t)d_aux | (uintptr_t)d_recs) & 15u) || (((uintptr_t)d_n_recs | (uintptr_t)d_totals) & 7u))
+    return bsc_fail(BSC_ERR_ARG, "%s: the arrays and the records must be 16-byte, the count and the totals 8-byte aligned", who);
+  BSC_ENTER(ctx);
+  hipStream_t s = (hipStream_t)stream;
+  HIP_TRY(hipMemsetAsync(d_n_recs, 0, sizeof(unsigned long long), s));
+  if ((rc = bsc_var_select_run(ctx, who, d_core, d_aux, d_emit, n, p, d_totals, s))) return rc;
+  const int e = bsc_dev_launch_var_pack(d_core, d_aux, n, ctx->var.d_off, ctx->var.d_mask, d_recs, max_recs, d_n_recs, ctx->num_cus, stream);
+  if (e) return bsc_fail(BSC_ERR_HIP, "%s: pack launch failed: %s", who, hipGetErrorString((hipError_t)e));
+  return BSC_OK;
+}
+
+/* the encoders' tile workspaces, and what the context says of d_bto, exchanged with the variant stream's own around its encoder call: the kept
+ * stream's tile offsets stay where and what they are */
+static void bsc_var_enc_ws_swap(bsc_context *ctx) {
+#define BSC_SWAP_(T, a, b) \
+  do {                     \
+    T t_ = (a);            \
+    (a) = (b);             \
+    (b) = t_;              \
+  } while (0)
+  BSC_SWAP_(void *, ctx->d_btb, ctx->var.d_btb);
+  BSC_SWAP_(size_t, ctx->cap_btb, ctx->var.cap_btb);
+  BSC_SWAP_(void *, ctx->d_bto, ctx->var.d_bto);
+  BSC_SWAP_(size_t, ctx->cap_bto, ctx->var.cap_bto);
+  BSC_SWAP_(void *, ctx->d_bscn, ctx->var.d_bscn);
+  BSC_SWAP_(size_t, ctx->cap_bscn, ctx->var.cap_bscn);
+  BSC_SWAP_(void *, ctx->d_vtl, ctx->var.d_vtl);
+  BSC_SWAP_(size_t, ctx->cap_vtl, ctx->var.cap_vtl);
+  BSC_SWAP_(const void *, ctx->bto_for, ctx->var.bto_for);
+  BSC_SWAP_(uint32_t, ctx->bto_tiles, ctx->var.bto_tiles);
+  BSC_SWAP_(int, ctx->bto_text, ctx->var.bto_text);
+#undef BSC_SWAP_
+}
+
+int bsc_block_variants_kept(bsc_context *ctx, const bsc_var_params *p, uint64_t dev_cap, uint64_t *n_bytes, uint64_t *n_records, uint64_t totals[10]) {
+  static const char who[] = "bsc_block_variants_kept";
+  int rc;
+  if (!ctx || !n_bytes || !n_records) return bsc_fail(BSC_ERR_ARG, "%s: NULL argument", who);
+  *n_bytes = *n_records = 0;
+  for (int k = 0; totals && k < BSC_VAR_N_TOTALS; k++) totals[k] = 0;
+  if ((rc = bsc_var_params_check(who, p))) return rc;
+  if (ctx->meth_src != 1 || ctx->rec_pending || ctx->pending_sz)
+    return bsc_fail(BSC_ERR_ARG, "%s: the last call left no single block's arrays on the device", who);
+  BSC_ENTER(ctx);
+  hipStream_t s = ctx->stream;
+  ctx->var.bytes = 0;
+  ctx->var.bto_for = NULL;
+  /* d_tot: [0] the count the pack pass leaves (the encoder's d_n_recs), [1 .. 10] the totals, [11 .. 13] the encoder's {bytes, refused, records} */
+  if ((rc = bsc_reserve(&ctx->var.d_tot, &ctx->var.cap_tot, 14 * sizeof(unsigned long long)))) return rc;
+  unsigned long long *const d_tot = (unsigned long long *)ctx->var.d_tot;
+  HIP_TRY(hipMemsetAsync(d_tot, 0, 14 * sizeof(unsigned long long), s));
+  const uint32_t n = ctx->again.sz;
+  if ((rc = bsc_var_select_run(ctx, who, ctx->d_vout, ctx->d_out, ctx->again.emit, n, p, d_tot + 1, s))) return rc;
+  unsigned long long tot[BSC_VAR_N_TOTALS] = {0};
+  HIP_TRY(hipMemcpyAsync(tot, d_tot + 1, sizeof tot, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  const uint64_t n_rec = tot[0];
+  *n_records = n_rec;
+  for (int k = 0; totals && k < BSC_VAR_N_TOTALS; k++) totals[k] = tot[k];
+  if (!n_rec) return BSC_OK; /* (the count is known before anything is packed: the records' room is theirs, not the block's) */
+  if ((rc = bsc_reserve(&ctx->var.d_recs, &ctx->var.cap_recs, (size_t)n_rec * sizeof(bsc_vcf_rec)))) return rc;
+  int e = bsc_dev_launch_var_pack(ctx->d_vout, ctx->d_out, n, ctx->var.d_off, ctx->var.d_mask, ctx->var.d_recs, n_rec, d_tot, ctx->num_cus, (void *)s);
+  if (e) return bsc_fail(BSC_ERR_HIP, "%s: pack launch failed: %s", who, hipGetErrorString((hipError_t)e));
+  /* a buffer that came back (bsc_detached_free), the smallest that will do, as d_meth is taken */
+  if (!ctx->var.d_out && ctx->pool_mu_made) ctx->var.d_out = bsc_pool_get(ctx, (size_t)(dev_cap ? dev_cap : 1), &ctx->var.cap_out);
+  if ((rc = bsc_reserve(&ctx->var.d_out, &ctx->var.cap_out, (size_t)(dev_cap ? dev_cap : 1)))) return rc;
+  ctx->again.names.n = ctx->again.n_names; /* (the table itself is in d_bnm since the block's uploads: bsc_block_bcf_again) */
+  ctx->names_up = ctx->again.have_names ? &ctx->again.names : NULL;
+  ctx->names_up_n = ctx->again.n_names;
+  ctx->names_up_bytes = ctx->again.name_bytes;
+  bsc_var_enc_ws_swap(ctx);
+  rc = ctx->again.text
+           ? bsc_vcf_text_block_device(ctx, ctx->var.d_recs, d_tot, n_rec, ctx->again.contig, ctx->names_up, ctx->var.d_out, dev_cap, d_tot + 11, s)
+           : bsc_bcf_block_device(ctx, ctx->var.d_recs, d_tot, n_rec, ctx->again.rid, &ctx->again.ids, ctx->names_up, ctx->var.d_out, dev_cap, d_tot + 11, s);
+  bsc_var_enc_ws_swap(ctx);
+  ctx->names_up = NULL;
+  if (rc) {
+    ctx->var.bto_for = NULL;
+    return rc;
+  }
+  unsigned long long enc[3] = {0, 0, 0};
+  HIP_TRY(hipMemcpyAsync(enc, d_tot + 11, sizeof enc, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  *n_bytes = enc[0];
+  if (enc[0] > dev_cap) {
+    ctx->var.bto_for = NULL;
+    return bsc_fail(BSC_ERR_ARG, "%s: the block's variant stream has %llu bytes, dev_cap is %llu", who, enc[0], (unsigned long long)dev_cap);
+  }
+  if (enc[2] != n_rec)
+    return bsc_fail(BSC_ERR_RANGE, "%s: %llu records selected, the encoder wrote %llu (refused: %llu)", who, (unsigned long long)n_rec, enc[2], enc[1]);
+  ctx->var.bytes = enc[0];
+  return BSC_OK;
+}
+
+int bsc_variants_stream_read(bsc_context *ctx, uint64_t off, uint64_t n, void *dst) {
+  if (!ctx || (!dst && n)) return bsc_fail(BSC_ERR_ARG, "bsc_variants_stream_read: NULL argument");
+  if (off + n < off || off + n > ctx->var.bytes || off + n > ctx->var.cap_out) return bsc_fail(BSC_ERR_ARG, "bsc_variants_stream_read: beyond the stream's end");
+  if (!n) return BSC_OK;
+  BSC_ENTER(ctx);
+  HIP_TRY(hipMemcpyAsync(dst, (const char *)ctx->var.d_out + off, (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+  return BSC_OK;
+}
+
+int bsc_variants_stream_detach(bsc_context *ctx, void **d_stream, uint64_t *n_bytes) {
+  if (!ctx || !d_stream || !n_bytes) return bsc_fail(BSC_ERR_ARG, "bsc_variants_stream_detach: NULL argument");
+  *d_stream = NULL;
+  *n_bytes = 0;
+  if (!ctx->var.d_out || !ctx->var.bytes) return bsc_fail(BSC_ERR_ARG, "bsc_variants_stream_detach: the last call left no variant stream on the device");
+  BSC_ENTER(ctx);
+  bsc_pool_init(ctx);
+  if (!ctx->s_det) HIP_TRY(hipStreamCreateWithFlags(&ctx->s_det, hipStreamNonBlocking));
+  *d_stream = ctx->var.d_out;
+  *n_bytes = ctx->var.bytes;
+  bsc_pool_book(ctx, ctx->var.d_out, ctx->var.cap_out);
+  ctx->var.d_out = NULL;
+  ctx->var.cap_out = 0;
+  ctx->var.bytes = 0;
+  ctx->var.bto_for = NULL;
+  return BSC_OK;
+}
+
+int bsc_block_variants_csi_kept(bsc_context *ctx, int min_shift, const bsc_csi_entry **entries, uint64_t *n_entries, uint64_t *n_records) {
+  static const char who[] = "bsc_block_variants_csi_kept";
+  if (!ctx || !entries || !n_entries) return bsc_fail(BSC_ERR_ARG, "%s: NULL argument", who);
+  *entries = NULL;
+  *n_entries = 0;
+  if (n_records) *n_records = 0;
+  if (min_shift < 0 || min_shift > 31) return bsc_fail(BSC_ERR_ARG, "%s: min_shift %d is not 0 .. 31", who, min_shift);
+  if (!ctx->var.bytes) return BSC_OK; /* (a block with no variant has no entry) */
+  if (!ctx->var.d_out || ctx->var.bto_for != ctx->var.d_out) return bsc_fail(BSC_ERR_ARG, "%s: the context holds no variant stream", who);
+  BSC_ENTER(ctx);
+  /* a run of records that share a window gives one entry, and every run holds a record: at most as many entries as the tiles hold records */
+  const uint32_t n_sync = ctx->var.bto_tiles;
+  const uint64_t cap = (uint64_t)n_sync * 64u + 2u;
+  int rc;
+  if ((rc = bsc_reserve(&ctx->var.d_csen, &ctx->var.cap_csen, (size_t)cap * sizeof(bsc_csi_entry)))) return rc;
+  if ((rc = bsc_reserve(&ctx->var.d_cstot, &ctx->var.cap_cstot, 3 * sizeof(unsigned long long)))) return rc;
+  if ((rc = bsc_csi_scan_device(ctx, ctx->var.bto_text ? BSC_CSI_VCF : BSC_CSI_BCF, ctx->var.d_out, ctx->var.bytes, ctx->var.d_bto, n_sync, min_shift,
+                                ctx->var.d_csen, cap, ctx->var.d_cstot, ctx->stream)))
+    return rc;
+  unsigned long long tot[3] = {0, 0, 0};
+  HIP_TRY(hipMemcpyAsync(tot, ctx->var.d_cstot, sizeof tot, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  if (tot[2]) return bsc_fail(BSC_ERR_ARG, "%s: the variant stream is not whole records in position order (error bits %llu)", who, tot[2]);
+  if (tot[0] > cap) return bsc_fail(BSC_ERR_RANGE, "%s: %llu entries, room for %llu", who, tot[0], (unsigned long long)cap);
+  if (tot[0] > ctx->var.cap_hcsen) {
+    free(ctx->var.h_csen);
+    ctx->var.cap_hcsen = 0;
+    ctx->var.h_csen = malloc((size_t)(tot[0] + tot[0] / 4) * sizeof(bsc_csi_entry));
+    if (!ctx->var.h_csen) return bsc_fail(BSC_ERR_NOMEM, "%s: out of host memory", who);
+    ctx->var.cap_hcsen = (size_t)(tot[0] + tot[0] / 4);
+  }
+  if (tot[0]) {
+    HIP_TRY(hipMemcpyAsync(ctx->var.h_csen, ctx->var.d_csen, (size_t)tot[0] * sizeof(bsc_csi_entry), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+  }
+  *entries = ctx->var.h_csen;
   *n_entries = tot[0];
   if (n_records) *n_records = tot[1];
   return BSC_OK;

@@ -21,7 +21,8 @@ def run(bam_path: str, reference: Dict[str, np.ndarray], bcf_path: str, sample: 
         meth_regions=None, meth_regions_path: Optional[str] = None, meth_window: Optional[int] = None, bigwig_path: Optional[str] = None,
         cov_bigwig_path: Optional[str] = None,
         bigwig_section: int = 1024, bigwig_zoom: int = 1024, bigwig_compress: bool = False, bigbed_path: Optional[str] = None, bigbed_items: int = 512,
-        bigbed_zoom: int = 1024, bigbed_compress: bool = False, meth_index: Optional[str] = None, **reader_kw) -> dict:
+        bigbed_zoom: int = 1024, bigbed_compress: bool = False, meth_index: Optional[str] = None, variants_path: Optional[str] = None,
+        variants_params=None, **reader_kw) -> dict:
     """reference: contig name -> uint8 reference codes (0 = N, 1..4 = ACGT; position 1 first).  Returns a summary dict.
     under_conv / over_conv / min_qual (defaults 0.01 / 0.05 / 20, src/init_param.c:26-31) are the MODEL's parameters: without
     `caller` the run builds its SiteCaller from them; with one, they are taken from it and a differing explicit value is an error
@@ -72,7 +73,17 @@ def run(bam_path: str, reference: Dict[str, np.ndarray], bcf_path: str, sample: 
     block's items and summaries from the arrays it left on the device (SiteCaller.block_bigbed_kept, csrc/bigbeddev.hip), the file by
     bigbed.Writer.  bigbed_items: sites a block (1 .. 65535); bigbed_zoom: the width of a level-0 zoom window.  meth_params apply; the same
     conditions as bigwig_path.  bigbed_compress: every block leaves the device as a zlib stream (SiteCaller.block_bigbed_deflate); needs
-    bigbed_path and bigbed_items <= bigbed.Z_ITEMS_MAX."""
+    bigbed_path and bigbed_items <= bigbed.Z_ITEMS_MAX.
+
+    variants_path: the variant-only call set of the same run (include/bscall_amd.h has the rule): every block's records with an ALT
+    allele, selected on the device from the arrays the block left there and encoded by the block's own encoder
+    (SiteCaller.block_variants_kept, csrc/variantsdev.hip) — a file of the run's format and compression with the main file's header.
+    variants_params: a _lib.VarParams or a dict of min_phred / pass_only / known_only.  The summary gets "variant_records" and
+    "variant_totals" (the ten totals of the rule).  The same conditions as meth_path."""
+    if variants_params is not None and variants_path is None:
+        raise ValueError("variants_params select among the records variants_path names: they need variants_path")
+    if variants_path is not None and (shard_rank is not None or not device_reader or host_prep or host_bcf):
+        raise ValueError("variants_path is a single run on the device reader (device_reader=True, no shard_rank, no host_prep / host_bcf)")
     want_bb = bigbed_path is not None
     if bigbed_compress and not want_bb:
         raise ValueError("bigbed_compress needs bigbed_path")
@@ -157,6 +168,7 @@ def run(bam_path: str, reference: Dict[str, np.ndarray], bcf_path: str, sample: 
         per_contig = []
         n_blocks = n_records = 0
         meth_blobs, meth_lines = [], 0
+        var_blobs, var_totals = [], np.zeros(10, dtype=np.uint64)
         meth_entries = []  # meth_index: (contig number, BED_ENTRY[], bytes of the block's table)
         bw_sites = cov_sites = 0
         region_out, region_cur = [], None  # the summary's lines, contig by contig; (name, regions, names) of the contig attached
@@ -214,7 +226,7 @@ def run(bam_path: str, reference: Dict[str, np.ndarray], bcf_path: str, sample: 
                 region_cur = None
 
             def block_blobs():
-                nonlocal n_blocks, n_records, base_filter, passed, meth_lines, region_cur, bw_sites, cov_sites, bb_sites
+                nonlocal n_blocks, n_records, base_filter, passed, meth_lines, region_cur, bw_sites, cov_sites, bb_sites, var_totals
                 before, cur_tid = c.site_totals(), -1
                 for item in (rd.device_blocks() if device_reader else rd.blocks()):
                     if device_reader:
@@ -262,7 +274,7 @@ def run(bam_path: str, reference: Dict[str, np.ndarray], bcf_path: str, sample: 
                         else:
                             blob, n_rec, st = c.block_bcf_rawdev(dblk, ref, tid, names=names, left_trim=left_trim, right_trim=right_trim, min_qual=min_qual,
                                                                  reg_stop=len(codes), dbsnp=flags, with_stats=True, profile=prof,
-                                                                 keep=meth_path is not None or want_regions or want_bw or want_cov or want_bb)
+                                                                 keep=meth_path is not None or want_regions or want_bw or want_cov or want_bb or variants_path is not None)
                         if region_cur is not None:  # the block's cytosines into the attached regions' sums
                             c.block_meth_regions_kept(meth_params)
                         if want_cov:  # the coverage track, and the level track with it, from ONE sweep over the block's arrays
@@ -300,6 +312,10 @@ def run(bam_path: str, reference: Dict[str, np.ndarray], bcf_path: str, sample: 
                             meth_lines += ml
                             if meth_index is not None and mb:  # while the table is still the context's: the scan by the encoder's tile offsets
                                 meth_entries.append((tid, c.block_meth_index_kept(14)[0], len(mb)))
+                        if variants_path is not None:  # the same block's variant-only stream, by the block's own encoder
+                            vb, _, vt = c.block_variants_kept(variants_params)
+                            var_blobs.append(vb)
+                            var_totals += np.array(vt, dtype=np.uint64)
                         recs = None
                     elif host_prep:  # round 4's split: the process thread's per-template work here, then the block
                         tpl, pseq, st = prepare_templates(raw, seq, ms, left_trim, right_trim, min_qual, profile=prof, x=x, ref=ref)
@@ -353,6 +369,11 @@ def run(bam_path: str, reference: Dict[str, np.ndarray], bcf_path: str, sample: 
                         ix.members(sizes[:-1])
                         with open(meth_path + "." + meth_index, "wb") as f:
                             f.write(ix.finish())
+            if variants_path is not None:
+                if text:
+                    vcf.write_vcf_blobs(variants_path, header, var_blobs, compressed)
+                else:
+                    vcf.write_bcf(variants_path, header, var_blobs, compressed)
             if want_bw:
                 bw_writer.finish()
             if want_cov:
@@ -429,6 +450,9 @@ def run(bam_path: str, reference: Dict[str, np.ndarray], bcf_path: str, sample: 
         summary = {"blocks": n_blocks, "records": n_records, "report": report_text, "filter_cts": cts, "contigs": [n for n, _ in per_contig]}
         if meth_path is not None:
             summary["meth_lines"] = meth_lines
+        if variants_path is not None:
+            summary["variant_records"] = int(var_totals[0])
+            summary["variant_totals"] = tuple(int(v) for v in var_totals)
         if want_bw:
             summary["bigwig_sites"] = bw_sites
         if want_cov:

@@ -1658,6 +1658,75 @@ int bsc_bigbed_zstream_read(bsc_context *ctx, uint64_t off, uint64_t n, void *ds
 int bsc_last_raw_block_ms(bsc_context *ctx, float *ms);
 
 /*
+ * The variant-only call set (csrc/variantsdev.hip: bsc_var_select_kernel, the context's scan, bsc_var_pack_kernel; csrc/variants.c holds the
+ * host form, which is their checker): the records with an ALT allele — about one in a thousand of a WGBS run's records, where every called
+ * cytosine is one — as a second stream of the block, encoded by the encoder that made its kept stream.  The reference's users get it from
+ * `bcftools view` or gemBS's snpxtr over the whole file; its own `snps` counter counts every record (csrc/sitestats.hip:11-15).  The cost is
+ * the selection: a byte per position and a 16-byte head per emitted record; the block's main stream is not read again.
+ *
+ * VARIANT   A record is a variant when core.emit != 0 — and, in the per-position form where an emit-byte array is given, that position's
+ *           byte is != 0 too — and core.alt[0] != 0: the record whose ALT column is not '.'.
+ * PARAMS    bsc_var_params {min_phred, pass_only, known_only, reserved}; reserved must be 0 (BSC_ERR_ARG otherwise).  A variant is SELECTED
+ *           iff core.phred >= min_phred, and !pass_only || core.flt == 0, and !known_only || rs_found != 0.  rs_found is byte 49 of the aux
+ *           half: the dbSNP flag the block was given (snpxtr's mode).  The default is {0, 0, 0, 0}: every variant.
+ * SELECTED  The selected records in position order, as packed bsc_vcf_rec (core + aux, 128 bytes), byte for byte as they lie.  Records at
+ *           or beyond the count do not exist, whatever their bytes hold.
+ * TOTALS    Ten u64 over the selected records: [0] records, [1] snp (alt[1] == 0), [2] multi (alt[1] != 0), [3] het (gt one of 1, 2, 3, 5,
+ *           6, 8), [4] passed (flt == 0), [5] known (rs_found != 0), [6] known and passed, [7] transitions, [8] transversions, [9] the sum
+ *           of core.phred.  Transitions and transversions are counted for records with alt[1] == 0, ref_code in 1..4 (A, C, G, T) and
+ *           alt[0] one of "ACGT" only: the pair {REF, ALT} being {A, G} or {C, T} is a transition, anything else (REF == ALT included) a
+ *           transversion; a record with REF N or another ALT byte counts as neither.  Integer sums: no result depends on an order.
+ * STREAM    The selected records as encoded by the encoder of the block's kept stream — BCF2 records behind bsc_block_bcf_rawdev_keep, VCF
+ *           lines behind bsc_block_vcf_rawdev_keep — with that call's rid or contig, its ids and its names: the concatenation of the
+ *           selected records' byte ranges (lines) of the block's full stream.
+ *
+ *   bsc_var_params_default        {0, 0, 0, 0}
+ *   bsc_variants_select_recs      the host form, over packed records (the per-position gate is core.emit alone): out[<= cap] the selected
+ *                                 records, *n_out their number, totals (may be NULL).  cap too small: BSC_ERR_ARG, *n_out = the need, the
+ *                                 totals filled, nothing written to out.
+ *   bsc_variants_sites_device     over the dense per-position arrays d_core[n] / d_aux[n] (16-byte aligned) and d_emit[n], the chain's byte per
+ *                                 position, or NULL (core.emit alone gates): d_recs[min(count, max_recs)] packed records (16-byte
+ *                                 aligned; records beyond the room are counted, not stored, and nothing is written behind it), *d_n_recs a
+ *                                 device u64 = the count — what bsc_bcf_block_device and bsc_vcf_text_block_device take —, d_totals ten
+ *                                 device u64.  n = 0 gives zeros.  Asynchronous on `stream`; workspaces of the context's: one call in
+ *                                 flight per context.
+ *   bsc_block_variants_kept       the follow-up of bsc_block_bcf_rawdev_keep / bsc_block_vcf_rawdev_keep (and of bsc_block_bcf_again behind
+ *                                 them): preconditions and refusals of bsc_block_meth_kept.  Select, scan and pack over the arrays that
+ *                                 block left in HBM (by the chain's emit byte where the block has one), then the block's own encoder over
+ *                                 the packed records into a buffer of the context's own (room: dev_cap bytes), with tile workspaces of its
+ *                                 own.  dev_cap too small: BSC_ERR_ARG with *n_bytes = the room needed (*n_records and the totals are
+ *                                 filled), and the call may be repeated.  A block with no variant: 0 / 0 and BSC_OK.  The kept stream,
+ *                                 its tile offsets and bsc_block_csi_kept, the methylation tables and their index scan, the region
+ *                                 accumulators, the bigWig and bigBed data are untouched, before or after; site statistics, bsc_get_stats
+ *                                 and the read profile are not counted again.  Waits.
+ *   bsc_variants_stream_read      bytes [off, off + n) of that stream -> dst, queued on the context's stream (bsc_meth_stream_read's twin)
+ *   bsc_variants_stream_detach    the stream handed over as bsc_meth_stream_detach hands a table over: bsc_detached_read / _wait / _free and
+ *                                 bsc_bgzf_write_device serve it; it counts against the four pooled buffers
+ *   bsc_block_variants_csi_kept   bsc_block_csi_kept's twin for that stream, BEFORE it is detached: bsc_csi_scan_device with the variant
+ *                                 encoder's own 64-record tile offsets as d_sync; the entries go to bsc_csi_add of the variant file's index.
+ *                                 The entries stay valid until the next call of this entry on the context.
+ * Not built: sharded runs, the batched and host-buffer block entries, a format for the variant stream other than the kept stream's, indels
+ * (the caller makes none).
+ */
+typedef struct {
+  uint32_t min_phred; /* selected: core.phred >= min_phred */
+  int32_t pass_only;  /* != 0: core.flt == 0 only */
+  int32_t known_only; /* != 0: rs_found != 0 only */
+  uint32_t reserved;  /* 0 */
+} bsc_var_params;
+#define BSC_VAR_N_TOTALS 10
+void bsc_var_params_default(bsc_var_params *p);
+int bsc_variants_select_recs(const bsc_vcf_rec *recs, size_t n, const bsc_var_params *p, bsc_vcf_rec *out, uint64_t cap, uint64_t *n_out,
+                             uint64_t totals[10]);
+int bsc_variants_sites_device(bsc_context *ctx, const void *d_core, const void *d_aux, const void *d_emit, uint32_t n, const bsc_var_params *p,
+                              void *d_recs, uint64_t max_recs, void *d_n_recs, void *d_totals, void *stream);
+int bsc_block_variants_kept(bsc_context *ctx, const bsc_var_params *p, uint64_t dev_cap, uint64_t *n_bytes, uint64_t *n_records,
+                            uint64_t totals[10]);
+int bsc_variants_stream_read(bsc_context *ctx, uint64_t off, uint64_t n, void *dst);
+int bsc_variants_stream_detach(bsc_context *ctx, void **d_stream, uint64_t *n_bytes);
+int bsc_block_variants_csi_kept(bsc_context *ctx, int min_shift, const bsc_csi_entry **entries, uint64_t *n_entries, uint64_t *n_records);
+
+/*
  * dbSNP index (host C + zlib; csrc/dbsnp.c): the reader of the compressed index bin/dbSNP_idx writes.  In the reference
  * the index never touches the likelihoods: an entry names the record (VCF ID), forces the AA / TT homozygous-reference
  * record of a site flagged in its `fq_mask` to be written (rs_found & 2, src/print_vcf.c:139) and feeds the dbSNP

@@ -145,7 +145,7 @@ static void *pinned(size_t n) { /* page-locked: the copy-out is a true DMA, queu
  * ONE writer: three of them writing pieces of one file in parallel were 2.5 x slower (0.70 s against 0.28 for the 2.9 GB of a contig-sized
  * block: writes to one inode take turns anyway).  Page-locking a host buffer for a whole stream would cost more than the calling. */
 #define PIECE ((size_t)32 << 20)
-#define N_JOB 4 /* (a block is two jobs with --meth) */
+#define N_JOB 4 /* (a block is two jobs with --meth, three with --variants beside it) */
 typedef struct {
   void *d;        /* the stream on the device; NULL: only close_fd */
   uint64_t n, at; /* its length, where it goes in the file */
@@ -531,8 +531,16 @@ int main(int argc, char **argv) {
   const char *meth_index = NULL; /* --meth-index tbi | csi */
   bsc_meth_params mpar;
   bsc_meth_params_default(&mpar);
+  const char *variants_path = NULL; /* --variants out: the records with an ALT allele, in the run's format */
+  bsc_var_params vpar;
+  bsc_var_params_default(&vpar);
+  int variants_opts = 0;
   if (argc >= 2 && !strcmp(argv[argc - 1], "--meth") && (argc == 2 || strcmp(argv[argc - 2], "--meth"))) {
     fprintf(stderr, "%s: --meth takes the path of the methylation table to write (bedMethyl)\n", argv[0]);
+    return 2;
+  }
+  if (argc >= 2 && !strcmp(argv[argc - 1], "--variants") && (argc == 2 || strcmp(argv[argc - 2], "--variants"))) {
+    fprintf(stderr, "%s: --variants takes the path of the variant-only file to write\n", argv[0]);
     return 2;
   }
   if (argc == 2 && !strcmp(argv[1], "-D")) {
@@ -561,6 +569,15 @@ int main(int argc, char **argv) {
       argc -= k;
       continue;
     }
+    if (!strcmp(argv[1], "--variants-pass") || !strcmp(argv[1], "--variants-known")) { /* no value */
+      if (argv[1][11] == 'p') vpar.pass_only = 1;
+      else vpar.known_only = 1;
+      variants_opts = 1;
+      argv[1] = argv[0];
+      argv += 1;
+      argc -= 1;
+      continue;
+    }
     if (!strcmp(argv[1], "--meth-bigbed-compress") || !strcmp(argv[1], "--meth-bgzf")) { /* no value */
       if (argv[1][8] == 'g') meth_bgzf = 1;
       else bigbed_z = 1;
@@ -585,6 +602,17 @@ int main(int argc, char **argv) {
     else if (!strcmp(argv[1], "--world")) world = atoi(argv[2]);
     else if (!strcmp(argv[1], "--merge")) merge = atoi(argv[2]);
     else if (!strcmp(argv[1], "--meth")) meth_path = argv[2];
+    else if (!strcmp(argv[1], "--variants")) variants_path = argv[2];
+    else if (!strcmp(argv[1], "--variants-min-qual")) {
+      char *end = NULL;
+      const unsigned long v = strtoul(argv[2], &end, 10);
+      if (!argv[2][0] || *end || argv[2][0] == '-' || v > 0xfffffffful) {
+        fprintf(stderr, "%s: %s takes a count, not '%s'\n", argv[0], argv[1], argv[2]);
+        return 2;
+      }
+      vpar.min_phred = (uint32_t)v;
+      variants_opts = 1;
+    }
     else if (!strcmp(argv[1], "--meth-index")) {
       if (strcmp(argv[2], "tbi") && strcmp(argv[2], "csi")) {
         fprintf(stderr, "%s: --meth-index takes tbi or csi, not '%s'\n", argv[0], argv[2]);
@@ -651,7 +679,7 @@ int main(int argc, char **argv) {
     argc -= 2;
   }
   if (argc < 5 || world < 1 || (rank >= 0 && rank >= world)) {
-    fprintf(stderr, "usage: %s [-O u|b] [--format bcf|vcf] [--index] [-D dbsnp.idx] [--meth out.bed [--meth-bgzf] [--meth-index tbi|csi] [--meth-merge | --meth-all] [--meth-min-cov n] [--meth-min-gq n] [--meth-pass]] [--meth-regions regions.bed | --meth-window n --meth-regions-out out.tsv] [--meth-bigwig out.bw [--meth-bigwig-section n] [--meth-bigwig-zoom n] [--meth-bigwig-compress: zlib sections, n <= 8157]: the methylation level as a bigWig track, per cytosine even with --meth-merge, under the --meth-* thresholds and --meth-all] [--cov-bigwig cov.bw: the depth of the same sites as a bigWig track, under the same --meth-bigwig-* switches] [--meth-bigbed out.bb [--meth-bigbed-items n] [--meth-bigbed-zoom n] [--meth-bigbed-compress: zlib blocks, n <= 652]] [--rank r --world n | --merge n] in.bam ref.fa out.bcf report.json [sample]\n", argv[0]);
+    fprintf(stderr, "usage: %s [-O u|b] [--format bcf|vcf] [--index] [-D dbsnp.idx] [--meth out.bed [--meth-bgzf] [--meth-index tbi|csi] [--meth-merge | --meth-all] [--meth-min-cov n] [--meth-min-gq n] [--meth-pass]] [--meth-regions regions.bed | --meth-window n --meth-regions-out out.tsv] [--meth-bigwig out.bw [--meth-bigwig-section n] [--meth-bigwig-zoom n] [--meth-bigwig-compress: zlib sections, n <= 8157]: the methylation level as a bigWig track, per cytosine even with --meth-merge, under the --meth-* thresholds and --meth-all] [--cov-bigwig cov.bw: the depth of the same sites as a bigWig track, under the same --meth-bigwig-* switches] [--meth-bigbed out.bb [--meth-bigbed-items n] [--meth-bigbed-zoom n] [--meth-bigbed-compress: zlib blocks, n <= 652]] [--variants out: the records with an ALT allele, in the run's format and compression, with out.csi under --index [--variants-min-qual n] [--variants-pass] [--variants-known: dbSNP sites only, with -D]] [--rank r --world n | --merge n] in.bam ref.fa out.bcf report.json [sample]\n", argv[0]);
     return 2;
   }
   if (text && (rank >= 0 || merge > 0)) {
@@ -696,6 +724,18 @@ int main(int argc, char **argv) {
   }
   if (meth_path && (getenv("BAM2BCF_HOST_PREP") || getenv("BAM2BCF_HOST_BCF") || getenv("BAM2BCF_HOST_READER"))) {
     fprintf(stderr, "%s: --meth encodes what the device reader's blocks leave on the device: not with BAM2BCF_HOST_READER / _HOST_BCF / _HOST_PREP\n", argv[0]);
+    return 2;
+  }
+  if (variants_opts && !variants_path) {
+    fprintf(stderr, "%s: --variants-min-qual / --variants-pass / --variants-known select among the records --variants writes: they need --variants out\n", argv[0]);
+    return 2;
+  }
+  if (variants_path && (rank >= 0 || world > 1 || merge > 0)) {
+    fprintf(stderr, "%s: --variants writes a single run's file; a sharded run (--rank / --world / --merge) has none\n", argv[0]);
+    return 2;
+  }
+  if (variants_path && (getenv("BAM2BCF_HOST_PREP") || getenv("BAM2BCF_HOST_BCF") || getenv("BAM2BCF_HOST_READER"))) {
+    fprintf(stderr, "%s: --variants selects from what the device reader's blocks leave on the device: not with BAM2BCF_HOST_READER / _HOST_BCF / _HOST_PREP\n", argv[0]);
     return 2;
   }
   if (meth_bgzf && !meth_path) {
@@ -890,6 +930,10 @@ int main(int argc, char **argv) {
     fclose(mf);
     if (bgzf || meth_bgzf) CHECK(bsc_bgzf_open(ctx, &zm));
   }
+  int var_fd = -1; /* --variants: the file, where its next bytes go, its compressor and index, the sums of the blocks' totals */
+  uint64_t var_at = 0, var_tot[BSC_VAR_N_TOTALS] = {0};
+  bsc_bgzf *zv = NULL;
+  bsc_csi *vcsi = NULL;
   bsc_tbx *tbx = NULL;
   bsc_bgzf *zw = NULL;
   bsc_csi *csi = NULL;
@@ -941,6 +985,38 @@ int main(int argc, char **argv) {
     }
     if (meth_index) /* the table has no header: its index begins with the first block (it keeps its own copy of the names) */
       CHECK(bsc_tbx_open(zm, meth_index[0] == 't' ? BSC_TBX_TBI : BSC_TBX_CSI, 14, n_ref, names, lens, &tbx));
+    if (variants_path) { /* the variant-only file: the main file's header, then a block's selected records as they come — its own compressor and
+                          * its own index under -O b / --index, as the --meth table has */
+      FILE *vf = fopen(variants_path, "wb");
+      if (!vf) {
+        perror(variants_path);
+        return 1;
+      }
+      if (bgzf) {
+        char *hb = NULL;
+        size_t hn = 0;
+        FILE *hm = open_memstream(&hb, &hn);
+        if (!hm) {
+          perror("open_memstream");
+          return 1;
+        }
+        write_header(hm, n_ref, names, lens, sample, text);
+        if (fclose(hm)) {
+          perror("open_memstream");
+          return 1;
+        }
+        CHECK(bsc_bgzf_open(ctx, &zv));
+        CHECK(bsc_bgzf_write(zv, hb, hn));
+        free(hb);
+        if (index) CHECK(bsc_csi_open(zv, text ? BSC_CSI_VCF : BSC_CSI_BCF, 14, n_ref, names, lens, &vcsi));
+      } else {
+        write_header(vf, n_ref, names, lens, sample, text);
+        fflush(vf);
+        var_at = (uint64_t)ftello(vf);
+      }
+      var_fd = dup(fileno(vf));
+      fclose(vf);
+    }
     if (bgzf) { /* the header into the compressor: its members come out with the first block's */
       char *hb = NULL;
       size_t hn = 0;
@@ -1236,6 +1312,37 @@ int main(int argc, char **argv) {
           meth_at += n_m;
         }
       }
+      if (n_bytes && variants_path) { /* the block's variant-only stream, selected from the same arrays and encoded by the block's own encoder: a
+                                       * buffer and a job of its own */
+        uint64_t v_cap = (uint64_t)n / 4 + 65536, v_bytes = 0, v_recs = 0, vt[BSC_VAR_N_TOTALS];
+        int vrc = bsc_block_variants_kept(ctx, &vpar, v_cap, &v_bytes, &v_recs, vt);
+        if (vrc == BSC_ERR_ARG && v_bytes > v_cap) vrc = bsc_block_variants_kept(ctx, &vpar, v_bytes, &v_bytes, &v_recs, vt);
+        CHECK(vrc);
+        for (int k = 0; k < BSC_VAR_N_TOTALS; k++) var_tot[k] += vt[k];
+        if (v_bytes && vcsi) { /* its index entries, by the variant encoder's own tile offsets: noted at the writer's logical length */
+          const bsc_csi_entry *ce = NULL;
+          uint64_t cn = 0;
+          CHECK(bsc_block_variants_csi_kept(ctx, 14, &ce, &cn, NULL));
+          CHECK(bsc_csi_add(vcsi, dblk.tid, ce, cn, v_bytes));
+        }
+        if (v_bytes) {
+          void *d_v = NULL;
+          uint64_t n_v = 0;
+          CHECK(bsc_variants_stream_detach(ctx, &d_v, &n_v));
+          if (zv) {
+            CHECK(bsc_bgzf_write_device(zv, d_v, n_v));
+            CHECK(bsc_detached_free(ctx, d_v));
+            d_v = NULL;
+            n_v = 0;
+            CHECK(bsc_bgzf_take(zv, &d_v, &n_v));
+          }
+          if (n_v) {
+            const out_job j = {d_v, n_v, var_at, var_fd, 0};
+            writer_push(&W, j);
+          }
+          var_at += n_v;
+        }
+      }
       if (n_bytes) { /* the stream changes hands: the output thread reads it out and writes it while this one goes on to the next block */
         void *d_stream = NULL;
         uint64_t n_det = 0;
@@ -1380,6 +1487,34 @@ int main(int argc, char **argv) {
       tbx = NULL;
     }
   }
+  if (zv) { /* the variant file's last member and its end-of-file marker; its index */
+    void *d_z = NULL;
+    uint64_t n_z = 0;
+    CHECK(bsc_bgzf_close(zv, &d_z, &n_z));
+    zv = NULL;
+    if (n_z) {
+      const out_job j = {d_z, n_z, var_at, var_fd, 0};
+      writer_push(&W, j);
+    }
+    var_at += n_z;
+    if (vcsi) {
+      const long need = bsc_csi_finish(vcsi, NULL, 0);
+      CHECK(need);
+      uint8_t *ib = xrealloc(NULL, (size_t)need);
+      CHECK(bsc_csi_finish(vcsi, ib, (uint64_t)need));
+      char *ip = xrealloc(NULL, strlen(variants_path) + 8);
+      sprintf(ip, "%s.csi", variants_path);
+      FILE *fi = fopen(ip, "wb");
+      if (!fi || fwrite(ib, 1, (size_t)need, fi) != (size_t)need || fclose(fi)) {
+        perror(ip);
+        return 1;
+      }
+      free(ip);
+      free(ib);
+      bsc_csi_close(vcsi);
+      vcsi = NULL;
+    }
+  }
   if (W.started) { /* the output thread writes what it still holds, then goes */
     pthread_mutex_lock(&W.mu);
     W.quit = 1;
@@ -1395,6 +1530,10 @@ int main(int argc, char **argv) {
   }
   if (meth_fd >= 0 && close(meth_fd)) {
     perror(meth_path);
+    return 1;
+  }
+  if (var_fd >= 0 && close(var_fd)) {
+    perror(variants_path);
     return 1;
   }
   if (bw) { /* every block's data are in: the section count, the indexes, the zoom levels, the summary and the header */
@@ -1521,6 +1660,10 @@ int main(int argc, char **argv) {
     if (bigwig_path) printf("%llu methylation bigWig sites written\n", (unsigned long long)bw_sites);
     if (cov_path) printf("%llu coverage bigWig sites written\n", (unsigned long long)cw_sites);
     if (bigbed_path) printf("%llu bedMethyl bigBed items written\n", (unsigned long long)bb_sites);
+    if (variants_path)
+      printf("%llu variant records written (snp %llu, multi %llu, het %llu, pass %llu, known %llu, ts %llu, tv %llu)\n", (unsigned long long)var_tot[0],
+             (unsigned long long)var_tot[1], (unsigned long long)var_tot[2], (unsigned long long)var_tot[3], (unsigned long long)var_tot[4],
+             (unsigned long long)var_tot[5], (unsigned long long)var_tot[7], (unsigned long long)var_tot[8]);
   }
   if (getenv("BAM2BCF_TIMING")) {
     uint64_t rc4[4] = {0, 0, 0, 0};
