@@ -23,12 +23,14 @@
  *                     kernels use the same header, so GPU output must equal this flavour bit for bit — and on a host
  *                     whose libm is glibc's FMA variant the two flavours are themselves identical (tests/test_bsmath.py).
  *
- * Pinning status: the reference's own sources for this path all include include/bs_call.h, which
- * includes <htslib/sam.h>, <htslib/vcf.h>, <htslib/faidx.h>; htslib is not in this image and writing
- * stand-in headers is not allowed, so the reference is NOT built here (no oracle/_ref).  The libm
- * flavour is pinned bit-for-bit by the ten known-answer vectors that SURVEY.md section 8c records from
- * the reference itself (tests/golden/kav_survey8c.json, tests/test_oracle_kav.py) and cross-checked
- * against an independently written pure-Python restatement (oracle/py_model.py).
+ * Pinning status: everything restated in this file is held, byte for byte, against the reference's OWN code — its unchanged
+ * sources compiled against opaque htslib typedefs behind oracle/ref_driver.c (`make ref` in this directory ->
+ * _ref/libbscall_ref.so, never committed): the libm flavour of orc_calc_gt_prob_* / orc_fisher_* / the tables against
+ * calc_gt_prob / fisher / init_param, orc_accumulate + orc_call_sites against call_genotypes_ML and its calc threads
+ * (tests/test_ref_pin.py; the kernels: tests/test_gpu_ref_pin.py).  Where that binary cannot be built the pin is carried by
+ * tests/golden/ref_vectors.json, recorded from it, and by the ten known-answer vectors of SURVEY.md section 8c
+ * (tests/golden/kav_survey8c.json, tests/test_oracle_kav.py); oracle/py_model.py is an independently written cross-check.
+ * orc_vcf.c (print_vcf.c calls htslib) is NOT pinned this way.
  */
 #include <math.h>
 #include <pthread.h>

@@ -7,9 +7,9 @@
   indel normalisation  src/process_template.c:62-108
   get_al_qual       src/al_utils.c:19-35        (incl. the sq[k] indexing)
   meth_profile      src/meth_profile.c:48-77    (the non-CpG read profile, with the positions process_template.c:76-108 tracks)
-Pinning: like the rest of the oracle, nothing in this image can run the reference's own code for this stage (it needs
-the gt/ containers built against htslib-dependent headers); the restatement is pinned by the hand-worked cases of
-tests/test_prep.py, each derived from the cited lines.
+Pinning: held against the reference's own process_template_vector and meth_profile (oracle/_ref/libbscall_ref.so behind
+oracle/ref_driver.c) by tests/test_ref_pin.py, on the hand-worked cases of tests/test_prep.py — each derived from the cited
+lines — and on random alignments.  get_al_qual is not part of that binary's driver: hand-worked only.
 A template is a dict: pos [fwd, rev], span [2], reads [list of ints or None, ...], misms [list of [type, position, size]
 per read], mapq, orientation, bs_strand.  Types: 0 MISMS, 1 INS (CIGAR D), 2 DEL (CIGAR I), 3 SOFT.
 """

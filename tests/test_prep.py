@@ -1,8 +1,8 @@
 """Read pre-processing (csrc/prep.c, host C) against hand-worked cases — one per branch of
 trim_read / trim_soft_clips / handle_overlap / the indel normalisation, each derived by hand from the cited lines of the
 reference — and against the pure-Python restatement (oracle/py_prep.py) on random valid alignments.
-Pinning caveat (same as the rest of the oracle): the reference's own code for this stage cannot be built in this image;
-the hand-worked cases are the anchor.  CPU only: this stage is host code."""
+The same cases and generators run through the reference's own code in tests/test_ref_pin.py (level 3).  CPU only: this stage
+is host code."""
 import numpy as np
 import pytest
 
