@@ -119,7 +119,7 @@ BD_FN uint8_t bd_bs_strand(const uint8_t *s, const uint8_t *end) {
         break;
       case 'B': {
         const uint8_t st = *s++;
-        unsigned sz = 0;
+        uint32_t sz = 0;
         if (st == 'c' || st == 'C' || st == 'A') sz = 1;
         else if (st == 's' || st == 'S') sz = 2;
         else if (st == 'i' || st == 'I' || st == 'f') sz = 4;
@@ -128,7 +128,8 @@ BD_FN uint8_t bd_bs_strand(const uint8_t *s, const uint8_t *end) {
         if (s + 4 <= end && sz != 0) {
           const uint32_t n = bd_le32(s);
           s += 4;
-          if ((uint64_t)n * sz <= (uint64_t)(end - s)) s += (size_t)n * sz; else ok = 0;
+          const uint32_t skip = n * sz; /* the reference's product: unsigned, 32 bits — a count of 2^30 dwords skips nothing */
+          if ((uint64_t)skip <= (uint64_t)(end - s)) s += skip; else ok = 0;
         } else ok = 0;
       } break;
       default: break;

@@ -905,11 +905,12 @@ static uint8_t bs_strand_of(const uint8_t *s, const uint8_t *end) {
         if (s < end) s++; else ok = 0;
         break;
       case 'B': {
-        const unsigned sz = sub_size[*s++];
+        const uint32_t sz = sub_size[*s++];
         if (s + 4 <= end && sz != 0) {
           const uint32_t n = le32(s);
           s += 4;
-          if ((uint64_t)n * sz <= (uint64_t)(end - s)) s += (size_t)n * sz; else ok = 0;
+          const uint32_t skip = n * sz; /* the reference's product: unsigned, 32 bits — a count of 2^30 dwords skips nothing */
+          if ((uint64_t)skip <= (uint64_t)(end - s)) s += skip; else ok = 0;
         } else ok = 0;
       } break;
       default: break; /* an unknown type: the reference moves on without consuming a value */

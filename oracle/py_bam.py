@@ -152,8 +152,9 @@ def get_bs_strand(aux):
             if s + 4 <= end and sz:
                 n = struct.unpack_from("<I", aux, s)[0]
                 s += 4
-                if s + n * sz <= end:
-                    s += n * sz
+                skip = (n * sz) & 0xFFFFFFFF  # the reference's product is unsigned and 32 bits wide (src/input_sam.c:211)
+                if s + skip <= end:
+                    s += skip
                 else:
                     ok = False
             else:

@@ -10,6 +10,7 @@
  *   call_genotypes_ML, init/join_calc_threads src/call_genotypes.c   (HOT LOOP A, the calc-thread pool, HOT LOOP B)
  *   process_template_vector                   src/process_template.c (with trim_read, trim_soft_clips, handle_overlap)
  *   meth_profile                              src/meth_profile.c
+ *   get_next_align_details                    src/input_sam.c        (with get_bam_misms, get_seq_and_qual, get_bs_strand)
  * The driver only builds their inputs (gt_vector / align_details / work_t) from flat arrays laid out as
  * bs_call_amd/abi.py lays them out, plays the threads the reference's main program would have run around them, and copies
  * the results out.  The reference's asserts are live: hand over only inputs it accepts (see oracle/ref_loader.py).
@@ -19,6 +20,7 @@
  *   2  refdrv_open / refdrv_block / refdrv_close                           one call_genotypes_ML block
  *   3  refdrv_prep_block (between refdrv_open and refdrv_close)            process_template_vector: the per-template stage,
  *                                                                          the read profile, then the same block as level 2
+ *   R  refdrv_align_details                                                the record parser, one BAM record at a time
  */
 #include <pthread.h>
 #include <stdint.h>
@@ -372,4 +374,142 @@ int refdrv_prep_block(const drv_raw_template *raw, uint32_t nr, const uint8_t *s
   else memcpy(out_prof, st->meth_profile->memory, sizeof(meth_cts) * used);
   free_align_list(list);
   return ret;
+}
+
+/* ---- level R: the record parser ------------------------------------------------------------------------------------------------
+ * get_next_align_details reads its record through htslib's sam_read1 (sam_itr_next with an iterator).  There is no htslib here:
+ * these two are ours, and sam_read1 hands over the next record of the buffer refdrv_align_details was given — a BAM file's
+ * alignment records as the file holds them, block_size first. */
+static const uint8_t *rd_records;
+static const uint64_t *rd_offsets;
+static uint64_t rd_n, rd_next;
+static uint8_t *rd_buf; /* the record in hand */
+static uint64_t rd_buf_cap;
+
+static uint32_t rd_le32(const uint8_t *p) { return p[0] | (uint32_t)p[1] << 8 | (uint32_t)p[2] << 16 | (uint32_t)p[3] << 24; }
+
+int sam_read1(htsFile *fp, bam_hdr_t *h, bam1_t *b) {
+  (void)fp, (void)h;
+  if (rd_next >= rd_n) return -1;
+  const uint8_t *p = rd_records + rd_offsets[rd_next++];
+  const uint32_t block_size = rd_le32(p);
+  p += 4;
+  bam1_core_t *const c = &b->core;
+  c->tid = (int32_t)rd_le32(p);
+  c->pos = (int32_t)rd_le32(p + 4);
+  c->l_qname = p[8];
+  c->qual = p[9];
+  c->bin = (uint16_t)(p[10] | p[11] << 8);
+  c->n_cigar = (uint16_t)(p[12] | p[13] << 8);
+  c->flag = (uint16_t)(p[14] | p[15] << 8);
+  c->l_qseq = (int32_t)rd_le32(p + 16);
+  c->mtid = (int32_t)rd_le32(p + 20);
+  c->mpos = (int32_t)rd_le32(p + 24);
+  c->isize = (int32_t)rd_le32(p + 28);
+  /* data points at the name, in a copy placed so that the CIGAR behind the name is dword-aligned: bam_get_cigar reads it as uint32_t */
+  const uint32_t l_data = block_size - 32, shift = (4u - (c->l_qname & 3u)) & 3u;
+  if ((uint64_t)l_data + 8 > rd_buf_cap) {
+    free(rd_buf);
+    rd_buf_cap = 2 * ((uint64_t)l_data + 8);
+    rd_buf = malloc(rd_buf_cap);
+    if (!rd_buf) return -2;
+  }
+  memcpy(rd_buf + shift, p + 32, l_data);
+  b->data = rd_buf + shift;
+  b->l_data = (int)l_data;
+  b->m_data = block_size - 32;
+  return (int)block_size;
+}
+
+int sam_itr_next(htsFile *fp, hts_itr_t *itr, bam1_t *b) {
+  (void)fp, (void)itr, (void)b;
+  return -1;
+}
+
+typedef struct {
+  int32_t ret;
+  uint32_t filtered, reverse, alignment_flag, align_length, orientation, forward_position, reverse_position;
+  uint32_t mapq, reference_span, bs_strand; /* mapq[ix], reference_span[ix]: ix = 1 for a reverse-strand record */
+  uint32_t n_misms;
+  uint64_t misms_off; /* into out_misms */
+  uint32_t read_len, pad; /* the used length of read[ix] (l_qseq) */
+  uint64_t read_off;  /* into out_seq */
+} drv_align_out;
+_Static_assert(sizeof(drv_align_out) == 72, "ALIGN_OUT layout");
+
+/* records: n alignment records (block_size, the 32 fixed bytes, the data), record i at records + offsets[i]; records_len: the
+ * buffer's size.  One get_next_align_details per record with a fresh align_details.  A record the reference does not use
+ * (ret = 1) leaves its span, strand, list and read empty, as the reference leaves them.  Returns 0; -1: a record does not lie
+ * in the buffer or its fixed fields do not fit its block_size; -2 / -3: ms_cap / seq_cap too small. */
+int refdrv_align_details(const uint8_t *records, uint64_t records_len, const uint64_t *offsets, uint64_t n, uint64_t mapq_thresh,
+                         uint64_t max_template_len, int keep_unmatched, int ignore_dup, drv_align_out *out, drv_misms *out_misms,
+                         uint64_t ms_cap, uint8_t *out_seq, uint64_t seq_cap) {
+  for (uint64_t i = 0; i < n; i++) {
+    if (offsets[i] + 36 > records_len) return -1;
+    const uint8_t *p = records + offsets[i];
+    const uint64_t bs = rd_le32(p), l_name = p[12], n_cigar = p[16] | (uint32_t)p[17] << 8, l_seq = rd_le32(p + 20);
+    if (bs < 32 || offsets[i] + 4 + bs > records_len || 32 + l_name + 4 * n_cigar + (l_seq + 1) / 2 + l_seq > bs) return -1;
+  }
+  rd_records = records;
+  rd_offsets = offsets;
+  rd_n = n;
+  rd_next = 0;
+  uint64_t ms_at = 0, seq_at = 0;
+  int rc = 0;
+  for (uint64_t i = 0; i < n && !rc; i++) {
+    align_details al;
+    memset(&al, 0, sizeof al);
+    for (int k = 0; k < 2; k++) al.mismatches[k] = gt_vector_new(8, sizeof(gt_misms));
+    bam1_t b;
+    memset(&b, 0, sizeof b);
+    bool reverse = false;
+    gt_filter_reason filtered = gt_flt_none;
+    uint32_t align_length = 0, alignment_flag = 0;
+    const int ret = get_next_align_details(NULL, NULL, NULL, &b, &al, mapq_thresh, max_template_len, keep_unmatched != 0, ignore_dup != 0,
+                                           &reverse, &filtered, &align_length, &alignment_flag);
+    const int ix = reverse ? 1 : 0;
+    drv_align_out *o = out + i;
+    memset(o, 0, sizeof *o);
+    o->ret = ret;
+    o->filtered = (uint32_t)filtered;
+    o->reverse = reverse ? 1 : 0;
+    o->alignment_flag = alignment_flag;
+    o->align_length = align_length;
+    o->orientation = (uint32_t)al.orientation;
+    o->forward_position = al.forward_position;
+    o->reverse_position = al.reverse_position;
+    o->mapq = al.mapq[ix];
+    o->reference_span = al.reference_span[ix];
+    o->bs_strand = (uint32_t)al.bs_strand;
+    o->misms_off = ms_at;
+    o->read_off = seq_at;
+    const uint64_t nm = gt_vector_get_used(al.mismatches[ix]);
+    if (ms_at + nm > ms_cap) rc = -2;
+    else {
+      const gt_misms *m = gt_vector_get_mem(al.mismatches[ix], gt_misms);
+      for (uint64_t z = 0; z < nm; z++) {
+        out_misms[ms_at + z].type = (uint32_t)m[z].misms_type;
+        out_misms[ms_at + z].position = m[z].position;
+        out_misms[ms_at + z].size = m[z].size;
+      }
+      o->n_misms = (uint32_t)nm;
+      ms_at += nm;
+    }
+    if (!rc && al.read[ix]) {
+      const uint64_t len = gt_vector_get_used(al.read[ix]);
+      if (seq_at + len > seq_cap) rc = -3;
+      else {
+        if (len) memcpy(out_seq + seq_at, gt_vector_get_mem(al.read[ix], uint8_t), len);
+        o->read_len = (uint32_t)len;
+        seq_at += len;
+      }
+    }
+    for (int k = 0; k < 2; k++) {
+      if (al.read[k]) gt_vector_delete(al.read[k]);
+      gt_vector_delete(al.mismatches[k]);
+    }
+  }
+  rd_records = NULL;
+  rd_n = rd_next = 0;
+  return rc;
 }

@@ -1,7 +1,7 @@
 """ctypes mirror of oracle/ref_driver.c: the REFERENCE'S OWN functions, compiled from its unchanged sources into
 oracle/_ref/libbscall_ref.so (oracle/Makefile, target `ref`; never committed).
 
-TEST INFRASTRUCTURE.  Import only from tests/ and tools/make_ref_vectors.py.
+TEST INFRASTRUCTURE.  Import only from tests/ and tools/make_ref_vectors.py / make_ref_align_vectors.py.
 
 The reference's asserts are live and abort the process, and gt_fatal_error exits it.  So:
   * hand over only inputs the reference accepts — templates oracle/py_prep.py accepts, blocks for which
@@ -38,6 +38,16 @@ def available():
     return os.path.exists(LIB)
 
 
+def has_align_details():
+    """The binary is there AND holds level R (refdrv_align_details).  oracle/_ref/ is not part of a checkout: a binary built by an
+    earlier recipe stays where the reference's tree is absent and the recipe skips.  Read from the file's symbol strings, without
+    loading the library (a process that holds the GPU asks too)."""
+    if not available():
+        return False
+    with open(LIB, "rb") as f:
+        return b"\0refdrv_align_details\0" in f.read()
+
+
 def build(ref=None):
     """Runs the recipe (it skips, successfully, where the reference's tree is absent) -> available()."""
     cmd = ["make", "-C", HERE, "ref"] + (["REF=%s" % ref] if ref else [])
@@ -69,6 +79,10 @@ def lib():
         L.refdrv_prep_block.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32,
                                         C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p,
                                         C.c_void_p, C.c_void_p, C.c_void_p]
+        if hasattr(L, "refdrv_align_details"):  # a binary left by an earlier recipe (kept where the reference's tree is absent) has no level R
+            L.refdrv_align_details.restype = C.c_int
+            L.refdrv_align_details.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_int, C.c_int, C.c_void_p,
+                                               C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64]
         _lib = L
     return _lib
 
@@ -159,6 +173,36 @@ class Session:
         return dict(x=x, tpl=tpl, seq=oseq[:n_seq].copy(), stats=stats, prof=prof[: int(used[0])].copy(), pile=pile, gtm=gtm, skip=skip)
 
 
+# ---- level R: the record parser ------------------------------------------------------------------------------------------
+# one entry per record (oracle/ref_driver.c drv_align_out): what get_next_align_details returned and left in its align_details
+ALIGN_OUT = np.dtype([("ret", "<i4"), ("filtered", "<u4"), ("reverse", "<u4"), ("alignment_flag", "<u4"), ("align_length", "<u4"), ("orientation", "<u4"),
+                      ("forward_position", "<u4"), ("reverse_position", "<u4"), ("mapq", "<u4"), ("reference_span", "<u4"), ("bs_strand", "<u4"),
+                      ("n_misms", "<u4"), ("misms_off", "<u8"), ("read_len", "<u4"), ("_pad", "<u4"), ("read_off", "<u8")])
+assert ALIGN_OUT.itemsize == 72
+
+
+def align_details(records, offsets, mapq_thresh=20, max_template_len=1000, keep_unmatched=False, ignore_dup=False):
+    """get_next_align_details (src/input_sam.c) once per BAM alignment record.  records: the records' bytes as a BAM file holds
+    them (block_size first), record i at offsets[i] -> (ALIGN_OUT[n], MISMS[] of all lists, the bytes of all reads).  mapq[ix],
+    reference_span[ix], the list and the read are those of the record's own side (ix = 1 for a reverse-strand record)."""
+    A = _abi()
+    assert has_align_details(), "oracle/_ref/libbscall_ref.so has no refdrv_align_details: rebuild it (`%s`)" % RECIPE
+    records = np.ascontiguousarray(records, dtype=np.uint8)
+    offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+    n = len(offsets)
+    ms_cap = seq_cap = 1
+    for o in offsets.tolist():
+        ms_cap += int(records[o + 16]) | int(records[o + 17]) << 8
+        seq_cap += int.from_bytes(records[o + 20 : o + 24].tobytes(), "little")
+    out = np.zeros(n, dtype=ALIGN_OUT)
+    ms = np.zeros(ms_cap, dtype=A.MISMS)
+    seq = np.zeros(seq_cap, dtype=np.uint8)
+    rc = lib().refdrv_align_details(_ptr(records), len(records), _ptr(offsets), n, int(mapq_thresh), int(max_template_len), int(bool(keep_unmatched)),
+                                    int(bool(ignore_dup)), _ptr(out), _ptr(ms), ms_cap, _ptr(seq), seq_cap)
+    assert rc == 0, rc
+    return out, ms[: int(out["n_misms"].sum())].copy(), seq[: int(out["read_len"].sum())].copy()
+
+
 # ---- the functions a child process runs: dict of arrays in, dict of arrays out ---------------------------------------------
 # params (float64): under_conv, over_conv, ref_bias[, min_qual, n_calc_threads[, left_trim0, left_trim1, right_trim0, right_trim1]]
 def _fn_calc_gt_prob(a):
@@ -189,15 +233,27 @@ def _fn_prep_block(a):
             "gtm": r["gtm"].view(np.uint8), "skip": r["skip"]}
 
 
-FUNCTIONS = {"calc_gt_prob": _fn_calc_gt_prob, "fisher": _fn_fisher, "block": _fn_block, "prep_block": _fn_prep_block}
+def _fn_align_details(a):
+    """params (uint64): mapq_thresh, max_template_len, keep_unmatched, ignore_dup"""
+    p = [int(v) for v in a["params"]]
+    out, ms, seq = align_details(a["records"], a["offsets"], p[0], p[1], p[2], p[3])
+    return {"align": out.view(np.uint8), "misms": ms.view(np.uint8), "reads": seq}
+
+
+FUNCTIONS = {"calc_gt_prob": _fn_calc_gt_prob, "fisher": _fn_fisher, "block": _fn_block, "prep_block": _fn_prep_block,
+             "align_details": _fn_align_details}
 # which arrays are records: they travel as their bytes (a .npy of a padded record dtype does not round-trip its offsets)
-_RECORDS = {"gt": "GT_METH", "gtm": "GT_METH", "pile": "PILEUP", "tpl": "TEMPLATE", "raw": "RAW_TEMPLATE", "misms": "MISMS"}
+_RECORDS = {"gt": "GT_METH", "gtm": "GT_METH", "pile": "PILEUP", "tpl": "TEMPLATE", "raw": "RAW_TEMPLATE", "misms": "MISMS", "align": "ALIGN_OUT"}
+
+
+def _record_dtype(name):
+    return ALIGN_OUT if _RECORDS[name] == "ALIGN_OUT" else getattr(_abi(), _RECORDS[name])
 
 
 def _as_bytes(name, arr):
     arr = np.ascontiguousarray(arr)
     if name in _RECORDS:
-        arr = np.ascontiguousarray(arr, dtype=getattr(_abi(), _RECORDS[name])).view(np.uint8)
+        arr = np.ascontiguousarray(arr, dtype=_record_dtype(name)).view(np.uint8)
     return arr
 
 
@@ -205,7 +261,6 @@ def run_in_child(fn_name, arrays, timeout=120):
     """Runs FUNCTIONS[fn_name] in a fresh Python process (this file as a script: no torch, no product library, no GPU) and
     returns its arrays; record arrays come back as their dtypes.  An abort in reference code ends the child, not the caller."""
     assert fn_name in FUNCTIONS and available()
-    A = _abi()
     with tempfile.TemporaryDirectory(prefix="bsc_ref_") as td:
         for k, v in arrays.items():
             np.save(os.path.join(td, "in_%s.npy" % k), _as_bytes(k, v))
@@ -217,7 +272,7 @@ def run_in_child(fn_name, arrays, timeout=120):
             if f.startswith("out_") and f.endswith(".npy"):
                 k = f[4:-4]
                 v = np.load(os.path.join(td, f))
-                out[k] = v.view(getattr(A, _RECORDS[k])) if k in _RECORDS else v
+                out[k] = v.view(_record_dtype(k)) if k in _RECORDS else v
         return out
 
 

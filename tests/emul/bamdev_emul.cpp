@@ -239,6 +239,17 @@ int bd_emul_run(const uint8_t *stream, uint64_t len, const uint64_t *rec_off, ui
   }
   return 0;
 }
+// One record alone (tests/test_ref_pin_bam.py): rec[0 .. avail) -> its 64-byte descriptor as bd_parse fills it; where the record is used
+// (BD_ST_USE) also its list by bd_misms_of (ms: room for n_cigar entries; d->n_ms are written) and its decoded bytes by bd_base_byte
+// (bytes: room for l_seq).  Returns the descriptor's status.
+int bd_emul_record(const uint8_t *rec, uint64_t avail, const bd_params *par, bd_desc *d, bd_misms *ms, uint8_t *bytes) {
+  bd_parse(rec, avail, 0, *par, *d);
+  if (d->status != BD_ST_USE) return d->status;
+  if (d->n_ms) bd_misms_of(rec, *d, ms);
+  const uint8_t *seq4 = rec + 36 + d->l_name + 4 * d->n_cigar, *qual = seq4 + (d->l_seq + 1) / 2;
+  for (uint32_t i = 0; i < d->l_seq; i++) bytes[i] = bd_base_byte(seq4, qual, i);
+  return d->status;
+}
 const char *bd_emul_error(void) { return G.err_text; }
 int bd_emul_error_code(void) { return G.err_code; }
 uint64_t bd_emul_n_blocks(void) { return G.blocks.size(); }

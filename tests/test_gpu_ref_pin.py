@@ -1,12 +1,14 @@
 """The kernels against the REFERENCE'S OWN BINARY (oracle/_ref/libbscall_ref.so: the reference's unchanged sources behind
 oracle/ref_driver.c, built by `make -C oracle ref` on a machine that has the reference's tree).  The rest of the GPU suite
 compares the kernels with the oracle, this project's restatement of the reference; here the expected bytes were computed by the
-reference's calc_gt_prob, call_genotypes_ML, process_template_vector and meth_profile themselves.
+reference's calc_gt_prob, call_genotypes_ML, process_template_vector, meth_profile and — for the device BAM reader's record parser
+(bsc_bam_parse_kernel, bsc_bam_misms_kernel, bsc_bam_decode_kernel) — get_next_align_details themselves.
 
 The reference's code never runs in this process (it holds the GPU, and the reference's asserts abort): every reference result
 comes from oracle.ref_loader.run_in_child — a fresh Python process that opens no GPU — once per module.  Where the binary is
 absent the tests do not skip: they fall back to tests/golden/ref_vectors.json / .bin, recorded from the same binary (smaller inputs:
-2048 sites, one heterozygous-dense block, one block of 119 raw templates), and print that they did.
+2048 sites, one heterozygous-dense block, one block of 119 raw templates), and to tests/golden/ref_align_details.json / .bin (the
+reduced set of BAM records of tests/bam_record_cases.py), and print that they did.
 
 Flavour policy as in tests/test_gpu_parity.py: with libm_exact every byte; otherwise integers exact, doubles to 1e-11."""
 import os
@@ -20,7 +22,9 @@ from bs_call_amd.abi import GT_METH, PILEUP, VCF_CORE
 from bs_call_amd.caller import ReadProfile
 from oracle import ref_loader as R
 
+import bam_record_cases as BC
 import ref_pin_cases as K
+import test_gpu_bamdev as GB
 import test_gpu_parity as TP
 import test_gpu_reads_chain as RC
 import test_prep as T
@@ -264,3 +268,96 @@ def test_block_records_raw_against_process_template_vector(full, oracle, prep, l
     else:
         OC.same_records(got, *OC.records(want["tpl"], want["seq"], x, y, refc))
     assert len(got) > 50
+
+
+# ---- BAM records: the device reader's parse, list and decode kernels against get_next_align_details -------------------------------------
+BAM_VARIANTS = [({}, "kernels"), ({"BSC_BAMDEV_REPLAY": "1"}, "replay"), ({"BSC_BAMDEV_SLAB_KB": "64", "BSC_BAMDEV_PASS_KB": "1"}, "small passes")]
+
+
+@pytest.fixture(scope="module")
+def bam_sets():
+    """group -> RefSet (tests/bam_record_cases.py): the records with what the reference's parser made of them, from a child process or
+    from the recorded fixture"""
+    if not (HAVE_REF and R.has_align_details()):  # absent, or left by an earlier recipe that had no refdrv_align_details
+        print("\n[ref pin] oracle/_ref/libbscall_ref.so is not used, or has no refdrv_align_details (recipe: `%s`): the reduced set of BAM records and the reference's results "
+              "for it from tests/golden/ref_align_details.json" % R.RECIPE)
+        return BC.golden_sets()
+
+    def in_child(records, offsets, ku, idup):
+        r = R.run_in_child("align_details", dict(records=records, offsets=offsets,
+                                                 params=np.array([BC.MAPQ_THRESH, BC.MAX_TEMPLATE_LEN, int(ku), int(idup)], dtype=np.uint64)))
+        return r["align"], r["misms"], r["reads"]
+
+    return BC.live_sets(in_child)
+
+
+_BAM_FILES = {}
+
+
+def _bam_file(bam_sets, tmp_path_factory, group, setting=BC.SETTINGS[0]):
+    """(path, reader keywords, the reference's templates, its tally, csrc/bamio.c's blocks, records left out) of a group written as a file —
+    once per module.  A file group holds its records without those whose CIGAR disagrees with l_seq (they are held against the
+    reference on the CPU alone); the fixed group the records a reader accepts (bam_record_cases.gpu_flag_file)."""
+    key = BC.setting_key(setting)
+    if (group, key) not in _BAM_FILES:
+        rs = bam_sets[group]
+        a = rs.res[key][0]
+        keep, out = BC.gpu_flag_file(rs, key) if group == "fixed" else (BC.file_records(rs, key), [])
+        path = str(tmp_path_factory.mktemp("refpin_bam") / ("%s_%s.bam" % (group, key)))
+        BC.write_bam_raw(path, [rs.raws[i] for i in keep])
+        kw = dict(keep_unmatched=setting[0], ignore_duplicates=setting[1])
+        host = GB.TB.c_blocks(path, **kw)  # no try: the host reader accepts the file, or the test fails here
+        used = [i for i in keep if int(a["ret"][i]) == 0]
+        _BAM_FILES[(group, key)] = (path, kw, [BC.template_of(rs, key, i) for i in used], BC.tally(rs, key, keep), host, (keep, out))
+    return _BAM_FILES[(group, key)]
+
+
+def _same_as_the_reference(what, got, want_tpl, want_tally, host):
+    blocks, cts, bases = got
+    ts = BC.flatten_blocks(blocks)
+    assert len(ts) == len(want_tpl), "%s: %d templates, the reference uses %d records" % (what, len(ts), len(want_tpl))
+    for k, (t, w) in enumerate(zip(ts, want_tpl)):
+        assert t == w, "%s: template %d: reference %s, device %s" % (what, k, w, t)
+    assert (cts, bases) == want_tally, what
+    assert got == host, what + ": csrc/bamio.c's blocks"
+
+
+@pytest.mark.parametrize("variant", range(len(BAM_VARIANTS)), ids=[v[1].replace(" ", "_") for v in BAM_VARIANTS])
+@pytest.mark.parametrize("group", BC.FILE_GROUPS)
+def test_device_reader_against_get_next_align_details(full, bam_sets, tmp_path_factory, group, variant):
+    """The aux, CIGAR, sequence and mix groups as single-end files, one used record one template: positions, orientation, MAPQ, span,
+    strand, the mismatch list and the decoded bytes of every template are the reference's per-record results, and the blocks
+    csrc/bamio.c's — with the parallel kernels, with the one-lane replay, and with 64-KB slabs and 1-KB passes (the mix's 8-KB records
+    lie across slabs)."""
+    path, kw, want_tpl, want_tally, host, _ = _bam_file(bam_sets, tmp_path_factory, group)
+    env, what = BAM_VARIANTS[variant]
+    got, info = GB.dev_blocks(full, path, env, **kw)
+    _same_as_the_reference("%s, %s" % (group, what), got, want_tpl, want_tally, host)
+    assert info["malformed"] == 0 and len(want_tpl) == sum(len(b[2]) for b in host[0]) >= 40
+
+
+def test_device_reader_against_get_next_align_details_on_a_one_cu_context(one_cu, bam_sets, tmp_path_factory):
+    """The same through a context created under BSC_NUM_CUS=1.  (The reader's own grids follow the record count, not the CU count: this
+    run pins that the reader does not depend on the context's grid, not a grid-stride round.)"""
+    for group in BC.FILE_GROUPS:
+        path, kw, want_tpl, want_tally, host, _ = _bam_file(bam_sets, tmp_path_factory, group)
+        got, _ = GB.dev_blocks(one_cu, path, {}, **kw)
+        _same_as_the_reference("%s, one CU" % group, got, want_tpl, want_tally, host)
+
+
+@pytest.mark.parametrize("setting", [BC.SETTINGS[0], BC.SETTINGS[3]], ids=BC.setting_key)
+@pytest.mark.parametrize("variant", [0, 2], ids=["kernels", "small_passes"])
+def test_device_reader_flag_sweep_against_get_next_align_details(full, bam_sets, tmp_path_factory, setting, variant):
+    """Every flag value with the mate right and left of the record, and the fixed fields' edge cases: the file holds the records the
+    reference filters and those it uses with PAIRED cleared; lone mates, which read_input asserts on and csrc/bamio.c refuses, are left
+    out — at most 2 % of the sweep.  The device's filter counters and base sums are the reference's tally, its templates the reference's
+    used records."""
+    path, kw, want_tpl, want_tally, host, (keep, out) = _bam_file(bam_sets, tmp_path_factory, "fixed", setting)
+    n_out, n_sweep = BC.sweep_share(bam_sets["fixed"], out)
+    print("\n[ref pin] flag sweep %s: %d records in the file, left out %d of the sweep's %d (%.2f %%), %d of all %d"
+          % (BC.setting_key(setting), len(keep), n_out, n_sweep, 100.0 * n_out / n_sweep, len(out), len(bam_sets["fixed"])))
+    assert n_out <= 0.02 * n_sweep
+    env, what = BAM_VARIANTS[variant]
+    got, info = GB.dev_blocks(full, path, env, **kw)
+    _same_as_the_reference("flag sweep %s, %s" % (BC.setting_key(setting), what), got, want_tpl, want_tally, host)
+    assert sum(want_tally[0]) > 100 and len(want_tpl) > 20 and info["malformed"] == 0

@@ -5,7 +5,8 @@ records — the test input of csrc/bamio.c and oracle/py_bam.py; there is no sam
 write_bam(path, refs, records, text=None, block=0xff00)
   refs     [(name, length), ...]
   records  dicts: name, flag, tid, pos (0-based, -1 = none), mapq, cigar [(op char, length), ...], mtid, mpos, tlen, seq (str over
-           =ACMGRSVTWYHKDBN), qual (list of ints; None = 0xff), aux (bytes, already encoded; see aux_* helpers)
+           =ACMGRSVTWYHKDBN), qual (list of ints; None = 0xff), aux (bytes, already encoded; see aux_* helpers); a CIGAR operation
+           may also be given as its code 0..15 (9..15 have no letter)
 A synthetic WGBS generator for end-to-end tests lives in wgbs_records()."""
 import struct
 import zlib
@@ -52,8 +53,9 @@ def encode_record(r) -> bytes:
         packed[i >> 1] |= SEQ_CODES[c] << (4 if i % 2 == 0 else 0)
     qual = r.get("qual")
     qb = bytes([0xFF] * l_seq) if qual is None else bytes(qual)
-    cig = b"".join(struct.pack("<I", n << 4 | CIGAR_CODES[op]) for op, n in r.get("cigar", []))
-    span = sum(n for op, n in r.get("cigar", []) if op in "MDN=X")
+    ops = [(CIGAR_CODES[op] if isinstance(op, str) else int(op), n) for op, n in r.get("cigar", [])]
+    cig = b"".join(struct.pack("<I", n << 4 | op) for op, n in ops)
+    span = sum(n for op, n in ops if op in (0, 2, 3, 7, 8))
     pos = r.get("pos", -1)
     body = struct.pack("<iiBBHHHIiii", r.get("tid", -1), pos, len(name), r.get("mapq", 0), reg2bin(max(pos, 0), max(pos, 0) + max(span, 1)),
                        len(r.get("cigar", [])), r["flag"], l_seq, r.get("mtid", -1), r.get("mpos", -1), r.get("tlen", 0))
