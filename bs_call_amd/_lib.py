@@ -242,6 +242,14 @@ EXPORTS = (
     "bsc_variants_stream_read",
     "bsc_variants_stream_detach",
     "bsc_block_variants_csi_kept",
+    "bsc_cpg_reads_params_default",
+    "bsc_cpg_reads_sites_host",
+    "bsc_cpg_reads_format",
+    "bsc_cpg_reads_device",
+    "bsc_cpg_reads_text_device",
+    "bsc_block_cpg_reads_kept",
+    "bsc_cpg_reads_stream_read",
+    "bsc_cpg_reads_stream_detach",
 )
 
 
@@ -271,6 +279,15 @@ class VarParams(C.Structure):
 
     def __init__(self, min_phred=0, pass_only=0, known_only=0, reserved=0):
         super().__init__(int(min_phred), int(pass_only), int(known_only), int(reserved))
+
+
+class CpgReadsParams(C.Structure):
+    """bsc_cpg_reads_params; the defaults are bsc_cpg_reads_params_default's."""
+
+    _fields_ = [("min_sites", C.c_uint32), ("min_cov", C.c_uint32)]
+
+    def __init__(self, min_sites=4, min_cov=1):
+        super().__init__(int(min_sites), int(min_cov))
 
 
 class BwParams(C.Structure):
@@ -840,6 +857,22 @@ def load():
     L.bsc_variants_stream_detach.argtypes = [vp, C.POINTER(vp), C.POINTER(u64)]
     L.bsc_block_variants_csi_kept.restype = i32
     L.bsc_block_variants_csi_kept.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(u64), C.POINTER(u64)]
+    L.bsc_cpg_reads_params_default.restype = None
+    L.bsc_cpg_reads_params_default.argtypes = [C.POINTER(CpgReadsParams)]
+    L.bsc_cpg_reads_sites_host.restype = i32
+    L.bsc_cpg_reads_sites_host.argtypes = [vp, u32, vp, u64, u32, u32, vp, i32, C.POINTER(CpgReadsParams), vp, u64, C.POINTER(u64), C.POINTER(u64)]
+    L.bsc_cpg_reads_format.restype = C.c_long
+    L.bsc_cpg_reads_format.argtypes = [C.c_char_p, vp, C.c_size_t, C.POINTER(CpgReadsParams), vp, C.c_size_t, C.POINTER(u64)]
+    L.bsc_cpg_reads_device.restype = i32
+    L.bsc_cpg_reads_device.argtypes = [vp, vp, u32, vp, u64, u32, u32, vp, C.POINTER(CpgReadsParams), vp, u64, vp, vp, vp]
+    L.bsc_cpg_reads_text_device.restype = i32
+    L.bsc_cpg_reads_text_device.argtypes = [vp, vp, vp, u64, C.c_char_p, C.POINTER(CpgReadsParams), vp, u64, vp, vp]
+    L.bsc_block_cpg_reads_kept.restype = i32
+    L.bsc_block_cpg_reads_kept.argtypes = [vp, C.c_char_p, C.POINTER(CpgReadsParams), u64, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)]
+    L.bsc_cpg_reads_stream_read.restype = i32
+    L.bsc_cpg_reads_stream_read.argtypes = [vp, u64, u64, vp]
+    L.bsc_cpg_reads_stream_detach.restype = i32
+    L.bsc_cpg_reads_stream_detach.argtypes = [vp, C.POINTER(vp), C.POINTER(u64)]
     L.bsc_meth_cpg_format_recs.argtypes = [vp, C.c_size_t, C.c_char_p, C.POINTER(MethParams), vp, C.c_size_t, C.POINTER(u64)]
     L.bsc_meth_cpg_block_device.restype = i32
     L.bsc_meth_cpg_block_device.argtypes = [vp, vp, vp, u64, C.c_char_p, C.POINTER(MethParams), vp, u64, vp, vp]

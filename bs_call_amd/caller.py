@@ -1236,6 +1236,52 @@ class SiteCaller:
         buf = (C.c_uint8 * (16 * n.value)).from_address(p.value)
         return np.frombuffer(buf, dtype=CSI_ENTRY).copy(), int(r.value)
 
+    # -- the read-level CpG concordance table (csrc/cpgreadsdev.hip) ------------------------------------------
+    @staticmethod
+    def _cr_params(params):
+        if params is None:
+            return _lib.CpgReadsParams()
+        if isinstance(params, _lib.CpgReadsParams):
+            return params
+        return _lib.CpgReadsParams(**params)
+
+    def cpg_reads_device(self, d_tpl, nr, d_seq, seq_bytes, x, y, d_ref, d_sites, sites_cap, d_n_sites, d_totals, params=None, stream=None):
+        """bsc_cpg_reads_device: the inputs of reads_chain_device (prepared templates, their read bytes, the block x .. y, d_ref the codes of
+        x .. y + 2) -> one bsc_cpg_reads_site per reference CpG in d_sites[<= sites_cap], their count (a device u64) in d_n_sites and the
+        eight totals in d_totals (asynchronous on `stream`)."""
+        cp = self._cr_params(params)
+        _check(self._L.bsc_cpg_reads_device(self._h, d_tpl, nr, d_seq, seq_bytes, x, y, d_ref, C.byref(cp), d_sites, sites_cap, d_n_sites, d_totals,
+                                            stream))
+
+    def cpg_reads_text_device(self, d_sites, d_n_sites, max_sites, contig, d_out, out_cap, d_totals2, params=None, stream=None):
+        """bsc_cpg_reads_text_device: the table's lines of d_sites[min(*d_n_sites, max_sites)] -> d_out[<= out_cap]; d_totals2: {bytes, lines}."""
+        cp = self._cr_params(params)
+        name = contig.encode() if isinstance(contig, str) else contig
+        _check(self._L.bsc_cpg_reads_text_device(self._h, d_sites, d_n_sites, max_sites, name, C.byref(cp), d_out, out_cap, d_totals2, stream))
+
+    def block_cpg_reads_kept(self, contig, params=None, cap=None):
+        """bsc_block_cpg_reads_kept + bsc_cpg_reads_stream_read: the read-level CpG table of the block the last *_keep call called, from the
+        prepared templates, reads and reference codes it left on the device.  params: a _lib.CpgReadsParams, a dict of its fields, or None
+        ({4, 1}).  Returns (bytes, lines, totals[8]).  cap: the room on the device (default: asked for and given on a second call)."""
+        cp = self._cr_params(params)
+        name = contig.encode() if isinstance(contig, str) else contig
+        nb, nl, tot = C.c_uint64(0), C.c_uint64(0), (C.c_uint64 * 8)()
+        room = 1 << 16 if cap is None else int(cap)
+        rc = self._L.bsc_block_cpg_reads_kept(self._h, name, C.byref(cp), room, C.byref(nb), C.byref(nl), tot)
+        if rc == -1 and nb.value > room and cap is None:
+            room = int(nb.value)
+            rc = self._L.bsc_block_cpg_reads_kept(self._h, name, C.byref(cp), room, C.byref(nb), C.byref(nl), tot)
+        _check(rc)
+        return self.cpg_reads_stream_read(0, nb.value), int(nl.value), tuple(int(v) for v in tot)
+
+    def cpg_reads_stream_read(self, off, n):
+        """bsc_cpg_reads_stream_read: bytes [off, off + n) of the table the last block_cpg_reads_kept left on the device."""
+        out = np.empty(max(int(n), 1), dtype=np.uint8)
+        _check(self._L.bsc_cpg_reads_stream_read(self._h, int(off), int(n), _ptr(out)))
+        if n:
+            self.synchronize()
+        return out[: int(n)].tobytes()
+
     def blocks_records(self, blocks, ref, out=None, all_positions=False, reg_start=1, reg_stop=0xFFFFFFFF, dbsnp=None, with_stats=False,
                        submit_only=False):
         """Several blocks in one launch sequence (bsc_blocks_records): blocks = [(templates, seq, x, y), ...] in genome order;
@@ -1627,3 +1673,50 @@ def prepare_templates(raw, seq, misms, left_trim=(0, 0), right_trim=(0, 0), min_
                                                _ptr(out_tpl), _ptr(out_seq), cap, C.byref(used), _ptr(st), C.byref(pf)))
         profile.used = int(pf.used)
     return out_tpl, out_seq[: used.value].copy(), st[0]
+
+
+def cpg_reads_sites_host(tpl, seq, x, y, ref, min_qual=20, params=None, cap=None):
+    """The host form of the read-level CpG table (bsc_cpg_reads_sites_host; csrc/cpgreads.c): prepared TEMPLATE[nr] + their read bytes, the
+    block x .. y and its reference codes (x .. y + 2) -> (SITE records[min(count, cap)], count, totals[8]).  No GPU involved.  cap: the
+    room (default: every site)."""
+    from .cpgreads import SITE
+
+    L = _lib.load()
+    tpl = np.ascontiguousarray(tpl, dtype=TEMPLATE)
+    seq = np.ascontiguousarray(seq, dtype=np.uint8)
+    ref = np.ascontiguousarray(ref, dtype=np.uint8)
+    if ref.size < int(y) - int(x) + 2:
+        raise ValueError("ref must hold the codes of x .. y + 1 at least")
+    cp = SiteCaller._cr_params(params)
+    room = int(y) - int(x) + 1 if cap is None else int(cap)
+    out = np.zeros(max(room, 1), dtype=SITE)
+    n, tot = C.c_uint64(0), (C.c_uint64 * 8)()
+    _check(L.bsc_cpg_reads_sites_host(_ptr(tpl), len(tpl), _ptr(seq), seq.size, int(x), int(y), _ptr(ref), int(min_qual), C.byref(cp), _ptr(out), room,
+                                      C.byref(n), tot))
+    return out[: min(int(n.value), room)].copy(), int(n.value), tuple(int(v) for v in tot)
+
+
+def cpg_reads_format_host(contig, recs, params=None, cap=None):
+    """bsc_cpg_reads_format: the table's lines of SITE records -> (bytes, lines).  cap: the room (default: asked for first); a room too
+    small gives (None, the length needed)."""
+    from .cpgreads import SITE
+
+    L = _lib.load()
+    recs = np.ascontiguousarray(recs, dtype=SITE)
+    cp = SiteCaller._cr_params(params)
+    name = contig.encode() if isinstance(contig, str) else contig
+    t2 = (C.c_uint64 * 2)()
+    if cap is None:
+        need = L.bsc_cpg_reads_format(name, _ptr(recs), len(recs), C.byref(cp), None, 0, t2)
+        if need < 0:
+            _check(int(need))
+        cap = int(need)
+    buf = np.full(max(int(cap), 1) + 8, 0xA5, dtype=np.uint8)
+    got = L.bsc_cpg_reads_format(name, _ptr(recs), len(recs), C.byref(cp), _ptr(buf), int(cap), t2)
+    if got < 0:
+        _check(int(got))
+    assert (buf[int(cap) :] == 0xA5).all() and int(t2[0]) == got
+    if got > int(cap):
+        assert (buf == 0xA5).all()
+        return None, int(got)
+    return buf[:got].tobytes(), int(t2[1])

@@ -119,6 +119,16 @@ int bsc_dev_launch_var_select(const void *core, const void *aux, const void *emi
                               void *tile_mask, void *scan_tmp, size_t scan_tmp_bytes, void *totals, int num_cus, void *stream); /* variantsdev.hip */
 int bsc_dev_launch_var_pack(const void *core, const void *aux, uint32_t n, const void *tile_off, const void *tile_mask, void *out, uint64_t out_cap,
                             void *total, int num_cus, void *stream);
+int bsc_dev_launch_cr_sites(const void *ref, uint32_t n, void *tile_cnt, void *tile_off, void *tile_mask, void *scan_tmp, size_t scan_tmp_bytes,
+                            int num_cus, void *stream); /* cpgreadsdev.hip */
+int bsc_dev_launch_cr_init(uint32_t x, uint32_t n, const void *tile_off, const void *tile_mask, void *sites, uint64_t cap, void *n_sites, void *totals,
+                           int num_cus, void *stream);
+int bsc_dev_launch_cr_walk(const void *tpl, uint32_t nr, const void *seq, uint64_t seq_bytes, uint32_t x, uint32_t y, uint32_t min_qual,
+                           uint32_t min_sites, const void *tile_off, const void *tile_mask, void *sites, uint64_t cap, void *totals, int num_cus,
+                           void *stream);
+int bsc_dev_launch_cr_text(const void *sites, const void *n_sites, uint64_t max_sites, const char *contig, uint32_t contig_len, uint32_t min_cov,
+                           void *tile_bytes, void *tile_off, void *line_len, void *scan_tmp, size_t scan_tmp_bytes, void *out, uint64_t out_cap,
+                           void *totals2, int num_cus, void *stream);
 int bsc_dev_launch_csi_scan(int format, const void *s, uint64_t n_bytes, const void *sync, uint32_t n_sync, int min_shift, void *cnt, void *off,
                             void *scan_tmp, size_t scan_tmp_bytes, void *entries, uint64_t cap, void *totals, int num_cus, void *stream); /* csidev.hip */
 int bsc_dev_launch_bed_scan(const void *s, uint64_t n_bytes, const void *sync, uint32_t n_sync, int min_shift, void *cnt, void *off, void *scan_tmp,
@@ -303,6 +313,18 @@ struct bsc_context {
     bsc_csi_entry *h_csen;
     size_t cap_hcsen;
   } var;
+  struct { /* the read-level CpG table (cpgreadsdev.hip): the workspaces of a call — sites per tile, their prefix sum, the tiles' site masks, scan
+            * scratch; the text encoder's tile bytes, tile offsets, scan scratch and line lengths; bsc_block_cpg_reads_kept: the records, {count,
+            * eight totals, bytes, lines}, the table and its length.  src_*: the block whose prepared templates, reads and reference codes are in
+            * d_tpl / d_seq / d_ref (set where a single block's chain is queued from them, cleared wherever one of the three is about to be
+            * rewritten) */
+    void *d_cnt, *d_off, *d_mask, *d_tmp, *d_tb, *d_to, *d_ttmp, *d_len, *d_sites, *d_tot, *d_out;
+    size_t cap_cnt, cap_off, cap_mask, cap_tmp, cap_tb, cap_to, cap_ttmp, cap_len, cap_sites, cap_tot, cap_out;
+    uint64_t bytes;
+    int src_ok;
+    uint32_t src_nr, src_x, src_y;
+    uint64_t src_seq_bytes;
+  } cr;
   struct { /* streams handed to the caller (bsc_bcf_stream_detach) come back here (bsc_detached_free) and are taken again by the next block:
             * no hipMalloc / hipFree — a device-wide wait — in the steady state of a run that writes behind the calling */
     void *p[4];
@@ -720,6 +742,17 @@ int bsc_destroy(bsc_context *ctx) {
   hipFree(ctx->var.d_csen);
   hipFree(ctx->var.d_cstot);
   free(ctx->var.h_csen);
+  hipFree(ctx->cr.d_cnt);
+  hipFree(ctx->cr.d_off);
+  hipFree(ctx->cr.d_mask);
+  hipFree(ctx->cr.d_tmp);
+  hipFree(ctx->cr.d_tb);
+  hipFree(ctx->cr.d_to);
+  hipFree(ctx->cr.d_ttmp);
+  hipFree(ctx->cr.d_len);
+  hipFree(ctx->cr.d_sites);
+  hipFree(ctx->cr.d_tot);
+  hipFree(ctx->cr.d_out);
   hipFree(ctx->mr.d_reg);
   hipFree(ctx->mr.d_acc);
   free(ctx->mr.h_start);
@@ -1074,6 +1107,7 @@ static int bsc_accumulate_queue2(bsc_context *ctx, const bsc_template *tpl, uint
   int rc;
   size_t scan_bytes = 0;
   if ((rc = bsc_reserve(&ctx->d_cts, &ctx->cap_cts, (size_t)n_wt * 64u * 104u))) return rc;
+  ctx->cr.src_ok = 0; /* (d_tpl / d_seq / d_ref are about to be rewritten) */
   if ((rc = bsc_reserve(&ctx->d_tpl, &ctx->cap_tpl, (size_t)(nr ? nr : 1) * sizeof(bsc_template)))) return rc;
   if ((rc = bsc_reserve(&ctx->d_seq, &ctx->cap_seq, (size_t)(seq_bytes ? seq_bytes : 1)))) return rc;
   if ((rc = bsc_accumulate_reserve(ctx, nr, x, y, &scan_bytes))) return rc;
@@ -1382,6 +1416,7 @@ static int bsc_blocks_submit_to_(bsc_context *ctx, const bsc_block_desc *blocks,
   BSC_ENTER(ctx);
   size_t scan_bytes = 0;
   if ((rc = bsc_accumulate_reserve(ctx, nr, 1u, P, &scan_bytes))) return rc;
+  ctx->cr.src_ok = 0; /* (d_tpl / d_seq / d_ref are about to be rewritten) */
   if ((rc = bsc_reserve(&ctx->d_tpl, &ctx->cap_tpl, (size_t)(nr ? nr : 1) * sizeof(bsc_template)))) return rc;
   if ((rc = bsc_reserve(&ctx->d_seq, &ctx->cap_seq, (size_t)(seq_bytes ? seq_bytes : 1)))) return rc;
   if ((rc = bsc_reserve(&ctx->d_cts, &ctx->cap_cts, (size_t)P * 104u))) return rc;
@@ -2484,6 +2519,7 @@ static int bsc_records_queue(bsc_context *ctx, const bsc_template *tpl, uint32_t
     if ((rc = bsc_reserve(&ctx->d_tpl, &ctx->cap_tpl, (size_t)(nr ? nr : 1) * sizeof(bsc_template)))) return rc;
     if ((rc = bsc_reserve(&ctx->d_seq, &ctx->cap_seq, (size_t)(seq_bytes ? seq_bytes : 1)))) return rc;
   }
+  ctx->cr.src_ok = 0; /* (d_tpl / d_seq / d_ref are about to be rewritten) */
   if ((rc = bsc_reserve(&ctx->d_ref, &ctx->cap_ref, (size_t)sz + 2))) return rc;
   ctx->again.valid = ctx->meth_src = 0; /* (d_out is about to be rewritten) */
   if ((rc = bsc_reserve(&ctx->d_out, &ctx->cap_out, (size_t)sz * 64u))) return rc; /* the chain's aux array */
@@ -2568,6 +2604,12 @@ static int bsc_records_queue(bsc_context *ctx, const bsc_template *tpl, uint32_t
     ctx->again.sz = sz;
     ctx->meth_src = -1; /* ONE block's arrays: bsc_block_meth_kept's source once the block has come back kept (bsc_bcf_finish) */
     ctx->meth_x = x;
+    ctx->cr.src_ok = 1; /* this block's prepared templates, reads and reference codes: nothing queued behind the uploads / the pre-processing
+                         * writes to them (the binning passes write d_rd and the bin lists, the chain and the encoders their own arrays) */
+    ctx->cr.src_nr = nr;
+    ctx->cr.src_x = x;
+    ctx->cr.src_y = y;
+    ctx->cr.src_seq_bytes = seq_bytes;
     ctx->again.rid = bcf->rid;
     ctx->again.text = bcf->text;
     if (bcf->text) {
@@ -2758,6 +2800,7 @@ static int bsc_block_records_rawdev_(bsc_context *ctx, const void *d_raw, uint32
   int rc;
   const int timing = ctx->stage_timing; /* BSC_STAGE_TIMING at bsc_create: where a block's host time goes, to stderr */
   double t0 = timing ? bsc_now_s() : 0.0, t1;
+  ctx->cr.src_ok = 0; /* (d_tpl / d_seq / d_ref are about to be rewritten) */
   if ((rc = bsc_reserve(&ctx->d_tpl, &ctx->cap_tpl, (size_t)nr * sizeof(bsc_template)))) return rc;
   if ((rc = bsc_reserve(&ctx->d_seq, &ctx->cap_seq, (size_t)cap))) return rc;
   hipStream_t s = ctx->stream;
@@ -4058,6 +4101,7 @@ static int bsc_blocks_queue(bsc_context *ctx, const bsc_block_desc *blocks, uint
   }
   if ((rc = bsc_accumulate_reserve(ctx, nr, 1u, P, &scan_bytes))) return rc; /* P positions = P / 64 bins */
   if ((rc = bsc_reserve(&ctx->d_fscr, &ctx->cap_fscr, bsc_dev_chain_scratch_bytes(ctx->num_cus)))) return rc;
+  ctx->cr.src_ok = 0; /* (d_tpl / d_seq / d_ref are about to be rewritten) */
   if ((rc = bsc_reserve(&ctx->d_tpl, &ctx->cap_tpl, (size_t)(nr ? nr : 1) * sizeof(bsc_template)))) return rc;
   if ((rc = bsc_reserve(&ctx->d_seq, &ctx->cap_seq, (size_t)(seq_bytes ? seq_bytes : 1)))) return rc;
   if ((rc = bsc_reserve(&ctx->d_ref, &ctx->cap_ref, (size_t)ref64))) return rc;
@@ -5107,6 +5151,156 @@ int bsc_block_variants_csi_kept(bsc_context *ctx, int min_shift, const bsc_csi_e
   *entries = ctx->var.h_csen;
   *n_entries = tot[0];
   if (n_records) *n_records = tot[1];
+  return BSC_OK;
+}
+
+/* ---- the read-level CpG concordance table (cpgreadsdev.hip): include/bscall_amd.h has the rule, csrc/cpgreads.c the host form ------------------- */
+static int bsc_cr_params_check(const char *who, const bsc_cpg_reads_params *p) {
+  if (!p) return bsc_fail(BSC_ERR_ARG, "%s: NULL argument", who);
+  if (p->min_sites == 0) return bsc_fail(BSC_ERR_ARG, "%s: min_sites is 0", who);
+  return BSC_OK;
+}
+
+/* the site pass and the scan over d_ref (y - x + 3 codes) on stream s, in the context's workspaces */
+static int bsc_cr_sites_run(bsc_context *ctx, const char *who, const void *d_ref, uint32_t sz, hipStream_t s) {
+  const uint32_t n_tiles = (uint32_t)(((uint64_t)sz + 63u) / 64u);
+  size_t scan_bytes = 0;
+  int rc;
+  if (bsc_dev_scan_tmp_bytes(n_tiles, &scan_bytes)) return bsc_fail(BSC_ERR_HIP, "%s: scan size query failed", who);
+  if ((rc = bsc_reserve(&ctx->cr.d_cnt, &ctx->cr.cap_cnt, (size_t)n_tiles * 4u))) return rc;
+  if ((rc = bsc_reserve(&ctx->cr.d_off, &ctx->cr.cap_off, (size_t)n_tiles * 4u))) return rc;
+  if ((rc = bsc_reserve(&ctx->cr.d_mask, &ctx->cr.cap_mask, (size_t)n_tiles * 8u))) return rc;
+  if ((rc = bsc_reserve(&ctx->cr.d_tmp, &ctx->cr.cap_tmp, scan_bytes ? scan_bytes : 1))) return rc;
+  const int e = bsc_dev_launch_cr_sites(d_ref, sz, ctx->cr.d_cnt, ctx->cr.d_off, ctx->cr.d_mask, ctx->cr.d_tmp, scan_bytes, ctx->num_cus, (void *)s);
+  if (e) return bsc_fail(BSC_ERR_HIP, "%s: site pass launch failed: %s", who, hipGetErrorString((hipError_t)e));
+  return BSC_OK;
+}
+
+/* the records' heads and the walk behind bsc_cr_sites_run; d_totals: eight u64, zeroed here */
+static int bsc_cr_walk_run(bsc_context *ctx, const char *who, const void *d_tpl, uint32_t nr, const void *d_seq, uint64_t seq_bytes, uint32_t x, uint32_t y,
+                           const bsc_cpg_reads_params *p, void *d_sites, uint64_t cap, void *d_n_sites, void *d_totals, hipStream_t s) {
+  HIP_TRY(hipMemsetAsync(d_totals, 0, BSC_CPG_READS_N_TOTALS * sizeof(unsigned long long), s));
+  int e = bsc_dev_launch_cr_init(x, y - x + 1u, ctx->cr.d_off, ctx->cr.d_mask, d_sites, cap, d_n_sites, d_totals, ctx->num_cus, (void *)s);
+  if (!e)
+    e = bsc_dev_launch_cr_walk(d_tpl, nr, d_seq, seq_bytes, x, y, (uint32_t)ctx->params.min_qual, p->min_sites, ctx->cr.d_off, ctx->cr.d_mask, d_sites, cap,
+                               d_totals, ctx->num_cus, (void *)s);
+  if (e) return bsc_fail(BSC_ERR_HIP, "%s: walk launch failed: %s", who, hipGetErrorString((hipError_t)e));
+  return BSC_OK;
+}
+
+int bsc_cpg_reads_device(bsc_context *ctx, const void *d_tpl, uint32_t nr, const void *d_seq, uint64_t seq_bytes, uint32_t x, uint32_t y,
+                         const void *d_ref, const bsc_cpg_reads_params *p, void *d_sites, uint64_t sites_cap, void *d_n_sites, void *d_totals,
+                         void *stream) {
+  static const char who[] = "bsc_cpg_reads_device";
+  int rc;
+  if (!ctx || !d_ref || !d_n_sites || !d_totals || (nr && (!d_tpl || !d_seq)) || (sites_cap && !d_sites)) return bsc_fail(BSC_ERR_ARG, "%s: NULL argument", who);
+  if ((rc = bsc_cr_params_check(who, p))) return rc;
+  if (y < x) return bsc_fail(BSC_ERR_ARG, "%s: y (%u) < x (%u)", who, y, x);
+  if ((uint64_t)y - x + 1 > 0x0fffffffull) return bsc_fail(BSC_ERR_ARG, "%s: block longer than 2^28 - 1 positions", who);
+  if ((((uintptr_t)d_tpl | (uintptr_t)d_sites | (uintptr_t)d_n_sites | (uintptr_t)d_totals) & 7u))
+    return bsc_fail(BSC_ERR_ARG, "%s: the templates, the records, the count and the totals must be 8-byte aligned", who);
+  BSC_ENTER(ctx);
+  hipStream_t s = (hipStream_t)stream;
+  if ((rc = bsc_cr_sites_run(ctx, who, d_ref, y - x + 1u, s))) return rc;
+  return bsc_cr_walk_run(ctx, who, d_tpl, nr, d_seq, seq_bytes, x, y, p, d_sites, sites_cap, d_n_sites, d_totals, s);
+}
+
+int bsc_cpg_reads_text_device(bsc_context *ctx, const void *d_sites, const void *d_n_sites, uint64_t max_sites, const char *contig,
+                              const bsc_cpg_reads_params *p, void *d_out, uint64_t out_cap, void *d_totals2, void *stream) {
+  static const char who[] = "bsc_cpg_reads_text_device";
+  uint32_t contig_len = 0;
+  int rc;
+  if (!ctx || !d_n_sites || !d_totals2 || (max_sites && !d_sites) || (out_cap && !d_out)) return bsc_fail(BSC_ERR_ARG, "%s: NULL argument", who);
+  if ((rc = bsc_cr_params_check(who, p))) return rc;
+  if ((rc = bsc_contig_check(who, contig, &contig_len))) return rc;
+  if (((uintptr_t)d_out & 15u) || (((uintptr_t)d_sites | (uintptr_t)d_n_sites | (uintptr_t)d_totals2) & 7u))
+    return bsc_fail(BSC_ERR_ARG, "%s: d_out must be 16-byte, the records, the count and the totals 8-byte aligned", who);
+  if ((max_sites + 63u) / 64u > 0x7ffffffeull) return bsc_fail(BSC_ERR_ARG, "%s: more than 2^37 records", who);
+  BSC_ENTER(ctx);
+  hipStream_t s = (hipStream_t)stream;
+  const uint32_t n_tiles = (uint32_t)((max_sites + 63u) / 64u);
+  size_t scan_bytes = 0;
+  if (bsc_dev_scan_tmp_bytes_u64(n_tiles + 1u, &scan_bytes)) return bsc_fail(BSC_ERR_HIP, "%s: scan size query failed", who);
+  if ((rc = bsc_reserve(&ctx->cr.d_tb, &ctx->cr.cap_tb, ((size_t)n_tiles + 1u) * 8u))) return rc;
+  if ((rc = bsc_reserve(&ctx->cr.d_to, &ctx->cr.cap_to, ((size_t)n_tiles + 1u) * 8u))) return rc;
+  if ((rc = bsc_reserve(&ctx->cr.d_ttmp, &ctx->cr.cap_ttmp, scan_bytes ? scan_bytes : 1))) return rc;
+  if ((rc = bsc_reserve(&ctx->cr.d_len, &ctx->cr.cap_len, ((size_t)n_tiles + 1u) * 128u))) return rc;
+  HIP_TRY(hipMemsetAsync(d_totals2, 0, 2 * sizeof(unsigned long long), s));
+  const int e = bsc_dev_launch_cr_text(d_sites, d_n_sites, max_sites, contig, contig_len, p->min_cov, ctx->cr.d_tb, ctx->cr.d_to, ctx->cr.d_len, ctx->cr.d_ttmp,
+                                       scan_bytes, d_out, out_cap, d_totals2, ctx->num_cus, stream);
+  if (e) return bsc_fail(BSC_ERR_HIP, "%s: encoder launch failed: %s", who, hipGetErrorString((hipError_t)e));
+  return BSC_OK;
+}
+
+int bsc_block_cpg_reads_kept(bsc_context *ctx, const char *contig, const bsc_cpg_reads_params *p, uint64_t dev_cap, uint64_t *n_bytes, uint64_t *n_lines,
+                             uint64_t totals[8]) {
+  static const char who[] = "bsc_block_cpg_reads_kept";
+  int rc;
+  uint32_t contig_len = 0;
+  if (!ctx || !n_bytes || !n_lines) return bsc_fail(BSC_ERR_ARG, "%s: NULL argument", who);
+  *n_bytes = *n_lines = 0;
+  for (int k = 0; totals && k < BSC_CPG_READS_N_TOTALS; k++) totals[k] = 0;
+  if ((rc = bsc_cr_params_check(who, p))) return rc;
+  if ((rc = bsc_contig_check(who, contig, &contig_len))) return rc;
+  if (ctx->meth_src != 1 || ctx->rec_pending || ctx->pending_sz)
+    return bsc_fail(BSC_ERR_ARG, "%s: the last call left no single block's arrays on the device", who);
+  if (!ctx->cr.src_ok) return bsc_fail(BSC_ERR_ARG, "%s: the last block's prepared templates, reads and reference are no longer on the device", who);
+  BSC_ENTER(ctx);
+  hipStream_t s = ctx->stream;
+  ctx->cr.bytes = 0;
+  const uint32_t x = ctx->cr.src_x, y = ctx->cr.src_y, nr = ctx->cr.src_nr;
+  /* d_tot: [0] the count, [1 .. 8] the totals, [9 .. 10] the encoder's {bytes, lines} */
+  if ((rc = bsc_reserve(&ctx->cr.d_tot, &ctx->cr.cap_tot, 11 * sizeof(unsigned long long)))) return rc;
+  unsigned long long *const d_tot = (unsigned long long *)ctx->cr.d_tot;
+  if ((rc = bsc_cr_sites_run(ctx, who, ctx->d_ref, y - x + 1u, s))) return rc;
+  /* the count is the scan's: the records' room is theirs, not the block's */
+  const uint32_t n_tiles = (uint32_t)(((uint64_t)(y - x) + 64u) / 64u);
+  unsigned int last_off = 0, last_cnt = 0;
+  HIP_TRY(hipMemcpyAsync(&last_off, (const uint32_t *)ctx->cr.d_off + (n_tiles - 1u), 4, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipMemcpyAsync(&last_cnt, (const uint32_t *)ctx->cr.d_cnt + (n_tiles - 1u), 4, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  const uint64_t n_sites = (uint64_t)last_off + last_cnt;
+  if ((rc = bsc_reserve(&ctx->cr.d_sites, &ctx->cr.cap_sites, (size_t)(n_sites ? n_sites : 1) * sizeof(bsc_cpg_reads_site)))) return rc;
+  if ((rc = bsc_cr_walk_run(ctx, who, ctx->d_tpl, nr, ctx->d_seq, ctx->cr.src_seq_bytes, x, y, p, ctx->cr.d_sites, n_sites, d_tot, d_tot + 1, s))) return rc;
+  /* a buffer that came back (bsc_detached_free), the smallest that will do, as d_meth is taken */
+  if (!ctx->cr.d_out && ctx->pool_mu_made) ctx->cr.d_out = bsc_pool_get(ctx, (size_t)(dev_cap ? dev_cap : 1), &ctx->cr.cap_out);
+  if ((rc = bsc_reserve(&ctx->cr.d_out, &ctx->cr.cap_out, (size_t)(dev_cap ? dev_cap : 1)))) return rc;
+  if ((rc = bsc_cpg_reads_text_device(ctx, ctx->cr.d_sites, d_tot, n_sites, contig, p, ctx->cr.d_out, dev_cap, d_tot + 9, s))) return rc;
+  unsigned long long tot[11] = {0};
+  HIP_TRY(hipMemcpyAsync(tot, d_tot, sizeof tot, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  *n_bytes = tot[9];
+  *n_lines = tot[10];
+  for (int k = 0; totals && k < BSC_CPG_READS_N_TOTALS; k++) totals[k] = tot[1 + k];
+  if (tot[0] != n_sites) return bsc_fail(BSC_ERR_RANGE, "%s: %llu sites counted, %llu records made", who, (unsigned long long)n_sites, tot[0]);
+  if (tot[9] > dev_cap) return bsc_fail(BSC_ERR_ARG, "%s: the block's table has %llu bytes, dev_cap is %llu", who, tot[9], (unsigned long long)dev_cap);
+  ctx->cr.bytes = tot[9];
+  return BSC_OK;
+}
+
+int bsc_cpg_reads_stream_read(bsc_context *ctx, uint64_t off, uint64_t n, void *dst) {
+  if (!ctx || (!dst && n)) return bsc_fail(BSC_ERR_ARG, "bsc_cpg_reads_stream_read: NULL argument");
+  if (off + n < off || off + n > ctx->cr.bytes || off + n > ctx->cr.cap_out) return bsc_fail(BSC_ERR_ARG, "bsc_cpg_reads_stream_read: beyond the table's end");
+  if (!n) return BSC_OK;
+  BSC_ENTER(ctx);
+  HIP_TRY(hipMemcpyAsync(dst, (const char *)ctx->cr.d_out + off, (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+  return BSC_OK;
+}
+
+int bsc_cpg_reads_stream_detach(bsc_context *ctx, void **d_stream, uint64_t *n_bytes) {
+  if (!ctx || !d_stream || !n_bytes) return bsc_fail(BSC_ERR_ARG, "bsc_cpg_reads_stream_detach: NULL argument");
+  *d_stream = NULL;
+  *n_bytes = 0;
+  if (!ctx->cr.d_out || !ctx->cr.bytes) return bsc_fail(BSC_ERR_ARG, "bsc_cpg_reads_stream_detach: the last call left no table on the device");
+  BSC_ENTER(ctx);
+  bsc_pool_init(ctx);
+  if (!ctx->s_det) HIP_TRY(hipStreamCreateWithFlags(&ctx->s_det, hipStreamNonBlocking));
+  *d_stream = ctx->cr.d_out;
+  *n_bytes = ctx->cr.bytes;
+  bsc_pool_book(ctx, ctx->cr.d_out, ctx->cr.cap_out);
+  ctx->cr.d_out = NULL;
+  ctx->cr.cap_out = 0;
+  ctx->cr.bytes = 0;
   return BSC_OK;
 }
 

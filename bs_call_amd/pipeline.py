@@ -22,7 +22,7 @@ def run(bam_path: str, reference: Dict[str, np.ndarray], bcf_path: str, sample: 
         cov_bigwig_path: Optional[str] = None,
         bigwig_section: int = 1024, bigwig_zoom: int = 1024, bigwig_compress: bool = False, bigbed_path: Optional[str] = None, bigbed_items: int = 512,
         bigbed_zoom: int = 1024, bigbed_compress: bool = False, meth_index: Optional[str] = None, variants_path: Optional[str] = None,
-        variants_params=None, **reader_kw) -> dict:
+        variants_params=None, cpg_reads_path: Optional[str] = None, cpg_reads_params=None, **reader_kw) -> dict:
     """reference: contig name -> uint8 reference codes (0 = N, 1..4 = ACGT; position 1 first).  Returns a summary dict.
     under_conv / over_conv / min_qual (defaults 0.01 / 0.05 / 20, src/init_param.c:26-31) are the MODEL's parameters: without
     `caller` the run builds its SiteCaller from them; with one, they are taken from it and a differing explicit value is an error
@@ -79,7 +79,16 @@ def run(bam_path: str, reference: Dict[str, np.ndarray], bcf_path: str, sample: 
     allele, selected on the device from the arrays the block left there and encoded by the block's own encoder
     (SiteCaller.block_variants_kept, csrc/variantsdev.hip) — a file of the run's format and compression with the main file's header.
     variants_params: a _lib.VarParams or a dict of min_phred / pass_only / known_only.  The summary gets "variant_records" and
-    "variant_totals" (the ten totals of the rule).  The same conditions as meth_path."""
+    "variant_totals" (the ten totals of the rule).  The same conditions as meth_path.
+    cpg_reads_path: the read-level CpG concordance table of the same run (include/bscall_amd.h has the rule): behind every block the walk over
+    the prepared templates, reads and reference codes the block left on the device (SiteCaller.block_cpg_reads_kept, csrc/cpgreadsdev.hip)
+    — a line per reference CpG a template reads, plain text or BGZF as `compressed` says.  cpg_reads_params: a _lib.CpgReadsParams or a dict
+    of min_sites / min_cov.  The summary gets "cpg_reads_lines" and "cpg_reads_totals" (the eight totals of the rule).  The same conditions as
+    meth_path."""
+    if cpg_reads_params is not None and cpg_reads_path is None:
+        raise ValueError("cpg_reads_params are thresholds of the table cpg_reads_path names: they need cpg_reads_path")
+    if cpg_reads_path is not None and (shard_rank is not None or not device_reader or host_prep or host_bcf):
+        raise ValueError("cpg_reads_path is a single run on the device reader (device_reader=True, no shard_rank, no host_prep / host_bcf)")
     if variants_params is not None and variants_path is None:
         raise ValueError("variants_params select among the records variants_path names: they need variants_path")
     if variants_path is not None and (shard_rank is not None or not device_reader or host_prep or host_bcf):
@@ -169,6 +178,7 @@ def run(bam_path: str, reference: Dict[str, np.ndarray], bcf_path: str, sample: 
         n_blocks = n_records = 0
         meth_blobs, meth_lines = [], 0
         var_blobs, var_totals = [], np.zeros(10, dtype=np.uint64)
+        reads_blobs, reads_lines, reads_totals = [], 0, np.zeros(8, dtype=np.uint64)
         meth_entries = []  # meth_index: (contig number, BED_ENTRY[], bytes of the block's table)
         bw_sites = cov_sites = 0
         region_out, region_cur = [], None  # the summary's lines, contig by contig; (name, regions, names) of the contig attached
@@ -226,7 +236,7 @@ def run(bam_path: str, reference: Dict[str, np.ndarray], bcf_path: str, sample: 
                 region_cur = None
 
             def block_blobs():
-                nonlocal n_blocks, n_records, base_filter, passed, meth_lines, region_cur, bw_sites, cov_sites, bb_sites, var_totals
+                nonlocal n_blocks, n_records, base_filter, passed, meth_lines, region_cur, bw_sites, cov_sites, bb_sites, var_totals, reads_lines, reads_totals
                 before, cur_tid = c.site_totals(), -1
                 for item in (rd.device_blocks() if device_reader else rd.blocks()):
                     if device_reader:
@@ -274,7 +284,8 @@ def run(bam_path: str, reference: Dict[str, np.ndarray], bcf_path: str, sample: 
                         else:
                             blob, n_rec, st = c.block_bcf_rawdev(dblk, ref, tid, names=names, left_trim=left_trim, right_trim=right_trim, min_qual=min_qual,
                                                                  reg_stop=len(codes), dbsnp=flags, with_stats=True, profile=prof,
-                                                                 keep=meth_path is not None or want_regions or want_bw or want_cov or want_bb or variants_path is not None)
+                                                                 keep=meth_path is not None or want_regions or want_bw or want_cov or want_bb or variants_path is not None
+                                                                 or cpg_reads_path is not None)
                         if region_cur is not None:  # the block's cytosines into the attached regions' sums
                             c.block_meth_regions_kept(meth_params)
                         if want_cov:  # the coverage track, and the level track with it, from ONE sweep over the block's arrays
@@ -316,6 +327,11 @@ def run(bam_path: str, reference: Dict[str, np.ndarray], bcf_path: str, sample: 
                             vb, _, vt = c.block_variants_kept(variants_params)
                             var_blobs.append(vb)
                             var_totals += np.array(vt, dtype=np.uint64)
+                        if cpg_reads_path is not None:  # the same block's read-level CpG table, from its prepared reads still on the device
+                            rb, rl, rt = c.block_cpg_reads_kept(name, cpg_reads_params)
+                            reads_blobs.append(rb)
+                            reads_lines += rl
+                            reads_totals += np.array(rt, dtype=np.uint64)
                         recs = None
                     elif host_prep:  # round 4's split: the process thread's per-template work here, then the block
                         tpl, pseq, st = prepare_templates(raw, seq, ms, left_trim, right_trim, min_qual, profile=prof, x=x, ref=ref)
@@ -374,6 +390,8 @@ def run(bam_path: str, reference: Dict[str, np.ndarray], bcf_path: str, sample: 
                     vcf.write_vcf_blobs(variants_path, header, var_blobs, compressed)
                 else:
                     vcf.write_bcf(variants_path, header, var_blobs, compressed)
+            if cpg_reads_path is not None:
+                vcf.write_vcf_blobs(cpg_reads_path, "", reads_blobs, compressed)
             if want_bw:
                 bw_writer.finish()
             if want_cov:
@@ -453,6 +471,9 @@ def run(bam_path: str, reference: Dict[str, np.ndarray], bcf_path: str, sample: 
         if variants_path is not None:
             summary["variant_records"] = int(var_totals[0])
             summary["variant_totals"] = tuple(int(v) for v in var_totals)
+        if cpg_reads_path is not None:
+            summary["cpg_reads_lines"] = reads_lines
+            summary["cpg_reads_totals"] = tuple(int(v) for v in reads_totals)
         if want_bw:
             summary["bigwig_sites"] = bw_sites
         if want_cov:

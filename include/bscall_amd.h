@@ -1727,6 +1727,98 @@ int bsc_variants_stream_detach(bsc_context *ctx, void **d_stream, uint64_t *n_by
 int bsc_block_variants_csi_kept(bsc_context *ctx, int min_shift, const bsc_csi_entry **entries, uint64_t *n_entries, uint64_t *n_records);
 
 /*
+ * The read-level CpG concordance table (csrc/cpgreadsdev.hip: the site pass, the context's scan, the walk, the text encoder; csrc/cpgreads.c
+ * holds the host form, which is their checker; bs_call_amd/cpgreads.py the Python rule).  Every other output is a function of the
+ * per-position records; the pile-up has forgotten which bases came from one molecule.  This table is made from the prepared templates, their
+ * read bytes and the block's reference codes while a block call still has them in HBM: per reference CpG how many templates read it methylated
+ * and unmethylated, how many of those come from templates that cover enough CpGs to be judged and how many of these are discordant (PDR =
+ * d / e), and the 2x2 table of the site with its reference-next CpG (methylation-haplotype blocks, allelic-methylation tests).  The reference
+ * has no such output: the rule is this project's own.
+ *
+ * Inputs    those of bsc_reads_chain_device: prepared templates tpl[nr] (bsc_template), their read bytes seq (seq_bytes of them; a byte is
+ *           base | qual << 2, base 0 A, 1 C, 2 G, 3 T), the block x .. y, ref = the reference codes (0 N, 1 .. 4 ACGT) of positions x .. y + 2,
+ *           min_qual of the context's bsc_params.  A read k with off[k] + len[k] > seq_bytes is absent (as len[k] == 0).
+ * COUNTS    A read byte counts iff min_qual <= byte >> 2 < 63: the pile-up's rule (src/call_genotypes.c:217; accdev.h applies it as a window
+ *           test on the byte).
+ * SITE      A position p with x <= p <= y, ref(p) == 2 and ref(p + 1) == 3 is a site.  The sites of a block in ascending order are s_0 < s_1
+ *           < ...; NEXT(s_i) = s_{i+1}, and the last site has none.  Sites are a property of the reference alone: a site no read covers is
+ *           still a site.
+ * BYTE(t, q)  For k = 0, then k = 1: if len[k] > 0, pos[k] <= q, q - pos[k] < len[k] (compared in 64 bits) and seq[off[k] + q - pos[k]]
+ *           COUNTS, that byte is BYTE(t, q) and the search stops.  A position q < x or q > y has no byte.  If neither read gives one, there is
+ *           none.  The first counting byte decides whatever its base.
+ * STATE(t, s) for a site at p: bs_strand == 1 (C2T): from BYTE(t, p); base 1 -> M, base 3 -> U, anything else or no byte -> none.
+ *           bs_strand == 2 (G2A): from BYTE(t, p + 1); base 2 -> M, base 0 -> U, else none.  Any other bs_strand: none.  So a site at
+ *           p == y never has a G2A state.
+ * Per template  k_t is the number of sites with a state.  ELIGIBLE iff k_t >= min_sites.  DISCORDANT iff eligible and it has at least one M
+ *           and at least one U.
+ * Per site, all u32: m, u: templates with state M / U.  e: eligible templates with a state here.  d: discordant templates with a state here.
+ *           With n = NEXT(s): dist = n - s, and mm, mu, um, uu count templates whose (STATE(t, s), STATE(t, n)) is (M,M), (M,U), (U,M),
+ *           (U,U).  With no next site, dist and the four pair counts are 0.  A site between the two mates of a pair has no state, and the
+ *           pair across it is not counted: pairs are reference-neighbours only.
+ * RECORD    bsc_cpg_reads_site {pos, dist, m, u, e, d, mm, mu, um, uu}, 40 bytes.  There is one record per SITE of the block in position
+ *           order, zero-count sites included.
+ * TOTALS    Eight u64: [0] sites, [1] sum of m, [2] sum of u, [3] sum of mm + mu + um + uu, [4] templates with k_t >= 1, [5] eligible
+ *           templates, [6] discordant templates, [7] 0 — over every site of the block, stored or not.
+ * LINE      A line is written iff m + u >= max(1, min_cov).  Twelve tab-separated plain decimals and '\n':
+ *             chrom  start = pos - 1  end = pos + 1  m  u  e  d  dist  mm  mu  um  uu
+ *           start and end are those of a --meth-merge line of the same CpG (bsc_meth_cpg_*), so the two tables join on them.  No float is
+ *           written anywhere: PDR is d / e, and the reader divides.  contig: 1 .. 255 bytes without tab or newline.  Text totals: {bytes,
+ *           lines}.
+ * Params    bsc_cpg_reads_params {min_sites, min_cov}, default {4, 1}.  min_sites == 0 is refused with BSC_ERR_ARG.
+ * Not gated by the called genotype: a C->T SNP at a reference CpG reads as U; the join with the --meth-merge table (whose lines are
+ * genotype-gated) is the user's filter.
+ *
+ *   bsc_cpg_reads_params_default  {4, 1}
+ *   bsc_cpg_reads_sites_host      the host form: sites[<= cap] the records, *n_sites their number (records beyond cap are counted, not stored:
+ *                                 BSC_OK all the same), totals (eight u64; may be NULL)
+ *   bsc_cpg_reads_format          the lines of sites[n] -> buf.  Returns the length; the length needed, with nothing written, when cap is too
+ *                                 small; < 0 for a bad argument.  totals2 (may be NULL): {bytes, lines}
+ *   bsc_cpg_reads_device          the same records from device-resident inputs (d_tpl 8-byte aligned, d_ref y - x + 3 codes): d_sites[min(count,
+ *                                 sites_cap)] (8-byte aligned; nothing is written behind the room), *d_n_sites a device u64 = the count, d_totals
+ *                                 eight device u64.  Integer atomic adds alone: the bytes are a function of the input.  Asynchronous on
+ *                                 `stream`; workspaces of the context's, grow-only: one call in flight per context.  A refusal writes nothing.
+ *   bsc_cpg_reads_text_device     the lines of d_sites[min(*d_n_sites, max_sites)] -> d_out[<= out_cap] (16-byte aligned).  d_totals2: two device
+ *                                 u64 {bytes, lines}.  A stream longer than out_cap is cut at a 64-record boundary and its full length is
+ *                                 still reported, as the other text encoders do.
+ *   bsc_block_cpg_reads_kept      the follow-up of bsc_block_bcf_rawdev_keep / bsc_block_vcf_rawdev_keep (and of bsc_block_bcf_again behind
+ *                                 them): preconditions and refusals of bsc_block_meth_kept.  Reads the prepared templates, reads and
+ *                                 reference codes that block left in HBM — nothing queued behind the pre-processing writes to them — and
+ *                                 writes the table into a buffer of the context's own (room: dev_cap bytes).  dev_cap too small: BSC_ERR_ARG
+ *                                 with *n_bytes = the room needed (the totals are filled), and the call may be repeated.  A block with no
+ *                                 template gives its zero-count sites: no line.  The kept stream, its tile offsets and bsc_block_csi_kept,
+ *                                 the methylation tables, the region accumulators, the bigWig and bigBed data and the variant selection are
+ *                                 untouched, before or after.  Waits.
+ *   bsc_cpg_reads_stream_read     bytes [off, off + n) of that table -> dst, queued on the context's stream (bsc_meth_stream_read's twin)
+ *   bsc_cpg_reads_stream_detach   the table handed over as bsc_meth_stream_detach hands one over: bsc_detached_read / _wait / _free and
+ *                                 bsc_bgzf_write_device serve it; it counts against the four pooled buffers
+ * Not built: a tabix index of the table, sharded runs, the batched and host-buffer block entries, non-CpG contexts, pairs beyond the
+ * reference-next site, any float statistic of the 2x2 table.
+ */
+typedef struct {
+  uint32_t pos, dist, m, u, e, d, mm, mu, um, uu;
+} bsc_cpg_reads_site;
+typedef struct {
+  uint32_t min_sites; /* ELIGIBLE: k_t >= min_sites; 0 is refused */
+  uint32_t min_cov;   /* LINE: m + u >= max(1, min_cov) */
+} bsc_cpg_reads_params;
+#define BSC_CPG_READS_N_TOTALS 8
+void bsc_cpg_reads_params_default(bsc_cpg_reads_params *p);
+int bsc_cpg_reads_sites_host(const bsc_template *tpl, uint32_t nr, const uint8_t *seq, uint64_t seq_bytes, uint32_t x, uint32_t y, const uint8_t *ref,
+                             int32_t min_qual, const bsc_cpg_reads_params *p, bsc_cpg_reads_site *sites, uint64_t cap, uint64_t *n_sites,
+                             uint64_t totals[8]);
+long bsc_cpg_reads_format(const char *contig, const bsc_cpg_reads_site *sites, size_t n, const bsc_cpg_reads_params *p, char *buf, size_t cap,
+                          uint64_t totals2[2]);
+int bsc_cpg_reads_device(bsc_context *ctx, const void *d_tpl, uint32_t nr, const void *d_seq, uint64_t seq_bytes, uint32_t x, uint32_t y,
+                         const void *d_ref, const bsc_cpg_reads_params *p, void *d_sites, uint64_t sites_cap, void *d_n_sites, void *d_totals,
+                         void *stream);
+int bsc_cpg_reads_text_device(bsc_context *ctx, const void *d_sites, const void *d_n_sites, uint64_t max_sites, const char *contig,
+                              const bsc_cpg_reads_params *p, void *d_out, uint64_t out_cap, void *d_totals2, void *stream);
+int bsc_block_cpg_reads_kept(bsc_context *ctx, const char *contig, const bsc_cpg_reads_params *p, uint64_t dev_cap, uint64_t *n_bytes,
+                             uint64_t *n_lines, uint64_t totals[8]);
+int bsc_cpg_reads_stream_read(bsc_context *ctx, uint64_t off, uint64_t n, void *dst);
+int bsc_cpg_reads_stream_detach(bsc_context *ctx, void **d_stream, uint64_t *n_bytes);
+
+/*
  * dbSNP index (host C + zlib; csrc/dbsnp.c): the reader of the compressed index bin/dbSNP_idx writes.  In the reference
  * the index never touches the likelihoods: an entry names the record (VCF ID), forces the AA / TT homozygous-reference
  * record of a site flagged in its `fq_mask` to be written (rs_found & 2, src/print_vcf.c:139) and feeds the dbSNP

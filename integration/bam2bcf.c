@@ -93,6 +93,15 @@
  * every block; bsc_meth_regions_read at the next contig change and at the end), ten columns a region: chrom start end name sites A+B A B
  * level mean.  --meth-window n in the BED's place: fixed tiles of n bases over every contig.  The --meth-* thresholds and --meth-all
  * apply; --meth is not needed.  Contigs come out in the order their blocks do (the BAM header's); a contig without a block gives no line.
+ *
+ * --meth-reads out.tsv: the read-level CpG concordance table (include/bscall_amd.h has the rule) — a line per reference CpG that a template
+ * reads: chrom start end m u e d dist mm mu um uu, start / end those of the --meth-merge line of the same CpG.  Behind every block
+ * bsc_block_cpg_reads_kept walks the prepared templates, reads and reference codes the block call left in HBM; the table is detached
+ * (bsc_cpg_reads_stream_detach) and goes to the output thread as one more job for its own file, through a BGZF writer of its own under -O b
+ * or --meth-bgzf.  --meth-reads-min-sites n (default 4): a template is judged concordant / discordant from n CpGs with a state on;
+ * --meth-reads-min-cov n (default 1): m + u a line needs.  Not gated by the called genotype (a C>T SNP at a reference CpG reads as
+ * unmethylated): the join with the --meth-merge table is the filter.  Refused where --meth is: sharded runs, the BAM2BCF_HOST_* paths.
+ * Without the switch the program makes the calls it made before the switch existed.
  */
 #include <pthread.h>
 #include <stdio.h>
@@ -145,7 +154,7 @@ static void *pinned(size_t n) { /* page-locked: the copy-out is a true DMA, queu
  * ONE writer: three of them writing pieces of one file in parallel were 2.5 x slower (0.70 s against 0.28 for the 2.9 GB of a contig-sized
  * block: writes to one inode take turns anyway).  Page-locking a host buffer for a whole stream would cost more than the calling. */
 #define PIECE ((size_t)32 << 20)
-#define N_JOB 4 /* (a block is two jobs with --meth, three with --variants beside it) */
+#define N_JOB 4 /* (a block is two jobs with --meth, three with --variants beside it, four with --meth-reads: a push waits for a free slot) */
 typedef struct {
   void *d;        /* the stream on the device; NULL: only close_fd */
   uint64_t n, at; /* its length, where it goes in the file */
@@ -535,6 +544,14 @@ int main(int argc, char **argv) {
   bsc_var_params vpar;
   bsc_var_params_default(&vpar);
   int variants_opts = 0;
+  const char *reads_path = NULL; /* --meth-reads out.tsv: the read-level CpG concordance table */
+  bsc_cpg_reads_params crpar;
+  bsc_cpg_reads_params_default(&crpar);
+  int reads_opts = 0;
+  if (argc >= 2 && !strcmp(argv[argc - 1], "--meth-reads") && (argc == 2 || strcmp(argv[argc - 2], "--meth-reads"))) {
+    fprintf(stderr, "%s: --meth-reads takes the path of the read-level CpG table to write\n", argv[0]);
+    return 2;
+  }
   if (argc >= 2 && !strcmp(argv[argc - 1], "--meth") && (argc == 2 || strcmp(argv[argc - 2], "--meth"))) {
     fprintf(stderr, "%s: --meth takes the path of the methylation table to write (bedMethyl)\n", argv[0]);
     return 2;
@@ -613,6 +630,19 @@ int main(int argc, char **argv) {
       vpar.min_phred = (uint32_t)v;
       variants_opts = 1;
     }
+    else if (!strcmp(argv[1], "--meth-reads")) reads_path = argv[2];
+    else if (!strcmp(argv[1], "--meth-reads-min-sites") || !strcmp(argv[1], "--meth-reads-min-cov")) {
+      char *end = NULL;
+      const unsigned long v = strtoul(argv[2], &end, 10);
+      const int sites = argv[1][17] == 's';
+      if (!argv[2][0] || *end || argv[2][0] == '-' || v > 0xfffffffful || (sites && !v)) {
+        fprintf(stderr, "%s: %s takes a count%s, not '%s'\n", argv[0], argv[1], sites ? ", 1 or more" : "", argv[2]);
+        return 2;
+      }
+      if (sites) crpar.min_sites = (uint32_t)v;
+      else crpar.min_cov = (uint32_t)v;
+      reads_opts = 1;
+    }
     else if (!strcmp(argv[1], "--meth-index")) {
       if (strcmp(argv[2], "tbi") && strcmp(argv[2], "csi")) {
         fprintf(stderr, "%s: --meth-index takes tbi or csi, not '%s'\n", argv[0], argv[2]);
@@ -679,7 +709,7 @@ int main(int argc, char **argv) {
     argc -= 2;
   }
   if (argc < 5 || world < 1 || (rank >= 0 && rank >= world)) {
-    fprintf(stderr, "usage: %s [-O u|b] [--format bcf|vcf] [--index] [-D dbsnp.idx] [--meth out.bed [--meth-bgzf] [--meth-index tbi|csi] [--meth-merge | --meth-all] [--meth-min-cov n] [--meth-min-gq n] [--meth-pass]] [--meth-regions regions.bed | --meth-window n --meth-regions-out out.tsv] [--meth-bigwig out.bw [--meth-bigwig-section n] [--meth-bigwig-zoom n] [--meth-bigwig-compress: zlib sections, n <= 8157]: the methylation level as a bigWig track, per cytosine even with --meth-merge, under the --meth-* thresholds and --meth-all] [--cov-bigwig cov.bw: the depth of the same sites as a bigWig track, under the same --meth-bigwig-* switches] [--meth-bigbed out.bb [--meth-bigbed-items n] [--meth-bigbed-zoom n] [--meth-bigbed-compress: zlib blocks, n <= 652]] [--variants out: the records with an ALT allele, in the run's format and compression, with out.csi under --index [--variants-min-qual n] [--variants-pass] [--variants-known: dbSNP sites only, with -D]] [--rank r --world n | --merge n] in.bam ref.fa out.bcf report.json [sample]\n", argv[0]);
+    fprintf(stderr, "usage: %s [-O u|b] [--format bcf|vcf] [--index] [-D dbsnp.idx] [--meth out.bed [--meth-bgzf] [--meth-index tbi|csi] [--meth-merge | --meth-all] [--meth-min-cov n] [--meth-min-gq n] [--meth-pass]] [--meth-regions regions.bed | --meth-window n --meth-regions-out out.tsv] [--meth-bigwig out.bw [--meth-bigwig-section n] [--meth-bigwig-zoom n] [--meth-bigwig-compress: zlib sections, n <= 8157]: the methylation level as a bigWig track, per cytosine even with --meth-merge, under the --meth-* thresholds and --meth-all] [--cov-bigwig cov.bw: the depth of the same sites as a bigWig track, under the same --meth-bigwig-* switches] [--meth-bigbed out.bb [--meth-bigbed-items n] [--meth-bigbed-zoom n] [--meth-bigbed-compress: zlib blocks, n <= 652]] [--variants out: the records with an ALT allele, in the run's format and compression, with out.csi under --index [--variants-min-qual n] [--variants-pass] [--variants-known: dbSNP sites only, with -D]] [--meth-reads out.tsv: the read-level CpG concordance table, a line per reference CpG [--meth-reads-min-sites n] [--meth-reads-min-cov n]] [--rank r --world n | --merge n] in.bam ref.fa out.bcf report.json [sample]\n", argv[0]);
     return 2;
   }
   if (text && (rank >= 0 || merge > 0)) {
@@ -726,6 +756,18 @@ int main(int argc, char **argv) {
     fprintf(stderr, "%s: --meth encodes what the device reader's blocks leave on the device: not with BAM2BCF_HOST_READER / _HOST_BCF / _HOST_PREP\n", argv[0]);
     return 2;
   }
+  if (reads_opts && !reads_path) {
+    fprintf(stderr, "%s: --meth-reads-min-sites / --meth-reads-min-cov are thresholds of the table --meth-reads writes: they need --meth-reads out.tsv\n", argv[0]);
+    return 2;
+  }
+  if (reads_path && (rank >= 0 || world > 1 || merge > 0)) {
+    fprintf(stderr, "%s: --meth-reads writes a single run's table; a sharded run (--rank / --world / --merge) has none\n", argv[0]);
+    return 2;
+  }
+  if (reads_path && (getenv("BAM2BCF_HOST_PREP") || getenv("BAM2BCF_HOST_BCF") || getenv("BAM2BCF_HOST_READER"))) {
+    fprintf(stderr, "%s: --meth-reads walks the prepared reads the device reader's blocks leave on the device: not with BAM2BCF_HOST_READER / _HOST_BCF / _HOST_PREP\n", argv[0]);
+    return 2;
+  }
   if (variants_opts && !variants_path) {
     fprintf(stderr, "%s: --variants-min-qual / --variants-pass / --variants-known select among the records --variants writes: they need --variants out\n", argv[0]);
     return 2;
@@ -738,8 +780,8 @@ int main(int argc, char **argv) {
     fprintf(stderr, "%s: --variants selects from what the device reader's blocks leave on the device: not with BAM2BCF_HOST_READER / _HOST_BCF / _HOST_PREP\n", argv[0]);
     return 2;
   }
-  if (meth_bgzf && !meth_path) {
-    fprintf(stderr, "%s: --meth-bgzf compresses the table --meth writes: it needs --meth out.bed.gz\n", argv[0]);
+  if (meth_bgzf && !meth_path && !reads_path) {
+    fprintf(stderr, "%s: --meth-bgzf compresses the table --meth writes: it needs --meth out.bed.gz (or --meth-reads out.tsv.gz, whose table it compresses too)\n", argv[0]);
     return 2;
   }
   if (meth_index && !meth_path) {
@@ -929,6 +971,19 @@ int main(int argc, char **argv) {
     meth_fd = dup(fileno(mf));
     fclose(mf);
     if (bgzf || meth_bgzf) CHECK(bsc_bgzf_open(ctx, &zm));
+  }
+  int reads_fd = -1; /* --meth-reads: the file, where its next bytes go, its compressor, the sums of the blocks' totals and lines */
+  uint64_t reads_at = 0, reads_lines = 0, reads_tot[BSC_CPG_READS_N_TOTALS] = {0};
+  bsc_bgzf *zr = NULL;
+  if (reads_path) {
+    FILE *rf = fopen(reads_path, "wb");
+    if (!rf) {
+      perror(reads_path);
+      return 1;
+    }
+    reads_fd = dup(fileno(rf));
+    fclose(rf);
+    if (bgzf || meth_bgzf) CHECK(bsc_bgzf_open(ctx, &zr));
   }
   int var_fd = -1; /* --variants: the file, where its next bytes go, its compressor and index, the sums of the blocks' totals */
   uint64_t var_at = 0, var_tot[BSC_VAR_N_TOTALS] = {0};
@@ -1312,6 +1367,32 @@ int main(int argc, char **argv) {
           meth_at += n_m;
         }
       }
+      if (n_bytes && reads_path) { /* the block's read-level CpG table, from the prepared templates, reads and reference codes the call left on the
+                                    * device: a buffer and a job of its own */
+        uint64_t r_cap = (uint64_t)n * 2 + 4096, r_bytes = 0, r_lines = 0, rt[BSC_CPG_READS_N_TOTALS];
+        int rrc = bsc_block_cpg_reads_kept(ctx, REF_NAME(dblk.tid), &crpar, r_cap, &r_bytes, &r_lines, rt);
+        if (rrc == BSC_ERR_ARG && r_bytes > r_cap) rrc = bsc_block_cpg_reads_kept(ctx, REF_NAME(dblk.tid), &crpar, r_bytes, &r_bytes, &r_lines, rt);
+        CHECK(rrc);
+        reads_lines += r_lines;
+        for (int k = 0; k < BSC_CPG_READS_N_TOTALS; k++) reads_tot[k] += rt[k];
+        if (r_bytes) {
+          void *d_r = NULL;
+          uint64_t n_r = 0;
+          CHECK(bsc_cpg_reads_stream_detach(ctx, &d_r, &n_r));
+          if (zr) {
+            CHECK(bsc_bgzf_write_device(zr, d_r, n_r));
+            CHECK(bsc_detached_free(ctx, d_r));
+            d_r = NULL;
+            n_r = 0;
+            CHECK(bsc_bgzf_take(zr, &d_r, &n_r));
+          }
+          if (n_r) {
+            const out_job j = {d_r, n_r, reads_at, reads_fd, 0};
+            writer_push(&W, j);
+          }
+          reads_at += n_r;
+        }
+      }
       if (n_bytes && variants_path) { /* the block's variant-only stream, selected from the same arrays and encoded by the block's own encoder: a
                                        * buffer and a job of its own */
         uint64_t v_cap = (uint64_t)n / 4 + 65536, v_bytes = 0, v_recs = 0, vt[BSC_VAR_N_TOTALS];
@@ -1487,6 +1568,17 @@ int main(int argc, char **argv) {
       tbx = NULL;
     }
   }
+  if (zr) { /* the read-level table's last member and its end-of-file marker */
+    void *d_z = NULL;
+    uint64_t n_z = 0;
+    CHECK(bsc_bgzf_close(zr, &d_z, &n_z));
+    zr = NULL;
+    if (n_z) {
+      const out_job j = {d_z, n_z, reads_at, reads_fd, 0};
+      writer_push(&W, j);
+    }
+    reads_at += n_z;
+  }
   if (zv) { /* the variant file's last member and its end-of-file marker; its index */
     void *d_z = NULL;
     uint64_t n_z = 0;
@@ -1530,6 +1622,10 @@ int main(int argc, char **argv) {
   }
   if (meth_fd >= 0 && close(meth_fd)) {
     perror(meth_path);
+    return 1;
+  }
+  if (reads_fd >= 0 && close(reads_fd)) {
+    perror(reads_path);
     return 1;
   }
   if (var_fd >= 0 && close(var_fd)) {
@@ -1664,6 +1760,9 @@ int main(int argc, char **argv) {
       printf("%llu variant records written (snp %llu, multi %llu, het %llu, pass %llu, known %llu, ts %llu, tv %llu)\n", (unsigned long long)var_tot[0],
              (unsigned long long)var_tot[1], (unsigned long long)var_tot[2], (unsigned long long)var_tot[3], (unsigned long long)var_tot[4],
              (unsigned long long)var_tot[5], (unsigned long long)var_tot[7], (unsigned long long)var_tot[8]);
+    if (reads_path)
+      printf("%llu CpG sites in the read-level table, %llu lines written (eligible templates %llu, discordant %llu)\n", (unsigned long long)reads_tot[0],
+             (unsigned long long)reads_lines, (unsigned long long)reads_tot[5], (unsigned long long)reads_tot[6]);
   }
   if (getenv("BAM2BCF_TIMING")) {
     uint64_t rc4[4] = {0, 0, 0, 0};
