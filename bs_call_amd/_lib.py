@@ -250,6 +250,15 @@ EXPORTS = (
     "bsc_block_cpg_reads_kept",
     "bsc_cpg_reads_stream_read",
     "bsc_cpg_reads_stream_detach",
+    "bsc_asm_params_default",
+    "bsc_asm_pairs_host",
+    "bsc_asm_format",
+    "bsc_asm_fisher_p",
+    "bsc_asm_device",
+    "bsc_asm_text_device",
+    "bsc_block_asm_kept",
+    "bsc_asm_stream_read",
+    "bsc_asm_stream_detach",
 )
 
 
@@ -288,6 +297,15 @@ class CpgReadsParams(C.Structure):
 
     def __init__(self, min_sites=4, min_cov=1):
         super().__init__(int(min_sites), int(min_cov))
+
+
+class AsmParams(C.Structure):
+    """bsc_asm_params; the defaults are bsc_asm_params_default's."""
+
+    _fields_ = [("min_phred", C.c_uint32), ("pass_only", C.c_int32), ("max_dist", C.c_uint32), ("min_cov", C.c_uint32)]
+
+    def __init__(self, min_phred=20, pass_only=0, max_dist=500, min_cov=2):
+        super().__init__(int(min_phred), int(pass_only), int(max_dist), int(min_cov))
 
 
 class BwParams(C.Structure):
@@ -873,6 +891,24 @@ def load():
     L.bsc_cpg_reads_stream_read.argtypes = [vp, u64, u64, vp]
     L.bsc_cpg_reads_stream_detach.restype = i32
     L.bsc_cpg_reads_stream_detach.argtypes = [vp, C.POINTER(vp), C.POINTER(u64)]
+    L.bsc_asm_params_default.restype = None
+    L.bsc_asm_params_default.argtypes = [C.POINTER(AsmParams)]
+    L.bsc_asm_pairs_host.restype = i32
+    L.bsc_asm_pairs_host.argtypes = [vp, u32, vp, u64, u32, u32, vp, i32, vp, vp, vp, C.POINTER(AsmParams), vp, u64, C.POINTER(u64), C.POINTER(u64)]
+    L.bsc_asm_format.restype = C.c_long
+    L.bsc_asm_format.argtypes = [C.c_char_p, vp, C.c_size_t, C.POINTER(AsmParams), vp, C.c_size_t, C.POINTER(u64)]
+    L.bsc_asm_fisher_p.restype = C.c_double
+    L.bsc_asm_fisher_p.argtypes = [vp, vp]
+    L.bsc_asm_device.restype = i32
+    L.bsc_asm_device.argtypes = [vp, vp, u32, vp, u64, u32, u32, vp, vp, vp, C.POINTER(AsmParams), vp, u64, vp, vp, vp]
+    L.bsc_asm_text_device.restype = i32
+    L.bsc_asm_text_device.argtypes = [vp, vp, vp, u64, C.c_char_p, C.POINTER(AsmParams), vp, u64, vp, vp]
+    L.bsc_block_asm_kept.restype = i32
+    L.bsc_block_asm_kept.argtypes = [vp, C.c_char_p, C.POINTER(AsmParams), u64, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)]
+    L.bsc_asm_stream_read.restype = i32
+    L.bsc_asm_stream_read.argtypes = [vp, u64, u64, vp]
+    L.bsc_asm_stream_detach.restype = i32
+    L.bsc_asm_stream_detach.argtypes = [vp, C.POINTER(vp), C.POINTER(u64)]
     L.bsc_meth_cpg_format_recs.argtypes = [vp, C.c_size_t, C.c_char_p, C.POINTER(MethParams), vp, C.c_size_t, C.POINTER(u64)]
     L.bsc_meth_cpg_block_device.restype = i32
     L.bsc_meth_cpg_block_device.argtypes = [vp, vp, vp, u64, C.c_char_p, C.POINTER(MethParams), vp, u64, vp, vp]

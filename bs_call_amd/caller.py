@@ -1282,6 +1282,53 @@ class SiteCaller:
             self.synchronize()
         return out[: int(n)].tobytes()
 
+    # -- the allele-specific methylation table (csrc/asmdev.hip) ----------------------------------------------
+    @staticmethod
+    def _asm_params(params):
+        if params is None:
+            return _lib.AsmParams()
+        if isinstance(params, _lib.AsmParams):
+            return params
+        return _lib.AsmParams(**params)
+
+    def asm_device(self, d_tpl, nr, d_seq, seq_bytes, x, y, d_ref, d_core, d_emit, d_pairs, pairs_cap, d_n_pairs, d_totals, params=None, stream=None):
+        """bsc_asm_device: the inputs of cpg_reads_device, the block's dense bsc_vcf_core records d_core and its emit bytes d_emit (or None) ->
+        one bsc_asm_pair per (heterozygous SNP, CpG of its window) in d_pairs[<= pairs_cap], their count (a device u64) in d_n_pairs and the
+        eight totals in d_totals (queued on `stream`; waits for the two counts)."""
+        cp = self._asm_params(params)
+        _check(self._L.bsc_asm_device(self._h, d_tpl, nr, d_seq, seq_bytes, x, y, d_ref, d_core, d_emit, C.byref(cp), d_pairs, pairs_cap, d_n_pairs,
+                                      d_totals, stream))
+
+    def asm_text_device(self, d_pairs, d_n_pairs, max_pairs, contig, d_out, out_cap, d_totals2, params=None, stream=None):
+        """bsc_asm_text_device: the table's lines of d_pairs[min(*d_n_pairs, max_pairs)] -> d_out[<= out_cap]; d_totals2: {bytes, lines}."""
+        cp = self._asm_params(params)
+        name = contig.encode() if isinstance(contig, str) else contig
+        _check(self._L.bsc_asm_text_device(self._h, d_pairs, d_n_pairs, max_pairs, name, C.byref(cp), d_out, out_cap, d_totals2, stream))
+
+    def block_asm_kept(self, contig, params=None, cap=None):
+        """bsc_block_asm_kept + bsc_asm_stream_read: the allele-specific methylation table of the block the last *_keep call called, from the
+        dense records, the prepared templates, reads and reference codes it left on the device.  params: a _lib.AsmParams, a dict of its
+        fields, or None ({20, 0, 500, 2}).  Returns (bytes, lines, totals[8]).  cap: the room on the device (default: asked for and given on
+        a second call)."""
+        cp = self._asm_params(params)
+        name = contig.encode() if isinstance(contig, str) else contig
+        nb, nl, tot = C.c_uint64(0), C.c_uint64(0), (C.c_uint64 * 8)()
+        room = 1 << 16 if cap is None else int(cap)
+        rc = self._L.bsc_block_asm_kept(self._h, name, C.byref(cp), room, C.byref(nb), C.byref(nl), tot)
+        if rc == -1 and nb.value > room and cap is None:
+            room = int(nb.value)
+            rc = self._L.bsc_block_asm_kept(self._h, name, C.byref(cp), room, C.byref(nb), C.byref(nl), tot)
+        _check(rc)
+        return self.asm_stream_read(0, nb.value), int(nl.value), tuple(int(v) for v in tot)
+
+    def asm_stream_read(self, off, n):
+        """bsc_asm_stream_read: bytes [off, off + n) of the table the last block_asm_kept left on the device."""
+        out = np.empty(max(int(n), 1), dtype=np.uint8)
+        _check(self._L.bsc_asm_stream_read(self._h, int(off), int(n), _ptr(out)))
+        if n:
+            self.synchronize()
+        return out[: int(n)].tobytes()
+
     def blocks_records(self, blocks, ref, out=None, all_positions=False, reg_start=1, reg_stop=0xFFFFFFFF, dbsnp=None, with_stats=False,
                        submit_only=False):
         """Several blocks in one launch sequence (bsc_blocks_records): blocks = [(templates, seq, x, y), ...] in genome order;
@@ -1720,3 +1767,75 @@ def cpg_reads_format_host(contig, recs, params=None, cap=None):
         assert (buf == 0xA5).all()
         return None, int(got)
     return buf[:got].tobytes(), int(t2[1])
+
+
+def asm_pairs_host(tpl, seq, x, y, ref, core, emit=None, lfact=None, min_qual=20, params=None, cap=None):
+    """The host form of the allele-specific methylation table (bsc_asm_pairs_host; csrc/asm.c): prepared TEMPLATE[nr] + their read bytes, the
+    block x .. y, its reference codes (x .. y + 2), its VCF_CORE records and (optionally) its emit bytes -> (PAIR records[min(count, cap)],
+    count, totals[8]).  lfact: ln k! for k < 256 (default: asm.lfact_table(), which bsc_get_tables equals).  No GPU involved.  cap: the room
+    (default: asked for first)."""
+    from .asm import PAIR, lfact_table
+
+    L = _lib.load()
+    tpl = np.ascontiguousarray(tpl, dtype=TEMPLATE)
+    seq = np.ascontiguousarray(seq, dtype=np.uint8)
+    ref = np.ascontiguousarray(ref, dtype=np.uint8)
+    core = np.ascontiguousarray(core, dtype=VCF_CORE)
+    n_pos = int(y) - int(x) + 1
+    if ref.size < n_pos + 1 or len(core) != n_pos:
+        raise ValueError("ref must hold the codes of x .. y + 1 at least, core one record per position")
+    if emit is not None:
+        emit = np.ascontiguousarray(emit, dtype=np.uint8)
+        if emit.size != n_pos:
+            raise ValueError("emit must hold one byte per position")
+    lf = np.ascontiguousarray(lfact_table() if lfact is None else lfact, dtype=np.float64)
+    assert lf.size == 256
+    cp = SiteCaller._asm_params(params)
+    n, tot = C.c_uint64(0), (C.c_uint64 * 8)()
+    args = (_ptr(tpl), len(tpl), _ptr(seq), seq.size, int(x), int(y), _ptr(ref), int(min_qual), _ptr(core), None if emit is None else _ptr(emit), _ptr(lf),
+            C.byref(cp))
+    if cap is None:
+        _check(L.bsc_asm_pairs_host(*args, None, 0, C.byref(n), tot))
+        cap = int(n.value)
+    room = int(cap)
+    out = np.zeros(max(room, 1), dtype=PAIR)
+    _check(L.bsc_asm_pairs_host(*args, _ptr(out), room, C.byref(n), tot))
+    return out[: min(int(n.value), room)].copy(), int(n.value), tuple(int(v) for v in tot)
+
+
+def asm_format_host(contig, recs, params=None, cap=None):
+    """bsc_asm_format: the table's lines of PAIR records -> (bytes, lines).  cap: the room (default: asked for first); a room too small gives
+    (None, the length needed)."""
+    from .asm import PAIR
+
+    L = _lib.load()
+    recs = np.ascontiguousarray(recs, dtype=PAIR)
+    cp = SiteCaller._asm_params(params)
+    name = contig.encode() if isinstance(contig, str) else contig
+    t2 = (C.c_uint64 * 2)()
+    if cap is None:
+        need = L.bsc_asm_format(name, _ptr(recs), len(recs), C.byref(cp), None, 0, t2)
+        if need < 0:
+            _check(int(need))
+        cap = int(need)
+    buf = np.full(max(int(cap), 1) + 8, 0xA5, dtype=np.uint8)
+    got = L.bsc_asm_format(name, _ptr(recs), len(recs), C.byref(cp), _ptr(buf), int(cap), t2)
+    if got < 0:
+        _check(int(got))
+    assert (buf[int(cap) :] == 0xA5).all() and int(t2[0]) == got
+    if got > int(cap):
+        assert (buf == 0xA5).all()
+        return None, int(got)
+    return buf[:got].tobytes(), int(t2[1])
+
+
+def asm_fisher_p_host(tables, lfact=None):
+    """bsc_asm_fisher_p over the rows of an n x 4 integer array (each >= 0, a row's sum <= 46340) -> float64[n]: the z of the rule's AQ."""
+    from .asm import lfact_table
+
+    L = _lib.load()
+    c = np.ascontiguousarray(tables, dtype=np.int32).reshape(-1, 4)
+    if len(c) and (c.min() < 0 or c.sum(axis=1).max() > 46340):
+        raise ValueError("counts must be >= 0 and a table's sum <= 46340")
+    lf = np.ascontiguousarray(lfact_table() if lfact is None else lfact, dtype=np.float64)
+    return np.array([L.bsc_asm_fisher_p(_ptr(row), _ptr(lf)) for row in c], dtype=np.float64)

@@ -129,6 +129,18 @@ int bsc_dev_launch_cr_walk(const void *tpl, uint32_t nr, const void *seq, uint64
 int bsc_dev_launch_cr_text(const void *sites, const void *n_sites, uint64_t max_sites, const char *contig, uint32_t contig_len, uint32_t min_cov,
                            void *tile_bytes, void *tile_off, void *line_len, void *scan_tmp, size_t scan_tmp_bytes, void *out, uint64_t out_cap,
                            void *totals2, int num_cus, void *stream);
+int bsc_dev_launch_asm_snps(const void *core, const void *emit, uint32_t n, uint32_t min_phred, int pass_only, void *snp_cnt, void *snp_off, void *snp_mask,
+                            void *scan_tmp, size_t scan_tmp_bytes, int num_cus, void *stream); /* asmdev.hip */
+int bsc_dev_launch_asm_spans(uint32_t n, uint32_t W, uint32_t n_snps, const void *snp_off, const void *snp_mask, const void *tile_off, const void *tile_mask,
+                             void *snp_idx, void *first, void *cnt, void *pair_off, void *n_pairs, void *scan_tmp, size_t scan_tmp_bytes, int num_cus,
+                             void *stream);
+int bsc_dev_launch_asm_pairs(const void *tpl, uint32_t nr, const void *seq, uint64_t seq_bytes, uint32_t x, uint32_t y, uint32_t min_qual, uint32_t W,
+                             const void *core, uint32_t n_snps, uint64_t n_pairs, const void *snp_off, const void *snp_mask, const void *snp_idx,
+                             const void *first, const void *pair_off, const void *tile_off, const void *tile_mask, const void *tables, void *pairs,
+                             uint64_t cap, void *d_n_pairs, void *totals, int num_cus, void *stream);
+int bsc_dev_launch_asm_text(const void *pairs, const void *n_pairs, uint64_t max_pairs, const char *contig, uint32_t contig_len, uint32_t min_cov,
+                            void *tile_bytes, void *tile_off, void *line_len, void *scan_tmp, size_t scan_tmp_bytes, void *out, uint64_t out_cap,
+                            void *totals2, int num_cus, void *stream);
 int bsc_dev_launch_csi_scan(int format, const void *s, uint64_t n_bytes, const void *sync, uint32_t n_sync, int min_shift, void *cnt, void *off,
                             void *scan_tmp, size_t scan_tmp_bytes, void *entries, uint64_t cap, void *totals, int num_cus, void *stream); /* csidev.hip */
 int bsc_dev_launch_bed_scan(const void *s, uint64_t n_bytes, const void *sync, uint32_t n_sync, int min_shift, void *cnt, void *off, void *scan_tmp,
@@ -325,6 +337,15 @@ struct bsc_context {
     uint32_t src_nr, src_x, src_y;
     uint64_t src_seq_bytes;
   } cr;
+  struct { /* the allele-specific methylation table (asmdev.hip): the workspaces of a call — SNPs per tile, their prefix sum, the tiles' SNP masks,
+            * scan scratch, the record count; per SNP its block index, its first site's rank, its sites, their prefix sum, scan scratch; the text
+            * encoder's tile bytes, tile offsets, scan scratch and line lengths; bsc_block_asm_kept: the records, {count, eight totals, bytes,
+            * lines}, the table and its length.  (The site masks are cr's workspaces: a function of the reference codes alone.) */
+    void *d_scnt, *d_soff, *d_smask, *d_stmp, *d_np, *d_idx, *d_first, *d_cnt, *d_poff, *d_ptmp, *d_tb, *d_to, *d_ttmp, *d_len, *d_pairs, *d_tot, *d_out;
+    size_t cap_scnt, cap_soff, cap_smask, cap_stmp, cap_np, cap_idx, cap_first, cap_cnt, cap_poff, cap_ptmp, cap_tb, cap_to, cap_ttmp, cap_len, cap_pairs,
+        cap_tot, cap_out;
+    uint64_t bytes;
+  } asm_;
   struct { /* streams handed to the caller (bsc_bcf_stream_detach) come back here (bsc_detached_free) and are taken again by the next block:
             * no hipMalloc / hipFree — a device-wide wait — in the steady state of a run that writes behind the calling */
     void *p[4];
@@ -753,6 +774,23 @@ int bsc_destroy(bsc_context *ctx) {
   hipFree(ctx->cr.d_sites);
   hipFree(ctx->cr.d_tot);
   hipFree(ctx->cr.d_out);
+  hipFree(ctx->asm_.d_scnt);
+  hipFree(ctx->asm_.d_soff);
+  hipFree(ctx->asm_.d_smask);
+  hipFree(ctx->asm_.d_stmp);
+  hipFree(ctx->asm_.d_np);
+  hipFree(ctx->asm_.d_idx);
+  hipFree(ctx->asm_.d_first);
+  hipFree(ctx->asm_.d_cnt);
+  hipFree(ctx->asm_.d_poff);
+  hipFree(ctx->asm_.d_ptmp);
+  hipFree(ctx->asm_.d_tb);
+  hipFree(ctx->asm_.d_to);
+  hipFree(ctx->asm_.d_ttmp);
+  hipFree(ctx->asm_.d_len);
+  hipFree(ctx->asm_.d_pairs);
+  hipFree(ctx->asm_.d_tot);
+  hipFree(ctx->asm_.d_out);
   hipFree(ctx->mr.d_reg);
   hipFree(ctx->mr.d_acc);
   free(ctx->mr.h_start);
@@ -5301,6 +5339,187 @@ int bsc_cpg_reads_stream_detach(bsc_context *ctx, void **d_stream, uint64_t *n_b
   ctx->cr.d_out = NULL;
   ctx->cr.cap_out = 0;
   ctx->cr.bytes = 0;
+  return BSC_OK;
+}
+
+/* ---- the allele-specific methylation table (asmdev.hip): include/bscall_amd.h has the rule, csrc/asm.c the host form ---------------------------- */
+static int bsc_asm_params_check(const char *who, const bsc_asm_params *p) {
+  if (!p) return bsc_fail(BSC_ERR_ARG, "%s: NULL argument", who);
+  if (p->max_dist < 1 || p->max_dist > 65535) return bsc_fail(BSC_ERR_ARG, "%s: max_dist %u is not 1 .. 65535", who, p->max_dist);
+  return BSC_OK;
+}
+
+/* the site pass, the SNP pass, the windows and their scans on stream s, in the context's workspaces: *n_snps and *n_pairs, each waited for.
+ * Writes nothing of the caller's */
+static int bsc_asm_count(bsc_context *ctx, const char *who, uint32_t x, uint32_t y, const void *d_ref, const void *d_core, const void *d_emit,
+                         const bsc_asm_params *p, uint32_t *n_snps, uint64_t *n_pairs, hipStream_t s) {
+  const uint32_t sz = y - x + 1u, n_tiles = (uint32_t)(((uint64_t)sz + 63u) / 64u);
+  size_t scan_bytes = 0;
+  int rc;
+  *n_snps = 0;
+  *n_pairs = 0;
+  if ((rc = bsc_cr_sites_run(ctx, who, d_ref, sz, s))) return rc;
+  if (bsc_dev_scan_tmp_bytes(n_tiles, &scan_bytes)) return bsc_fail(BSC_ERR_HIP, "%s: scan size query failed", who);
+  if ((rc = bsc_reserve(&ctx->asm_.d_scnt, &ctx->asm_.cap_scnt, (size_t)n_tiles * 4u))) return rc;
+  if ((rc = bsc_reserve(&ctx->asm_.d_soff, &ctx->asm_.cap_soff, (size_t)n_tiles * 4u))) return rc;
+  if ((rc = bsc_reserve(&ctx->asm_.d_smask, &ctx->asm_.cap_smask, (size_t)n_tiles * 8u))) return rc;
+  if ((rc = bsc_reserve(&ctx->asm_.d_stmp, &ctx->asm_.cap_stmp, scan_bytes ? scan_bytes : 1))) return rc;
+  if ((rc = bsc_reserve(&ctx->asm_.d_np, &ctx->asm_.cap_np, sizeof(unsigned long long)))) return rc;
+  int e = bsc_dev_launch_asm_snps(d_core, d_emit, sz, p->min_phred, p->pass_only != 0, ctx->asm_.d_scnt, ctx->asm_.d_soff, ctx->asm_.d_smask, ctx->asm_.d_stmp,
+                                  scan_bytes, ctx->num_cus, (void *)s);
+  if (e) return bsc_fail(BSC_ERR_HIP, "%s: SNP pass launch failed: %s", who, hipGetErrorString((hipError_t)e));
+  unsigned int last_off = 0, last_cnt = 0;
+  HIP_TRY(hipMemcpyAsync(&last_off, (const uint32_t *)ctx->asm_.d_soff + (n_tiles - 1u), 4, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipMemcpyAsync(&last_cnt, (const uint32_t *)ctx->asm_.d_scnt + (n_tiles - 1u), 4, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  const uint32_t ns = last_off + last_cnt;
+  *n_snps = ns;
+  if (!ns) return BSC_OK;
+  if (bsc_dev_scan_tmp_bytes(ns, &scan_bytes)) return bsc_fail(BSC_ERR_HIP, "%s: scan size query failed", who);
+  if ((rc = bsc_reserve(&ctx->asm_.d_idx, &ctx->asm_.cap_idx, (size_t)ns * 4u))) return rc;
+  if ((rc = bsc_reserve(&ctx->asm_.d_first, &ctx->asm_.cap_first, (size_t)ns * 4u))) return rc;
+  if ((rc = bsc_reserve(&ctx->asm_.d_cnt, &ctx->asm_.cap_cnt, (size_t)ns * 4u))) return rc;
+  if ((rc = bsc_reserve(&ctx->asm_.d_poff, &ctx->asm_.cap_poff, (size_t)ns * 4u))) return rc;
+  if ((rc = bsc_reserve(&ctx->asm_.d_ptmp, &ctx->asm_.cap_ptmp, scan_bytes ? scan_bytes : 1))) return rc;
+  e = bsc_dev_launch_asm_spans(sz, p->max_dist, ns, ctx->asm_.d_soff, ctx->asm_.d_smask, ctx->cr.d_off, ctx->cr.d_mask, ctx->asm_.d_idx, ctx->asm_.d_first,
+                               ctx->asm_.d_cnt, ctx->asm_.d_poff, ctx->asm_.d_np, ctx->asm_.d_ptmp, scan_bytes, ctx->num_cus, (void *)s);
+  if (e) return bsc_fail(BSC_ERR_HIP, "%s: window pass launch failed: %s", who, hipGetErrorString((hipError_t)e));
+  unsigned long long np = 0;
+  HIP_TRY(hipMemcpyAsync(&np, ctx->asm_.d_np, sizeof np, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  if (np > 0xffffffffull) return bsc_fail(BSC_ERR_RANGE, "%s: %llu records in one block, more than 2^32 - 1", who, np);
+  *n_pairs = np;
+  return BSC_OK;
+}
+
+/* the records behind bsc_asm_count: heads, walk, Fisher's test; d_totals: eight u64, zeroed here */
+static int bsc_asm_fill(bsc_context *ctx, const char *who, const void *d_tpl, uint32_t nr, const void *d_seq, uint64_t seq_bytes, uint32_t x, uint32_t y,
+                        const void *d_core, const bsc_asm_params *p, uint32_t n_snps, uint64_t n_pairs, void *d_pairs, uint64_t cap, void *d_n_pairs,
+                        void *d_totals, hipStream_t s) {
+  HIP_TRY(hipMemsetAsync(d_totals, 0, BSC_ASM_N_TOTALS * sizeof(unsigned long long), s));
+  const int e = bsc_dev_launch_asm_pairs(d_tpl, nr, d_seq, seq_bytes, x, y, (uint32_t)ctx->params.min_qual, p->max_dist, d_core, n_snps, n_pairs,
+                                         ctx->asm_.d_soff, ctx->asm_.d_smask, ctx->asm_.d_idx, ctx->asm_.d_first, ctx->asm_.d_poff, ctx->cr.d_off,
+                                         ctx->cr.d_mask, ctx->d_tables, d_pairs, cap, d_n_pairs, d_totals, ctx->num_cus, (void *)s);
+  if (e) return bsc_fail(BSC_ERR_HIP, "%s: walk launch failed: %s", who, hipGetErrorString((hipError_t)e));
+  return BSC_OK;
+}
+
+int bsc_asm_device(bsc_context *ctx, const void *d_tpl, uint32_t nr, const void *d_seq, uint64_t seq_bytes, uint32_t x, uint32_t y, const void *d_ref,
+                   const void *d_core, const void *d_emit, const bsc_asm_params *p, void *d_pairs, uint64_t pairs_cap, void *d_n_pairs, void *d_totals,
+                   void *stream) {
+  static const char who[] = "bsc_asm_device";
+  int rc;
+  if (!ctx || !d_ref || !d_core || !d_n_pairs || !d_totals || (nr && (!d_tpl || !d_seq)) || (pairs_cap && !d_pairs))
+    return bsc_fail(BSC_ERR_ARG, "%s: NULL argument", who);
+  if ((rc = bsc_asm_params_check(who, p))) return rc;
+  if (y < x) return bsc_fail(BSC_ERR_ARG, "%s: y (%u) < x (%u)", who, y, x);
+  if ((uint64_t)y - x + 1 > 0x0fffffffull) return bsc_fail(BSC_ERR_ARG, "%s: block longer than 2^28 - 1 positions", who);
+  if ((((uintptr_t)d_tpl | (uintptr_t)d_pairs | (uintptr_t)d_n_pairs | (uintptr_t)d_totals) & 7u) || ((uintptr_t)d_core & 15u))
+    return bsc_fail(BSC_ERR_ARG, "%s: the templates, the records, the count and the totals must be 8-byte, the dense records 16-byte aligned", who);
+  BSC_ENTER(ctx);
+  hipStream_t s = (hipStream_t)stream;
+  uint32_t n_snps = 0;
+  uint64_t n_pairs = 0;
+  if ((rc = bsc_asm_count(ctx, who, x, y, d_ref, d_core, d_emit, p, &n_snps, &n_pairs, s))) return rc;
+  return bsc_asm_fill(ctx, who, d_tpl, nr, d_seq, seq_bytes, x, y, d_core, p, n_snps, n_pairs, d_pairs, pairs_cap, d_n_pairs, d_totals, s);
+}
+
+int bsc_asm_text_device(bsc_context *ctx, const void *d_pairs, const void *d_n_pairs, uint64_t max_pairs, const char *contig, const bsc_asm_params *p,
+                        void *d_out, uint64_t out_cap, void *d_totals2, void *stream) {
+  static const char who[] = "bsc_asm_text_device";
+  uint32_t contig_len = 0;
+  int rc;
+  if (!ctx || !d_n_pairs || !d_totals2 || (max_pairs && !d_pairs) || (out_cap && !d_out)) return bsc_fail(BSC_ERR_ARG, "%s: NULL argument", who);
+  if ((rc = bsc_asm_params_check(who, p))) return rc;
+  if ((rc = bsc_contig_check(who, contig, &contig_len))) return rc;
+  if (((uintptr_t)d_out & 15u) || (((uintptr_t)d_pairs | (uintptr_t)d_n_pairs | (uintptr_t)d_totals2) & 7u))
+    return bsc_fail(BSC_ERR_ARG, "%s: d_out must be 16-byte, the records, the count and the totals 8-byte aligned", who);
+  if ((max_pairs + 63u) / 64u > 0x7ffffffeull) return bsc_fail(BSC_ERR_ARG, "%s: more than 2^37 records", who);
+  BSC_ENTER(ctx);
+  hipStream_t s = (hipStream_t)stream;
+  const uint32_t n_tiles = (uint32_t)((max_pairs + 63u) / 64u);
+  size_t scan_bytes = 0;
+  if (bsc_dev_scan_tmp_bytes_u64(n_tiles + 1u, &scan_bytes)) return bsc_fail(BSC_ERR_HIP, "%s: scan size query failed", who);
+  if ((rc = bsc_reserve(&ctx->asm_.d_tb, &ctx->asm_.cap_tb, ((size_t)n_tiles + 1u) * 8u))) return rc;
+  if ((rc = bsc_reserve(&ctx->asm_.d_to, &ctx->asm_.cap_to, ((size_t)n_tiles + 1u) * 8u))) return rc;
+  if ((rc = bsc_reserve(&ctx->asm_.d_ttmp, &ctx->asm_.cap_ttmp, scan_bytes ? scan_bytes : 1))) return rc;
+  if ((rc = bsc_reserve(&ctx->asm_.d_len, &ctx->asm_.cap_len, ((size_t)n_tiles + 1u) * 128u))) return rc;
+  HIP_TRY(hipMemsetAsync(d_totals2, 0, 2 * sizeof(unsigned long long), s));
+  const int e = bsc_dev_launch_asm_text(d_pairs, d_n_pairs, max_pairs, contig, contig_len, p->min_cov, ctx->asm_.d_tb, ctx->asm_.d_to, ctx->asm_.d_len,
+                                        ctx->asm_.d_ttmp, scan_bytes, d_out, out_cap, d_totals2, ctx->num_cus, stream);
+  if (e) return bsc_fail(BSC_ERR_HIP, "%s: encoder launch failed: %s", who, hipGetErrorString((hipError_t)e));
+  return BSC_OK;
+}
+
+int bsc_block_asm_kept(bsc_context *ctx, const char *contig, const bsc_asm_params *p, uint64_t dev_cap, uint64_t *n_bytes, uint64_t *n_lines,
+                       uint64_t totals[8]) {
+  static const char who[] = "bsc_block_asm_kept";
+  int rc;
+  uint32_t contig_len = 0;
+  if (!ctx || !n_bytes || !n_lines) return bsc_fail(BSC_ERR_ARG, "%s: NULL argument", who);
+  *n_bytes = *n_lines = 0;
+  for (int k = 0; totals && k < BSC_ASM_N_TOTALS; k++) totals[k] = 0;
+  if ((rc = bsc_asm_params_check(who, p))) return rc;
+  if ((rc = bsc_contig_check(who, contig, &contig_len))) return rc;
+  if (ctx->meth_src != 1 || ctx->rec_pending || ctx->pending_sz)
+    return bsc_fail(BSC_ERR_ARG, "%s: the last call left no single block's arrays on the device", who);
+  if (!ctx->cr.src_ok) return bsc_fail(BSC_ERR_ARG, "%s: the last block's prepared templates, reads and reference are no longer on the device", who);
+  if (ctx->again.sz != ctx->cr.src_y - ctx->cr.src_x + 1u)
+    return bsc_fail(BSC_ERR_ARG, "%s: the dense records (%u positions) are not those of the block whose reads are on the device", who, ctx->again.sz);
+  BSC_ENTER(ctx);
+  hipStream_t s = ctx->stream;
+  ctx->asm_.bytes = 0;
+  const uint32_t x = ctx->cr.src_x, y = ctx->cr.src_y, nr = ctx->cr.src_nr;
+  /* d_tot: [0] the count, [1 .. 8] the totals, [9 .. 10] the encoder's {bytes, lines} */
+  if ((rc = bsc_reserve(&ctx->asm_.d_tot, &ctx->asm_.cap_tot, 11 * sizeof(unsigned long long)))) return rc;
+  unsigned long long *const d_tot = (unsigned long long *)ctx->asm_.d_tot;
+  uint32_t n_snps = 0;
+  uint64_t n_pairs = 0;
+  if ((rc = bsc_asm_count(ctx, who, x, y, ctx->d_ref, ctx->d_vout, ctx->again.emit, p, &n_snps, &n_pairs, s))) return rc;
+  /* the count is known before a record is made: the records' room is theirs */
+  if ((rc = bsc_reserve(&ctx->asm_.d_pairs, &ctx->asm_.cap_pairs, (size_t)(n_pairs ? n_pairs : 1) * sizeof(bsc_asm_pair)))) return rc;
+  if ((rc = bsc_asm_fill(ctx, who, ctx->d_tpl, nr, ctx->d_seq, ctx->cr.src_seq_bytes, x, y, ctx->d_vout, p, n_snps, n_pairs, ctx->asm_.d_pairs, n_pairs, d_tot,
+                         d_tot + 1, s)))
+    return rc;
+  /* a buffer that came back (bsc_detached_free), the smallest that will do, as d_meth is taken */
+  if (!ctx->asm_.d_out && ctx->pool_mu_made) ctx->asm_.d_out = bsc_pool_get(ctx, (size_t)(dev_cap ? dev_cap : 1), &ctx->asm_.cap_out);
+  if ((rc = bsc_reserve(&ctx->asm_.d_out, &ctx->asm_.cap_out, (size_t)(dev_cap ? dev_cap : 1)))) return rc;
+  if ((rc = bsc_asm_text_device(ctx, ctx->asm_.d_pairs, d_tot, n_pairs, contig, p, ctx->asm_.d_out, dev_cap, d_tot + 9, s))) return rc;
+  unsigned long long tot[11] = {0};
+  HIP_TRY(hipMemcpyAsync(tot, d_tot, sizeof tot, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  *n_bytes = tot[9];
+  *n_lines = tot[10];
+  for (int k = 0; totals && k < BSC_ASM_N_TOTALS; k++) totals[k] = tot[1 + k];
+  if (tot[0] != n_pairs) return bsc_fail(BSC_ERR_RANGE, "%s: %llu records counted, %llu made", who, (unsigned long long)n_pairs, tot[0]);
+  if (tot[9] > dev_cap) return bsc_fail(BSC_ERR_ARG, "%s: the block's table has %llu bytes, dev_cap is %llu", who, tot[9], (unsigned long long)dev_cap);
+  ctx->asm_.bytes = tot[9];
+  return BSC_OK;
+}
+
+int bsc_asm_stream_read(bsc_context *ctx, uint64_t off, uint64_t n, void *dst) {
+  if (!ctx || (!dst && n)) return bsc_fail(BSC_ERR_ARG, "bsc_asm_stream_read: NULL argument");
+  if (off + n < off || off + n > ctx->asm_.bytes || off + n > ctx->asm_.cap_out) return bsc_fail(BSC_ERR_ARG, "bsc_asm_stream_read: beyond the table's end");
+  if (!n) return BSC_OK;
+  BSC_ENTER(ctx);
+  HIP_TRY(hipMemcpyAsync(dst, (const char *)ctx->asm_.d_out + off, (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+  return BSC_OK;
+}
+
+int bsc_asm_stream_detach(bsc_context *ctx, void **d_stream, uint64_t *n_bytes) {
+  if (!ctx || !d_stream || !n_bytes) return bsc_fail(BSC_ERR_ARG, "bsc_asm_stream_detach: NULL argument");
+  *d_stream = NULL;
+  *n_bytes = 0;
+  if (!ctx->asm_.d_out || !ctx->asm_.bytes) return bsc_fail(BSC_ERR_ARG, "bsc_asm_stream_detach: the last call left no table on the device");
+  BSC_ENTER(ctx);
+  bsc_pool_init(ctx);
+  if (!ctx->s_det) HIP_TRY(hipStreamCreateWithFlags(&ctx->s_det, hipStreamNonBlocking));
+  *d_stream = ctx->asm_.d_out;
+  *n_bytes = ctx->asm_.bytes;
+  bsc_pool_book(ctx, ctx->asm_.d_out, ctx->asm_.cap_out);
+  ctx->asm_.d_out = NULL;
+  ctx->asm_.cap_out = 0;
+  ctx->asm_.bytes = 0;
   return BSC_OK;
 }
 

@@ -22,7 +22,8 @@ def run(bam_path: str, reference: Dict[str, np.ndarray], bcf_path: str, sample: 
         cov_bigwig_path: Optional[str] = None,
         bigwig_section: int = 1024, bigwig_zoom: int = 1024, bigwig_compress: bool = False, bigbed_path: Optional[str] = None, bigbed_items: int = 512,
         bigbed_zoom: int = 1024, bigbed_compress: bool = False, meth_index: Optional[str] = None, variants_path: Optional[str] = None,
-        variants_params=None, cpg_reads_path: Optional[str] = None, cpg_reads_params=None, **reader_kw) -> dict:
+        variants_params=None, cpg_reads_path: Optional[str] = None, cpg_reads_params=None, asm_path: Optional[str] = None, asm_params=None,
+        **reader_kw) -> dict:
     """reference: contig name -> uint8 reference codes (0 = N, 1..4 = ACGT; position 1 first).  Returns a summary dict.
     under_conv / over_conv / min_qual (defaults 0.01 / 0.05 / 20, src/init_param.c:26-31) are the MODEL's parameters: without
     `caller` the run builds its SiteCaller from them; with one, they are taken from it and a differing explicit value is an error
@@ -84,7 +85,16 @@ def run(bam_path: str, reference: Dict[str, np.ndarray], bcf_path: str, sample: 
     the prepared templates, reads and reference codes the block left on the device (SiteCaller.block_cpg_reads_kept, csrc/cpgreadsdev.hip)
     — a line per reference CpG a template reads, plain text or BGZF as `compressed` says.  cpg_reads_params: a _lib.CpgReadsParams or a dict
     of min_sites / min_cov.  The summary gets "cpg_reads_lines" and "cpg_reads_totals" (the eight totals of the rule).  The same conditions as
-    meth_path."""
+    meth_path.
+    asm_path: the allele-specific methylation table of the same run (include/bscall_amd.h has the rule): behind every block, for each
+    heterozygous SNP the block's call wrote and each reference CpG within max_dist of it, the templates of allele 1 / allele 2 that read the
+    CpG methylated / unmethylated and the phred of Fisher's p of that table (SiteCaller.block_asm_kept, csrc/asmdev.hip) — lines ordered by
+    SNP, plain text or BGZF as `compressed` says.  asm_params: a _lib.AsmParams or a dict of min_phred / pass_only / max_dist / min_cov.  The
+    summary gets "asm_lines" and "asm_totals" (the eight totals of the rule).  The same conditions as meth_path."""
+    if asm_params is not None and asm_path is None:
+        raise ValueError("asm_params are thresholds of the table asm_path names: they need asm_path")
+    if asm_path is not None and (shard_rank is not None or not device_reader or host_prep or host_bcf):
+        raise ValueError("asm_path is a single run on the device reader (device_reader=True, no shard_rank, no host_prep / host_bcf)")
     if cpg_reads_params is not None and cpg_reads_path is None:
         raise ValueError("cpg_reads_params are thresholds of the table cpg_reads_path names: they need cpg_reads_path")
     if cpg_reads_path is not None and (shard_rank is not None or not device_reader or host_prep or host_bcf):
@@ -179,6 +189,7 @@ def run(bam_path: str, reference: Dict[str, np.ndarray], bcf_path: str, sample: 
         meth_blobs, meth_lines = [], 0
         var_blobs, var_totals = [], np.zeros(10, dtype=np.uint64)
         reads_blobs, reads_lines, reads_totals = [], 0, np.zeros(8, dtype=np.uint64)
+        asm_blobs, asm_lines, asm_totals = [], 0, np.zeros(8, dtype=np.uint64)
         meth_entries = []  # meth_index: (contig number, BED_ENTRY[], bytes of the block's table)
         bw_sites = cov_sites = 0
         region_out, region_cur = [], None  # the summary's lines, contig by contig; (name, regions, names) of the contig attached
@@ -236,7 +247,7 @@ def run(bam_path: str, reference: Dict[str, np.ndarray], bcf_path: str, sample: 
                 region_cur = None
 
             def block_blobs():
-                nonlocal n_blocks, n_records, base_filter, passed, meth_lines, region_cur, bw_sites, cov_sites, bb_sites, var_totals, reads_lines, reads_totals
+                nonlocal n_blocks, n_records, base_filter, passed, meth_lines, region_cur, bw_sites, cov_sites, bb_sites, var_totals, reads_lines, reads_totals, asm_lines, asm_totals
                 before, cur_tid = c.site_totals(), -1
                 for item in (rd.device_blocks() if device_reader else rd.blocks()):
                     if device_reader:
@@ -285,7 +296,7 @@ def run(bam_path: str, reference: Dict[str, np.ndarray], bcf_path: str, sample: 
                             blob, n_rec, st = c.block_bcf_rawdev(dblk, ref, tid, names=names, left_trim=left_trim, right_trim=right_trim, min_qual=min_qual,
                                                                  reg_stop=len(codes), dbsnp=flags, with_stats=True, profile=prof,
                                                                  keep=meth_path is not None or want_regions or want_bw or want_cov or want_bb or variants_path is not None
-                                                                 or cpg_reads_path is not None)
+                                                                 or cpg_reads_path is not None or asm_path is not None)
                         if region_cur is not None:  # the block's cytosines into the attached regions' sums
                             c.block_meth_regions_kept(meth_params)
                         if want_cov:  # the coverage track, and the level track with it, from ONE sweep over the block's arrays
@@ -332,6 +343,11 @@ def run(bam_path: str, reference: Dict[str, np.ndarray], bcf_path: str, sample: 
                             reads_blobs.append(rb)
                             reads_lines += rl
                             reads_totals += np.array(rt, dtype=np.uint64)
+                        if asm_path is not None:  # the same block's allele-specific table, from its dense records and its prepared reads
+                            ab, al, at = c.block_asm_kept(name, asm_params)
+                            asm_blobs.append(ab)
+                            asm_lines += al
+                            asm_totals += np.array(at, dtype=np.uint64)
                         recs = None
                     elif host_prep:  # round 4's split: the process thread's per-template work here, then the block
                         tpl, pseq, st = prepare_templates(raw, seq, ms, left_trim, right_trim, min_qual, profile=prof, x=x, ref=ref)
@@ -392,6 +408,8 @@ def run(bam_path: str, reference: Dict[str, np.ndarray], bcf_path: str, sample: 
                     vcf.write_bcf(variants_path, header, var_blobs, compressed)
             if cpg_reads_path is not None:
                 vcf.write_vcf_blobs(cpg_reads_path, "", reads_blobs, compressed)
+            if asm_path is not None:
+                vcf.write_vcf_blobs(asm_path, "", asm_blobs, compressed)
             if want_bw:
                 bw_writer.finish()
             if want_cov:
@@ -474,6 +492,9 @@ def run(bam_path: str, reference: Dict[str, np.ndarray], bcf_path: str, sample: 
         if cpg_reads_path is not None:
             summary["cpg_reads_lines"] = reads_lines
             summary["cpg_reads_totals"] = tuple(int(v) for v in reads_totals)
+        if asm_path is not None:
+            summary["asm_lines"] = asm_lines
+            summary["asm_totals"] = tuple(int(v) for v in asm_totals)
         if want_bw:
             summary["bigwig_sites"] = bw_sites
         if want_cov:

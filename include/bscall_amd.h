@@ -1819,6 +1819,106 @@ int bsc_cpg_reads_stream_read(bsc_context *ctx, uint64_t off, uint64_t n, void *
 int bsc_cpg_reads_stream_detach(bsc_context *ctx, void **d_stream, uint64_t *n_bytes);
 
 /*
+ * The allele-specific methylation table (csrc/asmdev.hip: the SNP pass, the windows, the records' heads, the walk, Fisher's test, the text
+ * encoder; csrc/asm.c holds the host form, which is their checker; bs_call_amd/asm.py the Python rule).  The caller decides genotype and
+ * methylation from the same reads; this is the output that uses both: for a heterozygous SNP the caller wrote and a reference CpG near it, do the
+ * templates that carry allele 1 read the CpG differently from those that carry allele 2 (imprinting, cis-acting variants)?  It is made while a
+ * block call still has the dense per-position records, the prepared templates, their read bytes and the reference codes in HBM.  The
+ * reference has no such output: the rule is this project's own.
+ *
+ * Inputs    those of the read-level CpG table (tpl[nr], seq, x .. y, ref = the codes of x .. y + 2, min_qual), and core = the y - x + 1
+ *           bsc_vcf_core records of the block with, optionally, emit = a byte per position (the chain's emit bytes: bsc_variants_sites_device
+ *           has the same pair).  COUNTS, SITE, BYTE(t, q) and STATE(t, s) are those of the read-level CpG table, verbatim.
+ * SNP       A position h in x .. y is a SNP when core[h - x].emit != 0 and, where the emit bytes are given, emit[h - x] != 0; gt is one of 1, 2,
+ *           3, 5, 6, 8 (AC, AG, AT, CG, CT, GT: allele 1 is the first letter, allele 2 the second); phred >= min_phred; and !pass_only or
+ *           flt == 0.
+ * ALLELE(t, h)  0 (none), 1 or 2.  bs_strand other than 1 or 2: 0.  bs_strand == 1 and gt == 6 (CT): 0 — on a C2T template a C/T SNP cannot be
+ *           told from conversion, and counting its unconverted Cs alone would bias the table.  bs_strand == 2 and gt == 2 (AG): 0, for the same
+ *           reason.  Otherwise with b the base of BYTE(t, h) (no byte: 0), the genome bases b may stand for are, on a C2T template, {C, T} for a
+ *           read T and {b} for any other base; on a G2A template {G, A} for a read A and {b} for any other.  If exactly one of the two alleles
+ *           is in that set, ALLELE is its number; otherwise 0.
+ * WINDOW    With W = max_dist the sites of h are the sites s with max(x, h - W) <= s <= min(y, h + W), computed in 64 bits (h - W below 0 is
+ *           0), in ascending order, the sites no read covers included.  A site with h == s or h == s + 1 is in the window but OVERLAPPED: the
+ *           SNP makes or unmakes the CpG on one allele, and the site never has a state for this SNP.
+ * RECORD    bsc_asm_pair {snp_pos, cpg_pos, m1, u1, m2, u2, aq, info}, eight u32, 32 bytes: one per (SNP, window site), ordered by SNP position,
+ *           then by site position.  m1: templates with ALLELE(t, h) == 1 and STATE(t, s) == M; u1, m2, u2 alike.  info = gt | flags << 8: flag 1
+ *           OVERLAPPED (the counts stay 0), flag 2 DEEP: m1 + u1 + m2 + u2 > 46340 — beyond that the `int` products of the reference's Fisher
+ *           test (src/stats_utils.c:25-91) leave 31 bits.
+ * AQ        0 for an OVERLAPPED or DEEP record.  Otherwise z = Fisher's two-sided p of the table {c0, c1, c2, c3} = {m1, u1, m2, u2} by the
+ *           statements of fisher_dev (csrc/callmath.h), with one addition: a point term exp(arg) is 0.0 when arg < -700.0 (such a term is below
+ *           1e-304 and cannot change a z >= 1e-100 in the last bit, so no result depends on how exp underflows or on flushed subnormals), and
+ *           aq = z >= 1e-100 ? (uint32_t)(int)(-(log(z) / ln 10) * 10.0 + 0.5) : 1000 — the form FS has.  No float is written anywhere.
+ * TOTALS    Eight u64: [0] SNPs, [1] records, [2] (template, SNP) observations with ALLELE != 0, [3] of them those with allele 1, [4] the sum
+ *           of m1 + u1 + m2 + u2, [5] DEEP records, [6], [7] 0.  [0] .. [4] run over every record, stored or not; DEEP is a property of a
+ *           record's counts, which exist only where the record is stored: [5] runs over the stored records.
+ * LINE      A line is written iff the record is neither OVERLAPPED nor DEEP and m1 + u1 >= c and m2 + u2 >= c, c = max(1, min_cov).  Eleven
+ *           tab-separated fields and '\n':
+ *             chrom  start = cpg_pos - 1  end = cpg_pos + 1  snp_pos  gt  m1  u1  m2  u2  aq  dist
+ *           gt is the genotype's two letters (a gt byte above 9: NN), dist = cpg_pos - snp_pos as a signed decimal.  start and end are those of
+ *           the --meth-merge and --meth-reads lines of the same CpG: the three tables join on them.  Lines are ordered by SNP, then by site —
+ *           NOT by start: windows of neighbouring SNPs overlap.  No index is built.  Text totals: {bytes, lines}.
+ * Params    bsc_asm_params {min_phred, pass_only, max_dist, min_cov}, default {20, 0, 500, 2}.  max_dist outside 1 .. 65535 is refused with
+ *           BSC_ERR_ARG; more than 2^32 - 1 records in a block with BSC_ERR_RANGE.
+ * No template spans two blocks (a block ends at a coverage gap): nothing is lost at block borders.
+ *
+ *   bsc_asm_params_default     {20, 0, 500, 2}
+ *   bsc_asm_pairs_host         the host form: pairs[<= cap] the records, *n_pairs their number (records beyond cap are counted, not stored:
+ *                              BSC_OK all the same), totals (eight u64; may be NULL).  emit may be NULL.  lfact_256: ln k! for k = 0 .. 255
+ *                              (bsc_get_tables)
+ *   bsc_asm_format             the lines of pairs[n] -> buf.  Returns the length; the length needed, with nothing written, when cap is too small;
+ *                              < 0 for a bad argument.  totals2 (may be NULL): {bytes, lines}
+ *   bsc_asm_fisher_p           z of AQ for one table {c0, c1, c2, c3} (each >= 0, their sum <= 46340), the clamp included: the host form's
+ *                              Fisher test on its own, which the tests compare with the reference's.  -1.0 for a table outside that range
+ *   bsc_asm_device             the same records from device-resident inputs (d_tpl 8-byte, d_core 16-byte aligned, d_ref y - x + 3 codes, d_emit
+ *                              y - x + 1 bytes or NULL): d_pairs[min(count, pairs_cap)] (8-byte aligned; nothing is written behind the room),
+ *                              *d_n_pairs a device u64 = the count, d_totals eight device u64.  Integer atomic adds alone: the bytes are a function
+ *                              of the input.  Queued on `stream`, on which it waits twice for a count (the SNPs, the records) before the records
+ *                              are made; workspaces of the context's, grow-only: one call in flight per context.  A refusal writes nothing.
+ *   bsc_asm_text_device        the lines of d_pairs[min(*d_n_pairs, max_pairs)] -> d_out[<= out_cap] (16-byte aligned).  d_totals2: two device
+ *                              u64 {bytes, lines}.  A stream longer than out_cap is cut at a 64-record boundary and its full length is still
+ *                              reported, as the other text encoders do.
+ *   bsc_block_asm_kept         the follow-up of bsc_block_bcf_rawdev_keep / bsc_block_vcf_rawdev_keep (and of bsc_block_bcf_again behind them):
+ *                              the preconditions of bsc_block_cpg_reads_kept and bsc_block_variants_kept together.  Reads the dense records and
+ *                              emit bytes, the prepared templates, reads and reference codes that block left in HBM and writes the table into a
+ *                              buffer of the context's own (room: dev_cap bytes).  dev_cap too small: BSC_ERR_ARG with *n_bytes = the room
+ *                              needed (the totals are filled), and the call may be repeated.  The kept stream, its tile offsets and
+ *                              bsc_block_csi_kept, the methylation tables, the region accumulators, the bigWig and bigBed data, the variant
+ *                              selection and the read-level CpG table are untouched, before or after.  Waits.
+ *   bsc_asm_stream_read        bytes [off, off + n) of that table -> dst, queued on the context's stream (bsc_meth_stream_read's twin)
+ *   bsc_asm_stream_detach      the table handed over as bsc_meth_stream_detach hands one over: bsc_detached_read / _wait / _free and
+ *                              bsc_bgzf_write_device serve it; it counts against the four pooled buffers
+ * Not built: sharded runs, the batched and host-buffer block entries, non-CpG contexts, a per-SNP aggregate, multiple-testing correction,
+ * phasing across SNPs.
+ */
+typedef struct {
+  uint32_t snp_pos, cpg_pos, m1, u1, m2, u2, aq, info;
+} bsc_asm_pair;
+typedef struct {
+  uint32_t min_phred; /* SNP: phred >= min_phred */
+  int32_t pass_only;  /* SNP: flt == 0 */
+  uint32_t max_dist;  /* WINDOW: W, 1 .. 65535 */
+  uint32_t min_cov;   /* LINE: m1 + u1 and m2 + u2 >= max(1, min_cov) */
+} bsc_asm_params;
+#define BSC_ASM_N_TOTALS 8
+#define BSC_ASM_OVERLAPPED 1u
+#define BSC_ASM_DEEP 2u
+void bsc_asm_params_default(bsc_asm_params *p);
+int bsc_asm_pairs_host(const bsc_template *tpl, uint32_t nr, const uint8_t *seq, uint64_t seq_bytes, uint32_t x, uint32_t y, const uint8_t *ref,
+                       int32_t min_qual, const bsc_vcf_core *core, const uint8_t *emit, const double *lfact_256, const bsc_asm_params *p,
+                       bsc_asm_pair *pairs, uint64_t cap, uint64_t *n_pairs, uint64_t totals[8]);
+long bsc_asm_format(const char *contig, const bsc_asm_pair *pairs, size_t n, const bsc_asm_params *p, char *buf, size_t cap, uint64_t totals2[2]);
+double bsc_asm_fisher_p(const int32_t c[4], const double *lfact_256);
+int bsc_asm_device(bsc_context *ctx, const void *d_tpl, uint32_t nr, const void *d_seq, uint64_t seq_bytes, uint32_t x, uint32_t y, const void *d_ref,
+                   const void *d_core, const void *d_emit, const bsc_asm_params *p, void *d_pairs, uint64_t pairs_cap, void *d_n_pairs,
+                   void *d_totals, void *stream);
+int bsc_asm_text_device(bsc_context *ctx, const void *d_pairs, const void *d_n_pairs, uint64_t max_pairs, const char *contig, const bsc_asm_params *p,
+                        void *d_out, uint64_t out_cap, void *d_totals2, void *stream);
+int bsc_block_asm_kept(bsc_context *ctx, const char *contig, const bsc_asm_params *p, uint64_t dev_cap, uint64_t *n_bytes, uint64_t *n_lines,
+                       uint64_t totals[8]);
+int bsc_asm_stream_read(bsc_context *ctx, uint64_t off, uint64_t n, void *dst);
+int bsc_asm_stream_detach(bsc_context *ctx, void **d_stream, uint64_t *n_bytes);
+
+/*
  * dbSNP index (host C + zlib; csrc/dbsnp.c): the reader of the compressed index bin/dbSNP_idx writes.  In the reference
  * the index never touches the likelihoods: an entry names the record (VCF ID), forces the AA / TT homozygous-reference
  * record of a site flagged in its `fq_mask` to be written (rs_found & 2, src/print_vcf.c:139) and feeds the dbSNP

@@ -102,6 +102,16 @@
  * --meth-reads-min-cov n (default 1): m + u a line needs.  Not gated by the called genotype (a C>T SNP at a reference CpG reads as
  * unmethylated): the join with the --meth-merge table is the filter.  Refused where --meth is: sharded runs, the BAM2BCF_HOST_* paths.
  * Without the switch the program makes the calls it made before the switch existed.
+ *
+ * --meth-asm out.tsv: the allele-specific methylation table (include/bscall_amd.h has the rule) — a line per (heterozygous SNP the block's call
+ * wrote, reference CpG within --meth-asm-window bases of it) that templates of both alleles read: chrom start end snp_pos gt m1 u1 m2 u2 aq dist,
+ * start / end those of the --meth-merge and --meth-reads lines of the same CpG, aq the phred of Fisher's two-sided p of {m1, u1, m2, u2}.  The
+ * lines are ordered by SNP, then by CpG — NOT by start: the windows of neighbouring SNPs overlap — and the file has no index.  Behind every
+ * block bsc_block_asm_kept reads the dense records, the prepared templates, reads and reference codes the block call left in HBM; the table is
+ * detached (bsc_asm_stream_detach) and goes to the output thread as one more job for its own file, through a BGZF writer of its own when the
+ * name ends in .gz, under -O b or --meth-bgzf.  --meth-asm-window n (default 500, 1 .. 65535), --meth-asm-min-qual n (default 20: the QUAL a SNP
+ * needs), --meth-asm-min-cov n (default 2: m1 + u1 and m2 + u2 a line needs), --meth-asm-pass (PASS SNPs only).  Refused where --meth-reads is.
+ * Without the switch the program makes the calls it made before the switch existed.
  */
 #include <pthread.h>
 #include <stdio.h>
@@ -154,7 +164,8 @@ static void *pinned(size_t n) { /* page-locked: the copy-out is a true DMA, queu
  * ONE writer: three of them writing pieces of one file in parallel were 2.5 x slower (0.70 s against 0.28 for the 2.9 GB of a contig-sized
  * block: writes to one inode take turns anyway).  Page-locking a host buffer for a whole stream would cost more than the calling. */
 #define PIECE ((size_t)32 << 20)
-#define N_JOB 4 /* (a block is two jobs with --meth, three with --variants beside it, four with --meth-reads: a push waits for a free slot) */
+#define N_JOB 4 /* (a block is two jobs with --meth, three with --variants beside it, four with --meth-reads, five with --meth-asm: a push waits for a
+                 * free slot) */
 typedef struct {
   void *d;        /* the stream on the device; NULL: only close_fd */
   uint64_t n, at; /* its length, where it goes in the file */
@@ -548,6 +559,14 @@ int main(int argc, char **argv) {
   bsc_cpg_reads_params crpar;
   bsc_cpg_reads_params_default(&crpar);
   int reads_opts = 0;
+  const char *asm_path = NULL; /* --meth-asm out.tsv: the allele-specific methylation table */
+  bsc_asm_params aspar;
+  bsc_asm_params_default(&aspar);
+  int asm_opts = 0;
+  if (argc >= 2 && !strcmp(argv[argc - 1], "--meth-asm") && (argc == 2 || strcmp(argv[argc - 2], "--meth-asm"))) {
+    fprintf(stderr, "%s: --meth-asm takes the path of the allele-specific methylation table to write\n", argv[0]);
+    return 2;
+  }
   if (argc >= 2 && !strcmp(argv[argc - 1], "--meth-reads") && (argc == 2 || strcmp(argv[argc - 2], "--meth-reads"))) {
     fprintf(stderr, "%s: --meth-reads takes the path of the read-level CpG table to write\n", argv[0]);
     return 2;
@@ -584,6 +603,14 @@ int main(int argc, char **argv) {
       argv[k] = argv[0];
       argv += k;
       argc -= k;
+      continue;
+    }
+    if (!strcmp(argv[1], "--meth-asm-pass")) { /* no value */
+      aspar.pass_only = 1;
+      asm_opts = 1;
+      argv[1] = argv[0];
+      argv += 1;
+      argc -= 1;
       continue;
     }
     if (!strcmp(argv[1], "--variants-pass") || !strcmp(argv[1], "--variants-known")) { /* no value */
@@ -642,6 +669,20 @@ int main(int argc, char **argv) {
       if (sites) crpar.min_sites = (uint32_t)v;
       else crpar.min_cov = (uint32_t)v;
       reads_opts = 1;
+    }
+    else if (!strcmp(argv[1], "--meth-asm")) asm_path = argv[2];
+    else if (!strcmp(argv[1], "--meth-asm-window") || !strcmp(argv[1], "--meth-asm-min-qual") || !strcmp(argv[1], "--meth-asm-min-cov")) {
+      char *end = NULL;
+      const unsigned long v = strtoul(argv[2], &end, 10);
+      const int window = argv[1][11] == 'w', qual = argv[1][15] == 'q';
+      if (!argv[2][0] || *end || argv[2][0] == '-' || v > 0xfffffffful || (window && (v < 1 || v > 65535))) {
+        fprintf(stderr, "%s: %s takes a count%s, not '%s'\n", argv[0], argv[1], window ? ", 1 .. 65535" : "", argv[2]);
+        return 2;
+      }
+      if (window) aspar.max_dist = (uint32_t)v;
+      else if (qual) aspar.min_phred = (uint32_t)v;
+      else aspar.min_cov = (uint32_t)v;
+      asm_opts = 1;
     }
     else if (!strcmp(argv[1], "--meth-index")) {
       if (strcmp(argv[2], "tbi") && strcmp(argv[2], "csi")) {
@@ -709,7 +750,7 @@ int main(int argc, char **argv) {
     argc -= 2;
   }
   if (argc < 5 || world < 1 || (rank >= 0 && rank >= world)) {
-    fprintf(stderr, "usage: %s [-O u|b] [--format bcf|vcf] [--index] [-D dbsnp.idx] [--meth out.bed [--meth-bgzf] [--meth-index tbi|csi] [--meth-merge | --meth-all] [--meth-min-cov n] [--meth-min-gq n] [--meth-pass]] [--meth-regions regions.bed | --meth-window n --meth-regions-out out.tsv] [--meth-bigwig out.bw [--meth-bigwig-section n] [--meth-bigwig-zoom n] [--meth-bigwig-compress: zlib sections, n <= 8157]: the methylation level as a bigWig track, per cytosine even with --meth-merge, under the --meth-* thresholds and --meth-all] [--cov-bigwig cov.bw: the depth of the same sites as a bigWig track, under the same --meth-bigwig-* switches] [--meth-bigbed out.bb [--meth-bigbed-items n] [--meth-bigbed-zoom n] [--meth-bigbed-compress: zlib blocks, n <= 652]] [--variants out: the records with an ALT allele, in the run's format and compression, with out.csi under --index [--variants-min-qual n] [--variants-pass] [--variants-known: dbSNP sites only, with -D]] [--meth-reads out.tsv: the read-level CpG concordance table, a line per reference CpG [--meth-reads-min-sites n] [--meth-reads-min-cov n]] [--rank r --world n | --merge n] in.bam ref.fa out.bcf report.json [sample]\n", argv[0]);
+    fprintf(stderr, "usage: %s [-O u|b] [--format bcf|vcf] [--index] [-D dbsnp.idx] [--meth out.bed [--meth-bgzf] [--meth-index tbi|csi] [--meth-merge | --meth-all] [--meth-min-cov n] [--meth-min-gq n] [--meth-pass]] [--meth-regions regions.bed | --meth-window n --meth-regions-out out.tsv] [--meth-bigwig out.bw [--meth-bigwig-section n] [--meth-bigwig-zoom n] [--meth-bigwig-compress: zlib sections, n <= 8157]: the methylation level as a bigWig track, per cytosine even with --meth-merge, under the --meth-* thresholds and --meth-all] [--cov-bigwig cov.bw: the depth of the same sites as a bigWig track, under the same --meth-bigwig-* switches] [--meth-bigbed out.bb [--meth-bigbed-items n] [--meth-bigbed-zoom n] [--meth-bigbed-compress: zlib blocks, n <= 652]] [--variants out: the records with an ALT allele, in the run's format and compression, with out.csi under --index [--variants-min-qual n] [--variants-pass] [--variants-known: dbSNP sites only, with -D]] [--meth-reads out.tsv: the read-level CpG concordance table, a line per reference CpG [--meth-reads-min-sites n] [--meth-reads-min-cov n]] [--meth-asm out.tsv: the allele-specific methylation table, a line per heterozygous SNP and CpG near it [--meth-asm-window n] [--meth-asm-min-qual n] [--meth-asm-min-cov n] [--meth-asm-pass]] [--rank r --world n | --merge n] in.bam ref.fa out.bcf report.json [sample]\n", argv[0]);
     return 2;
   }
   if (text && (rank >= 0 || merge > 0)) {
@@ -768,6 +809,18 @@ int main(int argc, char **argv) {
     fprintf(stderr, "%s: --meth-reads walks the prepared reads the device reader's blocks leave on the device: not with BAM2BCF_HOST_READER / _HOST_BCF / _HOST_PREP\n", argv[0]);
     return 2;
   }
+  if (asm_opts && !asm_path) {
+    fprintf(stderr, "%s: --meth-asm-window / --meth-asm-min-qual / --meth-asm-min-cov / --meth-asm-pass are thresholds of the table --meth-asm writes: they need --meth-asm out.tsv\n", argv[0]);
+    return 2;
+  }
+  if (asm_path && (rank >= 0 || world > 1 || merge > 0)) {
+    fprintf(stderr, "%s: --meth-asm writes a single run's table; a sharded run (--rank / --world / --merge) has none\n", argv[0]);
+    return 2;
+  }
+  if (asm_path && (getenv("BAM2BCF_HOST_PREP") || getenv("BAM2BCF_HOST_BCF") || getenv("BAM2BCF_HOST_READER"))) {
+    fprintf(stderr, "%s: --meth-asm reads the records and the prepared reads the device reader's blocks leave on the device: not with BAM2BCF_HOST_READER / _HOST_BCF / _HOST_PREP\n", argv[0]);
+    return 2;
+  }
   if (variants_opts && !variants_path) {
     fprintf(stderr, "%s: --variants-min-qual / --variants-pass / --variants-known select among the records --variants writes: they need --variants out\n", argv[0]);
     return 2;
@@ -780,7 +833,7 @@ int main(int argc, char **argv) {
     fprintf(stderr, "%s: --variants selects from what the device reader's blocks leave on the device: not with BAM2BCF_HOST_READER / _HOST_BCF / _HOST_PREP\n", argv[0]);
     return 2;
   }
-  if (meth_bgzf && !meth_path && !reads_path) {
+  if (meth_bgzf && !meth_path && !reads_path && !asm_path) {
     fprintf(stderr, "%s: --meth-bgzf compresses the table --meth writes: it needs --meth out.bed.gz (or --meth-reads out.tsv.gz, whose table it compresses too)\n", argv[0]);
     return 2;
   }
@@ -984,6 +1037,20 @@ int main(int argc, char **argv) {
     reads_fd = dup(fileno(rf));
     fclose(rf);
     if (bgzf || meth_bgzf) CHECK(bsc_bgzf_open(ctx, &zr));
+  }
+  int asm_fd = -1; /* --meth-asm: the file, where its next bytes go, its compressor, the sums of the blocks' totals and lines */
+  uint64_t asm_at = 0, asm_lines = 0, asm_tot[BSC_ASM_N_TOTALS] = {0};
+  bsc_bgzf *za = NULL;
+  if (asm_path) {
+    FILE *af = fopen(asm_path, "wb");
+    if (!af) {
+      perror(asm_path);
+      return 1;
+    }
+    asm_fd = dup(fileno(af));
+    fclose(af);
+    const size_t al = strlen(asm_path);
+    if (bgzf || meth_bgzf || (al > 3 && !strcmp(asm_path + al - 3, ".gz"))) CHECK(bsc_bgzf_open(ctx, &za));
   }
   int var_fd = -1; /* --variants: the file, where its next bytes go, its compressor and index, the sums of the blocks' totals */
   uint64_t var_at = 0, var_tot[BSC_VAR_N_TOTALS] = {0};
@@ -1393,6 +1460,32 @@ int main(int argc, char **argv) {
           reads_at += n_r;
         }
       }
+      if (n_bytes && asm_path) { /* the block's allele-specific methylation table, from the dense records and the prepared reads the call left on the
+                                  * device: a buffer and a job of its own */
+        uint64_t a_cap = (uint64_t)n / 4 + 65536, a_bytes = 0, a_lines = 0, at8[BSC_ASM_N_TOTALS];
+        int arc = bsc_block_asm_kept(ctx, REF_NAME(dblk.tid), &aspar, a_cap, &a_bytes, &a_lines, at8);
+        if (arc == BSC_ERR_ARG && a_bytes > a_cap) arc = bsc_block_asm_kept(ctx, REF_NAME(dblk.tid), &aspar, a_bytes, &a_bytes, &a_lines, at8);
+        CHECK(arc);
+        asm_lines += a_lines;
+        for (int k = 0; k < BSC_ASM_N_TOTALS; k++) asm_tot[k] += at8[k];
+        if (a_bytes) {
+          void *d_a = NULL;
+          uint64_t n_a = 0;
+          CHECK(bsc_asm_stream_detach(ctx, &d_a, &n_a));
+          if (za) {
+            CHECK(bsc_bgzf_write_device(za, d_a, n_a));
+            CHECK(bsc_detached_free(ctx, d_a));
+            d_a = NULL;
+            n_a = 0;
+            CHECK(bsc_bgzf_take(za, &d_a, &n_a));
+          }
+          if (n_a) {
+            const out_job j = {d_a, n_a, asm_at, asm_fd, 0};
+            writer_push(&W, j);
+          }
+          asm_at += n_a;
+        }
+      }
       if (n_bytes && variants_path) { /* the block's variant-only stream, selected from the same arrays and encoded by the block's own encoder: a
                                        * buffer and a job of its own */
         uint64_t v_cap = (uint64_t)n / 4 + 65536, v_bytes = 0, v_recs = 0, vt[BSC_VAR_N_TOTALS];
@@ -1579,6 +1672,17 @@ int main(int argc, char **argv) {
     }
     reads_at += n_z;
   }
+  if (za) { /* the allele-specific table's last member and its end-of-file marker */
+    void *d_z = NULL;
+    uint64_t n_z = 0;
+    CHECK(bsc_bgzf_close(za, &d_z, &n_z));
+    za = NULL;
+    if (n_z) {
+      const out_job j = {d_z, n_z, asm_at, asm_fd, 0};
+      writer_push(&W, j);
+    }
+    asm_at += n_z;
+  }
   if (zv) { /* the variant file's last member and its end-of-file marker; its index */
     void *d_z = NULL;
     uint64_t n_z = 0;
@@ -1626,6 +1730,10 @@ int main(int argc, char **argv) {
   }
   if (reads_fd >= 0 && close(reads_fd)) {
     perror(reads_path);
+    return 1;
+  }
+  if (asm_fd >= 0 && close(asm_fd)) {
+    perror(asm_path);
     return 1;
   }
   if (var_fd >= 0 && close(var_fd)) {
@@ -1763,6 +1871,9 @@ int main(int argc, char **argv) {
     if (reads_path)
       printf("%llu CpG sites in the read-level table, %llu lines written (eligible templates %llu, discordant %llu)\n", (unsigned long long)reads_tot[0],
              (unsigned long long)reads_lines, (unsigned long long)reads_tot[5], (unsigned long long)reads_tot[6]);
+    if (asm_path)
+      printf("%llu heterozygous SNPs in the allele-specific methylation table, %llu SNP-CpG pairs, %llu lines written (allele observations %llu)\n",
+             (unsigned long long)asm_tot[0], (unsigned long long)asm_tot[1], (unsigned long long)asm_lines, (unsigned long long)asm_tot[2]);
   }
   if (getenv("BAM2BCF_TIMING")) {
     uint64_t rc4[4] = {0, 0, 0, 0};
