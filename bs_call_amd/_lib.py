@@ -259,6 +259,13 @@ EXPORTS = (
     "bsc_block_asm_kept",
     "bsc_asm_stream_read",
     "bsc_asm_stream_detach",
+    "bsc_mbias_params_default",
+    "bsc_mbias_host",
+    "bsc_mbias_format",
+    "bsc_mbias_device",
+    "bsc_block_mbias_rawdev",
+    "bsc_mbias_read",
+    "bsc_mbias_reset",
 )
 
 
@@ -306,6 +313,15 @@ class AsmParams(C.Structure):
 
     def __init__(self, min_phred=20, pass_only=0, max_dist=500, min_cov=2):
         super().__init__(int(min_phred), int(pass_only), int(max_dist), int(min_cov))
+
+
+class MbiasParams(C.Structure):
+    """bsc_mbias_params; the default is bsc_mbias_params_default's."""
+
+    _fields_ = [("n_cycles", C.c_uint32)]
+
+    def __init__(self, n_cycles=512):
+        super().__init__(int(n_cycles))
 
 
 class BwParams(C.Structure):
@@ -909,6 +925,20 @@ def load():
     L.bsc_asm_stream_read.argtypes = [vp, u64, u64, vp]
     L.bsc_asm_stream_detach.restype = i32
     L.bsc_asm_stream_detach.argtypes = [vp, C.POINTER(vp), C.POINTER(u64)]
+    L.bsc_mbias_params_default.restype = None
+    L.bsc_mbias_params_default.argtypes = [C.POINTER(MbiasParams)]
+    L.bsc_mbias_host.restype = i32
+    L.bsc_mbias_host.argtypes = [vp, u32, vp, u64, vp, u64, u32, u32, vp, i32, C.POINTER(MbiasParams), vp, C.POINTER(u64)]
+    L.bsc_mbias_format.restype = C.c_long
+    L.bsc_mbias_format.argtypes = [vp, C.POINTER(MbiasParams), vp, C.c_size_t]
+    L.bsc_mbias_device.restype = i32
+    L.bsc_mbias_device.argtypes = [vp, vp, u32, vp, u64, vp, u64, u32, u32, vp, C.POINTER(MbiasParams), vp, vp, vp]
+    L.bsc_block_mbias_rawdev.restype = i32
+    L.bsc_block_mbias_rawdev.argtypes = [vp, vp, u32, vp, u64, vp, u64, C.POINTER(MbiasParams), C.POINTER(u64)]
+    L.bsc_mbias_read.restype = i32
+    L.bsc_mbias_read.argtypes = [vp, vp, C.POINTER(u64)]
+    L.bsc_mbias_reset.restype = i32
+    L.bsc_mbias_reset.argtypes = [vp]
     L.bsc_meth_cpg_format_recs.argtypes = [vp, C.c_size_t, C.c_char_p, C.POINTER(MethParams), vp, C.c_size_t, C.POINTER(u64)]
     L.bsc_meth_cpg_block_device.restype = i32
     L.bsc_meth_cpg_block_device.argtypes = [vp, vp, vp, u64, C.c_char_p, C.POINTER(MethParams), vp, u64, vp, vp]

@@ -1329,6 +1329,51 @@ class SiteCaller:
             self.synchronize()
         return out[: int(n)].tobytes()
 
+    # -- the M-bias table (csrc/mbiasdev.hip) -------------------------------------------------------------------------------------------
+    @staticmethod
+    def _mb_params(params):
+        if params is None:
+            return _lib.MbiasParams()
+        if isinstance(params, _lib.MbiasParams):
+            return params
+        if isinstance(params, dict):
+            return _lib.MbiasParams(**params)
+        return _lib.MbiasParams(int(params))
+
+    def mbias_device(self, d_raw, nr, d_seq, seq_bytes, d_misms, n_misms, x, y, d_ref, d_counts, d_totals, params=None, stream=None):
+        """bsc_mbias_device: the raw templates of a block (d_raw, d_seq, d_misms as the device reader leaves them), the block x .. y and d_ref,
+        the codes of x .. y + 2 -> ADDED into d_counts (12 * n_cycles * 2 device u64) and d_totals (eight device u64); asynchronous on
+        `stream`.  params: a _lib.MbiasParams, a dict, n_cycles or None ({512})."""
+        mp = self._mb_params(params)
+        _check(self._L.bsc_mbias_device(self._h, d_raw, nr, d_seq, seq_bytes, d_misms, n_misms, x, y, d_ref, C.byref(mp), d_counts, d_totals, stream))
+
+    def block_mbias_rawdev(self, d_raw, nr, d_seq, seq_bytes, d_misms, n_misms, params=None):
+        """bsc_block_mbias_rawdev: the raw block the last *_keep call called (the SAME device pointers) added into the context's M-bias
+        accumulator.  Returns the accumulator's totals[8] so far."""
+        mp = self._mb_params(params)
+        tot = (C.c_uint64 * 8)()
+        _check(self._L.bsc_block_mbias_rawdev(self._h, d_raw, nr, d_seq, seq_bytes, d_misms, n_misms, C.byref(mp), tot))
+        self._mbias_cycles = int(mp.n_cycles)  # the accumulator's: what mbias_read sizes its array by
+        return tuple(int(v) for v in tot)
+
+    def mbias_read(self, params=None):
+        """bsc_mbias_read: (counts[2][2][3][n_cycles][2] u64, totals[8]) of the context's accumulator, n_cycles that of the block_mbias_rawdev
+        calls that made it.  params (optional): the n_cycles the caller expects — ValueError where the accumulator's differs.  The library
+        copies the accumulator's own size whatever the caller believes, so the copy lands in an array of the largest table and is cut."""
+        made = getattr(self, "_mbias_cycles", None)
+        if params is not None and made is not None and int(self._mb_params(params).n_cycles) != made:
+            raise ValueError("the accumulator has %d cycles, not %d" % (made, int(self._mb_params(params).n_cycles)))
+        room = np.zeros(12 * 1024 * 2, dtype=np.uint64)  # BSC_MBIAS_N_BINS * BSC_MBIAS_MAX_CYCLES * 2
+        tot = (C.c_uint64 * 8)()
+        _check(self._L.bsc_mbias_read(self._h, _ptr(room), tot))
+        n = made if made is not None else int(self._mb_params(params).n_cycles)
+        return room[: 12 * n * 2].reshape(2, 2, 3, n, 2).copy(), tuple(int(v) for v in tot)
+
+    def mbias_reset(self):
+        """bsc_mbias_reset: drops the context's M-bias accumulator."""
+        _check(self._L.bsc_mbias_reset(self._h))
+        self._mbias_cycles = None
+
     def blocks_records(self, blocks, ref, out=None, all_positions=False, reg_start=1, reg_stop=0xFFFFFFFF, dbsnp=None, with_stats=False,
                        submit_only=False):
         """Several blocks in one launch sequence (bsc_blocks_records): blocks = [(templates, seq, x, y), ...] in genome order;
@@ -1839,3 +1884,49 @@ def asm_fisher_p_host(tables, lfact=None):
         raise ValueError("counts must be >= 0 and a table's sum <= 46340")
     lf = np.ascontiguousarray(lfact_table() if lfact is None else lfact, dtype=np.float64)
     return np.array([L.bsc_asm_fisher_p(_ptr(row), _ptr(lf)) for row in c], dtype=np.float64)
+
+
+def mbias_host(raw, seq, misms, x, y, ref, min_qual=20, params=None, counts=None, totals=None):
+    """The host form of the M-bias table (bsc_mbias_host; csrc/mbias.c): RAW_TEMPLATE[nr], their read bytes and MISMS lists, the block x .. y
+    and its reference codes (x .. y + 2) ADDED into counts[2][2][3][n_cycles][2] / totals[8] (made of zeros when None).  No GPU involved.
+    Returns (counts, totals)."""
+    from .abi import MISMS, RAW_TEMPLATE
+
+    L = _lib.load()
+    raw = np.ascontiguousarray(raw, dtype=RAW_TEMPLATE)
+    seq = np.ascontiguousarray(seq, dtype=np.uint8)
+    misms = np.ascontiguousarray(misms, dtype=MISMS)
+    ref = np.ascontiguousarray(ref, dtype=np.uint8)
+    if int(y) >= int(x) and ref.size < int(y) - int(x) + 3:
+        raise ValueError("ref must hold the codes of x .. y + 2")
+    mp = SiteCaller._mb_params(params)
+    if counts is None:
+        counts = np.zeros((2, 2, 3, int(mp.n_cycles) if 1 <= int(mp.n_cycles) <= 1024 else 1, 2), dtype=np.uint64)  # (a refused n_cycles: any table)
+    if totals is None:
+        totals = np.zeros(8, dtype=np.uint64)
+    assert counts.dtype == np.uint64 and counts.flags.c_contiguous and totals.dtype == np.uint64
+    _check(L.bsc_mbias_host(_ptr(raw), len(raw), _ptr(seq), seq.size, _ptr(misms), len(misms), int(x), int(y), _ptr(ref), int(min_qual), C.byref(mp),
+                            _ptr(counts), totals.ctypes.data_as(C.POINTER(C.c_uint64))))
+    return counts, totals
+
+
+def mbias_format_host(counts, cap=None):
+    """bsc_mbias_format: the table's text of counts[2][2][3][n_cycles][2] -> (bytes, length).  cap: the room (default: asked for first); a room
+    too small gives (None, the length needed), with nothing written."""
+    L = _lib.load()
+    counts = np.ascontiguousarray(counts, dtype=np.uint64)
+    mp = _lib.MbiasParams(counts.shape[3])
+    if cap is None:
+        need = L.bsc_mbias_format(_ptr(counts), C.byref(mp), None, 0)
+        if need < 0:
+            _check(int(need))
+        cap = int(need)
+    buf = np.full(max(int(cap), 1) + 8, 0xA5, dtype=np.uint8)
+    got = L.bsc_mbias_format(_ptr(counts), C.byref(mp), _ptr(buf), int(cap))
+    if got < 0:
+        _check(int(got))
+    assert (buf[int(cap) :] == 0xA5).all()
+    if got > int(cap):
+        assert (buf == 0xA5).all()
+        return None, int(got)
+    return buf[:got].tobytes(), int(got)

@@ -141,6 +141,8 @@ int bsc_dev_launch_asm_pairs(const void *tpl, uint32_t nr, const void *seq, uint
 int bsc_dev_launch_asm_text(const void *pairs, const void *n_pairs, uint64_t max_pairs, const char *contig, uint32_t contig_len, uint32_t min_cov,
                             void *tile_bytes, void *tile_off, void *line_len, void *scan_tmp, size_t scan_tmp_bytes, void *out, uint64_t out_cap,
                             void *totals2, int num_cus, void *stream);
+int bsc_dev_launch_mbias(const void *raw, uint32_t nr, const void *seq, uint64_t seq_bytes, const void *misms, uint64_t n_misms, uint32_t x, uint32_t y,
+                         const void *ref, uint32_t min_qual, uint32_t n_cycles, void *counts, void *totals, int num_cus, void *stream); /* mbiasdev.hip */
 int bsc_dev_launch_csi_scan(int format, const void *s, uint64_t n_bytes, const void *sync, uint32_t n_sync, int min_shift, void *cnt, void *off,
                             void *scan_tmp, size_t scan_tmp_bytes, void *entries, uint64_t cap, void *totals, int num_cus, void *stream); /* csidev.hip */
 int bsc_dev_launch_bed_scan(const void *s, uint64_t n_bytes, const void *sync, uint32_t n_sync, int min_shift, void *cnt, void *off, void *scan_tmp,
@@ -346,6 +348,11 @@ struct bsc_context {
         cap_tot, cap_out;
     uint64_t bytes;
   } asm_;
+  struct { /* the M-bias table (mbiasdev.hip): bsc_block_mbias_rawdev's accumulator — 12 * n_cycles * 2 u64 cells and, behind them, the eight
+            * totals — made at the first call, dropped by bsc_mbias_reset; n_cycles == 0: none */
+    void *d_acc;
+    uint32_t n_cycles;
+  } mb;
   struct { /* streams handed to the caller (bsc_bcf_stream_detach) come back here (bsc_detached_free) and are taken again by the next block:
             * no hipMalloc / hipFree — a device-wide wait — in the steady state of a run that writes behind the calling */
     void *p[4];
@@ -774,6 +781,7 @@ int bsc_destroy(bsc_context *ctx) {
   hipFree(ctx->cr.d_sites);
   hipFree(ctx->cr.d_tot);
   hipFree(ctx->cr.d_out);
+  hipFree(ctx->mb.d_acc);
   hipFree(ctx->asm_.d_scnt);
   hipFree(ctx->asm_.d_soff);
   hipFree(ctx->asm_.d_smask);
@@ -5520,6 +5528,91 @@ int bsc_asm_stream_detach(bsc_context *ctx, void **d_stream, uint64_t *n_bytes) 
   ctx->asm_.d_out = NULL;
   ctx->asm_.cap_out = 0;
   ctx->asm_.bytes = 0;
+  return BSC_OK;
+}
+
+/* ---- the M-bias table (mbiasdev.hip): include/bscall_amd.h has the rule, csrc/mbias.c the host form ------------------------------------------------ */
+static int bsc_mb_params_check(const char *who, const bsc_mbias_params *p) {
+  if (!p) return bsc_fail(BSC_ERR_ARG, "%s: NULL argument", who);
+  if (p->n_cycles < 1 || p->n_cycles > BSC_MBIAS_MAX_CYCLES)
+    return bsc_fail(BSC_ERR_ARG, "%s: n_cycles (%u) outside 1 .. %u", who, p->n_cycles, BSC_MBIAS_MAX_CYCLES);
+  return BSC_OK;
+}
+
+int bsc_mbias_device(bsc_context *ctx, const void *d_raw, uint32_t nr, const void *d_seq, uint64_t seq_bytes, const void *d_misms, uint64_t n_misms,
+                     uint32_t x, uint32_t y, const void *d_ref, const bsc_mbias_params *p, void *d_counts, void *d_totals, void *stream) {
+  static const char who[] = "bsc_mbias_device";
+  int rc;
+  if (!ctx || !d_ref || !d_counts || !d_totals || (nr && !d_raw) || (seq_bytes && !d_seq) || (n_misms && !d_misms))
+    return bsc_fail(BSC_ERR_ARG, "%s: NULL argument", who);
+  if ((rc = bsc_mb_params_check(who, p))) return rc;
+  if (y < x) return bsc_fail(BSC_ERR_ARG, "%s: y (%u) < x (%u)", who, y, x);
+  if ((((uintptr_t)d_raw | (uintptr_t)d_counts | (uintptr_t)d_totals) & 7u) || ((uintptr_t)d_misms & 3u))
+    return bsc_fail(BSC_ERR_ARG, "%s: the templates, the table and the totals must be 8-byte, the lists 4-byte aligned", who);
+  BSC_ENTER(ctx);
+  const int32_t mq = ctx->params.min_qual;
+  const int e = bsc_dev_launch_mbias(d_raw, nr, d_seq, seq_bytes, d_misms, n_misms, x, y, d_ref, mq > 0 ? (uint32_t)mq : 0u, p->n_cycles, d_counts, d_totals,
+                                     ctx->num_cus, stream);
+  if (e) return bsc_fail(BSC_ERR_HIP, "%s: launch failed: %s", who, hipGetErrorString((hipError_t)e));
+  return BSC_OK;
+}
+
+int bsc_block_mbias_rawdev(bsc_context *ctx, const void *d_raw, uint32_t nr, const void *d_seq, uint64_t seq_bytes, const void *d_misms,
+                           uint64_t n_misms, const bsc_mbias_params *p, uint64_t totals[8]) {
+  static const char who[] = "bsc_block_mbias_rawdev";
+  int rc;
+  if (!ctx) return bsc_fail(BSC_ERR_ARG, "%s: NULL argument", who);
+  if ((rc = bsc_mb_params_check(who, p))) return rc;
+  if (ctx->meth_src != 1 || ctx->rec_pending || ctx->pending_sz)
+    return bsc_fail(BSC_ERR_ARG, "%s: the last call left no single block's arrays on the device", who);
+  if (!ctx->cr.src_ok) return bsc_fail(BSC_ERR_ARG, "%s: the last block's reference codes are no longer on the device", who);
+  if (ctx->mb.n_cycles && ctx->mb.n_cycles != p->n_cycles)
+    return bsc_fail(BSC_ERR_ARG, "%s: n_cycles is %u, the accumulator's %u (bsc_mbias_reset drops it)", who, p->n_cycles, ctx->mb.n_cycles);
+  BSC_ENTER(ctx);
+  hipStream_t s = ctx->stream;
+  const size_t cells = (size_t)BSC_MBIAS_N_BINS * p->n_cycles * 2u;
+  if (!ctx->mb.n_cycles) {
+    void *acc = NULL;
+    HIP_TRY(hipMalloc(&acc, (cells + BSC_MBIAS_N_TOTALS) * sizeof(unsigned long long)));
+    hipError_t e = hipMemsetAsync(acc, 0, (cells + BSC_MBIAS_N_TOTALS) * sizeof(unsigned long long), s);
+    if (e != hipSuccess) {
+      hipFree(acc);
+      return bsc_fail(BSC_ERR_HIP, "%s: hipMemsetAsync failed: %s", who, hipGetErrorString(e));
+    }
+    ctx->mb.d_acc = acc;
+    ctx->mb.n_cycles = p->n_cycles;
+  }
+  unsigned long long *const d_tot = (unsigned long long *)ctx->mb.d_acc + cells;
+  if ((rc = bsc_mbias_device(ctx, d_raw, nr, d_seq, seq_bytes, d_misms, n_misms, ctx->cr.src_x, ctx->cr.src_y, ctx->d_ref, p, ctx->mb.d_acc, d_tot, (void *)s)))
+    return rc;
+  unsigned long long tot[BSC_MBIAS_N_TOTALS] = {0};
+  if (totals) HIP_TRY(hipMemcpyAsync(tot, d_tot, sizeof tot, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s)); /* the reader's next block overwrites the raw arrays */
+  for (int k = 0; totals && k < BSC_MBIAS_N_TOTALS; k++) totals[k] = tot[k];
+  return BSC_OK;
+}
+
+int bsc_mbias_read(bsc_context *ctx, uint64_t *counts_host, uint64_t totals[8]) {
+  if (!ctx) return bsc_fail(BSC_ERR_ARG, "bsc_mbias_read: NULL argument");
+  if (!ctx->mb.n_cycles) return bsc_fail(BSC_ERR_ARG, "bsc_mbias_read: the context has no M-bias accumulator");
+  BSC_ENTER(ctx);
+  const size_t cells = (size_t)BSC_MBIAS_N_BINS * ctx->mb.n_cycles * 2u;
+  if (counts_host) HIP_TRY(hipMemcpyAsync(counts_host, ctx->mb.d_acc, cells * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
+  if (totals)
+    HIP_TRY(hipMemcpyAsync(totals, (const unsigned long long *)ctx->mb.d_acc + cells, BSC_MBIAS_N_TOTALS * sizeof(unsigned long long), hipMemcpyDeviceToHost,
+                           ctx->stream));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  return BSC_OK;
+}
+
+int bsc_mbias_reset(bsc_context *ctx) {
+  if (!ctx) return bsc_fail(BSC_ERR_ARG, "bsc_mbias_reset: NULL argument");
+  if (!ctx->mb.n_cycles) return BSC_OK;
+  BSC_ENTER(ctx);
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  hipFree(ctx->mb.d_acc);
+  ctx->mb.d_acc = NULL;
+  ctx->mb.n_cycles = 0;
   return BSC_OK;
 }
 

@@ -23,7 +23,7 @@ def run(bam_path: str, reference: Dict[str, np.ndarray], bcf_path: str, sample: 
         bigwig_section: int = 1024, bigwig_zoom: int = 1024, bigwig_compress: bool = False, bigbed_path: Optional[str] = None, bigbed_items: int = 512,
         bigbed_zoom: int = 1024, bigbed_compress: bool = False, meth_index: Optional[str] = None, variants_path: Optional[str] = None,
         variants_params=None, cpg_reads_path: Optional[str] = None, cpg_reads_params=None, asm_path: Optional[str] = None, asm_params=None,
-        **reader_kw) -> dict:
+        mbias_path: Optional[str] = None, mbias_params=None, **reader_kw) -> dict:
     """reference: contig name -> uint8 reference codes (0 = N, 1..4 = ACGT; position 1 first).  Returns a summary dict.
     under_conv / over_conv / min_qual (defaults 0.01 / 0.05 / 20, src/init_param.c:26-31) are the MODEL's parameters: without
     `caller` the run builds its SiteCaller from them; with one, they are taken from it and a differing explicit value is an error
@@ -90,7 +90,20 @@ def run(bam_path: str, reference: Dict[str, np.ndarray], bcf_path: str, sample: 
     heterozygous SNP the block's call wrote and each reference CpG within max_dist of it, the templates of allele 1 / allele 2 that read the
     CpG methylated / unmethylated and the phred of Fisher's p of that table (SiteCaller.block_asm_kept, csrc/asmdev.hip) — lines ordered by
     SNP, plain text or BGZF as `compressed` says.  asm_params: a _lib.AsmParams or a dict of min_phred / pass_only / max_dist / min_cov.  The
-    summary gets "asm_lines" and "asm_totals" (the eight totals of the rule).  The same conditions as meth_path."""
+    summary gets "asm_lines" and "asm_totals" (the eight totals of the rule).  The same conditions as meth_path.
+    mbias_path: the M-bias table of the same run (include/bscall_amd.h has the rule): methylated / unmethylated calls per sequencing cycle by
+    read end, bisulfite strand and CpG / CHG / CHH, from the raw templates as sequenced — behind every block the walk over the raw arrays the
+    device reader left in HBM (SiteCaller.block_mbias_rawdev, csrc/mbiasdev.hip) into the context's accumulator, which the run resets before
+    and after; ONE table per run, plain text whatever `compressed` says.  mbias_params: a _lib.MbiasParams, a dict of n_cycles, or n_cycles
+    (default 512, 1 .. 1024).  The summary gets "mbias_totals" (the eight totals of the rule).  The same conditions as meth_path."""
+    if mbias_params is not None and mbias_path is None:
+        raise ValueError("mbias_params size the table mbias_path names: they need mbias_path")
+    if mbias_path is not None and (shard_rank is not None or not device_reader or host_prep or host_bcf):
+        raise ValueError("mbias_path is a single run on the device reader (device_reader=True, no shard_rank, no host_prep / host_bcf)")
+    if mbias_path is not None:
+        from . import mbias as _mbias
+
+        mbias_cycles = _mbias.n_cycles_of(mbias_params)
     if asm_params is not None and asm_path is None:
         raise ValueError("asm_params are thresholds of the table asm_path names: they need asm_path")
     if asm_path is not None and (shard_rank is not None or not device_reader or host_prep or host_bcf):
@@ -190,6 +203,9 @@ def run(bam_path: str, reference: Dict[str, np.ndarray], bcf_path: str, sample: 
         var_blobs, var_totals = [], np.zeros(10, dtype=np.uint64)
         reads_blobs, reads_lines, reads_totals = [], 0, np.zeros(8, dtype=np.uint64)
         asm_blobs, asm_lines, asm_totals = [], 0, np.zeros(8, dtype=np.uint64)
+        mbias_any = False
+        if mbias_path is not None:
+            c.mbias_reset()
         meth_entries = []  # meth_index: (contig number, BED_ENTRY[], bytes of the block's table)
         bw_sites = cov_sites = 0
         region_out, region_cur = [], None  # the summary's lines, contig by contig; (name, regions, names) of the contig attached
@@ -247,7 +263,7 @@ def run(bam_path: str, reference: Dict[str, np.ndarray], bcf_path: str, sample: 
                 region_cur = None
 
             def block_blobs():
-                nonlocal n_blocks, n_records, base_filter, passed, meth_lines, region_cur, bw_sites, cov_sites, bb_sites, var_totals, reads_lines, reads_totals, asm_lines, asm_totals
+                nonlocal n_blocks, n_records, base_filter, passed, meth_lines, region_cur, bw_sites, cov_sites, bb_sites, var_totals, reads_lines, reads_totals, asm_lines, asm_totals, mbias_any
                 before, cur_tid = c.site_totals(), -1
                 for item in (rd.device_blocks() if device_reader else rd.blocks()):
                     if device_reader:
@@ -296,7 +312,10 @@ def run(bam_path: str, reference: Dict[str, np.ndarray], bcf_path: str, sample: 
                             blob, n_rec, st = c.block_bcf_rawdev(dblk, ref, tid, names=names, left_trim=left_trim, right_trim=right_trim, min_qual=min_qual,
                                                                  reg_stop=len(codes), dbsnp=flags, with_stats=True, profile=prof,
                                                                  keep=meth_path is not None or want_regions or want_bw or want_cov or want_bb or variants_path is not None
-                                                                 or cpg_reads_path is not None or asm_path is not None)
+                                                                 or cpg_reads_path is not None or asm_path is not None or mbias_path is not None)
+                        if mbias_path is not None:  # the block's raw templates, still in the reader's buffers, into the run's accumulator
+                            c.block_mbias_rawdev(dblk.d_tpl, dblk.nr, dblk.d_seq, dblk.seq_bytes, dblk.d_misms, dblk.n_misms, mbias_cycles)
+                            mbias_any = True
                         if region_cur is not None:  # the block's cytosines into the attached regions' sums
                             c.block_meth_regions_kept(meth_params)
                         if want_cov:  # the coverage track, and the level track with it, from ONE sweep over the block's arrays
@@ -410,6 +429,11 @@ def run(bam_path: str, reference: Dict[str, np.ndarray], bcf_path: str, sample: 
                 vcf.write_vcf_blobs(cpg_reads_path, "", reads_blobs, compressed)
             if asm_path is not None:
                 vcf.write_vcf_blobs(asm_path, "", asm_blobs, compressed)
+            if mbias_path is not None:  # a run without a block has no accumulator: the header alone
+                mbias_counts, mbias_totals = c.mbias_read(mbias_cycles) if mbias_any else (_mbias.empty(mbias_cycles)[0], (0,) * 8)
+                c.mbias_reset()
+                with open(mbias_path, "wb") as f:
+                    f.write(_mbias.format_table(mbias_counts))
             if want_bw:
                 bw_writer.finish()
             if want_cov:
@@ -495,6 +519,8 @@ def run(bam_path: str, reference: Dict[str, np.ndarray], bcf_path: str, sample: 
         if asm_path is not None:
             summary["asm_lines"] = asm_lines
             summary["asm_totals"] = tuple(int(v) for v in asm_totals)
+        if mbias_path is not None:
+            summary["mbias_totals"] = tuple(int(v) for v in mbias_totals)
         if want_bw:
             summary["bigwig_sites"] = bw_sites
         if want_cov:

@@ -1919,6 +1919,94 @@ int bsc_asm_stream_read(bsc_context *ctx, uint64_t off, uint64_t n, void *dst);
 int bsc_asm_stream_detach(bsc_context *ctx, void **d_stream, uint64_t *n_bytes);
 
 /*
+ * The M-bias table (csrc/mbiasdev.hip: one walk over the RAW templates; csrc/mbias.c holds the host form, which is its checker;
+ * bs_call_amd/mbias.py the Python rule): methylated and unmethylated calls per sequencing cycle, split by read 1 / read 2, by bisulfite
+ * strand and by CpG / CHG / CHH — the curve from which the fixed trims (bsc_prep_params.left_trim / right_trim) and the under-conversion
+ * rate (the CHH level) are chosen.  It is the one output made from the templates as the reader leaves them, before the pre-processing.
+ * The reference has no such output: the rule is this project's own.
+ *
+ * Inputs    raw[nr] (bsc_raw_template), their read bytes seq (seq_bytes; a byte is base | qual << 2, base 0..3 = ACGT) and their mismatch
+ *           lists misms[n_misms] (bsc_misms); the block x .. y; ref = the reference codes (0 N, 1..4 ACGT) of positions x .. y + 2, as
+ *           bsc_block_*_rawdev take them; min_qual of the context's bsc_params; bsc_mbias_params {n_cycles}, default {512}, values outside
+ *           1 .. BSC_MBIAS_MAX_CYCLES (1024) refused with BSC_ERR_ARG.  bsc_prep_params is NOT an input: the table shows the reads as
+ *           sequenced, so that the trims can be chosen from it.
+ * READ      Read k of template t is walked iff len[k] > 0, off[k] + len[k] <= seq_bytes, misms_off[k] + n_misms[k] <= n_misms (both sums
+ *           in 64 bits, without wrapping), bs_strand is 1 or 2, orientation <= 1 and its list is not malformed (G below).  Otherwise it is
+ *           skipped and counted in totals[6] — except that a read of a template with bs_strand == 0, and a read with len[k] == 0, are
+ *           skipped without being counted anywhere.
+ * END       e = k ^ orientation: 0 = read 1, 1 = read 2 (the mapping csrc/prep.c uses for the fixed trims: read[0] is R1 on a FORWARD
+ *           template).
+ * CYCLE     Read[0] is the forward-aligned read; read[1] is stored in reference orientation, as BAM stores it.  Byte j has the 0-based
+ *           cycle c = j for k == 0 and c = len[k] - 1 - j for k == 1.  Soft-clipped bytes keep their cycles.  Hard-clipped bases are not
+ *           in seq: they are ignored, and the cycles of a hard-clipped read start behind them.
+ * G(j)      The genome position of byte j, from the list, in the convention of csrc/prep.c (its naming: CIGAR D -> BSC_MISMS_INS, CIGAR I
+ *           -> BSC_MISMS_DEL; `position` is an offset in the read as stored, soft clip included).  pos[k] is the position of the first
+ *           byte that is not soft-clipped.  The entries z = 0 .. n_misms[k] - 1 are walked in order with a read cursor that starts at 0:
+ *             BSC_MISMS_MISMS   ignored altogether.
+ *             SOFT, DEL         take the `size` bytes position .. position + size - 1 out of the mapping: they have no G.  The cursor becomes
+ *                               position + size.
+ *             INS               adds `size` to the genome offset of every byte at or behind `position`.  The cursor becomes position.
+ *           The list is malformed if an entry's position is below the cursor; if a DEL or SOFT entry has position + size > len[k]; if a
+ *           SOFT entry is neither entry 0 nor entry n_misms[k] - 1; or if an entry's type is none of the four.  A malformed list skips
+ *           the whole read (totals[6]).  For a byte j that is not taken out,
+ *             G(j) = pos[k] + (bytes i < j that are not taken out) + (the sizes of the INS entries with position <= j), in 64 bits.
+ *           A byte with G < x or G > y has no G.  The device never indexes outside seq, misms or ref, whatever the list holds.
+ * COUNTS    A byte counts iff min_qual <= byte >> 2 < 63: the pile-up's rule, the same as the read-level CpG table's.
+ * CONTEXT   r(p) = the reference code of p, and N for p outside x .. y + 2.  For a counting byte with a G:
+ *           bs_strand == 1 (C2T): a bin exists iff r(G) == C.  With n1 = r(G + 1), n2 = r(G + 2): CpG iff n1 == G; CHG iff n1 is A, C or T
+ *           and n2 == G; CHH iff n1 and n2 are each A, C or T; an N that is needed gives no bin.  State: base C -> meth, base T -> unmeth,
+ *           anything else -> none.
+ *           bs_strand == 2 (G2A): a bin exists iff r(G) == G.  With p1 = r(G - 1), p2 = r(G - 2): CpG iff p1 == C; CHG iff p1 is A, G or T
+ *           and p2 == C; CHH iff p1 and p2 are each A, G or T.  State: base G -> meth, base A -> unmeth.
+ *           The table depends on the block cut only through r() being N outside the block.
+ * TABLE     counts[e][s][ctx][c][state], u64: s = bs_strand - 1, ctx 0 CpG / 1 CHG / 2 CHH, c < n_cycles, state 0 meth / 1 unmeth —
+ *           BSC_MBIAS_N_BINS (12) x n_cycles x 2 cells.  A counting byte with a bin and a state and c >= n_cycles goes to totals[3] and to
+ *           no cell.  Mate overlap is NOT removed: both mates count where they overlap.
+ * TOTALS    Eight u64: [0] reads walked, [1] bytes with a G, [2] bytes added to a cell, [3] overflow (above), [4] sum of meth over the CpG
+ *           cells, [5] sum of unmeth over the CpG cells, [6] reads skipped, [7] 0.
+ * LINE      The first line is "#read\tstrand\tcontext\tcycle\tmeth\tunmeth\n".  Then for e in 0, 1, s in 0, 1, ctx in 0, 1, 2 the cycles
+ *           0 .. L(e), L(e) = the highest cycle at which any cell of end e is non-zero; an end with no count writes no line.  Columns: 1|2,
+ *           C2T|G2A, CpG|CHG|CHH, cycle + 1, and the two counts as plain decimals, tab separated, '\n'.  Lines inside the range with two
+ *           zeros are written (the reader plots them).  No float is written anywhere.
+ *
+ *   bsc_mbias_params_default   {512}
+ *   bsc_mbias_host             the host form, a plain loop: ADDS into counts[12 * n_cycles * 2] and totals[8] (neither is zeroed here, as
+ *                              bsc_meth_regions_sum_recs adds; totals may be NULL)
+ *   bsc_mbias_format           the table's text -> buf.  Returns the length; the length needed, with nothing written, when cap is too small;
+ *                              < 0 for a bad argument
+ *   bsc_mbias_device           the same walk over device-resident inputs (d_raw 8-byte, d_misms 4-byte aligned; d_ref y - x + 3 codes): ADDS
+ *                              into the caller's device table d_counts (12 * n_cycles * 2 u64) and d_totals (eight u64), both 8-byte aligned.
+ *                              Integer atomic adds alone: the bytes are a function of the input.  Asynchronous on `stream`; no workspace.  A
+ *                              refusal writes nothing.
+ *   bsc_block_mbias_rawdev     the follow-up of bsc_block_bcf_rawdev_keep / bsc_block_vcf_rawdev_keep on the SAME raw pointers, called before
+ *                              the reader's next block: x, y and the reference codes are those the block call left in HBM, and the
+ *                              refusals are bsc_block_cpg_reads_kept's when they are gone.  Adds into an accumulator of the context's own,
+ *                              made at the first call; a different n_cycles before bsc_mbias_reset is BSC_ERR_ARG.  totals (may be NULL):
+ *                              the accumulator's totals so far.  Everything else the context keeps is untouched, before or after.  Waits.
+ *   bsc_mbias_read             the accumulator -> counts_host[12 * n_cycles * 2] (may be NULL) and totals[8] (may be NULL), n_cycles that of
+ *                              the calls that made it.  BSC_ERR_ARG, with nothing written, while there is none.  Waits.
+ *   bsc_mbias_reset            drops the accumulator
+ * NOT built: suggested trim bounds, a plot, the table in the JSON report (whose layout follows the reference), sharded runs, removal of the
+ * mate overlap, a tabix index.
+ */
+typedef struct {
+  uint32_t n_cycles; /* 1 .. BSC_MBIAS_MAX_CYCLES */
+} bsc_mbias_params;
+#define BSC_MBIAS_MAX_CYCLES 1024u
+#define BSC_MBIAS_N_BINS 12u
+#define BSC_MBIAS_N_TOTALS 8
+void bsc_mbias_params_default(bsc_mbias_params *p);
+int bsc_mbias_host(const bsc_raw_template *raw, uint32_t nr, const uint8_t *seq, uint64_t seq_bytes, const bsc_misms *misms, uint64_t n_misms,
+                   uint32_t x, uint32_t y, const uint8_t *ref, int32_t min_qual, const bsc_mbias_params *p, uint64_t *counts, uint64_t totals[8]);
+long bsc_mbias_format(const uint64_t *counts, const bsc_mbias_params *p, char *buf, size_t cap);
+int bsc_mbias_device(bsc_context *ctx, const void *d_raw, uint32_t nr, const void *d_seq, uint64_t seq_bytes, const void *d_misms, uint64_t n_misms,
+                     uint32_t x, uint32_t y, const void *d_ref, const bsc_mbias_params *p, void *d_counts, void *d_totals, void *stream);
+int bsc_block_mbias_rawdev(bsc_context *ctx, const void *d_raw, uint32_t nr, const void *d_seq, uint64_t seq_bytes, const void *d_misms,
+                           uint64_t n_misms, const bsc_mbias_params *p, uint64_t totals[8]);
+int bsc_mbias_read(bsc_context *ctx, uint64_t *counts_host, uint64_t totals[8]);
+int bsc_mbias_reset(bsc_context *ctx);
+
+/*
  * dbSNP index (host C + zlib; csrc/dbsnp.c): the reader of the compressed index bin/dbSNP_idx writes.  In the reference
  * the index never touches the likelihoods: an entry names the record (VCF ID), forces the AA / TT homozygous-reference
  * record of a site flagged in its `fq_mask` to be written (rs_found & 2, src/print_vcf.c:139) and feeds the dbSNP

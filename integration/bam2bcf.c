@@ -112,6 +112,15 @@
  * name ends in .gz, under -O b or --meth-bgzf.  --meth-asm-window n (default 500, 1 .. 65535), --meth-asm-min-qual n (default 20: the QUAL a SNP
  * needs), --meth-asm-min-cov n (default 2: m1 + u1 and m2 + u2 a line needs), --meth-asm-pass (PASS SNPs only).  Refused where --meth-reads is.
  * Without the switch the program makes the calls it made before the switch existed.
+ *
+ * --mbias out.tsv: the M-bias table (include/bscall_amd.h has the rule) — methylated and unmethylated calls per sequencing cycle, by read 1 /
+ * read 2, bisulfite strand and CpG / CHG / CHH, from the RAW templates as sequenced (no trim, clip or overlap edit): what -L / -R and the
+ * under-conversion rate are chosen from.  Behind every block bsc_block_mbias_rawdev walks the block's raw arrays, still in the reader's
+ * buffers, into one accumulator of the context's; ONE table per run, over every block of every contig, is read (bsc_mbias_read), formatted
+ * (bsc_mbias_format) and written at the end, and one more line with its totals goes to stdout.  --mbias-cycles n (default 512, 1 .. 1024):
+ * the cycles the table holds; calls beyond them are counted in the line on stdout.  Plain text whatever -O says.  Refused where
+ * --meth-regions is: sharded runs, the BAM2BCF_HOST_* paths.  Without the switch the program makes the calls it made before the switch
+ * existed.
  */
 #include <pthread.h>
 #include <stdio.h>
@@ -563,6 +572,14 @@ int main(int argc, char **argv) {
   bsc_asm_params aspar;
   bsc_asm_params_default(&aspar);
   int asm_opts = 0;
+  const char *mbias_path = NULL; /* --mbias out.tsv: the M-bias table */
+  bsc_mbias_params mbpar;
+  bsc_mbias_params_default(&mbpar);
+  int mbias_opts = 0;
+  if (argc >= 2 && !strcmp(argv[argc - 1], "--mbias") && (argc == 2 || strcmp(argv[argc - 2], "--mbias"))) {
+    fprintf(stderr, "%s: --mbias takes the path of the M-bias table to write\n", argv[0]);
+    return 2;
+  }
   if (argc >= 2 && !strcmp(argv[argc - 1], "--meth-asm") && (argc == 2 || strcmp(argv[argc - 2], "--meth-asm"))) {
     fprintf(stderr, "%s: --meth-asm takes the path of the allele-specific methylation table to write\n", argv[0]);
     return 2;
@@ -671,6 +688,17 @@ int main(int argc, char **argv) {
       reads_opts = 1;
     }
     else if (!strcmp(argv[1], "--meth-asm")) asm_path = argv[2];
+    else if (!strcmp(argv[1], "--mbias")) mbias_path = argv[2];
+    else if (!strcmp(argv[1], "--mbias-cycles")) {
+      char *end = NULL;
+      const unsigned long v = strtoul(argv[2], &end, 10);
+      if (!argv[2][0] || *end || argv[2][0] == '-' || v < 1 || v > BSC_MBIAS_MAX_CYCLES) {
+        fprintf(stderr, "%s: --mbias-cycles takes a count, 1 .. %u, not '%s'\n", argv[0], BSC_MBIAS_MAX_CYCLES, argv[2]);
+        return 2;
+      }
+      mbpar.n_cycles = (uint32_t)v;
+      mbias_opts = 1;
+    }
     else if (!strcmp(argv[1], "--meth-asm-window") || !strcmp(argv[1], "--meth-asm-min-qual") || !strcmp(argv[1], "--meth-asm-min-cov")) {
       char *end = NULL;
       const unsigned long v = strtoul(argv[2], &end, 10);
@@ -750,7 +778,7 @@ int main(int argc, char **argv) {
     argc -= 2;
   }
   if (argc < 5 || world < 1 || (rank >= 0 && rank >= world)) {
-    fprintf(stderr, "usage: %s [-O u|b] [--format bcf|vcf] [--index] [-D dbsnp.idx] [--meth out.bed [--meth-bgzf] [--meth-index tbi|csi] [--meth-merge | --meth-all] [--meth-min-cov n] [--meth-min-gq n] [--meth-pass]] [--meth-regions regions.bed | --meth-window n --meth-regions-out out.tsv] [--meth-bigwig out.bw [--meth-bigwig-section n] [--meth-bigwig-zoom n] [--meth-bigwig-compress: zlib sections, n <= 8157]: the methylation level as a bigWig track, per cytosine even with --meth-merge, under the --meth-* thresholds and --meth-all] [--cov-bigwig cov.bw: the depth of the same sites as a bigWig track, under the same --meth-bigwig-* switches] [--meth-bigbed out.bb [--meth-bigbed-items n] [--meth-bigbed-zoom n] [--meth-bigbed-compress: zlib blocks, n <= 652]] [--variants out: the records with an ALT allele, in the run's format and compression, with out.csi under --index [--variants-min-qual n] [--variants-pass] [--variants-known: dbSNP sites only, with -D]] [--meth-reads out.tsv: the read-level CpG concordance table, a line per reference CpG [--meth-reads-min-sites n] [--meth-reads-min-cov n]] [--meth-asm out.tsv: the allele-specific methylation table, a line per heterozygous SNP and CpG near it [--meth-asm-window n] [--meth-asm-min-qual n] [--meth-asm-min-cov n] [--meth-asm-pass]] [--rank r --world n | --merge n] in.bam ref.fa out.bcf report.json [sample]\n", argv[0]);
+    fprintf(stderr, "usage: %s [-O u|b] [--format bcf|vcf] [--index] [-D dbsnp.idx] [--meth out.bed [--meth-bgzf] [--meth-index tbi|csi] [--meth-merge | --meth-all] [--meth-min-cov n] [--meth-min-gq n] [--meth-pass]] [--meth-regions regions.bed | --meth-window n --meth-regions-out out.tsv] [--meth-bigwig out.bw [--meth-bigwig-section n] [--meth-bigwig-zoom n] [--meth-bigwig-compress: zlib sections, n <= 8157]: the methylation level as a bigWig track, per cytosine even with --meth-merge, under the --meth-* thresholds and --meth-all] [--cov-bigwig cov.bw: the depth of the same sites as a bigWig track, under the same --meth-bigwig-* switches] [--meth-bigbed out.bb [--meth-bigbed-items n] [--meth-bigbed-zoom n] [--meth-bigbed-compress: zlib blocks, n <= 652]] [--variants out: the records with an ALT allele, in the run's format and compression, with out.csi under --index [--variants-min-qual n] [--variants-pass] [--variants-known: dbSNP sites only, with -D]] [--meth-reads out.tsv: the read-level CpG concordance table, a line per reference CpG [--meth-reads-min-sites n] [--meth-reads-min-cov n]] [--mbias out.tsv: methylation by read cycle, from the reads as sequenced [--mbias-cycles n]] [--meth-asm out.tsv: the allele-specific methylation table, a line per heterozygous SNP and CpG near it [--meth-asm-window n] [--meth-asm-min-qual n] [--meth-asm-min-cov n] [--meth-asm-pass]] [--rank r --world n | --merge n] in.bam ref.fa out.bcf report.json [sample]\n", argv[0]);
     return 2;
   }
   if (text && (rank >= 0 || merge > 0)) {
@@ -807,6 +835,18 @@ int main(int argc, char **argv) {
   }
   if (reads_path && (getenv("BAM2BCF_HOST_PREP") || getenv("BAM2BCF_HOST_BCF") || getenv("BAM2BCF_HOST_READER"))) {
     fprintf(stderr, "%s: --meth-reads walks the prepared reads the device reader's blocks leave on the device: not with BAM2BCF_HOST_READER / _HOST_BCF / _HOST_PREP\n", argv[0]);
+    return 2;
+  }
+  if (mbias_opts && !mbias_path) {
+    fprintf(stderr, "%s: --mbias-cycles sizes the table --mbias writes: it needs --mbias out.tsv\n", argv[0]);
+    return 2;
+  }
+  if (mbias_path && (rank >= 0 || world > 1 || merge > 0)) {
+    fprintf(stderr, "%s: --mbias writes a single run's table; a sharded run (--rank / --world / --merge) has none\n", argv[0]);
+    return 2;
+  }
+  if (mbias_path && (getenv("BAM2BCF_HOST_PREP") || getenv("BAM2BCF_HOST_BCF") || getenv("BAM2BCF_HOST_READER"))) {
+    fprintf(stderr, "%s: --mbias walks the raw blocks the device reader leaves on the device: not with BAM2BCF_HOST_READER / _HOST_BCF / _HOST_PREP\n", argv[0]);
     return 2;
   }
   if (asm_opts && !asm_path) {
@@ -1041,6 +1081,13 @@ int main(int argc, char **argv) {
   int asm_fd = -1; /* --meth-asm: the file, where its next bytes go, its compressor, the sums of the blocks' totals and lines */
   uint64_t asm_at = 0, asm_lines = 0, asm_tot[BSC_ASM_N_TOTALS] = {0};
   bsc_bgzf *za = NULL;
+  FILE *mbias_f = NULL; /* --mbias: opened now, so that a path that cannot be written stops the run before it starts; written at the end */
+  uint64_t mbias_tot[BSC_MBIAS_N_TOTALS] = {0};
+  int mbias_any = 0;
+  if (mbias_path && !(mbias_f = fopen(mbias_path, "wb"))) {
+    perror(mbias_path);
+    return 1;
+  }
   if (asm_path) {
     FILE *af = fopen(asm_path, "wb");
     if (!af) {
@@ -1310,6 +1357,10 @@ int main(int argc, char **argv) {
         rc = bsc_block_bcf_again(ctx, NULL, dev_cap, &n_bytes, &n_out);
       }
       CHECK(rc);
+      if (mbias_path) { /* the block's raw templates, still in the reader's buffers, into the run's M-bias accumulator */
+        CHECK(bsc_block_mbias_rawdev(ctx, dblk.d_tpl, dblk.nr, dblk.d_seq, dblk.seq_bytes, dblk.d_misms, dblk.n_misms, &mbpar, mbias_tot));
+        mbias_any = 1;
+      }
       t_gpu += (t1 = now()) - t0;
       t0 = t1;
       if (n_bytes && csi) { /* the index's entries of this block, while the encoder's tile offsets are still the stream's: noted at the writer's
@@ -1728,6 +1779,25 @@ int main(int argc, char **argv) {
     perror(meth_path);
     return 1;
   }
+  if (mbias_f) { /* the run's one M-bias table: the accumulator of every block, read, formatted and written here */
+    const size_t cells = (size_t)BSC_MBIAS_N_BINS * mbpar.n_cycles * 2u;
+    uint64_t *mb_counts = calloc(cells, sizeof *mb_counts);
+    if (!mb_counts) {
+      fprintf(stderr, "%s: out of memory\n", argv[0]);
+      return 1;
+    }
+    if (mbias_any) CHECK(bsc_mbias_read(ctx, mb_counts, mbias_tot)); /* (a run without a block has no accumulator: the header alone) */
+    const long mb_need = bsc_mbias_format(mb_counts, &mbpar, NULL, 0);
+    char *mb_text = mb_need > 0 ? malloc((size_t)mb_need) : NULL;
+    if (!mb_text || bsc_mbias_format(mb_counts, &mbpar, mb_text, (size_t)mb_need) != mb_need ||
+        fwrite(mb_text, 1, (size_t)mb_need, mbias_f) != (size_t)mb_need || fclose(mbias_f)) {
+      perror(mbias_path);
+      return 1;
+    }
+    mbias_f = NULL;
+    free(mb_text);
+    free(mb_counts);
+  }
   if (reads_fd >= 0 && close(reads_fd)) {
     perror(reads_path);
     return 1;
@@ -1874,6 +1944,10 @@ int main(int argc, char **argv) {
     if (asm_path)
       printf("%llu heterozygous SNPs in the allele-specific methylation table, %llu SNP-CpG pairs, %llu lines written (allele observations %llu)\n",
              (unsigned long long)asm_tot[0], (unsigned long long)asm_tot[1], (unsigned long long)asm_lines, (unsigned long long)asm_tot[2]);
+    if (mbias_path)
+      printf("M-bias table: %llu reads walked, %llu bytes mapped, %llu counted, %llu beyond the table, CpG %llu meth %llu unmeth, %llu reads skipped\n",
+             (unsigned long long)mbias_tot[0], (unsigned long long)mbias_tot[1], (unsigned long long)mbias_tot[2], (unsigned long long)mbias_tot[3],
+             (unsigned long long)mbias_tot[4], (unsigned long long)mbias_tot[5], (unsigned long long)mbias_tot[6]);
   }
   if (getenv("BAM2BCF_TIMING")) {
     uint64_t rc4[4] = {0, 0, 0, 0};
