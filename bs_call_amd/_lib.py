@@ -250,6 +250,14 @@ EXPORTS = (
     "bsc_block_cpg_reads_kept",
     "bsc_cpg_reads_stream_read",
     "bsc_cpg_reads_stream_detach",
+    "bsc_epi_params_default",
+    "bsc_epi_windows_host",
+    "bsc_epi_format",
+    "bsc_epi_device",
+    "bsc_epi_text_device",
+    "bsc_block_epi_kept",
+    "bsc_epi_stream_read",
+    "bsc_epi_stream_detach",
     "bsc_asm_params_default",
     "bsc_asm_pairs_host",
     "bsc_asm_format",
@@ -322,6 +330,15 @@ class MbiasParams(C.Structure):
 
     def __init__(self, n_cycles=512):
         super().__init__(int(n_cycles))
+
+
+class EpiParams(C.Structure):
+    """bsc_epi_params; the defaults are bsc_epi_params_default's."""
+
+    _fields_ = [("min_cov", C.c_uint32), ("reserved", C.c_uint32)]
+
+    def __init__(self, min_cov=10, reserved=0):
+        super().__init__(int(min_cov), int(reserved))
 
 
 class BwParams(C.Structure):
@@ -907,6 +924,22 @@ def load():
     L.bsc_cpg_reads_stream_read.argtypes = [vp, u64, u64, vp]
     L.bsc_cpg_reads_stream_detach.restype = i32
     L.bsc_cpg_reads_stream_detach.argtypes = [vp, C.POINTER(vp), C.POINTER(u64)]
+    L.bsc_epi_params_default.restype = None
+    L.bsc_epi_params_default.argtypes = [C.POINTER(EpiParams)]
+    L.bsc_epi_windows_host.restype = i32
+    L.bsc_epi_windows_host.argtypes = [vp, u32, vp, u64, u32, u32, vp, i32, C.POINTER(EpiParams), vp, u64, C.POINTER(u64), C.POINTER(u64)]
+    L.bsc_epi_format.restype = C.c_long
+    L.bsc_epi_format.argtypes = [C.c_char_p, vp, C.c_size_t, C.POINTER(EpiParams), vp, C.c_size_t, C.POINTER(u64)]
+    L.bsc_epi_device.restype = i32
+    L.bsc_epi_device.argtypes = [vp, vp, u32, vp, u64, u32, u32, vp, C.POINTER(EpiParams), vp, u64, vp, vp, vp]
+    L.bsc_epi_text_device.restype = i32
+    L.bsc_epi_text_device.argtypes = [vp, vp, vp, u64, C.c_char_p, C.POINTER(EpiParams), vp, u64, vp, vp]
+    L.bsc_block_epi_kept.restype = i32
+    L.bsc_block_epi_kept.argtypes = [vp, C.c_char_p, C.POINTER(EpiParams), u64, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)]
+    L.bsc_epi_stream_read.restype = i32
+    L.bsc_epi_stream_read.argtypes = [vp, u64, u64, vp]
+    L.bsc_epi_stream_detach.restype = i32
+    L.bsc_epi_stream_detach.argtypes = [vp, C.POINTER(vp), C.POINTER(u64)]
     L.bsc_asm_params_default.restype = None
     L.bsc_asm_params_default.argtypes = [C.POINTER(AsmParams)]
     L.bsc_asm_pairs_host.restype = i32

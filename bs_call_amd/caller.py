@@ -1374,6 +1374,50 @@ class SiteCaller:
         _check(self._L.bsc_mbias_reset(self._h))
         self._mbias_cycles = None
 
+    # -- the epiallele table (csrc/epidev.hip) ----------------------------------------------------------------
+    @staticmethod
+    def _epi_params(params):
+        if params is None:
+            return _lib.EpiParams()
+        if isinstance(params, _lib.EpiParams):
+            return params
+        return _lib.EpiParams(**params)
+
+    def epi_device(self, d_tpl, nr, d_seq, seq_bytes, x, y, d_ref, d_win, win_cap, d_n_win, d_totals, params=None, stream=None):
+        """bsc_epi_device: the inputs of cpg_reads_device -> one bsc_epi_window per window of four consecutive reference CpGs in
+        d_win[<= win_cap], their count (a device u64) in d_n_win and the eight totals in d_totals (asynchronous on `stream`)."""
+        ep = self._epi_params(params)
+        _check(self._L.bsc_epi_device(self._h, d_tpl, nr, d_seq, seq_bytes, x, y, d_ref, C.byref(ep), d_win, win_cap, d_n_win, d_totals, stream))
+
+    def epi_text_device(self, d_win, d_n_win, max_win, contig, d_out, out_cap, d_totals2, params=None, stream=None):
+        """bsc_epi_text_device: the table's lines of d_win[min(*d_n_win, max_win)] -> d_out[<= out_cap]; d_totals2: {bytes, lines}."""
+        ep = self._epi_params(params)
+        name = contig.encode() if isinstance(contig, str) else contig
+        _check(self._L.bsc_epi_text_device(self._h, d_win, d_n_win, max_win, name, C.byref(ep), d_out, out_cap, d_totals2, stream))
+
+    def block_epi_kept(self, contig, params=None, cap=None):
+        """bsc_block_epi_kept + bsc_epi_stream_read: the epiallele table of the block the last *_keep call called, from the prepared
+        templates, reads and reference codes it left on the device.  params: a _lib.EpiParams, a dict of its fields, or None ({10, 0}).
+        Returns (bytes, lines, totals[8]).  cap: the room on the device (default: asked for and given on a second call)."""
+        ep = self._epi_params(params)
+        name = contig.encode() if isinstance(contig, str) else contig
+        nb, nl, tot = C.c_uint64(0), C.c_uint64(0), (C.c_uint64 * 8)()
+        room = 1 << 16 if cap is None else int(cap)
+        rc = self._L.bsc_block_epi_kept(self._h, name, C.byref(ep), room, C.byref(nb), C.byref(nl), tot)
+        if rc == -1 and nb.value > room and cap is None:
+            room = int(nb.value)
+            rc = self._L.bsc_block_epi_kept(self._h, name, C.byref(ep), room, C.byref(nb), C.byref(nl), tot)
+        _check(rc)
+        return self.epi_stream_read(0, nb.value), int(nl.value), tuple(int(v) for v in tot)
+
+    def epi_stream_read(self, off, n):
+        """bsc_epi_stream_read: bytes [off, off + n) of the table the last block_epi_kept left on the device."""
+        out = np.empty(max(int(n), 1), dtype=np.uint8)
+        _check(self._L.bsc_epi_stream_read(self._h, int(off), int(n), _ptr(out)))
+        if n:
+            self.synchronize()
+        return out[: int(n)].tobytes()
+
     def blocks_records(self, blocks, ref, out=None, all_positions=False, reg_start=1, reg_stop=0xFFFFFFFF, dbsnp=None, with_stats=False,
                        submit_only=False):
         """Several blocks in one launch sequence (bsc_blocks_records): blocks = [(templates, seq, x, y), ...] in genome order;
@@ -1930,3 +1974,50 @@ def mbias_format_host(counts, cap=None):
         assert (buf == 0xA5).all()
         return None, int(got)
     return buf[:got].tobytes(), int(got)
+
+
+def epi_windows_host(tpl, seq, x, y, ref, min_qual=20, params=None, cap=None):
+    """The host form of the epiallele table (bsc_epi_windows_host; csrc/epi.c): prepared TEMPLATE[nr] + their read bytes, the block x .. y and
+    its reference codes (x .. y + 2) -> (WINDOW records[min(count, cap)], count, totals[8]).  No GPU involved.  cap: the room (default:
+    every window)."""
+    from .epialleles import WINDOW
+
+    L = _lib.load()
+    tpl = np.ascontiguousarray(tpl, dtype=TEMPLATE)
+    seq = np.ascontiguousarray(seq, dtype=np.uint8)
+    ref = np.ascontiguousarray(ref, dtype=np.uint8)
+    if ref.size < int(y) - int(x) + 2:
+        raise ValueError("ref must hold the codes of x .. y + 1 at least")
+    ep = SiteCaller._epi_params(params)
+    room = int(y) - int(x) + 1 if cap is None else int(cap)
+    out = np.zeros(max(room, 1), dtype=WINDOW)
+    n, tot = C.c_uint64(0), (C.c_uint64 * 8)()
+    _check(L.bsc_epi_windows_host(_ptr(tpl), len(tpl), _ptr(seq), seq.size, int(x), int(y), _ptr(ref), int(min_qual), C.byref(ep), _ptr(out), room,
+                                  C.byref(n), tot))
+    return out[: min(int(n.value), room)].copy(), int(n.value), tuple(int(v) for v in tot)
+
+
+def epi_format_host(contig, recs, params=None, cap=None):
+    """bsc_epi_format: the table's lines of WINDOW records -> (bytes, lines).  cap: the room (default: asked for first); a room too small
+    gives (None, the length needed)."""
+    from .epialleles import WINDOW
+
+    L = _lib.load()
+    recs = np.ascontiguousarray(recs, dtype=WINDOW)
+    ep = SiteCaller._epi_params(params)
+    name = contig.encode() if isinstance(contig, str) else contig
+    t2 = (C.c_uint64 * 2)()
+    if cap is None:
+        need = L.bsc_epi_format(name, _ptr(recs), len(recs), C.byref(ep), None, 0, t2)
+        if need < 0:
+            _check(int(need))
+        cap = int(need)
+    buf = np.full(max(int(cap), 1) + 8, 0xA5, dtype=np.uint8)
+    got = L.bsc_epi_format(name, _ptr(recs), len(recs), C.byref(ep), _ptr(buf), int(cap), t2)
+    if got < 0:
+        _check(int(got))
+    assert (buf[int(cap) :] == 0xA5).all() and int(t2[0]) == got
+    if got > int(cap):
+        assert (buf == 0xA5).all()
+        return None, int(got)
+    return buf[:got].tobytes(), int(t2[1])

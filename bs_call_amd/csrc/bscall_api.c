@@ -129,6 +129,13 @@ int bsc_dev_launch_cr_walk(const void *tpl, uint32_t nr, const void *seq, uint64
 int bsc_dev_launch_cr_text(const void *sites, const void *n_sites, uint64_t max_sites, const char *contig, uint32_t contig_len, uint32_t min_cov,
                            void *tile_bytes, void *tile_off, void *line_len, void *scan_tmp, size_t scan_tmp_bytes, void *out, uint64_t out_cap,
                            void *totals2, int num_cus, void *stream);
+int bsc_dev_launch_epi_init(uint32_t x, uint32_t n, const void *tile_off, const void *tile_mask, void *win, uint64_t cap, void *n_win, void *totals,
+                            int num_cus, void *stream); /* epidev.hip */
+int bsc_dev_launch_epi_walk(const void *tpl, uint32_t nr, const void *seq, uint64_t seq_bytes, uint32_t x, uint32_t y, uint32_t min_qual,
+                            const void *tile_off, const void *tile_mask, void *win, uint64_t cap, void *totals, int num_cus, void *stream);
+int bsc_dev_launch_epi_text(const void *win, const void *n_win, uint64_t max_win, const char *contig, uint32_t contig_len, uint32_t min_cov,
+                            void *tile_bytes, void *tile_off, void *line_len, void *scan_tmp, size_t scan_tmp_bytes, void *out, uint64_t out_cap,
+                            void *totals2, int num_cus, void *stream);
 int bsc_dev_launch_asm_snps(const void *core, const void *emit, uint32_t n, uint32_t min_phred, int pass_only, void *snp_cnt, void *snp_off, void *snp_mask,
                             void *scan_tmp, size_t scan_tmp_bytes, int num_cus, void *stream); /* asmdev.hip */
 int bsc_dev_launch_asm_spans(uint32_t n, uint32_t W, uint32_t n_snps, const void *snp_off, const void *snp_mask, const void *tile_off, const void *tile_mask,
@@ -353,6 +360,13 @@ struct bsc_context {
     void *d_acc;
     uint32_t n_cycles;
   } mb;
+  struct { /* the epiallele table (epidev.hip): the text encoder's tile bytes, tile offsets, scan scratch and line lengths; bsc_block_epi_kept: the
+            * records, {count, eight totals, bytes, lines}, the table and its length.  (The site masks and their scan are cr's workspaces: a
+            * function of the reference codes alone; the block whose prepared reads are resident is cr.src_*.) */
+    void *d_tb, *d_to, *d_ttmp, *d_len, *d_win, *d_tot, *d_out;
+    size_t cap_tb, cap_to, cap_ttmp, cap_len, cap_win, cap_tot, cap_out;
+    uint64_t bytes;
+  } ep;
   struct { /* streams handed to the caller (bsc_bcf_stream_detach) come back here (bsc_detached_free) and are taken again by the next block:
             * no hipMalloc / hipFree — a device-wide wait — in the steady state of a run that writes behind the calling */
     void *p[4];
@@ -782,6 +796,13 @@ int bsc_destroy(bsc_context *ctx) {
   hipFree(ctx->cr.d_tot);
   hipFree(ctx->cr.d_out);
   hipFree(ctx->mb.d_acc);
+  hipFree(ctx->ep.d_tb);
+  hipFree(ctx->ep.d_to);
+  hipFree(ctx->ep.d_ttmp);
+  hipFree(ctx->ep.d_len);
+  hipFree(ctx->ep.d_win);
+  hipFree(ctx->ep.d_tot);
+  hipFree(ctx->ep.d_out);
   hipFree(ctx->asm_.d_scnt);
   hipFree(ctx->asm_.d_soff);
   hipFree(ctx->asm_.d_smask);
@@ -5613,6 +5634,140 @@ int bsc_mbias_reset(bsc_context *ctx) {
   hipFree(ctx->mb.d_acc);
   ctx->mb.d_acc = NULL;
   ctx->mb.n_cycles = 0;
+  return BSC_OK;
+}
+
+/* ---- the epiallele table (epidev.hip): include/bscall_amd.h has the rule, csrc/epi.c the host form ----------------------------------------------- */
+static int bsc_epi_params_check(const char *who, const bsc_epi_params *p) {
+  if (!p) return bsc_fail(BSC_ERR_ARG, "%s: NULL argument", who);
+  if (p->reserved) return bsc_fail(BSC_ERR_ARG, "%s: reserved is %u, not 0", who, p->reserved);
+  return BSC_OK;
+}
+
+/* the records' heads and the walk behind bsc_cr_sites_run; d_totals: eight u64, zeroed here */
+static int bsc_epi_walk_run(bsc_context *ctx, const char *who, const void *d_tpl, uint32_t nr, const void *d_seq, uint64_t seq_bytes, uint32_t x, uint32_t y,
+                            void *d_win, uint64_t cap, void *d_n_win, void *d_totals, hipStream_t s) {
+  HIP_TRY(hipMemsetAsync(d_totals, 0, BSC_EPI_N_TOTALS * sizeof(unsigned long long), s));
+  int e = bsc_dev_launch_epi_init(x, y - x + 1u, ctx->cr.d_off, ctx->cr.d_mask, d_win, cap, d_n_win, d_totals, ctx->num_cus, (void *)s);
+  if (!e)
+    e = bsc_dev_launch_epi_walk(d_tpl, nr, d_seq, seq_bytes, x, y, (uint32_t)ctx->params.min_qual, ctx->cr.d_off, ctx->cr.d_mask, d_win, cap, d_totals,
+                                ctx->num_cus, (void *)s);
+  if (e) return bsc_fail(BSC_ERR_HIP, "%s: walk launch failed: %s", who, hipGetErrorString((hipError_t)e));
+  return BSC_OK;
+}
+
+int bsc_epi_device(bsc_context *ctx, const void *d_tpl, uint32_t nr, const void *d_seq, uint64_t seq_bytes, uint32_t x, uint32_t y, const void *d_ref,
+                   const bsc_epi_params *p, void *d_win, uint64_t win_cap, void *d_n_win, void *d_totals, void *stream) {
+  static const char who[] = "bsc_epi_device";
+  int rc;
+  if (!ctx || !d_ref || !d_n_win || !d_totals || (nr && (!d_tpl || !d_seq)) || (win_cap && !d_win)) return bsc_fail(BSC_ERR_ARG, "%s: NULL argument", who);
+  if ((rc = bsc_epi_params_check(who, p))) return rc;
+  if (y < x) return bsc_fail(BSC_ERR_ARG, "%s: y (%u) < x (%u)", who, y, x);
+  if ((uint64_t)y - x + 1 > 0x0fffffffull) return bsc_fail(BSC_ERR_ARG, "%s: block longer than 2^28 - 1 positions", who);
+  if ((((uintptr_t)d_tpl | (uintptr_t)d_win | (uintptr_t)d_n_win | (uintptr_t)d_totals) & 7u))
+    return bsc_fail(BSC_ERR_ARG, "%s: the templates, the records, the count and the totals must be 8-byte aligned", who);
+  BSC_ENTER(ctx);
+  hipStream_t s = (hipStream_t)stream;
+  if ((rc = bsc_cr_sites_run(ctx, who, d_ref, y - x + 1u, s))) return rc;
+  return bsc_epi_walk_run(ctx, who, d_tpl, nr, d_seq, seq_bytes, x, y, d_win, win_cap, d_n_win, d_totals, s);
+}
+
+int bsc_epi_text_device(bsc_context *ctx, const void *d_win, const void *d_n_win, uint64_t max_win, const char *contig, const bsc_epi_params *p,
+                        void *d_out, uint64_t out_cap, void *d_totals2, void *stream) {
+  static const char who[] = "bsc_epi_text_device";
+  uint32_t contig_len = 0;
+  int rc;
+  if (!ctx || !d_n_win || !d_totals2 || (max_win && !d_win) || (out_cap && !d_out)) return bsc_fail(BSC_ERR_ARG, "%s: NULL argument", who);
+  if ((rc = bsc_epi_params_check(who, p))) return rc;
+  if ((rc = bsc_contig_check(who, contig, &contig_len))) return rc;
+  if (((uintptr_t)d_out & 15u) || (((uintptr_t)d_win | (uintptr_t)d_n_win | (uintptr_t)d_totals2) & 7u))
+    return bsc_fail(BSC_ERR_ARG, "%s: d_out must be 16-byte, the records, the count and the totals 8-byte aligned", who);
+  if ((max_win + 63u) / 64u > 0x7ffffffeull) return bsc_fail(BSC_ERR_ARG, "%s: more than 2^37 records", who);
+  BSC_ENTER(ctx);
+  hipStream_t s = (hipStream_t)stream;
+  const uint32_t n_tiles = (uint32_t)((max_win + 63u) / 64u);
+  size_t scan_bytes = 0;
+  if (bsc_dev_scan_tmp_bytes_u64(n_tiles + 1u, &scan_bytes)) return bsc_fail(BSC_ERR_HIP, "%s: scan size query failed", who);
+  if ((rc = bsc_reserve(&ctx->ep.d_tb, &ctx->ep.cap_tb, ((size_t)n_tiles + 1u) * 8u))) return rc;
+  if ((rc = bsc_reserve(&ctx->ep.d_to, &ctx->ep.cap_to, ((size_t)n_tiles + 1u) * 8u))) return rc;
+  if ((rc = bsc_reserve(&ctx->ep.d_ttmp, &ctx->ep.cap_ttmp, scan_bytes ? scan_bytes : 1))) return rc;
+  if ((rc = bsc_reserve(&ctx->ep.d_len, &ctx->ep.cap_len, ((size_t)n_tiles + 1u) * 128u))) return rc;
+  HIP_TRY(hipMemsetAsync(d_totals2, 0, 2 * sizeof(unsigned long long), s));
+  const int e = bsc_dev_launch_epi_text(d_win, d_n_win, max_win, contig, contig_len, p->min_cov, ctx->ep.d_tb, ctx->ep.d_to, ctx->ep.d_len, ctx->ep.d_ttmp,
+                                        scan_bytes, d_out, out_cap, d_totals2, ctx->num_cus, stream);
+  if (e) return bsc_fail(BSC_ERR_HIP, "%s: encoder launch failed: %s", who, hipGetErrorString((hipError_t)e));
+  return BSC_OK;
+}
+
+int bsc_block_epi_kept(bsc_context *ctx, const char *contig, const bsc_epi_params *p, uint64_t dev_cap, uint64_t *n_bytes, uint64_t *n_lines,
+                       uint64_t totals[8]) {
+  static const char who[] = "bsc_block_epi_kept";
+  int rc;
+  uint32_t contig_len = 0;
+  if (!ctx || !n_bytes || !n_lines) return bsc_fail(BSC_ERR_ARG, "%s: NULL argument", who);
+  *n_bytes = *n_lines = 0;
+  for (int k = 0; totals && k < BSC_EPI_N_TOTALS; k++) totals[k] = 0;
+  if ((rc = bsc_epi_params_check(who, p))) return rc;
+  if ((rc = bsc_contig_check(who, contig, &contig_len))) return rc;
+  if (ctx->meth_src != 1 || ctx->rec_pending || ctx->pending_sz)
+    return bsc_fail(BSC_ERR_ARG, "%s: the last call left no single block's arrays on the device", who);
+  if (!ctx->cr.src_ok) return bsc_fail(BSC_ERR_ARG, "%s: the last block's prepared templates, reads and reference are no longer on the device", who);
+  BSC_ENTER(ctx);
+  hipStream_t s = ctx->stream;
+  ctx->ep.bytes = 0;
+  const uint32_t x = ctx->cr.src_x, y = ctx->cr.src_y, nr = ctx->cr.src_nr;
+  /* d_tot: [0] the count, [1 .. 8] the totals, [9 .. 10] the encoder's {bytes, lines} */
+  if ((rc = bsc_reserve(&ctx->ep.d_tot, &ctx->ep.cap_tot, 11 * sizeof(unsigned long long)))) return rc;
+  unsigned long long *const d_tot = (unsigned long long *)ctx->ep.d_tot;
+  if ((rc = bsc_cr_sites_run(ctx, who, ctx->d_ref, y - x + 1u, s))) return rc;
+  /* the count is the scan's: the records' room is the windows', not the block's */
+  const uint32_t n_tiles = (uint32_t)(((uint64_t)(y - x) + 64u) / 64u);
+  unsigned int last_off = 0, last_cnt = 0;
+  HIP_TRY(hipMemcpyAsync(&last_off, (const uint32_t *)ctx->cr.d_off + (n_tiles - 1u), 4, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipMemcpyAsync(&last_cnt, (const uint32_t *)ctx->cr.d_cnt + (n_tiles - 1u), 4, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  const uint64_t n_sites = (uint64_t)last_off + last_cnt, n_win = n_sites >= BSC_EPI_K ? n_sites - (BSC_EPI_K - 1) : 0;
+  if ((rc = bsc_reserve(&ctx->ep.d_win, &ctx->ep.cap_win, (size_t)(n_win ? n_win : 1) * sizeof(bsc_epi_window)))) return rc;
+  if ((rc = bsc_epi_walk_run(ctx, who, ctx->d_tpl, nr, ctx->d_seq, ctx->cr.src_seq_bytes, x, y, ctx->ep.d_win, n_win, d_tot, d_tot + 1, s))) return rc;
+  /* a buffer that came back (bsc_detached_free), the smallest that will do, as d_meth is taken */
+  if (!ctx->ep.d_out && ctx->pool_mu_made) ctx->ep.d_out = bsc_pool_get(ctx, (size_t)(dev_cap ? dev_cap : 1), &ctx->ep.cap_out);
+  if ((rc = bsc_reserve(&ctx->ep.d_out, &ctx->ep.cap_out, (size_t)(dev_cap ? dev_cap : 1)))) return rc;
+  if ((rc = bsc_epi_text_device(ctx, ctx->ep.d_win, d_tot, n_win, contig, p, ctx->ep.d_out, dev_cap, d_tot + 9, s))) return rc;
+  unsigned long long tot[11] = {0};
+  HIP_TRY(hipMemcpyAsync(tot, d_tot, sizeof tot, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  *n_bytes = tot[9];
+  *n_lines = tot[10];
+  for (int k = 0; totals && k < BSC_EPI_N_TOTALS; k++) totals[k] = tot[1 + k];
+  if (tot[0] != n_win) return bsc_fail(BSC_ERR_RANGE, "%s: %llu windows counted, %llu records made", who, (unsigned long long)n_win, tot[0]);
+  if (tot[9] > dev_cap) return bsc_fail(BSC_ERR_ARG, "%s: the block's table has %llu bytes, dev_cap is %llu", who, tot[9], (unsigned long long)dev_cap);
+  ctx->ep.bytes = tot[9];
+  return BSC_OK;
+}
+
+int bsc_epi_stream_read(bsc_context *ctx, uint64_t off, uint64_t n, void *dst) {
+  if (!ctx || (!dst && n)) return bsc_fail(BSC_ERR_ARG, "bsc_epi_stream_read: NULL argument");
+  if (off + n < off || off + n > ctx->ep.bytes || off + n > ctx->ep.cap_out) return bsc_fail(BSC_ERR_ARG, "bsc_epi_stream_read: beyond the table's end");
+  if (!n) return BSC_OK;
+  BSC_ENTER(ctx);
+  HIP_TRY(hipMemcpyAsync(dst, (const char *)ctx->ep.d_out + off, (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+  return BSC_OK;
+}
+
+int bsc_epi_stream_detach(bsc_context *ctx, void **d_stream, uint64_t *n_bytes) {
+  if (!ctx || !d_stream || !n_bytes) return bsc_fail(BSC_ERR_ARG, "bsc_epi_stream_detach: NULL argument");
+  *d_stream = NULL;
+  *n_bytes = 0;
+  if (!ctx->ep.d_out || !ctx->ep.bytes) return bsc_fail(BSC_ERR_ARG, "bsc_epi_stream_detach: the last call left no table on the device");
+  BSC_ENTER(ctx);
+  bsc_pool_init(ctx);
+  if (!ctx->s_det) HIP_TRY(hipStreamCreateWithFlags(&ctx->s_det, hipStreamNonBlocking));
+  *d_stream = ctx->ep.d_out;
+  *n_bytes = ctx->ep.bytes;
+  bsc_pool_book(ctx, ctx->ep.d_out, ctx->ep.cap_out);
+  ctx->ep.d_out = NULL;
+  ctx->ep.cap_out = 0;
+  ctx->ep.bytes = 0;
   return BSC_OK;
 }
 

@@ -23,7 +23,7 @@ def run(bam_path: str, reference: Dict[str, np.ndarray], bcf_path: str, sample: 
         bigwig_section: int = 1024, bigwig_zoom: int = 1024, bigwig_compress: bool = False, bigbed_path: Optional[str] = None, bigbed_items: int = 512,
         bigbed_zoom: int = 1024, bigbed_compress: bool = False, meth_index: Optional[str] = None, variants_path: Optional[str] = None,
         variants_params=None, cpg_reads_path: Optional[str] = None, cpg_reads_params=None, asm_path: Optional[str] = None, asm_params=None,
-        mbias_path: Optional[str] = None, mbias_params=None, **reader_kw) -> dict:
+        mbias_path: Optional[str] = None, mbias_params=None, epi_path: Optional[str] = None, epi_params=None, **reader_kw) -> dict:
     """reference: contig name -> uint8 reference codes (0 = N, 1..4 = ACGT; position 1 first).  Returns a summary dict.
     under_conv / over_conv / min_qual (defaults 0.01 / 0.05 / 20, src/init_param.c:26-31) are the MODEL's parameters: without
     `caller` the run builds its SiteCaller from them; with one, they are taken from it and a differing explicit value is an error
@@ -95,7 +95,16 @@ def run(bam_path: str, reference: Dict[str, np.ndarray], bcf_path: str, sample: 
     read end, bisulfite strand and CpG / CHG / CHH, from the raw templates as sequenced — behind every block the walk over the raw arrays the
     device reader left in HBM (SiteCaller.block_mbias_rawdev, csrc/mbiasdev.hip) into the context's accumulator, which the run resets before
     and after; ONE table per run, plain text whatever `compressed` says.  mbias_params: a _lib.MbiasParams, a dict of n_cycles, or n_cycles
-    (default 512, 1 .. 1024).  The summary gets "mbias_totals" (the eight totals of the rule).  The same conditions as meth_path."""
+    (default 512, 1 .. 1024).  The summary gets "mbias_totals" (the eight totals of the rule).  The same conditions as meth_path.
+    epi_path: the epiallele table of the same run (include/bscall_amd.h has the rule): behind every block, per window of four consecutive
+    reference CpGs, the templates that show each of the 16 methylation patterns, from the prepared templates, reads and reference codes the
+    block left on the device (SiteCaller.block_epi_kept, csrc/epidev.hip) — plain text, or BGZF where `compressed` says so or the name ends
+    in .gz.  epi_params: a _lib.EpiParams or a dict of min_cov.  The summary gets "epi_lines" and "epi_totals" (the eight totals of the
+    rule).  The same conditions as meth_path."""
+    if epi_params is not None and epi_path is None:
+        raise ValueError("epi_params are thresholds of the table epi_path names: they need epi_path")
+    if epi_path is not None and (shard_rank is not None or not device_reader or host_prep or host_bcf):
+        raise ValueError("epi_path is a single run on the device reader (device_reader=True, no shard_rank, no host_prep / host_bcf)")
     if mbias_params is not None and mbias_path is None:
         raise ValueError("mbias_params size the table mbias_path names: they need mbias_path")
     if mbias_path is not None and (shard_rank is not None or not device_reader or host_prep or host_bcf):
@@ -203,6 +212,7 @@ def run(bam_path: str, reference: Dict[str, np.ndarray], bcf_path: str, sample: 
         var_blobs, var_totals = [], np.zeros(10, dtype=np.uint64)
         reads_blobs, reads_lines, reads_totals = [], 0, np.zeros(8, dtype=np.uint64)
         asm_blobs, asm_lines, asm_totals = [], 0, np.zeros(8, dtype=np.uint64)
+        epi_blobs, epi_lines, epi_totals = [], 0, np.zeros(8, dtype=np.uint64)
         mbias_any = False
         if mbias_path is not None:
             c.mbias_reset()
@@ -263,7 +273,7 @@ def run(bam_path: str, reference: Dict[str, np.ndarray], bcf_path: str, sample: 
                 region_cur = None
 
             def block_blobs():
-                nonlocal n_blocks, n_records, base_filter, passed, meth_lines, region_cur, bw_sites, cov_sites, bb_sites, var_totals, reads_lines, reads_totals, asm_lines, asm_totals, mbias_any
+                nonlocal n_blocks, n_records, base_filter, passed, meth_lines, region_cur, bw_sites, cov_sites, bb_sites, var_totals, reads_lines, reads_totals, asm_lines, asm_totals, mbias_any, epi_lines, epi_totals
                 before, cur_tid = c.site_totals(), -1
                 for item in (rd.device_blocks() if device_reader else rd.blocks()):
                     if device_reader:
@@ -312,7 +322,7 @@ def run(bam_path: str, reference: Dict[str, np.ndarray], bcf_path: str, sample: 
                             blob, n_rec, st = c.block_bcf_rawdev(dblk, ref, tid, names=names, left_trim=left_trim, right_trim=right_trim, min_qual=min_qual,
                                                                  reg_stop=len(codes), dbsnp=flags, with_stats=True, profile=prof,
                                                                  keep=meth_path is not None or want_regions or want_bw or want_cov or want_bb or variants_path is not None
-                                                                 or cpg_reads_path is not None or asm_path is not None or mbias_path is not None)
+                                                                 or cpg_reads_path is not None or asm_path is not None or mbias_path is not None or epi_path is not None)
                         if mbias_path is not None:  # the block's raw templates, still in the reader's buffers, into the run's accumulator
                             c.block_mbias_rawdev(dblk.d_tpl, dblk.nr, dblk.d_seq, dblk.seq_bytes, dblk.d_misms, dblk.n_misms, mbias_cycles)
                             mbias_any = True
@@ -367,6 +377,11 @@ def run(bam_path: str, reference: Dict[str, np.ndarray], bcf_path: str, sample: 
                             asm_blobs.append(ab)
                             asm_lines += al
                             asm_totals += np.array(at, dtype=np.uint64)
+                        if epi_path is not None:  # the same block's epiallele table, from its prepared reads still on the device
+                            eb, el, et = c.block_epi_kept(name, epi_params)
+                            epi_blobs.append(eb)
+                            epi_lines += el
+                            epi_totals += np.array(et, dtype=np.uint64)
                         recs = None
                     elif host_prep:  # round 4's split: the process thread's per-template work here, then the block
                         tpl, pseq, st = prepare_templates(raw, seq, ms, left_trim, right_trim, min_qual, profile=prof, x=x, ref=ref)
@@ -429,6 +444,8 @@ def run(bam_path: str, reference: Dict[str, np.ndarray], bcf_path: str, sample: 
                 vcf.write_vcf_blobs(cpg_reads_path, "", reads_blobs, compressed)
             if asm_path is not None:
                 vcf.write_vcf_blobs(asm_path, "", asm_blobs, compressed)
+            if epi_path is not None:
+                vcf.write_vcf_blobs(epi_path, "", epi_blobs, compressed or str(epi_path).endswith(".gz"))
             if mbias_path is not None:  # a run without a block has no accumulator: the header alone
                 mbias_counts, mbias_totals = c.mbias_read(mbias_cycles) if mbias_any else (_mbias.empty(mbias_cycles)[0], (0,) * 8)
                 c.mbias_reset()
@@ -519,6 +536,9 @@ def run(bam_path: str, reference: Dict[str, np.ndarray], bcf_path: str, sample: 
         if asm_path is not None:
             summary["asm_lines"] = asm_lines
             summary["asm_totals"] = tuple(int(v) for v in asm_totals)
+        if epi_path is not None:
+            summary["epi_lines"] = epi_lines
+            summary["epi_totals"] = tuple(int(v) for v in epi_totals)
         if mbias_path is not None:
             summary["mbias_totals"] = tuple(int(v) for v in mbias_totals)
         if want_bw:

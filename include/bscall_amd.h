@@ -1792,7 +1792,7 @@ int bsc_block_variants_csi_kept(bsc_context *ctx, int min_shift, const bsc_csi_e
  *   bsc_cpg_reads_stream_detach   the table handed over as bsc_meth_stream_detach hands one over: bsc_detached_read / _wait / _free and
  *                                 bsc_bgzf_write_device serve it; it counts against the four pooled buffers
  * Not built: a tabix index of the table, sharded runs, the batched and host-buffer block entries, non-CpG contexts, pairs beyond the
- * reference-next site, any float statistic of the 2x2 table.
+ * reference-next site (the epiallele table below has the patterns of four consecutive sites), any float statistic of the 2x2 table.
  */
 typedef struct {
   uint32_t pos, dist, m, u, e, d, mm, mu, um, uu;
@@ -2005,6 +2005,84 @@ int bsc_block_mbias_rawdev(bsc_context *ctx, const void *d_raw, uint32_t nr, con
                            uint64_t n_misms, const bsc_mbias_params *p, uint64_t totals[8]);
 int bsc_mbias_read(bsc_context *ctx, uint64_t *counts_host, uint64_t totals[8]);
 int bsc_mbias_reset(bsc_context *ctx);
+
+/*
+ * The epiallele table (csrc/epidev.hip: the records' heads, the walk, the text encoder, behind the site pass and the scan of
+ * csrc/cpgreadsdev.hip; csrc/epi.c holds the host form, which is their checker; bs_call_amd/epialleles.py the Python rule).  Per window of
+ * four consecutive reference CpGs, how many templates show each of the 16 methylation patterns: what methclone, epipolymorphism,
+ * methylation entropy and the methylation-haplotype load start from.  The read-level CpG table stops at pairs, and a 2x2 table of neighbours
+ * cannot be turned into 4-site patterns afterwards; this one is made from the same prepared templates while they are in HBM.  The reference
+ * has no such output: the rule is this project's own.
+ *
+ * COUNTS, SITE, BYTE(t, q) and STATE(t, s) are those of the read-level CpG table above, word for word, and the inputs are those of
+ * bsc_cpg_reads_device.
+ * WINDOW    With the block's sites s_0 < s_1 < ... < s_{S-1}, window i (0 <= i <= S - 4) is (s_i, s_{i+1}, s_{i+2}, s_{i+3}).  K = 4 is a
+ *           constant of this table (BSC_EPI_K), not a parameter.  A block with S < 4 has no window.  Windows are a property of the reference
+ *           alone: a window no template reads is still a window.  Windows never cross a block, as NEXT does not.
+ * PATTERN(t, i)  is defined iff STATE(t, s_{i+j}) != none for all j = 0 .. 3.  Its code is the sum over j of [STATE(t, s_{i+j}) == M] << j:
+ *           code 0 = UUUU, 15 = MMMM, and bit 0 is the leftmost site.  A template gives at most one pattern per window, mates included:
+ *           BYTE already lets the first read win in an overlap.  A site in the gap between mates has no state, so no window containing
+ *           that site gets a pattern from that template.
+ * RECORD    bsc_epi_window {pos, span, c[16]}, 72 bytes, 8-byte aligned.  pos = s_i and span = s_{i+3} - s_i.  c[code] is the number of
+ *           templates with that pattern.  There is one record per window in position order, zero-count windows included.
+ * TOTALS    Eight u64, over every window whether stored or not: [0] windows, [1] the sum over all windows and codes of c, [2] templates
+ *           that gave at least one pattern, [3] the sum over observations of popcount(code), [4] templates with k_t >= 4 (k_t: the number
+ *           of sites with a state, as in the read-level table), [5 .. 7] 0.
+ * LINE      With n = the sum of c (64 bits) and k = the number of codes with c > 0, a line is written iff n >= max(1, min_cov).  Twenty
+ *           tab-separated plain decimals and '\n':
+ *             chrom  start = pos - 1  end = pos + span + 1  n  k  c0 ... c15
+ *           start is the start of the --meth-merge and --meth-reads lines of the window's first CpG, so the tables join.  No float is
+ *           written: epipolymorphism is 1 - sum c^2 / n^2 and entropy is - sum (c / n) log2 (c / n); the reader computes them.  contig:
+ *           1 .. 255 bytes without tab or newline.  Text totals: {bytes, lines}.
+ * Params    bsc_epi_params {min_cov, reserved}, default {10, 0}.  reserved != 0 is refused with BSC_ERR_ARG.
+ * Not gated by the called genotype, as the read-level table is not.
+ *
+ *   bsc_epi_params_default   {10, 0}
+ *   bsc_epi_windows_host     the host form: win[<= cap] the records, *n_win their number (records beyond cap are counted, not stored: BSC_OK
+ *                            all the same), totals (eight u64; may be NULL)
+ *   bsc_epi_format           the lines of win[n] -> buf.  Returns the length; the length needed, with nothing written, when cap is too
+ *                            small; < 0 for a bad argument.  totals2 (may be NULL): {bytes, lines}
+ *   bsc_epi_device           the same records from device-resident inputs (d_tpl 8-byte aligned, d_ref y - x + 3 codes): d_win[min(count,
+ *                            win_cap)] (8-byte aligned; nothing is written behind the room), *d_n_win a device u64 = the count, d_totals
+ *                            eight device u64.  Integer atomic adds alone: the bytes are a function of the input.  Asynchronous on
+ *                            `stream`; workspaces of the context's (the site masks are the read-level table's), grow-only: one call in
+ *                            flight per context.  A refusal writes nothing.
+ *   bsc_epi_text_device      the lines of d_win[min(*d_n_win, max_win)] -> d_out[<= out_cap] (16-byte aligned).  d_totals2: two device u64
+ *                            {bytes, lines}.  A stream longer than out_cap is cut at a 64-record boundary and its full length is still
+ *                            reported, as the other text encoders do.
+ *   bsc_block_epi_kept       the twin of bsc_block_cpg_reads_kept, with its preconditions and refusals: walks the prepared templates, reads
+ *                            and reference codes the last *_keep call left in HBM and writes the table into a buffer of the context's own
+ *                            (room: dev_cap bytes).  dev_cap too small: BSC_ERR_ARG with *n_bytes = the room needed (the totals are
+ *                            filled), and the call may be repeated.  Every other kept output — the kept stream, its index entries, the
+ *                            methylation, read-level and allele-specific tables — is untouched, before or after.  Waits.
+ *   bsc_epi_stream_read      bytes [off, off + n) of that table -> dst, queued on the context's stream
+ *   bsc_epi_stream_detach    the table handed over as bsc_cpg_reads_stream_detach hands one over: bsc_detached_read / _wait / _free and
+ *                            bsc_bgzf_write_device serve it; it counts against the four pooled buffers
+ * Not built: K != 4, non-CpG contexts, sharded runs, the batched and host-buffer block entries, a tabix index of the table, float columns.
+ */
+#define BSC_EPI_K 4
+typedef struct {
+  uint32_t pos;   /* s_i */
+  uint32_t span;  /* s_{i+3} - s_i */
+  uint32_t c[16]; /* templates per pattern code */
+} bsc_epi_window;
+typedef struct {
+  uint32_t min_cov;  /* LINE: n >= max(1, min_cov) */
+  uint32_t reserved; /* 0; anything else is refused */
+} bsc_epi_params;
+#define BSC_EPI_N_TOTALS 8
+void bsc_epi_params_default(bsc_epi_params *p);
+int bsc_epi_windows_host(const bsc_template *tpl, uint32_t nr, const uint8_t *seq, uint64_t seq_bytes, uint32_t x, uint32_t y, const uint8_t *ref,
+                         int32_t min_qual, const bsc_epi_params *p, bsc_epi_window *win, uint64_t cap, uint64_t *n_win, uint64_t totals[8]);
+long bsc_epi_format(const char *contig, const bsc_epi_window *win, size_t n, const bsc_epi_params *p, char *buf, size_t cap, uint64_t totals2[2]);
+int bsc_epi_device(bsc_context *ctx, const void *d_tpl, uint32_t nr, const void *d_seq, uint64_t seq_bytes, uint32_t x, uint32_t y, const void *d_ref,
+                   const bsc_epi_params *p, void *d_win, uint64_t win_cap, void *d_n_win, void *d_totals, void *stream);
+int bsc_epi_text_device(bsc_context *ctx, const void *d_win, const void *d_n_win, uint64_t max_win, const char *contig, const bsc_epi_params *p,
+                        void *d_out, uint64_t out_cap, void *d_totals2, void *stream);
+int bsc_block_epi_kept(bsc_context *ctx, const char *contig, const bsc_epi_params *p, uint64_t dev_cap, uint64_t *n_bytes, uint64_t *n_lines,
+                       uint64_t totals[8]);
+int bsc_epi_stream_read(bsc_context *ctx, uint64_t off, uint64_t n, void *dst);
+int bsc_epi_stream_detach(bsc_context *ctx, void **d_stream, uint64_t *n_bytes);
 
 /*
  * dbSNP index (host C + zlib; csrc/dbsnp.c): the reader of the compressed index bin/dbSNP_idx writes.  In the reference

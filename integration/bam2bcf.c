@@ -113,6 +113,15 @@
  * needs), --meth-asm-min-cov n (default 2: m1 + u1 and m2 + u2 a line needs), --meth-asm-pass (PASS SNPs only).  Refused where --meth-reads is.
  * Without the switch the program makes the calls it made before the switch existed.
  *
+ * --meth-epialleles out.tsv: the epiallele table (include/bscall_amd.h has the rule) — a line per window of four consecutive reference CpGs
+ * that templates read whole: chrom start end n k c0 .. c15, c<code> the templates with that methylation pattern (bit 0 the leftmost CpG, 15 = all
+ * methylated), n their sum, k the patterns seen; start is that of the --meth-merge and --meth-reads lines of the window's first CpG.  No float
+ * is written: epipolymorphism and entropy are the reader's (bs_call_amd/epialleles.py has both).  Behind every block bsc_block_epi_kept walks
+ * the prepared templates, reads and reference codes the block call left in HBM; the table is detached (bsc_epi_stream_detach) and goes to the
+ * output thread as one more job for its own file, through a BGZF writer of its own when the name ends in .gz, under -O b or --meth-bgzf.
+ * --meth-epialleles-min-cov n (default 10): the n a line needs.  Refused where --meth-reads is.  Without the switch the program makes the calls
+ * it made before the switch existed.
+ *
  * --mbias out.tsv: the M-bias table (include/bscall_amd.h has the rule) — methylated and unmethylated calls per sequencing cycle, by read 1 /
  * read 2, bisulfite strand and CpG / CHG / CHH, from the RAW templates as sequenced (no trim, clip or overlap edit): what -L / -R and the
  * under-conversion rate are chosen from.  Behind every block bsc_block_mbias_rawdev walks the block's raw arrays, still in the reader's
@@ -173,7 +182,7 @@ static void *pinned(size_t n) { /* page-locked: the copy-out is a true DMA, queu
  * ONE writer: three of them writing pieces of one file in parallel were 2.5 x slower (0.70 s against 0.28 for the 2.9 GB of a contig-sized
  * block: writes to one inode take turns anyway).  Page-locking a host buffer for a whole stream would cost more than the calling. */
 #define PIECE ((size_t)32 << 20)
-#define N_JOB 4 /* (a block is two jobs with --meth, three with --variants beside it, four with --meth-reads, five with --meth-asm: a push waits for a
+#define N_JOB 4 /* (a block is two jobs with --meth, three with --variants beside it, four with --meth-reads, five with --meth-asm, six with --meth-epialleles: a push waits for a
                  * free slot) */
 typedef struct {
   void *d;        /* the stream on the device; NULL: only close_fd */
@@ -572,6 +581,14 @@ int main(int argc, char **argv) {
   bsc_asm_params aspar;
   bsc_asm_params_default(&aspar);
   int asm_opts = 0;
+  const char *epi_path = NULL; /* --meth-epialleles out.tsv: the epiallele table */
+  bsc_epi_params eppar;
+  bsc_epi_params_default(&eppar);
+  int epi_opts = 0;
+  if (argc >= 2 && !strcmp(argv[argc - 1], "--meth-epialleles") && (argc == 2 || strcmp(argv[argc - 2], "--meth-epialleles"))) {
+    fprintf(stderr, "%s: --meth-epialleles takes the path of the epiallele table to write\n", argv[0]);
+    return 2;
+  }
   const char *mbias_path = NULL; /* --mbias out.tsv: the M-bias table */
   bsc_mbias_params mbpar;
   bsc_mbias_params_default(&mbpar);
@@ -699,6 +716,17 @@ int main(int argc, char **argv) {
       mbpar.n_cycles = (uint32_t)v;
       mbias_opts = 1;
     }
+    else if (!strcmp(argv[1], "--meth-epialleles")) epi_path = argv[2];
+    else if (!strcmp(argv[1], "--meth-epialleles-min-cov")) {
+      char *end = NULL;
+      const unsigned long v = strtoul(argv[2], &end, 10);
+      if (!argv[2][0] || *end || argv[2][0] == '-' || v > 0xfffffffful) {
+        fprintf(stderr, "%s: %s takes a count, not '%s'\n", argv[0], argv[1], argv[2]);
+        return 2;
+      }
+      eppar.min_cov = (uint32_t)v;
+      epi_opts = 1;
+    }
     else if (!strcmp(argv[1], "--meth-asm-window") || !strcmp(argv[1], "--meth-asm-min-qual") || !strcmp(argv[1], "--meth-asm-min-cov")) {
       char *end = NULL;
       const unsigned long v = strtoul(argv[2], &end, 10);
@@ -778,7 +806,7 @@ int main(int argc, char **argv) {
     argc -= 2;
   }
   if (argc < 5 || world < 1 || (rank >= 0 && rank >= world)) {
-    fprintf(stderr, "usage: %s [-O u|b] [--format bcf|vcf] [--index] [-D dbsnp.idx] [--meth out.bed [--meth-bgzf] [--meth-index tbi|csi] [--meth-merge | --meth-all] [--meth-min-cov n] [--meth-min-gq n] [--meth-pass]] [--meth-regions regions.bed | --meth-window n --meth-regions-out out.tsv] [--meth-bigwig out.bw [--meth-bigwig-section n] [--meth-bigwig-zoom n] [--meth-bigwig-compress: zlib sections, n <= 8157]: the methylation level as a bigWig track, per cytosine even with --meth-merge, under the --meth-* thresholds and --meth-all] [--cov-bigwig cov.bw: the depth of the same sites as a bigWig track, under the same --meth-bigwig-* switches] [--meth-bigbed out.bb [--meth-bigbed-items n] [--meth-bigbed-zoom n] [--meth-bigbed-compress: zlib blocks, n <= 652]] [--variants out: the records with an ALT allele, in the run's format and compression, with out.csi under --index [--variants-min-qual n] [--variants-pass] [--variants-known: dbSNP sites only, with -D]] [--meth-reads out.tsv: the read-level CpG concordance table, a line per reference CpG [--meth-reads-min-sites n] [--meth-reads-min-cov n]] [--mbias out.tsv: methylation by read cycle, from the reads as sequenced [--mbias-cycles n]] [--meth-asm out.tsv: the allele-specific methylation table, a line per heterozygous SNP and CpG near it [--meth-asm-window n] [--meth-asm-min-qual n] [--meth-asm-min-cov n] [--meth-asm-pass]] [--rank r --world n | --merge n] in.bam ref.fa out.bcf report.json [sample]\n", argv[0]);
+    fprintf(stderr, "usage: %s [-O u|b] [--format bcf|vcf] [--index] [-D dbsnp.idx] [--meth out.bed [--meth-bgzf] [--meth-index tbi|csi] [--meth-merge | --meth-all] [--meth-min-cov n] [--meth-min-gq n] [--meth-pass]] [--meth-regions regions.bed | --meth-window n --meth-regions-out out.tsv] [--meth-bigwig out.bw [--meth-bigwig-section n] [--meth-bigwig-zoom n] [--meth-bigwig-compress: zlib sections, n <= 8157]: the methylation level as a bigWig track, per cytosine even with --meth-merge, under the --meth-* thresholds and --meth-all] [--cov-bigwig cov.bw: the depth of the same sites as a bigWig track, under the same --meth-bigwig-* switches] [--meth-bigbed out.bb [--meth-bigbed-items n] [--meth-bigbed-zoom n] [--meth-bigbed-compress: zlib blocks, n <= 652]] [--variants out: the records with an ALT allele, in the run's format and compression, with out.csi under --index [--variants-min-qual n] [--variants-pass] [--variants-known: dbSNP sites only, with -D]] [--meth-reads out.tsv: the read-level CpG concordance table, a line per reference CpG [--meth-reads-min-sites n] [--meth-reads-min-cov n]] [--mbias out.tsv: methylation by read cycle, from the reads as sequenced [--mbias-cycles n]] [--meth-asm out.tsv: the allele-specific methylation table, a line per heterozygous SNP and CpG near it [--meth-asm-window n] [--meth-asm-min-qual n] [--meth-asm-min-cov n] [--meth-asm-pass]] [--meth-epialleles out.tsv: the epiallele table, a line per window of four reference CpGs [--meth-epialleles-min-cov n]] [--rank r --world n | --merge n] in.bam ref.fa out.bcf report.json [sample]\n", argv[0]);
     return 2;
   }
   if (text && (rank >= 0 || merge > 0)) {
@@ -849,6 +877,18 @@ int main(int argc, char **argv) {
     fprintf(stderr, "%s: --mbias walks the raw blocks the device reader leaves on the device: not with BAM2BCF_HOST_READER / _HOST_BCF / _HOST_PREP\n", argv[0]);
     return 2;
   }
+  if (epi_opts && !epi_path) {
+    fprintf(stderr, "%s: --meth-epialleles-min-cov is a threshold of the table --meth-epialleles writes: it needs --meth-epialleles out.tsv\n", argv[0]);
+    return 2;
+  }
+  if (epi_path && (rank >= 0 || world > 1 || merge > 0)) {
+    fprintf(stderr, "%s: --meth-epialleles writes a single run's table; a sharded run (--rank / --world / --merge) has none\n", argv[0]);
+    return 2;
+  }
+  if (epi_path && (getenv("BAM2BCF_HOST_PREP") || getenv("BAM2BCF_HOST_BCF") || getenv("BAM2BCF_HOST_READER"))) {
+    fprintf(stderr, "%s: --meth-epialleles walks the prepared reads the device reader's blocks leave on the device: not with BAM2BCF_HOST_READER / _HOST_BCF / _HOST_PREP\n", argv[0]);
+    return 2;
+  }
   if (asm_opts && !asm_path) {
     fprintf(stderr, "%s: --meth-asm-window / --meth-asm-min-qual / --meth-asm-min-cov / --meth-asm-pass are thresholds of the table --meth-asm writes: they need --meth-asm out.tsv\n", argv[0]);
     return 2;
@@ -873,7 +913,7 @@ int main(int argc, char **argv) {
     fprintf(stderr, "%s: --variants selects from what the device reader's blocks leave on the device: not with BAM2BCF_HOST_READER / _HOST_BCF / _HOST_PREP\n", argv[0]);
     return 2;
   }
-  if (meth_bgzf && !meth_path && !reads_path && !asm_path) {
+  if (meth_bgzf && !meth_path && !reads_path && !asm_path && !epi_path) {
     fprintf(stderr, "%s: --meth-bgzf compresses the table --meth writes: it needs --meth out.bed.gz (or --meth-reads out.tsv.gz, whose table it compresses too)\n", argv[0]);
     return 2;
   }
@@ -1081,6 +1121,9 @@ int main(int argc, char **argv) {
   int asm_fd = -1; /* --meth-asm: the file, where its next bytes go, its compressor, the sums of the blocks' totals and lines */
   uint64_t asm_at = 0, asm_lines = 0, asm_tot[BSC_ASM_N_TOTALS] = {0};
   bsc_bgzf *za = NULL;
+  int epi_fd = -1; /* --meth-epialleles: the file, where its next bytes go, its compressor, the sums of the blocks' totals and lines */
+  uint64_t epi_at = 0, epi_lines = 0, epi_tot[BSC_EPI_N_TOTALS] = {0};
+  bsc_bgzf *ze = NULL;
   FILE *mbias_f = NULL; /* --mbias: opened now, so that a path that cannot be written stops the run before it starts; written at the end */
   uint64_t mbias_tot[BSC_MBIAS_N_TOTALS] = {0};
   int mbias_any = 0;
@@ -1098,6 +1141,17 @@ int main(int argc, char **argv) {
     fclose(af);
     const size_t al = strlen(asm_path);
     if (bgzf || meth_bgzf || (al > 3 && !strcmp(asm_path + al - 3, ".gz"))) CHECK(bsc_bgzf_open(ctx, &za));
+  }
+  if (epi_path) {
+    FILE *ef = fopen(epi_path, "wb");
+    if (!ef) {
+      perror(epi_path);
+      return 1;
+    }
+    epi_fd = dup(fileno(ef));
+    fclose(ef);
+    const size_t el = strlen(epi_path);
+    if (bgzf || meth_bgzf || (el > 3 && !strcmp(epi_path + el - 3, ".gz"))) CHECK(bsc_bgzf_open(ctx, &ze));
   }
   int var_fd = -1; /* --variants: the file, where its next bytes go, its compressor and index, the sums of the blocks' totals */
   uint64_t var_at = 0, var_tot[BSC_VAR_N_TOTALS] = {0};
@@ -1537,6 +1591,32 @@ int main(int argc, char **argv) {
           asm_at += n_a;
         }
       }
+      if (n_bytes && epi_path) { /* the block's epiallele table, from the prepared templates, reads and reference codes the call left on the device: a
+                                  * buffer and a job of its own */
+        uint64_t e_cap = (uint64_t)n + 4096, e_bytes = 0, e_lines = 0, et[BSC_EPI_N_TOTALS];
+        int erc = bsc_block_epi_kept(ctx, REF_NAME(dblk.tid), &eppar, e_cap, &e_bytes, &e_lines, et);
+        if (erc == BSC_ERR_ARG && e_bytes > e_cap) erc = bsc_block_epi_kept(ctx, REF_NAME(dblk.tid), &eppar, e_bytes, &e_bytes, &e_lines, et);
+        CHECK(erc);
+        epi_lines += e_lines;
+        for (int k = 0; k < BSC_EPI_N_TOTALS; k++) epi_tot[k] += et[k];
+        if (e_bytes) {
+          void *d_e = NULL;
+          uint64_t n_e = 0;
+          CHECK(bsc_epi_stream_detach(ctx, &d_e, &n_e));
+          if (ze) {
+            CHECK(bsc_bgzf_write_device(ze, d_e, n_e));
+            CHECK(bsc_detached_free(ctx, d_e));
+            d_e = NULL;
+            n_e = 0;
+            CHECK(bsc_bgzf_take(ze, &d_e, &n_e));
+          }
+          if (n_e) {
+            const out_job j = {d_e, n_e, epi_at, epi_fd, 0};
+            writer_push(&W, j);
+          }
+          epi_at += n_e;
+        }
+      }
       if (n_bytes && variants_path) { /* the block's variant-only stream, selected from the same arrays and encoded by the block's own encoder: a
                                        * buffer and a job of its own */
         uint64_t v_cap = (uint64_t)n / 4 + 65536, v_bytes = 0, v_recs = 0, vt[BSC_VAR_N_TOTALS];
@@ -1734,6 +1814,17 @@ int main(int argc, char **argv) {
     }
     asm_at += n_z;
   }
+  if (ze) { /* the epiallele table's last member and its end-of-file marker */
+    void *d_z = NULL;
+    uint64_t n_z = 0;
+    CHECK(bsc_bgzf_close(ze, &d_z, &n_z));
+    ze = NULL;
+    if (n_z) {
+      const out_job j = {d_z, n_z, epi_at, epi_fd, 0};
+      writer_push(&W, j);
+    }
+    epi_at += n_z;
+  }
   if (zv) { /* the variant file's last member and its end-of-file marker; its index */
     void *d_z = NULL;
     uint64_t n_z = 0;
@@ -1804,6 +1895,10 @@ int main(int argc, char **argv) {
   }
   if (asm_fd >= 0 && close(asm_fd)) {
     perror(asm_path);
+    return 1;
+  }
+  if (epi_fd >= 0 && close(epi_fd)) {
+    perror(epi_path);
     return 1;
   }
   if (var_fd >= 0 && close(var_fd)) {
@@ -1944,6 +2039,9 @@ int main(int argc, char **argv) {
     if (asm_path)
       printf("%llu heterozygous SNPs in the allele-specific methylation table, %llu SNP-CpG pairs, %llu lines written (allele observations %llu)\n",
              (unsigned long long)asm_tot[0], (unsigned long long)asm_tot[1], (unsigned long long)asm_lines, (unsigned long long)asm_tot[2]);
+    if (epi_path)
+      printf("%llu windows of four CpGs in the epiallele table, %llu lines written (patterns %llu, templates with one %llu)\n",
+             (unsigned long long)epi_tot[0], (unsigned long long)epi_lines, (unsigned long long)epi_tot[1], (unsigned long long)epi_tot[2]);
     if (mbias_path)
       printf("M-bias table: %llu reads walked, %llu bytes mapped, %llu counted, %llu beyond the table, CpG %llu meth %llu unmeth, %llu reads skipped\n",
              (unsigned long long)mbias_tot[0], (unsigned long long)mbias_tot[1], (unsigned long long)mbias_tot[2], (unsigned long long)mbias_tot[3],
