@@ -258,6 +258,15 @@ EXPORTS = (
     "bsc_block_epi_kept",
     "bsc_epi_stream_read",
     "bsc_epi_stream_detach",
+    "bsc_pat_params_default",
+    "bsc_pat_count_sites",
+    "bsc_pat_recs_host",
+    "bsc_pat_format",
+    "bsc_pat_device",
+    "bsc_pat_text_device",
+    "bsc_block_pat_kept",
+    "bsc_pat_stream_read",
+    "bsc_pat_stream_detach",
     "bsc_asm_params_default",
     "bsc_asm_pairs_host",
     "bsc_asm_format",
@@ -339,6 +348,15 @@ class EpiParams(C.Structure):
 
     def __init__(self, min_cov=10, reserved=0):
         super().__init__(int(min_cov), int(reserved))
+
+
+class PatParams(C.Structure):
+    """bsc_pat_params; the defaults are bsc_pat_params_default's."""
+
+    _fields_ = [("min_sites", C.c_uint32), ("reserved", C.c_uint32)]
+
+    def __init__(self, min_sites=1, reserved=0):
+        super().__init__(int(min_sites), int(reserved))
 
 
 class BwParams(C.Structure):
@@ -940,6 +958,24 @@ def load():
     L.bsc_epi_stream_read.argtypes = [vp, u64, u64, vp]
     L.bsc_epi_stream_detach.restype = i32
     L.bsc_epi_stream_detach.argtypes = [vp, C.POINTER(vp), C.POINTER(u64)]
+    L.bsc_pat_params_default.restype = None
+    L.bsc_pat_params_default.argtypes = [C.POINTER(PatParams)]
+    L.bsc_pat_count_sites.restype = i32
+    L.bsc_pat_count_sites.argtypes = [vp, u64, u64, u64, C.POINTER(u64)]
+    L.bsc_pat_recs_host.restype = i32
+    L.bsc_pat_recs_host.argtypes = [vp, u32, vp, u64, u32, u32, vp, i32, C.POINTER(PatParams), vp, u64, C.POINTER(u64), C.POINTER(u64)]
+    L.bsc_pat_format.restype = C.c_long
+    L.bsc_pat_format.argtypes = [C.c_char_p, u64, vp, C.c_size_t, C.POINTER(PatParams), vp, C.c_size_t, C.POINTER(u64)]
+    L.bsc_pat_device.restype = i32
+    L.bsc_pat_device.argtypes = [vp, vp, u32, vp, u64, u32, u32, vp, C.POINTER(PatParams), vp, u64, vp, vp, vp]
+    L.bsc_pat_text_device.restype = i32
+    L.bsc_pat_text_device.argtypes = [vp, vp, vp, u64, C.c_char_p, u64, C.POINTER(PatParams), vp, u64, vp, vp]
+    L.bsc_block_pat_kept.restype = i32
+    L.bsc_block_pat_kept.argtypes = [vp, C.c_char_p, C.POINTER(PatParams), u64, u64, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)]
+    L.bsc_pat_stream_read.restype = i32
+    L.bsc_pat_stream_read.argtypes = [vp, u64, u64, vp]
+    L.bsc_pat_stream_detach.restype = i32
+    L.bsc_pat_stream_detach.argtypes = [vp, C.POINTER(vp), C.POINTER(u64)]
     L.bsc_asm_params_default.restype = None
     L.bsc_asm_params_default.argtypes = [C.POINTER(AsmParams)]
     L.bsc_asm_pairs_host.restype = i32

@@ -1418,6 +1418,53 @@ class SiteCaller:
             self.synchronize()
         return out[: int(n)].tobytes()
 
+    # -- the per-read CpG pattern table, PAT (csrc/patdev.hip) -----------------------------------------------
+    @staticmethod
+    def _pat_params(params):
+        if params is None:
+            return _lib.PatParams()
+        if isinstance(params, _lib.PatParams):
+            return params
+        return _lib.PatParams(**params)
+
+    def pat_device(self, d_tpl, nr, d_seq, seq_bytes, x, y, d_ref, d_rec, rec_cap, d_n_rec, d_totals, params=None, stream=None):
+        """bsc_pat_device: the inputs of cpg_reads_device -> one bsc_pat_rec per distinct (idx, pattern) of the block in d_rec[<= rec_cap], in
+        the table's order, their count (a device u64) in d_n_rec and the eight totals in d_totals (queued on `stream`; waits once, for the
+        slot count)."""
+        pp = self._pat_params(params)
+        _check(self._L.bsc_pat_device(self._h, d_tpl, nr, d_seq, seq_bytes, x, y, d_ref, C.byref(pp), d_rec, rec_cap, d_n_rec, d_totals, stream))
+
+    def pat_text_device(self, d_rec, d_n_rec, max_rec, contig, index_base, d_out, out_cap, d_totals2, params=None, stream=None):
+        """bsc_pat_text_device: the table's lines of d_rec[min(*d_n_rec, max_rec)] -> d_out[<= out_cap]; d_totals2: {bytes, lines}."""
+        pp = self._pat_params(params)
+        name = contig.encode() if isinstance(contig, str) else contig
+        _check(self._L.bsc_pat_text_device(self._h, d_rec, d_n_rec, max_rec, name, int(index_base), C.byref(pp), d_out, out_cap, d_totals2, stream))
+
+    def block_pat_kept(self, contig, params=None, index_base=0, cap=None, guess=None):
+        """bsc_block_pat_kept + bsc_pat_stream_read: the PAT table of the block the last *_keep call called, from the prepared templates,
+        reads and reference codes it left on the device.  params: a _lib.PatParams, a dict of its fields, or None ({1, 0}).  index_base: the
+        sites of the contig in front of the block's first position.  Returns (bytes, lines, totals[8]).  cap: the room on the device
+        (default: `guess` bytes, or 64 KiB, and where that is too small the room the first call asks for on a second call, which walks and
+        sorts the block again: a caller that knows the last block's need passes a guess above it)."""
+        pp = self._pat_params(params)
+        name = contig.encode() if isinstance(contig, str) else contig
+        nb, nl, tot = C.c_uint64(0), C.c_uint64(0), (C.c_uint64 * 8)()
+        room = (int(guess) if guess else 1 << 16) if cap is None else int(cap)
+        rc = self._L.bsc_block_pat_kept(self._h, name, C.byref(pp), int(index_base), room, C.byref(nb), C.byref(nl), tot)
+        if rc == -1 and nb.value > room and cap is None:
+            room = int(nb.value)
+            rc = self._L.bsc_block_pat_kept(self._h, name, C.byref(pp), int(index_base), room, C.byref(nb), C.byref(nl), tot)
+        _check(rc)
+        return self.pat_stream_read(0, nb.value), int(nl.value), tuple(int(v) for v in tot)
+
+    def pat_stream_read(self, off, n):
+        """bsc_pat_stream_read: bytes [off, off + n) of the table the last block_pat_kept left on the device."""
+        out = np.empty(max(int(n), 1), dtype=np.uint8)
+        _check(self._L.bsc_pat_stream_read(self._h, int(off), int(n), _ptr(out)))
+        if n:
+            self.synchronize()
+        return out[: int(n)].tobytes()
+
     def blocks_records(self, blocks, ref, out=None, all_positions=False, reg_start=1, reg_stop=0xFFFFFFFF, dbsnp=None, with_stats=False,
                        submit_only=False):
         """Several blocks in one launch sequence (bsc_blocks_records): blocks = [(templates, seq, x, y), ...] in genome order;
@@ -2021,3 +2068,63 @@ def epi_format_host(contig, recs, params=None, cap=None):
         assert (buf == 0xA5).all()
         return None, int(got)
     return buf[:got].tobytes(), int(t2[1])
+
+
+def pat_recs_host(tpl, seq, x, y, ref, min_qual=20, params=None, cap=None):
+    """The host form of the per-read CpG pattern table (bsc_pat_recs_host; csrc/pat.c): prepared TEMPLATE[nr] + their read bytes, the block
+    x .. y and its reference codes (x .. y + 2) -> (REC records[min(count, cap)], count, totals[8]).  No GPU involved.  cap: the room
+    (default: asked for with a room of 0 first)."""
+    from .pat import REC
+
+    L = _lib.load()
+    tpl = np.ascontiguousarray(tpl, dtype=TEMPLATE)
+    seq = np.ascontiguousarray(seq, dtype=np.uint8)
+    ref = np.ascontiguousarray(ref, dtype=np.uint8)
+    if ref.size < int(y) - int(x) + 2:
+        raise ValueError("ref must hold the codes of x .. y + 1 at least")
+    pp = SiteCaller._pat_params(params)
+    n, tot = C.c_uint64(0), (C.c_uint64 * 8)()
+    if cap is None:
+        _check(L.bsc_pat_recs_host(_ptr(tpl), len(tpl), _ptr(seq), seq.size, int(x), int(y), _ptr(ref), int(min_qual), C.byref(pp), None, 0, C.byref(n),
+                                   tot))
+        cap = int(n.value)
+    room = int(cap)
+    out = np.zeros(max(room, 1), dtype=REC)
+    _check(L.bsc_pat_recs_host(_ptr(tpl), len(tpl), _ptr(seq), seq.size, int(x), int(y), _ptr(ref), int(min_qual), C.byref(pp), _ptr(out), room,
+                               C.byref(n), tot))
+    return out[: min(int(n.value), room)].copy(), int(n.value), tuple(int(v) for v in tot)
+
+
+def pat_format_host(contig, index_base, recs, params=None, cap=None):
+    """bsc_pat_format: the table's lines of REC records -> (bytes, lines).  cap: the room (default: asked for first); a room too small gives
+    (None, the length needed)."""
+    from .pat import REC
+
+    L = _lib.load()
+    recs = np.ascontiguousarray(recs, dtype=REC)
+    pp = SiteCaller._pat_params(params)
+    name = contig.encode() if isinstance(contig, str) else contig
+    t2 = (C.c_uint64 * 2)()
+    if cap is None:
+        need = L.bsc_pat_format(name, int(index_base), _ptr(recs), len(recs), C.byref(pp), None, 0, t2)
+        if need < 0:
+            _check(int(need))
+        cap = int(need)
+    buf = np.full(max(int(cap), 1) + 8, 0xA5, dtype=np.uint8)
+    got = L.bsc_pat_format(name, int(index_base), _ptr(recs), len(recs), C.byref(pp), _ptr(buf), int(cap), t2)
+    if got < 0:
+        _check(int(got))
+    assert (buf[int(cap) :] == 0xA5).all() and int(t2[0]) == got
+    if got > int(cap):
+        assert (buf == 0xA5).all()
+        return None, int(got)
+    return buf[:got].tobytes(), int(t2[1])
+
+
+def pat_count_sites(codes, start, stop):
+    """bsc_pat_count_sites: the sites p with start <= p < stop (positions, 1 first) over a contig's codes as bsc_fasta_contig gives them."""
+    L = _lib.load()
+    codes = np.ascontiguousarray(codes, dtype=np.uint8)
+    n = C.c_uint64(0)
+    _check(L.bsc_pat_count_sites(_ptr(codes), codes.size, int(start), int(stop), C.byref(n)))
+    return int(n.value)

@@ -136,6 +136,16 @@ int bsc_dev_launch_epi_walk(const void *tpl, uint32_t nr, const void *seq, uint6
 int bsc_dev_launch_epi_text(const void *win, const void *n_win, uint64_t max_win, const char *contig, uint32_t contig_len, uint32_t min_cov,
                             void *tile_bytes, void *tile_off, void *line_len, void *scan_tmp, size_t scan_tmp_bytes, void *out, uint64_t out_cap,
                             void *totals2, int num_cus, void *stream);
+int bsc_dev_launch_pat_slots(const void *tpl, uint32_t nr, uint64_t seq_bytes, uint32_t x, uint32_t y, const void *tile_off, const void *tile_mask,
+                             void *cnt, void *slot_off, void *scan_tmp, size_t scan_tmp_bytes, void *n_sites, int num_cus, void *stream); /* patdev.hip */
+int bsc_dev_launch_pat_walk(const void *tpl, uint32_t nr, const void *seq, uint64_t seq_bytes, uint32_t x, uint32_t y, uint32_t min_qual,
+                            uint32_t min_sites, const void *tile_off, const void *tile_mask, const void *slot_off, uint32_t n_slots, void *slots,
+                            void *sorted, void *sort_tmp, size_t sort_tmp_bytes, void *flag, void *num, void *first, void *scan_tmp,
+                            size_t scan_tmp_bytes, void *rec, uint64_t cap, void *n_rec, void *totals, int num_cus, void *stream);
+int bsc_dev_launch_pat_text(const void *rec, const void *n_rec, uint64_t max_rec, const char *contig, uint32_t contig_len, uint64_t index_base,
+                            void *tile_bytes, void *tile_off, void *line_len, void *scan_tmp, size_t scan_tmp_bytes, void *out, uint64_t out_cap,
+                            void *totals2, int num_cus, void *stream);
+int bsc_dev_sort_pat_tmp_bytes(uint32_t n, size_t *bytes); /* sort.hip */
 int bsc_dev_launch_asm_snps(const void *core, const void *emit, uint32_t n, uint32_t min_phred, int pass_only, void *snp_cnt, void *snp_off, void *snp_mask,
                             void *scan_tmp, size_t scan_tmp_bytes, int num_cus, void *stream); /* asmdev.hip */
 int bsc_dev_launch_asm_spans(uint32_t n, uint32_t W, uint32_t n_snps, const void *snp_off, const void *snp_mask, const void *tile_off, const void *tile_mask,
@@ -367,6 +377,15 @@ struct bsc_context {
     size_t cap_tb, cap_to, cap_ttmp, cap_len, cap_win, cap_tot, cap_out;
     uint64_t bytes;
   } ep;
+  struct { /* the per-read CpG pattern table (patdev.hip): the templates' slot counts, their offsets and that scan's scratch; the site count; the
+            * slots as written and as sorted, the sort's scratch; the head flags, their numbers, the heads' slots and that scan's scratch; the
+            * text encoder's four; bsc_block_pat_kept: the records, {count, eight totals, bytes, lines}, the table and its length */
+    void *d_cnt, *d_soff, *d_stmp, *d_ns, *d_slots, *d_sorted, *d_sort, *d_flag, *d_num, *d_first, *d_ftmp, *d_tb, *d_to, *d_ttmp, *d_len, *d_rec, *d_tot,
+        *d_out;
+    size_t cap_cnt, cap_soff, cap_stmp, cap_ns, cap_slots, cap_sorted, cap_sort, cap_flag, cap_num, cap_first, cap_ftmp, cap_tb, cap_to, cap_ttmp, cap_len,
+        cap_rec, cap_tot, cap_out;
+    uint64_t bytes;
+  } pt;
   struct { /* streams handed to the caller (bsc_bcf_stream_detach) come back here (bsc_detached_free) and are taken again by the next block:
             * no hipMalloc / hipFree — a device-wide wait — in the steady state of a run that writes behind the calling */
     void *p[4];
@@ -803,6 +822,24 @@ int bsc_destroy(bsc_context *ctx) {
   hipFree(ctx->ep.d_win);
   hipFree(ctx->ep.d_tot);
   hipFree(ctx->ep.d_out);
+  hipFree(ctx->pt.d_cnt);
+  hipFree(ctx->pt.d_soff);
+  hipFree(ctx->pt.d_stmp);
+  hipFree(ctx->pt.d_ns);
+  hipFree(ctx->pt.d_slots);
+  hipFree(ctx->pt.d_sorted);
+  hipFree(ctx->pt.d_sort);
+  hipFree(ctx->pt.d_flag);
+  hipFree(ctx->pt.d_num);
+  hipFree(ctx->pt.d_first);
+  hipFree(ctx->pt.d_ftmp);
+  hipFree(ctx->pt.d_tb);
+  hipFree(ctx->pt.d_to);
+  hipFree(ctx->pt.d_ttmp);
+  hipFree(ctx->pt.d_len);
+  hipFree(ctx->pt.d_rec);
+  hipFree(ctx->pt.d_tot);
+  hipFree(ctx->pt.d_out);
   hipFree(ctx->asm_.d_scnt);
   hipFree(ctx->asm_.d_soff);
   hipFree(ctx->asm_.d_smask);
@@ -5768,6 +5805,179 @@ int bsc_epi_stream_detach(bsc_context *ctx, void **d_stream, uint64_t *n_bytes) 
   ctx->ep.d_out = NULL;
   ctx->ep.cap_out = 0;
   ctx->ep.bytes = 0;
+  return BSC_OK;
+}
+
+/* ---- the per-read CpG pattern table (patdev.hip): include/bscall_amd.h has the rule, csrc/pat.c the host form ------------------------------------- */
+static int bsc_pat_params_check(const char *who, const bsc_pat_params *p) {
+  if (!p) return bsc_fail(BSC_ERR_ARG, "%s: NULL argument", who);
+  if (p->reserved) return bsc_fail(BSC_ERR_ARG, "%s: reserved is %u, not 0", who, p->reserved);
+  return BSC_OK;
+}
+
+/* the site pass, the slot pass and its scan on stream s, in the context's workspaces: *n_slots, waited for.  Writes nothing of the caller's */
+static int bsc_pat_count(bsc_context *ctx, const char *who, const void *d_tpl, uint32_t nr, uint64_t seq_bytes, uint32_t x, uint32_t y, const void *d_ref,
+                         uint64_t *n_slots, hipStream_t s) {
+  size_t scan_bytes = 0;
+  int rc;
+  *n_slots = 0;
+  if (nr == 0xffffffffu) return bsc_fail(BSC_ERR_RANGE, "%s: 2^32 - 1 templates", who);
+  if ((rc = bsc_cr_sites_run(ctx, who, d_ref, y - x + 1u, s))) return rc;
+  if (bsc_dev_scan_tmp_bytes_u64(nr + 1u, &scan_bytes)) return bsc_fail(BSC_ERR_HIP, "%s: scan size query failed", who);
+  if ((rc = bsc_reserve(&ctx->pt.d_cnt, &ctx->pt.cap_cnt, ((size_t)nr + 1u) * 8u))) return rc;
+  if ((rc = bsc_reserve(&ctx->pt.d_soff, &ctx->pt.cap_soff, ((size_t)nr + 1u) * 8u))) return rc;
+  if ((rc = bsc_reserve(&ctx->pt.d_stmp, &ctx->pt.cap_stmp, scan_bytes ? scan_bytes : 1))) return rc;
+  if ((rc = bsc_reserve(&ctx->pt.d_ns, &ctx->pt.cap_ns, sizeof(unsigned long long)))) return rc;
+  const int e = bsc_dev_launch_pat_slots(d_tpl, nr, seq_bytes, x, y, ctx->cr.d_off, ctx->cr.d_mask, ctx->pt.d_cnt, ctx->pt.d_soff, ctx->pt.d_stmp, scan_bytes,
+                                         ctx->pt.d_ns, ctx->num_cus, (void *)s);
+  if (e) return bsc_fail(BSC_ERR_HIP, "%s: slot pass launch failed: %s", who, hipGetErrorString((hipError_t)e));
+  unsigned long long ns = 0;
+  HIP_TRY(hipMemcpyAsync(&ns, (const unsigned long long *)ctx->pt.d_soff + nr, sizeof ns, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  if (ns > 0xffffffffull) return bsc_fail(BSC_ERR_RANGE, "%s: %llu slots in one block, more than 2^32 - 1", who, ns);
+  *n_slots = ns;
+  return BSC_OK;
+}
+
+/* the walk, the sort, the heads and the records behind bsc_pat_count; d_totals: eight u64, zeroed here */
+static int bsc_pat_fill(bsc_context *ctx, const char *who, const void *d_tpl, uint32_t nr, const void *d_seq, uint64_t seq_bytes, uint32_t x, uint32_t y,
+                        const bsc_pat_params *p, uint64_t n_slots, void *d_rec, uint64_t cap, void *d_n_rec, void *d_totals, hipStream_t s) {
+  int rc;
+  const uint32_t n = (uint32_t)n_slots;
+  size_t scan_bytes = 0, sort_bytes = 0;
+  if (n) { /* every workspace first: a refusal for want of memory has written nothing of the caller's */
+    if (bsc_dev_scan_tmp_bytes(n, &scan_bytes) || bsc_dev_sort_pat_tmp_bytes(n, &sort_bytes)) return bsc_fail(BSC_ERR_HIP, "%s: scratch size query failed", who);
+    if ((rc = bsc_reserve(&ctx->pt.d_slots, &ctx->pt.cap_slots, (size_t)n * sizeof(bsc_pat_rec)))) return rc;
+    if ((rc = bsc_reserve(&ctx->pt.d_sorted, &ctx->pt.cap_sorted, (size_t)n * sizeof(bsc_pat_rec)))) return rc;
+    if ((rc = bsc_reserve(&ctx->pt.d_sort, &ctx->pt.cap_sort, sort_bytes ? sort_bytes : 1))) return rc;
+    if ((rc = bsc_reserve(&ctx->pt.d_flag, &ctx->pt.cap_flag, (size_t)n * 4u))) return rc;
+    if ((rc = bsc_reserve(&ctx->pt.d_num, &ctx->pt.cap_num, (size_t)n * 4u))) return rc;
+    if ((rc = bsc_reserve(&ctx->pt.d_first, &ctx->pt.cap_first, ((size_t)n + 1u) * 4u))) return rc;
+    if ((rc = bsc_reserve(&ctx->pt.d_ftmp, &ctx->pt.cap_ftmp, scan_bytes ? scan_bytes : 1))) return rc;
+  }
+  HIP_TRY(hipMemsetAsync(d_totals, 0, BSC_PAT_N_TOTALS * sizeof(unsigned long long), s));
+  HIP_TRY(hipMemcpyAsync((unsigned long long *)d_totals + 7, ctx->pt.d_ns, sizeof(unsigned long long), hipMemcpyDeviceToDevice, s));
+  if (!n) {
+    HIP_TRY(hipMemsetAsync(d_n_rec, 0, sizeof(unsigned long long), s));
+    return BSC_OK;
+  }
+  const int e = bsc_dev_launch_pat_walk(d_tpl, nr, d_seq, seq_bytes, x, y, (uint32_t)ctx->params.min_qual, p->min_sites, ctx->cr.d_off, ctx->cr.d_mask,
+                                        ctx->pt.d_soff, n, ctx->pt.d_slots, ctx->pt.d_sorted, ctx->pt.d_sort, sort_bytes, ctx->pt.d_flag, ctx->pt.d_num,
+                                        ctx->pt.d_first, ctx->pt.d_ftmp, scan_bytes, d_rec, cap, d_n_rec, d_totals, ctx->num_cus, (void *)s);
+  if (e) return bsc_fail(BSC_ERR_HIP, "%s: walk launch failed: %s", who, hipGetErrorString((hipError_t)e));
+  return BSC_OK;
+}
+
+int bsc_pat_device(bsc_context *ctx, const void *d_tpl, uint32_t nr, const void *d_seq, uint64_t seq_bytes, uint32_t x, uint32_t y, const void *d_ref,
+                   const bsc_pat_params *p, void *d_rec, uint64_t rec_cap, void *d_n_rec, void *d_totals, void *stream) {
+  static const char who[] = "bsc_pat_device";
+  int rc;
+  if (!ctx || !d_ref || !d_n_rec || !d_totals || (nr && (!d_tpl || !d_seq)) || (rec_cap && !d_rec)) return bsc_fail(BSC_ERR_ARG, "%s: NULL argument", who);
+  if ((rc = bsc_pat_params_check(who, p))) return rc;
+  if (y < x) return bsc_fail(BSC_ERR_ARG, "%s: y (%u) < x (%u)", who, y, x);
+  if ((uint64_t)y - x + 1 > 0x0fffffffull) return bsc_fail(BSC_ERR_ARG, "%s: block longer than 2^28 - 1 positions", who);
+  if ((((uintptr_t)d_tpl | (uintptr_t)d_rec | (uintptr_t)d_n_rec | (uintptr_t)d_totals) & 7u))
+    return bsc_fail(BSC_ERR_ARG, "%s: the templates, the records, the count and the totals must be 8-byte aligned", who);
+  BSC_ENTER(ctx);
+  hipStream_t s = (hipStream_t)stream;
+  uint64_t n_slots = 0;
+  if ((rc = bsc_pat_count(ctx, who, d_tpl, nr, seq_bytes, x, y, d_ref, &n_slots, s))) return rc;
+  return bsc_pat_fill(ctx, who, d_tpl, nr, d_seq, seq_bytes, x, y, p, n_slots, d_rec, rec_cap, d_n_rec, d_totals, s);
+}
+
+int bsc_pat_text_device(bsc_context *ctx, const void *d_rec, const void *d_n_rec, uint64_t max_rec, const char *contig, uint64_t index_base,
+                        const bsc_pat_params *p, void *d_out, uint64_t out_cap, void *d_totals2, void *stream) {
+  static const char who[] = "bsc_pat_text_device";
+  uint32_t contig_len = 0;
+  int rc;
+  if (!ctx || !d_n_rec || !d_totals2 || (max_rec && !d_rec) || (out_cap && !d_out)) return bsc_fail(BSC_ERR_ARG, "%s: NULL argument", who);
+  if ((rc = bsc_pat_params_check(who, p))) return rc;
+  if ((rc = bsc_contig_check(who, contig, &contig_len))) return rc;
+  if (index_base > (1ull << 63)) return bsc_fail(BSC_ERR_ARG, "%s: index_base above 2^63", who);
+  if (((uintptr_t)d_out & 15u) || (((uintptr_t)d_rec | (uintptr_t)d_n_rec | (uintptr_t)d_totals2) & 7u))
+    return bsc_fail(BSC_ERR_ARG, "%s: d_out must be 16-byte, the records, the count and the totals 8-byte aligned", who);
+  if ((max_rec + 63u) / 64u > 0x7ffffffeull) return bsc_fail(BSC_ERR_ARG, "%s: more than 2^37 records", who);
+  BSC_ENTER(ctx);
+  hipStream_t s = (hipStream_t)stream;
+  const uint32_t n_tiles = (uint32_t)((max_rec + 63u) / 64u);
+  size_t scan_bytes = 0;
+  if (bsc_dev_scan_tmp_bytes_u64(n_tiles + 1u, &scan_bytes)) return bsc_fail(BSC_ERR_HIP, "%s: scan size query failed", who);
+  if ((rc = bsc_reserve(&ctx->pt.d_tb, &ctx->pt.cap_tb, ((size_t)n_tiles + 1u) * 8u))) return rc;
+  if ((rc = bsc_reserve(&ctx->pt.d_to, &ctx->pt.cap_to, ((size_t)n_tiles + 1u) * 8u))) return rc;
+  if ((rc = bsc_reserve(&ctx->pt.d_ttmp, &ctx->pt.cap_ttmp, scan_bytes ? scan_bytes : 1))) return rc;
+  if ((rc = bsc_reserve(&ctx->pt.d_len, &ctx->pt.cap_len, ((size_t)n_tiles + 1u) * 128u))) return rc;
+  HIP_TRY(hipMemsetAsync(d_totals2, 0, 2 * sizeof(unsigned long long), s));
+  const int e = bsc_dev_launch_pat_text(d_rec, d_n_rec, max_rec, contig, contig_len, index_base, ctx->pt.d_tb, ctx->pt.d_to, ctx->pt.d_len, ctx->pt.d_ttmp,
+                                        scan_bytes, d_out, out_cap, d_totals2, ctx->num_cus, stream);
+  if (e) return bsc_fail(BSC_ERR_HIP, "%s: encoder launch failed: %s", who, hipGetErrorString((hipError_t)e));
+  return BSC_OK;
+}
+
+int bsc_block_pat_kept(bsc_context *ctx, const char *contig, const bsc_pat_params *p, uint64_t index_base, uint64_t dev_cap, uint64_t *n_bytes,
+                       uint64_t *n_lines, uint64_t totals[8]) {
+  static const char who[] = "bsc_block_pat_kept";
+  int rc;
+  uint32_t contig_len = 0;
+  if (!ctx || !n_bytes || !n_lines) return bsc_fail(BSC_ERR_ARG, "%s: NULL argument", who);
+  *n_bytes = *n_lines = 0;
+  for (int k = 0; totals && k < BSC_PAT_N_TOTALS; k++) totals[k] = 0;
+  if ((rc = bsc_pat_params_check(who, p))) return rc;
+  if ((rc = bsc_contig_check(who, contig, &contig_len))) return rc;
+  if (index_base > (1ull << 63)) return bsc_fail(BSC_ERR_ARG, "%s: index_base above 2^63", who);
+  if (ctx->meth_src != 1 || ctx->rec_pending || ctx->pending_sz)
+    return bsc_fail(BSC_ERR_ARG, "%s: the last call left no single block's arrays on the device", who);
+  if (!ctx->cr.src_ok) return bsc_fail(BSC_ERR_ARG, "%s: the last block's prepared templates, reads and reference are no longer on the device", who);
+  BSC_ENTER(ctx);
+  hipStream_t s = ctx->stream;
+  ctx->pt.bytes = 0;
+  const uint32_t x = ctx->cr.src_x, y = ctx->cr.src_y, nr = ctx->cr.src_nr;
+  /* d_tot: [0] the count, [1 .. 8] the totals, [9 .. 10] the encoder's {bytes, lines} */
+  if ((rc = bsc_reserve(&ctx->pt.d_tot, &ctx->pt.cap_tot, 11 * sizeof(unsigned long long)))) return rc;
+  unsigned long long *const d_tot = (unsigned long long *)ctx->pt.d_tot;
+  uint64_t n_slots = 0;
+  if ((rc = bsc_pat_count(ctx, who, ctx->d_tpl, nr, ctx->cr.src_seq_bytes, x, y, ctx->d_ref, &n_slots, s))) return rc;
+  /* the records are no more than the slots */
+  if ((rc = bsc_reserve(&ctx->pt.d_rec, &ctx->pt.cap_rec, (size_t)(n_slots ? n_slots : 1) * sizeof(bsc_pat_rec)))) return rc;
+  if ((rc = bsc_pat_fill(ctx, who, ctx->d_tpl, nr, ctx->d_seq, ctx->cr.src_seq_bytes, x, y, p, n_slots, ctx->pt.d_rec, n_slots, d_tot, d_tot + 1, s))) return rc;
+  /* a buffer that came back (bsc_detached_free), the smallest that will do, as d_meth is taken */
+  if (!ctx->pt.d_out && ctx->pool_mu_made) ctx->pt.d_out = bsc_pool_get(ctx, (size_t)(dev_cap ? dev_cap : 1), &ctx->pt.cap_out);
+  if ((rc = bsc_reserve(&ctx->pt.d_out, &ctx->pt.cap_out, (size_t)(dev_cap ? dev_cap : 1)))) return rc;
+  if ((rc = bsc_pat_text_device(ctx, ctx->pt.d_rec, d_tot, n_slots, contig, index_base, p, ctx->pt.d_out, dev_cap, d_tot + 9, s))) return rc;
+  unsigned long long tot[11] = {0};
+  HIP_TRY(hipMemcpyAsync(tot, d_tot, sizeof tot, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  *n_bytes = tot[9];
+  *n_lines = tot[10];
+  for (int k = 0; totals && k < BSC_PAT_N_TOTALS; k++) totals[k] = tot[1 + k];
+  if (tot[0] > n_slots) return bsc_fail(BSC_ERR_RANGE, "%s: %llu records of %llu slots", who, tot[0], (unsigned long long)n_slots);
+  if (tot[9] > dev_cap) return bsc_fail(BSC_ERR_ARG, "%s: the block's table has %llu bytes, dev_cap is %llu", who, tot[9], (unsigned long long)dev_cap);
+  ctx->pt.bytes = tot[9];
+  return BSC_OK;
+}
+
+int bsc_pat_stream_read(bsc_context *ctx, uint64_t off, uint64_t n, void *dst) {
+  if (!ctx || (!dst && n)) return bsc_fail(BSC_ERR_ARG, "bsc_pat_stream_read: NULL argument");
+  if (off + n < off || off + n > ctx->pt.bytes || off + n > ctx->pt.cap_out) return bsc_fail(BSC_ERR_ARG, "bsc_pat_stream_read: beyond the table's end");
+  if (!n) return BSC_OK;
+  BSC_ENTER(ctx);
+  HIP_TRY(hipMemcpyAsync(dst, (const char *)ctx->pt.d_out + off, (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+  return BSC_OK;
+}
+
+int bsc_pat_stream_detach(bsc_context *ctx, void **d_stream, uint64_t *n_bytes) {
+  if (!ctx || !d_stream || !n_bytes) return bsc_fail(BSC_ERR_ARG, "bsc_pat_stream_detach: NULL argument");
+  *d_stream = NULL;
+  *n_bytes = 0;
+  if (!ctx->pt.d_out || !ctx->pt.bytes) return bsc_fail(BSC_ERR_ARG, "bsc_pat_stream_detach: the last call left no table on the device");
+  BSC_ENTER(ctx);
+  bsc_pool_init(ctx);
+  if (!ctx->s_det) HIP_TRY(hipStreamCreateWithFlags(&ctx->s_det, hipStreamNonBlocking));
+  *d_stream = ctx->pt.d_out;
+  *n_bytes = ctx->pt.bytes;
+  bsc_pool_book(ctx, ctx->pt.d_out, ctx->pt.cap_out);
+  ctx->pt.d_out = NULL;
+  ctx->pt.cap_out = 0;
+  ctx->pt.bytes = 0;
   return BSC_OK;
 }
 

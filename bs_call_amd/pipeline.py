@@ -10,7 +10,7 @@ import numpy as np
 
 from . import _lib, report, vcf
 from .bam import BamReader, block_reference
-from .caller import ReadProfile, SiteCaller, gc_bins, prepare_templates
+from .caller import ReadProfile, SiteCaller, gc_bins, pat_count_sites, prepare_templates
 
 
 def run(bam_path: str, reference: Dict[str, np.ndarray], bcf_path: str, sample: str = "SAMPLE", report_path: Optional[str] = None,
@@ -23,7 +23,8 @@ def run(bam_path: str, reference: Dict[str, np.ndarray], bcf_path: str, sample: 
         bigwig_section: int = 1024, bigwig_zoom: int = 1024, bigwig_compress: bool = False, bigbed_path: Optional[str] = None, bigbed_items: int = 512,
         bigbed_zoom: int = 1024, bigbed_compress: bool = False, meth_index: Optional[str] = None, variants_path: Optional[str] = None,
         variants_params=None, cpg_reads_path: Optional[str] = None, cpg_reads_params=None, asm_path: Optional[str] = None, asm_params=None,
-        mbias_path: Optional[str] = None, mbias_params=None, epi_path: Optional[str] = None, epi_params=None, **reader_kw) -> dict:
+        mbias_path: Optional[str] = None, mbias_params=None, epi_path: Optional[str] = None, epi_params=None,
+        pat_path: Optional[str] = None, pat_params=None, **reader_kw) -> dict:
     """reference: contig name -> uint8 reference codes (0 = N, 1..4 = ACGT; position 1 first).  Returns a summary dict.
     under_conv / over_conv / min_qual (defaults 0.01 / 0.05 / 20, src/init_param.c:26-31) are the MODEL's parameters: without
     `caller` the run builds its SiteCaller from them; with one, they are taken from it and a differing explicit value is an error
@@ -100,7 +101,16 @@ def run(bam_path: str, reference: Dict[str, np.ndarray], bcf_path: str, sample: 
     reference CpGs, the templates that show each of the 16 methylation patterns, from the prepared templates, reads and reference codes the
     block left on the device (SiteCaller.block_epi_kept, csrc/epidev.hip) — plain text, or BGZF where `compressed` says so or the name ends
     in .gz.  epi_params: a _lib.EpiParams or a dict of min_cov.  The summary gets "epi_lines" and "epi_totals" (the eight totals of the
-    rule).  The same conditions as meth_path."""
+    rule).  The same conditions as meth_path.
+    pat_path: the per-read CpG pattern table (PAT) of the same run (include/bscall_amd.h has the rule): behind every block the templates'
+    methylation strings over the reference CpGs they cover, collapsed, counted and sorted on the device (SiteCaller.block_pat_kept,
+    csrc/patdev.hip) — `chrom index pattern count`, wgbstools-unpinned bytes, the index the CpG's 1-based ordinal within its contig, 64 CpGs a
+    line at the most; plain text, or BGZF where `compressed` says so or the name ends in .gz.  pat_params: a _lib.PatParams or a dict of
+    min_sites.  The summary gets "pat_lines" and "pat_totals" (the eight totals of the rule).  Refused where epi_path is."""
+    if pat_params is not None and pat_path is None:
+        raise ValueError("pat_params are thresholds of the table pat_path names: they need pat_path")
+    if pat_path is not None and (shard_rank is not None or not device_reader or host_prep or host_bcf):
+        raise ValueError("pat_path is a single run on the device reader (device_reader=True, no shard_rank, no host_prep / host_bcf)")
     if epi_params is not None and epi_path is None:
         raise ValueError("epi_params are thresholds of the table epi_path names: they need epi_path")
     if epi_path is not None and (shard_rank is not None or not device_reader or host_prep or host_bcf):
@@ -213,6 +223,7 @@ def run(bam_path: str, reference: Dict[str, np.ndarray], bcf_path: str, sample: 
         reads_blobs, reads_lines, reads_totals = [], 0, np.zeros(8, dtype=np.uint64)
         asm_blobs, asm_lines, asm_totals = [], 0, np.zeros(8, dtype=np.uint64)
         epi_blobs, epi_lines, epi_totals = [], 0, np.zeros(8, dtype=np.uint64)
+        pat_blobs, pat_lines, pat_totals = [], 0, np.zeros(8, dtype=np.uint64)
         mbias_any = False
         if mbias_path is not None:
             c.mbias_reset()
@@ -273,8 +284,10 @@ def run(bam_path: str, reference: Dict[str, np.ndarray], bcf_path: str, sample: 
                 region_cur = None
 
             def block_blobs():
-                nonlocal n_blocks, n_records, base_filter, passed, meth_lines, region_cur, bw_sites, cov_sites, bb_sites, var_totals, reads_lines, reads_totals, asm_lines, asm_totals, mbias_any, epi_lines, epi_totals
+                nonlocal n_blocks, n_records, base_filter, passed, meth_lines, region_cur, bw_sites, cov_sites, bb_sites, var_totals, reads_lines, reads_totals, asm_lines, asm_totals, mbias_any, epi_lines, epi_totals, pat_lines, pat_totals
                 before, cur_tid = c.site_totals(), -1
+                pat_base, pat_from = 0, 1  # the contig's CpGs in front of position pat_from
+                pat_room = 8.0  # the table's room in bytes a position: a quarter above the last block's need, so that a block is walked once
                 for item in (rd.device_blocks() if device_reader else rd.blocks()):
                     if device_reader:
                         dblk = item
@@ -288,6 +301,7 @@ def run(bam_path: str, reference: Dict[str, np.ndarray], bcf_path: str, sample: 
                             per_contig.append((refs[cur_tid][0], after - before))
                             before = after
                         cur_tid = tid
+                        pat_base, pat_from = 0, 1
                         if want_regions:
                             regions_flush()
                             if meth_window is not None:
@@ -322,7 +336,8 @@ def run(bam_path: str, reference: Dict[str, np.ndarray], bcf_path: str, sample: 
                             blob, n_rec, st = c.block_bcf_rawdev(dblk, ref, tid, names=names, left_trim=left_trim, right_trim=right_trim, min_qual=min_qual,
                                                                  reg_stop=len(codes), dbsnp=flags, with_stats=True, profile=prof,
                                                                  keep=meth_path is not None or want_regions or want_bw or want_cov or want_bb or variants_path is not None
-                                                                 or cpg_reads_path is not None or asm_path is not None or mbias_path is not None or epi_path is not None)
+                                                                 or cpg_reads_path is not None or asm_path is not None or mbias_path is not None or epi_path is not None
+                                                                 or pat_path is not None)
                         if mbias_path is not None:  # the block's raw templates, still in the reader's buffers, into the run's accumulator
                             c.block_mbias_rawdev(dblk.d_tpl, dblk.nr, dblk.d_seq, dblk.seq_bytes, dblk.d_misms, dblk.n_misms, mbias_cycles)
                             mbias_any = True
@@ -382,6 +397,14 @@ def run(bam_path: str, reference: Dict[str, np.ndarray], bcf_path: str, sample: 
                             epi_blobs.append(eb)
                             epi_lines += el
                             epi_totals += np.array(et, dtype=np.uint64)
+                        if pat_path is not None:  # the same block's pattern table; its index counts the contig's CpGs
+                            pat_base += pat_count_sites(codes, pat_from, x)
+                            pat_from = x
+                            pb, pl, pt = c.block_pat_kept(name, pat_params, index_base=pat_base, guess=int((y - x + 1) * pat_room) + 4096)
+                            pat_room = 1.25 * len(pb) / (y - x + 1) + 1.0
+                            pat_blobs.append(pb)
+                            pat_lines += pl
+                            pat_totals += np.array(pt, dtype=np.uint64)
                         recs = None
                     elif host_prep:  # round 4's split: the process thread's per-template work here, then the block
                         tpl, pseq, st = prepare_templates(raw, seq, ms, left_trim, right_trim, min_qual, profile=prof, x=x, ref=ref)
@@ -446,6 +469,8 @@ def run(bam_path: str, reference: Dict[str, np.ndarray], bcf_path: str, sample: 
                 vcf.write_vcf_blobs(asm_path, "", asm_blobs, compressed)
             if epi_path is not None:
                 vcf.write_vcf_blobs(epi_path, "", epi_blobs, compressed or str(epi_path).endswith(".gz"))
+            if pat_path is not None:
+                vcf.write_vcf_blobs(pat_path, "", pat_blobs, compressed or str(pat_path).endswith(".gz"))
             if mbias_path is not None:  # a run without a block has no accumulator: the header alone
                 mbias_counts, mbias_totals = c.mbias_read(mbias_cycles) if mbias_any else (_mbias.empty(mbias_cycles)[0], (0,) * 8)
                 c.mbias_reset()
@@ -539,6 +564,9 @@ def run(bam_path: str, reference: Dict[str, np.ndarray], bcf_path: str, sample: 
         if epi_path is not None:
             summary["epi_lines"] = epi_lines
             summary["epi_totals"] = tuple(int(v) for v in epi_totals)
+        if pat_path is not None:
+            summary["pat_lines"] = pat_lines
+            summary["pat_totals"] = tuple(int(v) for v in pat_totals)
         if mbias_path is not None:
             summary["mbias_totals"] = tuple(int(v) for v in mbias_totals)
         if want_bw:

@@ -2058,7 +2058,8 @@ int bsc_mbias_reset(bsc_context *ctx);
  *   bsc_epi_stream_read      bytes [off, off + n) of that table -> dst, queued on the context's stream
  *   bsc_epi_stream_detach    the table handed over as bsc_cpg_reads_stream_detach hands one over: bsc_detached_read / _wait / _free and
  *                            bsc_bgzf_write_device serve it; it counts against the four pooled buffers
- * Not built: K != 4, non-CpG contexts, sharded runs, the batched and host-buffer block entries, a tabix index of the table, float columns.
+ * Not built: K != 4 (the pattern table below has every template's whole string), non-CpG contexts, sharded runs, the batched and host-buffer
+ * block entries, a tabix index of the table, float columns.
  */
 #define BSC_EPI_K 4
 typedef struct {
@@ -2083,6 +2084,94 @@ int bsc_block_epi_kept(bsc_context *ctx, const char *contig, const bsc_epi_param
                        uint64_t totals[8]);
 int bsc_epi_stream_read(bsc_context *ctx, uint64_t off, uint64_t n, void *dst);
 int bsc_epi_stream_detach(bsc_context *ctx, void **d_stream, uint64_t *n_bytes);
+
+/*
+ * The per-read CpG pattern table, PAT (csrc/patdev.hip: the slot pass, the walk, the heads and the text encoder, behind the site pass and the
+ * scan of csrc/cpgreadsdev.hip, with the radix sort of csrc/sort.hip between walk and heads; csrc/pat.c holds the host form, which is their
+ * checker; bs_call_amd/pat.py the Python rule).  For every template the string of methylated / unmethylated calls over the reference CpGs it
+ * covers, identical strings collapsed and counted: `chrom  CpG-index  pattern  count`, patterns in C / T / ., lines sorted by index, then
+ * pattern — the interchange format of the read-level methylation tools (wgbstools and what is built on it).  It is the general form of the
+ * read-level table's pairs and of the epiallele table's K = 4.  The bytes are WGBSTOOLS-UNPINNED: no copy of that tool is at hand, the format
+ * is written from its description.  wgbstools counts CpGs genome-wide; this table's index is the CpG's 1-based ordinal within its CONTIG
+ * (bs_call_amd/pat.py has contig_offsets(fasta) and shift(lines, offset) to convert).  The reference has no such output: the rule is this
+ * project's own.
+ *
+ * COUNTS, SITE, BYTE(t, q) and STATE(t, s) are those of the read-level CpG table above, word for word, and the inputs are those of
+ * bsc_cpg_reads_device.
+ * ORDINAL   The block's sites in ascending order are s_0 < ... < s_{S-1}; the ordinal of s_i is i.
+ * PATTERN(t)  Let f and l be the first and last ordinals at which template t has a state and k_t the number of sites with a state.  No line
+ *           unless k_t >= max(1, min_sites).  The template's string has l - f + 1 characters: character j is 'C' where STATE(t, s_{f+j}) is
+ *           M, 'T' where it is U and '.' where there is none (a site in a mate gap, a low quality, another base, an overlap: BYTE's rule).
+ * PIECES    A line holds at most BSC_PAT_MAX_SITES = 64 sites, so that a record has a fixed size: the string is cut after every 64th
+ *           character counted from f, each piece is trimmed to its own first and last non-'.' character, a piece with no state gives
+ *           nothing, and a piece's index is the ordinal of its first remaining site.  min_sites is judged on the template, not on a piece.
+ *           A template of at most 64 spanned sites is one piece.  The cut is a limit of this table: a longer molecule's string is spread
+ *           over several lines.
+ * RECORD    bsc_pat_rec {idx, count, hi, lo}, 24 bytes, 8-byte aligned.  Site j of the piece sits in bits 127 - 2j and 126 - 2j of hi:lo,
+ *           codes 1 '.', 2 'C', 3 'T' and 0 behind the last site: the integer order of (idx, hi, lo) is the order of
+ *           `LC_ALL=C sort -k2,2n -k3,3` on the lines.  One record per distinct (idx, hi, lo) of the block, in that order; count = the
+ *           pieces that share the key.  A block whose pieces (on the device: whose slots, one per started 64 sites of a template's span)
+ *           exceed 2^32 - 1 is refused with BSC_ERR_RANGE.
+ * TOTALS    Eight u64, over every record whether stored or not: [0] records, [1] the sum of count (= pieces), [2] templates that gave a
+ *           line, [3] / [4] / [5] the sum of 'C' / 'T' / '.' over pieces, [6] templates cut into more than one piece (l - f + 1 > 64), [7] S.
+ * LINE      chrom \t index_base + idx + 1 \t pattern \t count \n.  index_base (u64; above 2^63 is refused) is the number of sites of the
+ *           contig in front of the block's first position, so that the index is the CpG's 1-based ordinal within its contig.  contig: 1 ..
+ *           255 bytes without tab or newline.  Text totals: {bytes, lines}.
+ * Params    bsc_pat_params {min_sites, reserved}, default {1, 0}.  reserved != 0 is refused with BSC_ERR_ARG.
+ * Not gated by the called genotype, as the read-level table is not.
+ *
+ *   bsc_pat_params_default   {1, 0}
+ *   bsc_pat_count_sites      host: *n = the sites p with from <= p < to (positions, 1 first; from >= 1) over a contig's codes as
+ *                            bsc_fasta_contig gives them.  A C at the contig's last position is no site.  The running index_base of a file.
+ *   bsc_pat_recs_host        the host form (qsort): rec[<= cap] the records, *n_rec their number (records beyond cap are counted, not
+ *                            stored: BSC_OK all the same), totals (eight u64; may be NULL)
+ *   bsc_pat_format           the lines of rec[n] -> buf.  Returns the length; the length needed, with nothing written, when cap is too
+ *                            small; < 0 for a bad argument.  totals2 (may be NULL): {bytes, lines}.  p is checked; no field of it changes a line
+ *   bsc_pat_device           the same records from device-resident inputs (d_tpl 8-byte aligned, d_ref y - x + 3 codes): d_rec[min(count,
+ *                            rec_cap)] (8-byte aligned; nothing is written behind the room), *d_n_rec a device u64 = the count, d_totals
+ *                            eight device u64.  Integer atomic adds alone, and equal keys are indistinguishable: the bytes are a function
+ *                            of the input.  Everything is queued on `stream`; the call waits once, for the slot count that sizes the sort
+ *                            (as bsc_asm_device waits for its counts), and returns with the rest in flight.  Workspaces of the context's
+ *                            (the site masks are the read-level table's), grow-only: one call in flight per context.  A refusal writes
+ *                            nothing.
+ *   bsc_pat_text_device      the lines of d_rec[min(*d_n_rec, max_rec)] -> d_out[<= out_cap] (16-byte aligned).  d_totals2: two device u64
+ *                            {bytes, lines}.  A stream longer than out_cap is cut at a 64-record boundary and its full length is still
+ *                            reported, as the other text encoders do.
+ *   bsc_block_pat_kept       the twin of bsc_block_epi_kept, with its preconditions and refusals: walks the prepared templates, reads and
+ *                            reference codes the last *_keep call left in HBM and writes the table into a buffer of the context's own
+ *                            (room: dev_cap bytes).  dev_cap too small: BSC_ERR_ARG with *n_bytes = the room needed (the totals are
+ *                            filled), and the call may be repeated.  Every other kept output is untouched, before or after.  Waits.
+ *   bsc_pat_stream_read      bytes [off, off + n) of that table -> dst, queued on the context's stream
+ *   bsc_pat_stream_detach    the table handed over as bsc_epi_stream_detach hands one over
+ * Not built: sharded runs, the batched and host-buffer block entries, non-CpG contexts, an index of the table, genome-wide indices in the
+ * run, lines longer than 64 sites.
+ */
+#define BSC_PAT_MAX_SITES 64
+typedef struct {
+  uint32_t idx;   /* the ordinal of the piece's first site */
+  uint32_t count; /* pieces with this (idx, hi, lo) */
+  uint64_t hi;    /* sites 0 .. 31: site j in bits 63 - 2j, 62 - 2j */
+  uint64_t lo;    /* sites 32 .. 63 */
+} bsc_pat_rec;
+typedef struct {
+  uint32_t min_sites; /* PATTERN: k_t >= max(1, min_sites) */
+  uint32_t reserved;  /* 0; anything else is refused */
+} bsc_pat_params;
+#define BSC_PAT_N_TOTALS 8
+void bsc_pat_params_default(bsc_pat_params *p);
+int bsc_pat_count_sites(const uint8_t *codes, uint64_t contig_len, uint64_t from, uint64_t to, uint64_t *n);
+int bsc_pat_recs_host(const bsc_template *tpl, uint32_t nr, const uint8_t *seq, uint64_t seq_bytes, uint32_t x, uint32_t y, const uint8_t *ref,
+                      int32_t min_qual, const bsc_pat_params *p, bsc_pat_rec *rec, uint64_t cap, uint64_t *n_rec, uint64_t totals[8]);
+long bsc_pat_format(const char *contig, uint64_t index_base, const bsc_pat_rec *rec, size_t n, const bsc_pat_params *p, char *buf, size_t cap,
+                    uint64_t totals2[2]);
+int bsc_pat_device(bsc_context *ctx, const void *d_tpl, uint32_t nr, const void *d_seq, uint64_t seq_bytes, uint32_t x, uint32_t y, const void *d_ref,
+                   const bsc_pat_params *p, void *d_rec, uint64_t rec_cap, void *d_n_rec, void *d_totals, void *stream);
+int bsc_pat_text_device(bsc_context *ctx, const void *d_rec, const void *d_n_rec, uint64_t max_rec, const char *contig, uint64_t index_base,
+                        const bsc_pat_params *p, void *d_out, uint64_t out_cap, void *d_totals2, void *stream);
+int bsc_block_pat_kept(bsc_context *ctx, const char *contig, const bsc_pat_params *p, uint64_t index_base, uint64_t dev_cap, uint64_t *n_bytes,
+                       uint64_t *n_lines, uint64_t totals[8]);
+int bsc_pat_stream_read(bsc_context *ctx, uint64_t off, uint64_t n, void *dst);
+int bsc_pat_stream_detach(bsc_context *ctx, void **d_stream, uint64_t *n_bytes);
 
 /*
  * dbSNP index (host C + zlib; csrc/dbsnp.c): the reader of the compressed index bin/dbSNP_idx writes.  In the reference

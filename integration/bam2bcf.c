@@ -122,6 +122,19 @@
  * --meth-epialleles-min-cov n (default 10): the n a line needs.  Refused where --meth-reads is.  Without the switch the program makes the calls
  * it made before the switch existed.
  *
+ * --meth-pat out.pat: the per-read CpG pattern table, PAT (include/bscall_amd.h has the rule) — a line per distinct methylation string of the
+ * block's templates: chrom index pattern count, the pattern in C (methylated) / T (unmethylated) / . (no call) over consecutive reference CpGs
+ * from the index on, identical strings collapsed, lines sorted by index, then pattern: the interchange format of the read-level methylation
+ * tools.  The bytes are wgbstools-unpinned (no copy of that tool is at hand: the format is written from its description), and the index is the
+ * CpG's 1-based ordinal within its CONTIG, not genome-wide (bs_call_amd/pat.py has contig_offsets and shift to convert); a line holds 64 CpGs at
+ * the most, a longer molecule's string is cut.  Behind every block bsc_block_pat_kept walks the prepared templates, reads and reference codes
+ * the block call left in HBM, sorts and collapses on the device; index_base is kept per contig: bsc_pat_count_sites advances it over the stretch
+ * between the previous block's start and this block's, and it is reset at the contig change.  Blocks of a contig do not overlap, so a key never
+ * occurs in two blocks and the concatenated tables are sorted within the contig.  The table is detached (bsc_pat_stream_detach) and goes to
+ * the output thread as one more job for its own file, through a BGZF writer of its own when the name ends in .gz, under -O b or --meth-bgzf.
+ * --meth-pat-min-sites n (default 1): the states a template needs.  Refused where --meth-epialleles is.  Without the switch the program makes
+ * the calls it made before the switch existed.
+ *
  * --mbias out.tsv: the M-bias table (include/bscall_amd.h has the rule) — methylated and unmethylated calls per sequencing cycle, by read 1 /
  * read 2, bisulfite strand and CpG / CHG / CHH, from the RAW templates as sequenced (no trim, clip or overlap edit): what -L / -R and the
  * under-conversion rate are chosen from.  Behind every block bsc_block_mbias_rawdev walks the block's raw arrays, still in the reader's
@@ -182,7 +195,7 @@ static void *pinned(size_t n) { /* page-locked: the copy-out is a true DMA, queu
  * ONE writer: three of them writing pieces of one file in parallel were 2.5 x slower (0.70 s against 0.28 for the 2.9 GB of a contig-sized
  * block: writes to one inode take turns anyway).  Page-locking a host buffer for a whole stream would cost more than the calling. */
 #define PIECE ((size_t)32 << 20)
-#define N_JOB 4 /* (a block is two jobs with --meth, three with --variants beside it, four with --meth-reads, five with --meth-asm, six with --meth-epialleles: a push waits for a
+#define N_JOB 4 /* (a block is two jobs with --meth, three with --variants beside it, four with --meth-reads, five with --meth-asm, six with --meth-epialleles, seven with --meth-pat: a push waits for a
                  * free slot) */
 typedef struct {
   void *d;        /* the stream on the device; NULL: only close_fd */
@@ -589,6 +602,14 @@ int main(int argc, char **argv) {
     fprintf(stderr, "%s: --meth-epialleles takes the path of the epiallele table to write\n", argv[0]);
     return 2;
   }
+  const char *pat_path = NULL; /* --meth-pat out.pat: the per-read CpG pattern table */
+  bsc_pat_params ptpar;
+  bsc_pat_params_default(&ptpar);
+  int pat_opts = 0;
+  if (argc >= 2 && !strcmp(argv[argc - 1], "--meth-pat") && (argc == 2 || strcmp(argv[argc - 2], "--meth-pat"))) {
+    fprintf(stderr, "%s: --meth-pat takes the path of the pattern table to write\n", argv[0]);
+    return 2;
+  }
   const char *mbias_path = NULL; /* --mbias out.tsv: the M-bias table */
   bsc_mbias_params mbpar;
   bsc_mbias_params_default(&mbpar);
@@ -716,6 +737,17 @@ int main(int argc, char **argv) {
       mbpar.n_cycles = (uint32_t)v;
       mbias_opts = 1;
     }
+    else if (!strcmp(argv[1], "--meth-pat")) pat_path = argv[2];
+    else if (!strcmp(argv[1], "--meth-pat-min-sites")) {
+      char *end = NULL;
+      const unsigned long v = strtoul(argv[2], &end, 10);
+      if (!argv[2][0] || *end || argv[2][0] == '-' || v > 0xfffffffful) {
+        fprintf(stderr, "%s: %s takes a count, not '%s'\n", argv[0], argv[1], argv[2]);
+        return 2;
+      }
+      ptpar.min_sites = (uint32_t)v;
+      pat_opts = 1;
+    }
     else if (!strcmp(argv[1], "--meth-epialleles")) epi_path = argv[2];
     else if (!strcmp(argv[1], "--meth-epialleles-min-cov")) {
       char *end = NULL;
@@ -806,7 +838,7 @@ int main(int argc, char **argv) {
     argc -= 2;
   }
   if (argc < 5 || world < 1 || (rank >= 0 && rank >= world)) {
-    fprintf(stderr, "usage: %s [-O u|b] [--format bcf|vcf] [--index] [-D dbsnp.idx] [--meth out.bed [--meth-bgzf] [--meth-index tbi|csi] [--meth-merge | --meth-all] [--meth-min-cov n] [--meth-min-gq n] [--meth-pass]] [--meth-regions regions.bed | --meth-window n --meth-regions-out out.tsv] [--meth-bigwig out.bw [--meth-bigwig-section n] [--meth-bigwig-zoom n] [--meth-bigwig-compress: zlib sections, n <= 8157]: the methylation level as a bigWig track, per cytosine even with --meth-merge, under the --meth-* thresholds and --meth-all] [--cov-bigwig cov.bw: the depth of the same sites as a bigWig track, under the same --meth-bigwig-* switches] [--meth-bigbed out.bb [--meth-bigbed-items n] [--meth-bigbed-zoom n] [--meth-bigbed-compress: zlib blocks, n <= 652]] [--variants out: the records with an ALT allele, in the run's format and compression, with out.csi under --index [--variants-min-qual n] [--variants-pass] [--variants-known: dbSNP sites only, with -D]] [--meth-reads out.tsv: the read-level CpG concordance table, a line per reference CpG [--meth-reads-min-sites n] [--meth-reads-min-cov n]] [--mbias out.tsv: methylation by read cycle, from the reads as sequenced [--mbias-cycles n]] [--meth-asm out.tsv: the allele-specific methylation table, a line per heterozygous SNP and CpG near it [--meth-asm-window n] [--meth-asm-min-qual n] [--meth-asm-min-cov n] [--meth-asm-pass]] [--meth-epialleles out.tsv: the epiallele table, a line per window of four reference CpGs [--meth-epialleles-min-cov n]] [--rank r --world n | --merge n] in.bam ref.fa out.bcf report.json [sample]\n", argv[0]);
+    fprintf(stderr, "usage: %s [-O u|b] [--format bcf|vcf] [--index] [-D dbsnp.idx] [--meth out.bed [--meth-bgzf] [--meth-index tbi|csi] [--meth-merge | --meth-all] [--meth-min-cov n] [--meth-min-gq n] [--meth-pass]] [--meth-regions regions.bed | --meth-window n --meth-regions-out out.tsv] [--meth-bigwig out.bw [--meth-bigwig-section n] [--meth-bigwig-zoom n] [--meth-bigwig-compress: zlib sections, n <= 8157]: the methylation level as a bigWig track, per cytosine even with --meth-merge, under the --meth-* thresholds and --meth-all] [--cov-bigwig cov.bw: the depth of the same sites as a bigWig track, under the same --meth-bigwig-* switches] [--meth-bigbed out.bb [--meth-bigbed-items n] [--meth-bigbed-zoom n] [--meth-bigbed-compress: zlib blocks, n <= 652]] [--variants out: the records with an ALT allele, in the run's format and compression, with out.csi under --index [--variants-min-qual n] [--variants-pass] [--variants-known: dbSNP sites only, with -D]] [--meth-reads out.tsv: the read-level CpG concordance table, a line per reference CpG [--meth-reads-min-sites n] [--meth-reads-min-cov n]] [--mbias out.tsv: methylation by read cycle, from the reads as sequenced [--mbias-cycles n]] [--meth-asm out.tsv: the allele-specific methylation table, a line per heterozygous SNP and CpG near it [--meth-asm-window n] [--meth-asm-min-qual n] [--meth-asm-min-cov n] [--meth-asm-pass]] [--meth-epialleles out.tsv: the epiallele table, a line per window of four reference CpGs [--meth-epialleles-min-cov n]] [--meth-pat out.pat: the per-read CpG pattern table (PAT: chrom index pattern count, wgbstools-unpinned bytes, the index per contig, 64 CpGs a line at the most) [--meth-pat-min-sites n]] [--rank r --world n | --merge n] in.bam ref.fa out.bcf report.json [sample]\n", argv[0]);
     return 2;
   }
   if (text && (rank >= 0 || merge > 0)) {
@@ -889,6 +921,18 @@ int main(int argc, char **argv) {
     fprintf(stderr, "%s: --meth-epialleles walks the prepared reads the device reader's blocks leave on the device: not with BAM2BCF_HOST_READER / _HOST_BCF / _HOST_PREP\n", argv[0]);
     return 2;
   }
+  if (pat_opts && !pat_path) {
+    fprintf(stderr, "%s: --meth-pat-min-sites is a threshold of the table --meth-pat writes: it needs --meth-pat out.pat\n", argv[0]);
+    return 2;
+  }
+  if (pat_path && (rank >= 0 || world > 1 || merge > 0)) {
+    fprintf(stderr, "%s: --meth-pat writes a single run's table; a sharded run (--rank / --world / --merge) has none\n", argv[0]);
+    return 2;
+  }
+  if (pat_path && (getenv("BAM2BCF_HOST_PREP") || getenv("BAM2BCF_HOST_BCF") || getenv("BAM2BCF_HOST_READER"))) {
+    fprintf(stderr, "%s: --meth-pat walks the prepared reads the device reader's blocks leave on the device: not with BAM2BCF_HOST_READER / _HOST_BCF / _HOST_PREP\n", argv[0]);
+    return 2;
+  }
   if (asm_opts && !asm_path) {
     fprintf(stderr, "%s: --meth-asm-window / --meth-asm-min-qual / --meth-asm-min-cov / --meth-asm-pass are thresholds of the table --meth-asm writes: they need --meth-asm out.tsv\n", argv[0]);
     return 2;
@@ -913,7 +957,7 @@ int main(int argc, char **argv) {
     fprintf(stderr, "%s: --variants selects from what the device reader's blocks leave on the device: not with BAM2BCF_HOST_READER / _HOST_BCF / _HOST_PREP\n", argv[0]);
     return 2;
   }
-  if (meth_bgzf && !meth_path && !reads_path && !asm_path && !epi_path) {
+  if (meth_bgzf && !meth_path && !reads_path && !asm_path && !epi_path && !pat_path) {
     fprintf(stderr, "%s: --meth-bgzf compresses the table --meth writes: it needs --meth out.bed.gz (or --meth-reads out.tsv.gz, whose table it compresses too)\n", argv[0]);
     return 2;
   }
@@ -1124,6 +1168,12 @@ int main(int argc, char **argv) {
   int epi_fd = -1; /* --meth-epialleles: the file, where its next bytes go, its compressor, the sums of the blocks' totals and lines */
   uint64_t epi_at = 0, epi_lines = 0, epi_tot[BSC_EPI_N_TOTALS] = {0};
   bsc_bgzf *ze = NULL;
+  int pat_fd = -1; /* --meth-pat: the file, where its next bytes go, its compressor, the sums of the blocks' totals and lines; the sites of the
+                    * contig in front of position pat_from */
+  uint64_t pat_at = 0, pat_lines = 0, pat_tot[BSC_PAT_N_TOTALS] = {0}, pat_base = 0, pat_from = 1;
+  uint64_t pat_room16 = 8 * 16; /* the table's room, sixteenths of a byte a position: 8 bytes at first (30x paired WGBS measured about 5), then a
+                                 * quarter more than the last block needed, so that a block is walked, sorted and encoded once */
+  bsc_bgzf *zp = NULL;
   FILE *mbias_f = NULL; /* --mbias: opened now, so that a path that cannot be written stops the run before it starts; written at the end */
   uint64_t mbias_tot[BSC_MBIAS_N_TOTALS] = {0};
   int mbias_any = 0;
@@ -1152,6 +1202,17 @@ int main(int argc, char **argv) {
     fclose(ef);
     const size_t el = strlen(epi_path);
     if (bgzf || meth_bgzf || (el > 3 && !strcmp(epi_path + el - 3, ".gz"))) CHECK(bsc_bgzf_open(ctx, &ze));
+  }
+  if (pat_path) {
+    FILE *pf = fopen(pat_path, "wb");
+    if (!pf) {
+      perror(pat_path);
+      return 1;
+    }
+    pat_fd = dup(fileno(pf));
+    fclose(pf);
+    const size_t pl = strlen(pat_path);
+    if (bgzf || meth_bgzf || (pl > 3 && !strcmp(pat_path + pl - 3, ".gz"))) CHECK(bsc_bgzf_open(ctx, &zp));
   }
   int var_fd = -1; /* --variants: the file, where its next bytes go, its compressor and index, the sums of the blocks' totals */
   uint64_t var_at = 0, var_tot[BSC_VAR_N_TOTALS] = {0};
@@ -1323,6 +1384,8 @@ int main(int argc, char **argv) {
       }
       if (rout && cur_tid >= 0) region_lines += regions_flush(ctx, rout, REF_NAME(cur_tid), r_regs, r_names, r_n);
       cur_tid = blk.tid;
+      pat_base = 0; /* --meth-pat: the index counts the contig's CpGs */
+      pat_from = 1;
       ctot[cur_tid].name = REF_NAME(cur_tid);
       if (sharded) { /* this contig's shard; the one before is closed by the output thread behind its last piece */
         if (out_fd >= 0) {
@@ -1617,6 +1680,39 @@ int main(int argc, char **argv) {
           epi_at += n_e;
         }
       }
+      if (pat_path) { /* the sites of the contig in front of the block: those between the block before, or the contig's start, and this one more */
+        uint64_t more = 0;
+        CHECK(bsc_pat_count_sites(codes, codes_len, pat_from, x, &more));
+        pat_base += more;
+        pat_from = x;
+      }
+      if (n_bytes && pat_path) { /* the block's pattern table, from the prepared templates, reads and reference codes the call left on the device: a
+                                  * buffer and a job of its own */
+        uint64_t p_cap = (uint64_t)n * pat_room16 / 16 + 4096, p_bytes = 0, p_lines = 0, pt8[BSC_PAT_N_TOTALS];
+        int prc = bsc_block_pat_kept(ctx, REF_NAME(dblk.tid), &ptpar, pat_base, p_cap, &p_bytes, &p_lines, pt8);
+        if (prc == BSC_ERR_ARG && p_bytes > p_cap) prc = bsc_block_pat_kept(ctx, REF_NAME(dblk.tid), &ptpar, pat_base, p_bytes, &p_bytes, &p_lines, pt8);
+        CHECK(prc);
+        pat_room16 = p_bytes * 20 / n + 16; /* (n >= 1) */
+        pat_lines += p_lines;
+        for (int k = 0; k < BSC_PAT_N_TOTALS; k++) pat_tot[k] += pt8[k];
+        if (p_bytes) {
+          void *d_p = NULL;
+          uint64_t n_p = 0;
+          CHECK(bsc_pat_stream_detach(ctx, &d_p, &n_p));
+          if (zp) {
+            CHECK(bsc_bgzf_write_device(zp, d_p, n_p));
+            CHECK(bsc_detached_free(ctx, d_p));
+            d_p = NULL;
+            n_p = 0;
+            CHECK(bsc_bgzf_take(zp, &d_p, &n_p));
+          }
+          if (n_p) {
+            const out_job j = {d_p, n_p, pat_at, pat_fd, 0};
+            writer_push(&W, j);
+          }
+          pat_at += n_p;
+        }
+      }
       if (n_bytes && variants_path) { /* the block's variant-only stream, selected from the same arrays and encoded by the block's own encoder: a
                                        * buffer and a job of its own */
         uint64_t v_cap = (uint64_t)n / 4 + 65536, v_bytes = 0, v_recs = 0, vt[BSC_VAR_N_TOTALS];
@@ -1825,6 +1921,17 @@ int main(int argc, char **argv) {
     }
     epi_at += n_z;
   }
+  if (zp) { /* the pattern table's last member and its end-of-file marker */
+    void *d_z = NULL;
+    uint64_t n_z = 0;
+    CHECK(bsc_bgzf_close(zp, &d_z, &n_z));
+    zp = NULL;
+    if (n_z) {
+      const out_job j = {d_z, n_z, pat_at, pat_fd, 0};
+      writer_push(&W, j);
+    }
+    pat_at += n_z;
+  }
   if (zv) { /* the variant file's last member and its end-of-file marker; its index */
     void *d_z = NULL;
     uint64_t n_z = 0;
@@ -1899,6 +2006,10 @@ int main(int argc, char **argv) {
   }
   if (epi_fd >= 0 && close(epi_fd)) {
     perror(epi_path);
+    return 1;
+  }
+  if (pat_fd >= 0 && close(pat_fd)) {
+    perror(pat_path);
     return 1;
   }
   if (var_fd >= 0 && close(var_fd)) {
@@ -2042,6 +2153,10 @@ int main(int argc, char **argv) {
     if (epi_path)
       printf("%llu windows of four CpGs in the epiallele table, %llu lines written (patterns %llu, templates with one %llu)\n",
              (unsigned long long)epi_tot[0], (unsigned long long)epi_lines, (unsigned long long)epi_tot[1], (unsigned long long)epi_tot[2]);
+    if (pat_path)
+      printf("%llu records in the per-read CpG pattern table, %llu lines written (pieces %llu, templates %llu, C %llu T %llu)\n",
+             (unsigned long long)pat_tot[0], (unsigned long long)pat_lines, (unsigned long long)pat_tot[1], (unsigned long long)pat_tot[2],
+             (unsigned long long)pat_tot[3], (unsigned long long)pat_tot[4]);
     if (mbias_path)
       printf("M-bias table: %llu reads walked, %llu bytes mapped, %llu counted, %llu beyond the table, CpG %llu meth %llu unmeth, %llu reads skipped\n",
              (unsigned long long)mbias_tot[0], (unsigned long long)mbias_tot[1], (unsigned long long)mbias_tot[2], (unsigned long long)mbias_tot[3],
