@@ -114,6 +114,10 @@ $(LIBDIR)/patdev.o: $(CSRC)/patdev.hip $(CSRC)/cpgreads_dev.h $(CSRC)/recstream_
 	@mkdir -p $(LIBDIR)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
+$(LIBDIR)/fragdev.o: $(CSRC)/fragdev.hip $(CSRC)/cpgreads_dev.h $(CSRC)/recstream_dev.h include/bscall_amd.h
+	@mkdir -p $(LIBDIR)
+	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+
 $(LIBDIR)/asmdev.o: $(CSRC)/asmdev.hip $(CSRC)/cpgreads_dev.h $(CSRC)/recstream_dev.h $(CSRC)/methtext_dev.h $(CSRC)/callmath.h $(CSRC)/devtables.h $(CSRC)/bsmath.h $(CSRC)/bsmath_tables.h include/bscall_amd.h
 	@mkdir -p $(LIBDIR)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
@@ -159,6 +163,10 @@ $(LIBDIR)/epi.o: $(CSRC)/epi.c include/bscall_amd.h
 	$(CC) $(CFLAGS) -c $< -o $@
 
 $(LIBDIR)/pat.o: $(CSRC)/pat.c include/bscall_amd.h
+	@mkdir -p $(LIBDIR)
+	$(CC) $(CFLAGS) -c $< -o $@
+
+$(LIBDIR)/frag.o: $(CSRC)/frag.c include/bscall_amd.h
 	@mkdir -p $(LIBDIR)
 	$(CC) $(CFLAGS) -c $< -o $@
 
@@ -218,7 +226,7 @@ $(LIBDIR)/synth_reads.o: $(CSRC)/synth_reads.c include/bscall_amd.h $(CSRC)/synt
 	@mkdir -p $(LIBDIR)
 	$(CC) $(CFLAGS) -c $< -o $@
 
-$(LIBDIR)/libbscall_amd.so: $(LIBDIR)/kernels.o $(LIBDIR)/fused.o $(LIBDIR)/accumulate.o $(LIBDIR)/sort.o $(LIBDIR)/vcfcore.o $(LIBDIR)/sitestats.o $(LIBDIR)/compact.o $(LIBDIR)/probe.o $(LIBDIR)/prepdev.o $(LIBDIR)/bcfdev.o $(LIBDIR)/vcftextdev.o $(LIBDIR)/methdev.o $(LIBDIR)/methregionsdev.o $(LIBDIR)/bigwigdev.o $(LIBDIR)/bwcovdev.o $(LIBDIR)/bigbeddev.o $(LIBDIR)/bgzfdev.o $(LIBDIR)/zlibdev.o $(LIBDIR)/bamdev.o $(LIBDIR)/dbsnpdev.o $(LIBDIR)/csidev.o $(LIBDIR)/beddev.o $(LIBDIR)/variantsdev.o $(LIBDIR)/cpgreadsdev.o $(LIBDIR)/asmdev.o $(LIBDIR)/mbiasdev.o $(LIBDIR)/epidev.o $(LIBDIR)/patdev.o $(LIBDIR)/bscall_api.o $(LIBDIR)/bamstream.o $(LIBDIR)/inflate_fast.o $(LIBDIR)/synth_reads.o $(LIBDIR)/vcf_format.o $(LIBDIR)/methbed.o $(LIBDIR)/methcpg.o $(LIBDIR)/methregions.o $(LIBDIR)/bigwig.o $(LIBDIR)/bigbed.o $(LIBDIR)/tabix.o $(LIBDIR)/variants.o $(LIBDIR)/cpgreads.o $(LIBDIR)/asm.o $(LIBDIR)/mbias.o $(LIBDIR)/epi.o $(LIBDIR)/pat.o $(LIBDIR)/dbsnp.o $(LIBDIR)/prep.o $(LIBDIR)/report.o $(LIBDIR)/bcf.o $(LIBDIR)/bamio.o $(LIBDIR)/refseq.o
+$(LIBDIR)/libbscall_amd.so: $(LIBDIR)/kernels.o $(LIBDIR)/fused.o $(LIBDIR)/accumulate.o $(LIBDIR)/sort.o $(LIBDIR)/vcfcore.o $(LIBDIR)/sitestats.o $(LIBDIR)/compact.o $(LIBDIR)/probe.o $(LIBDIR)/prepdev.o $(LIBDIR)/bcfdev.o $(LIBDIR)/vcftextdev.o $(LIBDIR)/methdev.o $(LIBDIR)/methregionsdev.o $(LIBDIR)/bigwigdev.o $(LIBDIR)/bwcovdev.o $(LIBDIR)/bigbeddev.o $(LIBDIR)/bgzfdev.o $(LIBDIR)/zlibdev.o $(LIBDIR)/bamdev.o $(LIBDIR)/dbsnpdev.o $(LIBDIR)/csidev.o $(LIBDIR)/beddev.o $(LIBDIR)/variantsdev.o $(LIBDIR)/cpgreadsdev.o $(LIBDIR)/asmdev.o $(LIBDIR)/mbiasdev.o $(LIBDIR)/epidev.o $(LIBDIR)/patdev.o $(LIBDIR)/fragdev.o $(LIBDIR)/bscall_api.o $(LIBDIR)/bamstream.o $(LIBDIR)/inflate_fast.o $(LIBDIR)/synth_reads.o $(LIBDIR)/vcf_format.o $(LIBDIR)/methbed.o $(LIBDIR)/methcpg.o $(LIBDIR)/methregions.o $(LIBDIR)/bigwig.o $(LIBDIR)/bigbed.o $(LIBDIR)/tabix.o $(LIBDIR)/variants.o $(LIBDIR)/cpgreads.o $(LIBDIR)/asm.o $(LIBDIR)/mbias.o $(LIBDIR)/epi.o $(LIBDIR)/pat.o $(LIBDIR)/frag.o $(LIBDIR)/dbsnp.o $(LIBDIR)/prep.o $(LIBDIR)/report.o $(LIBDIR)/bcf.o $(LIBDIR)/bamio.o $(LIBDIR)/refseq.o
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $^ -lm -lz -lpthread
 
 oracle:
@@ -349,15 +357,23 @@ pat-san: $(PAT_SAN_EXE)
 $(PAT_SAN_EXE): integration/pat_san.c $(CSRC)/pat.c include/bscall_amd.h
 	$(CC) -std=gnu11 -O1 -g -Wall -Wextra -fsanitize=address,undefined -fno-sanitize-recover=undefined -Iinclude $< $(CSRC)/pat.c -o $@
 
+# TEST ONLY: the host form of the per-region fragment summary (csrc/frag.c: seeded random templates and regions in heap blocks of exactly their
+# size, NULL totals, the formatter's rooms, the refusals) as a stand-alone program under AddressSanitizer + UndefinedBehaviorSanitizer, on the
+# CPU: $(FRAG_SAN_EXE)  ->  "ok" and exit 0, or the case that failed
+FRAG_SAN_EXE ?= $(LIBDIR)/frag_san
+frag-san: $(FRAG_SAN_EXE)
+$(FRAG_SAN_EXE): integration/frag_san.c $(CSRC)/frag.c include/bscall_amd.h
+	$(CC) -std=gnu11 -O1 -g -Wall -Wextra -fsanitize=address,undefined -fno-sanitize-recover=undefined -Iinclude $< $(CSRC)/frag.c -o $@
+
 # The library with its HOST C files under AddressSanitizer + UndefinedBehaviorSanitizer (gcc's runtimes; the device objects
 # are the ordinary ones): what tests/test_host_sanitizers.py and tools/fuzz_host_inputs.py run the readers and the host
 # logic under, on the CPU.  Load it with LD_PRELOAD=<libasan.so>:<libubsan.so> BSCALL_AMD_LIB=$(LIBDIR)/san/libbscall_amd_san.so.
 SANFLAGS = -O1 -g -fPIC -Wall -ffp-contract=off -std=gnu11 -I$(ROCM)/include -D__HIP_PLATFORM_AMD__ -fsanitize=address,undefined -fno-sanitize-recover=undefined -fno-omit-frame-pointer
-HOST_C = bscall_api synth_reads vcf_format methbed methcpg methregions bigwig bigbed tabix variants cpgreads asm mbias epi pat dbsnp prep report bcf bamio bamstream inflate_fast refseq
+HOST_C = bscall_api synth_reads vcf_format methbed methcpg methregions bigwig bigbed tabix variants cpgreads asm mbias epi pat frag dbsnp prep report bcf bamio bamstream inflate_fast refseq
 san: $(LIBDIR)/libbscall_amd.so
 	@mkdir -p $(LIBDIR)/san
 	for f in $(HOST_C); do $(CC) $(SANFLAGS) -c $(CSRC)/$$f.c -o $(LIBDIR)/san/$$f.o || exit 1; done
-	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $(LIBDIR)/san/libbscall_amd_san.so $(LIBDIR)/kernels.o $(LIBDIR)/fused.o $(LIBDIR)/accumulate.o $(LIBDIR)/sort.o $(LIBDIR)/vcfcore.o $(LIBDIR)/sitestats.o $(LIBDIR)/compact.o $(LIBDIR)/probe.o $(LIBDIR)/prepdev.o $(LIBDIR)/bcfdev.o $(LIBDIR)/vcftextdev.o $(LIBDIR)/methdev.o $(LIBDIR)/methregionsdev.o $(LIBDIR)/bigwigdev.o $(LIBDIR)/bwcovdev.o $(LIBDIR)/bigbeddev.o $(LIBDIR)/bgzfdev.o $(LIBDIR)/zlibdev.o $(LIBDIR)/bamdev.o $(LIBDIR)/dbsnpdev.o $(LIBDIR)/csidev.o $(LIBDIR)/beddev.o $(LIBDIR)/variantsdev.o $(LIBDIR)/cpgreadsdev.o $(LIBDIR)/asmdev.o $(LIBDIR)/mbiasdev.o $(LIBDIR)/epidev.o $(LIBDIR)/patdev.o $(addprefix $(LIBDIR)/san/,$(addsuffix .o,$(HOST_C))) -L$(dir $(shell $(CC) -print-file-name=libasan.so)) -lasan -lubsan -lm -lz -lpthread
+	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $(LIBDIR)/san/libbscall_amd_san.so $(LIBDIR)/kernels.o $(LIBDIR)/fused.o $(LIBDIR)/accumulate.o $(LIBDIR)/sort.o $(LIBDIR)/vcfcore.o $(LIBDIR)/sitestats.o $(LIBDIR)/compact.o $(LIBDIR)/probe.o $(LIBDIR)/prepdev.o $(LIBDIR)/bcfdev.o $(LIBDIR)/vcftextdev.o $(LIBDIR)/methdev.o $(LIBDIR)/methregionsdev.o $(LIBDIR)/bigwigdev.o $(LIBDIR)/bwcovdev.o $(LIBDIR)/bigbeddev.o $(LIBDIR)/bgzfdev.o $(LIBDIR)/zlibdev.o $(LIBDIR)/bamdev.o $(LIBDIR)/dbsnpdev.o $(LIBDIR)/csidev.o $(LIBDIR)/beddev.o $(LIBDIR)/variantsdev.o $(LIBDIR)/cpgreadsdev.o $(LIBDIR)/asmdev.o $(LIBDIR)/mbiasdev.o $(LIBDIR)/epidev.o $(LIBDIR)/patdev.o $(LIBDIR)/fragdev.o $(addprefix $(LIBDIR)/san/,$(addsuffix .o,$(HOST_C))) -L$(dir $(shell $(CC) -print-file-name=libasan.so)) -lasan -lubsan -lm -lz -lpthread
 
 # a plain-C host program against the C ABI: gcc only, links the shared library like bs_call would
 demo: $(LIBDIR)/demo_block $(LIBDIR)/bam2bcf
@@ -388,7 +404,7 @@ asm: $(CSRC)/kernels.hip
 	$(HIPCC) $(HIPFLAGS) -S --cuda-device-only -Rpass-analysis=kernel-resource-usage $< -o $(LIBDIR)/kernels.s
 
 clean:
-	rm -rf $(LIBDIR)/san; rm -f tests/devmath/libdevmath_probe.so tests/dbsnpdev/dbsnp_flat_host tests/csidev/csi_walk_host $(LIBDIR)/*.o $(LIBDIR)/*.so $(LIBDIR)/*.s $(LIBDIR)/demo_block $(LIBDIR)/bam2bcf $(LIBDIR)/methregions_san $(LIBDIR)/bigwig_san $(LIBDIR)/bigwig_z_san $(LIBDIR)/bigwig_cov_san $(LIBDIR)/bigbed_san $(LIBDIR)/tabix_san $(LIBDIR)/variants_san $(LIBDIR)/cpg_reads_san $(LIBDIR)/asm_san $(LIBDIR)/mbias_san $(LIBDIR)/epi_san $(LIBDIR)/pat_san
+	rm -rf $(LIBDIR)/san; rm -f tests/devmath/libdevmath_probe.so tests/dbsnpdev/dbsnp_flat_host tests/csidev/csi_walk_host $(LIBDIR)/*.o $(LIBDIR)/*.so $(LIBDIR)/*.s $(LIBDIR)/demo_block $(LIBDIR)/bam2bcf $(LIBDIR)/methregions_san $(LIBDIR)/bigwig_san $(LIBDIR)/bigwig_z_san $(LIBDIR)/bigwig_cov_san $(LIBDIR)/bigbed_san $(LIBDIR)/tabix_san $(LIBDIR)/variants_san $(LIBDIR)/cpg_reads_san $(LIBDIR)/asm_san $(LIBDIR)/mbias_san $(LIBDIR)/epi_san $(LIBDIR)/pat_san $(LIBDIR)/frag_san
 	$(MAKE) -C oracle clean
 
-.PHONY: all oracle demo asm clean glue-check san devmath-probe dbsnp-flat-host csi-walk-host tabix-san bigwig-cov-san variants-san cpg-reads-san asm-san mbias-san epi-san pat-san
+.PHONY: all oracle demo asm clean glue-check san devmath-probe dbsnp-flat-host csi-walk-host tabix-san bigwig-cov-san variants-san cpg-reads-san asm-san mbias-san epi-san pat-san frag-san

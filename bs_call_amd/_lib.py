@@ -267,6 +267,14 @@ EXPORTS = (
     "bsc_block_pat_kept",
     "bsc_pat_stream_read",
     "bsc_pat_stream_detach",
+    "bsc_frag_params_default",
+    "bsc_frag_regions_host",
+    "bsc_frag_format",
+    "bsc_frag_attach",
+    "bsc_frag_device",
+    "bsc_block_frag_kept",
+    "bsc_frag_read",
+    "bsc_frag_reset",
     "bsc_asm_params_default",
     "bsc_asm_pairs_host",
     "bsc_asm_format",
@@ -357,6 +365,15 @@ class PatParams(C.Structure):
 
     def __init__(self, min_sites=1, reserved=0):
         super().__init__(int(min_sites), int(reserved))
+
+
+class FragParams(C.Structure):
+    """bsc_frag_params; the defaults are bsc_frag_params_default's."""
+
+    _fields_ = [("min_sites", C.c_uint32), ("u_max_pct", C.c_uint32), ("m_min_pct", C.c_uint32), ("reserved", C.c_uint32)]
+
+    def __init__(self, min_sites=3, u_max_pct=25, m_min_pct=75, reserved=0):
+        super().__init__(int(min_sites), int(u_max_pct), int(m_min_pct), int(reserved))
 
 
 class BwParams(C.Structure):
@@ -976,6 +993,22 @@ def load():
     L.bsc_pat_stream_read.argtypes = [vp, u64, u64, vp]
     L.bsc_pat_stream_detach.restype = i32
     L.bsc_pat_stream_detach.argtypes = [vp, C.POINTER(vp), C.POINTER(u64)]
+    L.bsc_frag_params_default.restype = None
+    L.bsc_frag_params_default.argtypes = [C.POINTER(FragParams)]
+    L.bsc_frag_regions_host.restype = i32
+    L.bsc_frag_regions_host.argtypes = [vp, u32, vp, u64, u32, u32, vp, i32, C.POINTER(FragParams), vp, C.c_size_t, vp, C.POINTER(u64)]
+    L.bsc_frag_format.restype = C.c_long
+    L.bsc_frag_format.argtypes = [C.c_char_p, vp, vp, vp, C.c_size_t, vp, C.c_size_t]
+    L.bsc_frag_attach.restype = i32
+    L.bsc_frag_attach.argtypes = [vp, vp, u64]
+    L.bsc_frag_device.restype = i32
+    L.bsc_frag_device.argtypes = [vp, vp, u32, vp, u64, u32, u32, vp, C.POINTER(FragParams), vp, vp]
+    L.bsc_block_frag_kept.restype = i32
+    L.bsc_block_frag_kept.argtypes = [vp, C.POINTER(FragParams), C.POINTER(u64)]
+    L.bsc_frag_read.restype = i32
+    L.bsc_frag_read.argtypes = [vp, vp, u64]
+    L.bsc_frag_reset.restype = i32
+    L.bsc_frag_reset.argtypes = [vp]
     L.bsc_asm_params_default.restype = None
     L.bsc_asm_params_default.argtypes = [C.POINTER(AsmParams)]
     L.bsc_asm_pairs_host.restype = i32

@@ -1465,6 +1465,50 @@ class SiteCaller:
             self.synchronize()
         return out[: int(n)].tobytes()
 
+    # -- the per-region fragment methylation summary (csrc/fragdev.hip) ------------------------------------------
+    @staticmethod
+    def _frag_params(params):
+        if params is None:
+            return _lib.FragParams()
+        if isinstance(params, _lib.FragParams):
+            return params
+        return _lib.FragParams(**params)
+
+    def frag_attach(self, regions):
+        """bsc_frag_attach: the regions of ONE contig — (start, end) pairs, 0-based and half-open as in BED, sorted by (start, end) —
+        uploaded, their eight accumulators each zeroed.  An empty list detaches.  Refused (BscError) when unsorted or start > end: the
+        previous attachment then stays.  The accumulators are separate from meth_regions_attach's.  Returns the count."""
+        r = self._regions_array(regions)
+        _check(self._L.bsc_frag_attach(self._h, _ptr(r) if len(r) else None, len(r)))
+        self._n_frag_regions = len(r)
+        return len(r)
+
+    def frag_device(self, d_tpl, nr, d_seq, seq_bytes, x, y, d_ref, d_totals, params=None, stream=None):
+        """bsc_frag_device: the inputs of cpg_reads_device added into the attached regions' accumulators {frags, U, X, M, K, Mm, disc,
+        short}; the call's eight totals in d_totals (asynchronous on `stream`)."""
+        fp = self._frag_params(params)
+        _check(self._L.bsc_frag_device(self._h, d_tpl, nr, d_seq, seq_bytes, x, y, d_ref, C.byref(fp), d_totals, stream))
+
+    def block_frag_kept(self, params=None):
+        """bsc_block_frag_kept: the block the last *_keep call called, added into the attached regions' accumulators from the prepared
+        templates, reads and reference codes it left on the device.  params: a _lib.FragParams, a dict of its fields, or None
+        ({3, 25, 75, 0}).  Returns the call's eight totals."""
+        fp = self._frag_params(params)
+        tot = (C.c_uint64 * 8)()
+        _check(self._L.bsc_block_frag_kept(self._h, C.byref(fp), tot))
+        return tuple(int(v) for v in tot)
+
+    def frag_read(self):
+        """bsc_frag_read: the accumulators as uint64[n, 8] — per attached region {frags, U, X, M, K, Mm, disc, short} (waits)."""
+        n = getattr(self, "_n_frag_regions", 0)
+        acc = np.zeros((n, 8), dtype=np.uint64)
+        _check(self._L.bsc_frag_read(self._h, _ptr(acc) if n else None, n))
+        return acc
+
+    def frag_reset(self):
+        """bsc_frag_reset: the accumulators zeroed, the regions stay."""
+        _check(self._L.bsc_frag_reset(self._h))
+
     def blocks_records(self, blocks, ref, out=None, all_positions=False, reg_start=1, reg_stop=0xFFFFFFFF, dbsnp=None, with_stats=False,
                        submit_only=False):
         """Several blocks in one launch sequence (bsc_blocks_records): blocks = [(templates, seq, x, y), ...] in genome order;
@@ -2119,6 +2163,58 @@ def pat_format_host(contig, index_base, recs, params=None, cap=None):
         assert (buf == 0xA5).all()
         return None, int(got)
     return buf[:got].tobytes(), int(t2[1])
+
+
+def frag_regions_host(tpl, seq, x, y, ref, regions, min_qual=20, params=None, acc=None, with_totals=True):
+    """The host form of the per-region fragment summary (bsc_frag_regions_host; csrc/frag.c): prepared TEMPLATE[nr] + their read bytes, the
+    block x .. y, its reference codes (x .. y + 2) and (start, end) regions in any order -> (uint64[n, 8] accumulators, totals[8]).  acc:
+    accumulators to add into (default: zeros).  No GPU involved."""
+    from .methbed import _regions
+
+    L = _lib.load()
+    tpl = np.ascontiguousarray(tpl, dtype=TEMPLATE)
+    seq = np.ascontiguousarray(seq, dtype=np.uint8)
+    ref = np.ascontiguousarray(ref, dtype=np.uint8)
+    if ref.size < int(y) - int(x) + 2:
+        raise ValueError("ref must hold the codes of x .. y + 1 at least")
+    regs = _regions(regions)
+    fp = SiteCaller._frag_params(params)
+    out = np.zeros((len(regs), 8), dtype=np.uint64) if acc is None else np.ascontiguousarray(acc, dtype=np.uint64).reshape(len(regs), 8).copy()
+    tot = (C.c_uint64 * 8)()
+    _check(L.bsc_frag_regions_host(_ptr(tpl), len(tpl), _ptr(seq), seq.size, int(x), int(y), _ptr(ref), int(min_qual), C.byref(fp),
+                                   _ptr(regs) if len(regs) else None, len(regs), _ptr(out) if len(regs) else None, tot if with_totals else None))
+    return out, tuple(int(v) for v in tot)
+
+
+def frag_format_host(contig, regions, names, acc, cap=None):
+    """bsc_frag_format: the table's lines of one contig's regions and their accumulators -> bytes.  cap: the room (default: asked for
+    first); a room too small gives (None, the length needed); a bad argument raises ValueError."""
+    from .methbed import _regions
+
+    L = _lib.load()
+    regs = _regions(regions)
+    acc = np.ascontiguousarray(acc, dtype=np.uint64).reshape(-1, 8)
+    if len(acc) != len(regs) or (names is not None and len(names) != len(regs)):
+        raise ValueError("as many accumulators and names as regions")
+    name = contig if isinstance(contig, (bytes, bytearray)) else str(contig).encode()
+    nm = None
+    if names is not None:
+        nm = (C.c_char_p * max(len(regs), 1))(*[(None if s is None else s if isinstance(s, (bytes, bytearray)) else str(s).encode()) for s in names])
+    rp, ap = (regs.ctypes.data, acc.ctypes.data) if len(regs) else (None, None)
+    if cap is None:
+        need = L.bsc_frag_format(name, rp, nm, ap, len(regs), None, 0)
+        if need < 0:
+            raise ValueError("bsc_frag_format: bad argument")
+        cap = int(need)
+    buf = np.full(max(int(cap), 1) + 8, 0xA5, dtype=np.uint8)
+    got = L.bsc_frag_format(name, rp, nm, ap, len(regs), _ptr(buf) if cap else None, int(cap))
+    if got < 0:
+        raise ValueError("bsc_frag_format: bad argument")
+    assert (buf[int(cap) :] == 0xA5).all()
+    if got > int(cap):
+        assert (buf == 0xA5).all()
+        return None, int(got)
+    return buf[:got].tobytes()
 
 
 def pat_count_sites(codes, start, stop):

@@ -145,6 +145,10 @@ int bsc_dev_launch_pat_walk(const void *tpl, uint32_t nr, const void *seq, uint6
 int bsc_dev_launch_pat_text(const void *rec, const void *n_rec, uint64_t max_rec, const char *contig, uint32_t contig_len, uint64_t index_base,
                             void *tile_bytes, void *tile_off, void *line_len, void *scan_tmp, size_t scan_tmp_bytes, void *out, uint64_t out_cap,
                             void *totals2, int num_cus, void *stream);
+int bsc_dev_launch_frag_walk(const void *tpl, uint32_t nr, const void *seq, uint64_t seq_bytes, uint32_t x, uint32_t y, uint32_t min_qual,
+                             const void *tile_mask, const void *reg, uint32_t n_reg, const void *maxend, const void *long_idx, uint32_t n_long,
+                             uint32_t long_len, uint32_t min_sites, uint32_t u_max_pct, uint32_t m_min_pct, void *acc, void *totals, int num_cus,
+                             void *stream); /* fragdev.hip */
 int bsc_dev_sort_pat_tmp_bytes(uint32_t n, size_t *bytes); /* sort.hip */
 int bsc_dev_launch_asm_snps(const void *core, const void *emit, uint32_t n, uint32_t min_phred, int pass_only, void *snp_cnt, void *snp_off, void *snp_mask,
                             void *scan_tmp, size_t scan_tmp_bytes, int num_cus, void *stream); /* asmdev.hip */
@@ -386,6 +390,16 @@ struct bsc_context {
         cap_rec, cap_tot, cap_out;
     uint64_t bytes;
   } pt;
+  struct { /* bsc_frag_attach (fragdev.hip): a contig's regions, sorted by (start, end), their accumulators (eight u64 each), the running
+            * maximum of the ends of the regions that are not long and the indices of those that are, all in HBM; the kept entry's eight
+            * totals; the stream of the last accumulating call.  (The site masks are cr's workspaces.) */
+    uint64_t n;
+    void *d_reg, *d_acc, *d_maxend, *d_long, *d_tot;
+    size_t cap_tot;
+    uint32_t n_long, long_len, long_next; /* long_next: the bound the next attach takes, 0 = 65 536 (bsc_frag_long_bases_set) */
+    hipStream_t last;
+    int last_set; /* `last` names a caller's stream that may still be adding (NULL is one) */
+  } fr;
   struct { /* streams handed to the caller (bsc_bcf_stream_detach) come back here (bsc_detached_free) and are taken again by the next block:
             * no hipMalloc / hipFree — a device-wide wait — in the steady state of a run that writes behind the calling */
     void *p[4];
@@ -840,6 +854,11 @@ int bsc_destroy(bsc_context *ctx) {
   hipFree(ctx->pt.d_rec);
   hipFree(ctx->pt.d_tot);
   hipFree(ctx->pt.d_out);
+  hipFree(ctx->fr.d_reg);
+  hipFree(ctx->fr.d_acc);
+  hipFree(ctx->fr.d_maxend);
+  hipFree(ctx->fr.d_long);
+  hipFree(ctx->fr.d_tot);
   hipFree(ctx->asm_.d_scnt);
   hipFree(ctx->asm_.d_soff);
   hipFree(ctx->asm_.d_smask);
@@ -5978,6 +5997,180 @@ int bsc_pat_stream_detach(bsc_context *ctx, void **d_stream, uint64_t *n_bytes) 
   ctx->pt.d_out = NULL;
   ctx->pt.cap_out = 0;
   ctx->pt.bytes = 0;
+  return BSC_OK;
+}
+
+/* ---- the per-region fragment methylation summary (fragdev.hip): include/bscall_amd.h has the rule, csrc/frag.c the host form ------------------- */
+int bsc_frag_params_bad(const char *who, const bsc_frag_params *p); /* frag.c: the one check of the parameters, the host form's too */
+static int bsc_frag_params_check(const char *who, const bsc_frag_params *p) {
+  if (!p) return bsc_fail(BSC_ERR_ARG, "%s: NULL argument", who);
+  return bsc_frag_params_bad(who, p);
+}
+
+/* what may still be adding into the accumulators: the context's stream and the stream of the last accumulating call */
+static int bsc_frag_quiet(bsc_context *ctx) {
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  /* (a caller's NULL stream is a stream like any other: the context's own is non-blocking and does not order against it) */
+  if (ctx->fr.last_set && ctx->fr.last != ctx->stream) HIP_TRY(hipStreamSynchronize(ctx->fr.last));
+  ctx->fr.last = ctx->stream; /* (the caller's stream is not named again: it may be gone by the next call) */
+  ctx->fr.last_set = 0;
+  return BSC_OK;
+}
+
+int bsc_frag_attach(bsc_context *ctx, const bsc_meth_region *regions, uint64_t n) {
+  static const char who[] = "bsc_frag_attach";
+  if (!ctx || (n && !regions)) return bsc_fail(BSC_ERR_ARG, "%s: NULL argument", who);
+  if (n > (1ull << 27)) return bsc_fail(BSC_ERR_ARG, "%s: %llu regions, more than 2^27", who, (unsigned long long)n);
+  for (uint64_t k = 0; k < n; k++) {
+    if (regions[k].start > regions[k].end)
+      return bsc_fail(BSC_ERR_ARG, "%s: region %llu has start %u > end %u", who, (unsigned long long)k, regions[k].start, regions[k].end);
+    if (k && (regions[k].start < regions[k - 1].start || (regions[k].start == regions[k - 1].start && regions[k].end < regions[k - 1].end)))
+      return bsc_fail(BSC_ERR_ARG, "%s: region %llu lies before region %llu: sort by (start, end)", who, (unsigned long long)k, (unsigned long long)k - 1);
+  }
+  BSC_ENTER(ctx);
+  int rc;
+  const uint32_t long_len = ctx->fr.long_next ? ctx->fr.long_next : 65536u; /* LIMITS: a longer region goes into the list every template tests whole */
+  void *d_reg = NULL, *d_acc = NULL, *d_maxend = NULL, *d_long = NULL;
+  uint64_t n_long = 0;
+  if (n) { /* the new attachment whole, before the old one goes: a refusal leaves the old one */
+    uint32_t *h_maxend = malloc((size_t)n * sizeof *h_maxend), *h_long = NULL;
+    for (uint64_t k = 0; k < n; k++) n_long += regions[k].end - regions[k].start > long_len;
+    h_long = malloc((size_t)(n_long ? n_long : 1) * sizeof *h_long);
+    hipError_t e = h_maxend && h_long ? hipSuccess : hipErrorOutOfMemory;
+    if (e == hipSuccess) {
+      uint32_t run = 0;
+      uint64_t nl = 0;
+      for (uint64_t k = 0; k < n; k++) {
+        if (regions[k].end - regions[k].start > long_len) h_long[nl++] = (uint32_t)k;
+        else run = regions[k].end > run ? regions[k].end : run;
+        h_maxend[k] = run;
+      }
+      e = hipMalloc(&d_reg, (size_t)n * sizeof *regions);
+    }
+    if (e == hipSuccess) e = hipMalloc(&d_acc, (size_t)n * BSC_FRAG_N_SUMS * 8u);
+    if (e == hipSuccess) e = hipMalloc(&d_maxend, (size_t)n * 4u);
+    if (e == hipSuccess) e = hipMalloc(&d_long, (size_t)(n_long ? n_long : 1) * 4u);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_reg, regions, (size_t)n * sizeof *regions, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_maxend, h_maxend, (size_t)n * 4u, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess && n_long) e = hipMemcpyAsync(d_long, h_long, (size_t)n_long * 4u, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(d_acc, 0, (size_t)n * BSC_FRAG_N_SUMS * 8u, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream); /* (the host arrays are pageable: they are read by now) */
+    free(h_maxend);
+    free(h_long);
+    if (e != hipSuccess) {
+      (void)hipFree(d_reg);
+      (void)hipFree(d_acc);
+      (void)hipFree(d_maxend);
+      (void)hipFree(d_long);
+      (void)hipGetLastError();
+      return bsc_fail(e == hipErrorOutOfMemory ? BSC_ERR_NOMEM : BSC_ERR_HIP, "%s: %llu regions to the device: %s", who, (unsigned long long)n,
+                      hipGetErrorString(e));
+    }
+  }
+  if ((rc = bsc_frag_quiet(ctx))) { /* (a kernel of the old attachment may still be adding) */
+    (void)hipFree(d_reg);
+    (void)hipFree(d_acc);
+    (void)hipFree(d_maxend);
+    (void)hipFree(d_long);
+    return rc;
+  }
+  (void)hipFree(ctx->fr.d_reg);
+  (void)hipFree(ctx->fr.d_acc);
+  (void)hipFree(ctx->fr.d_maxend);
+  (void)hipFree(ctx->fr.d_long);
+  ctx->fr.d_reg = d_reg;
+  ctx->fr.d_acc = d_acc;
+  ctx->fr.d_maxend = d_maxend;
+  ctx->fr.d_long = d_long;
+  ctx->fr.n = n;
+  ctx->fr.n_long = (uint32_t)n_long;
+  ctx->fr.long_len = long_len;
+  ctx->fr.last = ctx->stream;
+  return BSC_OK;
+}
+
+/* TEST ONLY, not in the header: the length above which the NEXT bsc_frag_attach treats a region as long (0: the default, 65 536 bases), so
+ * that the small blocks of tests/test_gpu_frag.py have regions in the long list */
+int bsc_frag_long_bases_set(bsc_context *ctx, uint32_t bases) {
+  if (!ctx) return bsc_fail(BSC_ERR_ARG, "bsc_frag_long_bases_set: NULL argument");
+  ctx->fr.long_next = bases;
+  return BSC_OK;
+}
+
+/* the walk behind bsc_cr_sites_run on stream s; d_totals: eight u64, zeroed here */
+static int bsc_frag_walk_run(bsc_context *ctx, const char *who, const void *d_tpl, uint32_t nr, const void *d_seq, uint64_t seq_bytes, uint32_t x, uint32_t y,
+                             const bsc_frag_params *p, void *d_totals, hipStream_t s) {
+  HIP_TRY(hipMemsetAsync(d_totals, 0, BSC_FRAG_N_TOTALS * sizeof(unsigned long long), s));
+  ctx->fr.last = s;
+  ctx->fr.last_set = 1;
+  const int e = bsc_dev_launch_frag_walk(d_tpl, nr, d_seq, seq_bytes, x, y, (uint32_t)ctx->params.min_qual, ctx->cr.d_mask, ctx->fr.d_reg, (uint32_t)ctx->fr.n,
+                                         ctx->fr.d_maxend, ctx->fr.d_long, ctx->fr.n_long, ctx->fr.long_len, p->min_sites, p->u_max_pct, p->m_min_pct,
+                                         ctx->fr.d_acc, d_totals, ctx->num_cus, (void *)s);
+  if (e) return bsc_fail(BSC_ERR_HIP, "%s: walk launch failed: %s", who, hipGetErrorString((hipError_t)e));
+  return BSC_OK;
+}
+
+int bsc_frag_device(bsc_context *ctx, const void *d_tpl, uint32_t nr, const void *d_seq, uint64_t seq_bytes, uint32_t x, uint32_t y, const void *d_ref,
+                    const bsc_frag_params *p, void *d_totals, void *stream) {
+  static const char who[] = "bsc_frag_device";
+  int rc;
+  if (!ctx || !d_ref || !d_totals || (nr && (!d_tpl || !d_seq))) return bsc_fail(BSC_ERR_ARG, "%s: NULL argument", who);
+  if ((rc = bsc_frag_params_check(who, p))) return rc;
+  if (y < x) return bsc_fail(BSC_ERR_ARG, "%s: y (%u) < x (%u)", who, y, x);
+  if ((uint64_t)y - x + 1 > 0x0fffffffull) return bsc_fail(BSC_ERR_ARG, "%s: block longer than 2^28 - 1 positions", who);
+  if ((((uintptr_t)d_tpl | (uintptr_t)d_totals) & 7u)) return bsc_fail(BSC_ERR_ARG, "%s: the templates and the totals must be 8-byte aligned", who);
+  if (!ctx->fr.n) return bsc_fail(BSC_ERR_ARG, "%s: no regions are attached (bsc_frag_attach)", who);
+  BSC_ENTER(ctx);
+  hipStream_t s = (hipStream_t)stream;
+  if ((rc = bsc_cr_sites_run(ctx, who, d_ref, y - x + 1u, s))) return rc; /* (reserves its workspaces, the only ones, before it launches) */
+  return bsc_frag_walk_run(ctx, who, d_tpl, nr, d_seq, seq_bytes, x, y, p, d_totals, s);
+}
+
+int bsc_block_frag_kept(bsc_context *ctx, const bsc_frag_params *p, uint64_t totals[8]) {
+  static const char who[] = "bsc_block_frag_kept";
+  int rc;
+  if (!ctx) return bsc_fail(BSC_ERR_ARG, "%s: NULL argument", who);
+  for (int k = 0; totals && k < BSC_FRAG_N_TOTALS; k++) totals[k] = 0;
+  if ((rc = bsc_frag_params_check(who, p))) return rc;
+  if (ctx->meth_src != 1 || ctx->rec_pending || ctx->pending_sz)
+    return bsc_fail(BSC_ERR_ARG, "%s: the last call left no single block's arrays on the device", who);
+  if (!ctx->cr.src_ok) return bsc_fail(BSC_ERR_ARG, "%s: the last block's prepared templates, reads and reference are no longer on the device", who);
+  if (!ctx->fr.n) return bsc_fail(BSC_ERR_ARG, "%s: no regions are attached (bsc_frag_attach)", who);
+  BSC_ENTER(ctx);
+  hipStream_t s = ctx->stream;
+  if ((rc = bsc_frag_quiet(ctx))) return rc; /* (a device-level call on another stream may still be adding) */
+  const uint32_t x = ctx->cr.src_x, y = ctx->cr.src_y, nr = ctx->cr.src_nr;
+  if ((rc = bsc_reserve(&ctx->fr.d_tot, &ctx->fr.cap_tot, BSC_FRAG_N_TOTALS * sizeof(unsigned long long)))) return rc;
+  if ((rc = bsc_cr_sites_run(ctx, who, ctx->d_ref, y - x + 1u, s))) return rc;
+  if ((rc = bsc_frag_walk_run(ctx, who, ctx->d_tpl, nr, ctx->d_seq, ctx->cr.src_seq_bytes, x, y, p, ctx->fr.d_tot, s))) return rc;
+  unsigned long long tot[BSC_FRAG_N_TOTALS] = {0};
+  HIP_TRY(hipMemcpyAsync(tot, ctx->fr.d_tot, sizeof tot, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  for (int k = 0; totals && k < BSC_FRAG_N_TOTALS; k++) totals[k] = tot[k];
+  return BSC_OK;
+}
+
+int bsc_frag_read(bsc_context *ctx, uint64_t *acc_host, uint64_t n) {
+  if (!ctx || (n && !acc_host)) return bsc_fail(BSC_ERR_ARG, "bsc_frag_read: NULL argument");
+  if (n != ctx->fr.n)
+    return bsc_fail(BSC_ERR_ARG, "bsc_frag_read: %llu regions are attached, not %llu", (unsigned long long)ctx->fr.n, (unsigned long long)n);
+  if (!n) return BSC_OK;
+  BSC_ENTER(ctx);
+  int rc = bsc_frag_quiet(ctx);
+  if (rc) return rc;
+  HIP_TRY(hipMemcpyAsync(acc_host, ctx->fr.d_acc, (size_t)n * BSC_FRAG_N_SUMS * 8u, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  return BSC_OK;
+}
+
+int bsc_frag_reset(bsc_context *ctx) {
+  if (!ctx) return bsc_fail(BSC_ERR_ARG, "bsc_frag_reset: NULL argument");
+  if (!ctx->fr.n) return BSC_OK;
+  BSC_ENTER(ctx);
+  int rc = bsc_frag_quiet(ctx);
+  if (rc) return rc;
+  HIP_TRY(hipMemsetAsync(ctx->fr.d_acc, 0, (size_t)ctx->fr.n * BSC_FRAG_N_SUMS * 8u, ctx->stream));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
   return BSC_OK;
 }
 

@@ -24,7 +24,7 @@ def run(bam_path: str, reference: Dict[str, np.ndarray], bcf_path: str, sample: 
         bigbed_zoom: int = 1024, bigbed_compress: bool = False, meth_index: Optional[str] = None, variants_path: Optional[str] = None,
         variants_params=None, cpg_reads_path: Optional[str] = None, cpg_reads_params=None, asm_path: Optional[str] = None, asm_params=None,
         mbias_path: Optional[str] = None, mbias_params=None, epi_path: Optional[str] = None, epi_params=None,
-        pat_path: Optional[str] = None, pat_params=None, **reader_kw) -> dict:
+        pat_path: Optional[str] = None, pat_params=None, frag_path: Optional[str] = None, frag_params=None, **reader_kw) -> dict:
     """reference: contig name -> uint8 reference codes (0 = N, 1..4 = ACGT; position 1 first).  Returns a summary dict.
     under_conv / over_conv / min_qual (defaults 0.01 / 0.05 / 20, src/init_param.c:26-31) are the MODEL's parameters: without
     `caller` the run builds its SiteCaller from them; with one, they are taken from it and a differing explicit value is an error
@@ -106,7 +106,12 @@ def run(bam_path: str, reference: Dict[str, np.ndarray], bcf_path: str, sample: 
     methylation strings over the reference CpGs they cover, collapsed, counted and sorted on the device (SiteCaller.block_pat_kept,
     csrc/patdev.hip) — `chrom index pattern count`, wgbstools-unpinned bytes, the index the CpG's 1-based ordinal within its contig, 64 CpGs a
     line at the most; plain text, or BGZF where `compressed` says so or the name ends in .gz.  pat_params: a _lib.PatParams or a dict of
-    min_sites.  The summary gets "pat_lines" and "pat_totals" (the eight totals of the rule).  Refused where epi_path is."""
+    min_sites.  The summary gets "pat_lines" and "pat_totals" (the eight totals of the rule).  Refused where epi_path is.
+    frag_path: the per-region fragment methylation summary of the same run (include/bscall_amd.h has the rule) over the meth_regions /
+    meth_window intervals: per interval the templates that are mostly unmethylated, mixed and mostly methylated within it, twelve columns
+    whose first four join the meth_regions_path lines — attached, summed behind every block (SiteCaller.block_frag_kept, csrc/fragdev.hip)
+    and read where the region summary is.  With frag_path, meth_regions_path may be left out.  frag_params: a _lib.FragParams or a dict of
+    min_sites / u_max_pct / m_min_pct.  The summary gets "frag_lines" and "frag_totals".  The same conditions as meth_regions."""
     if pat_params is not None and pat_path is None:
         raise ValueError("pat_params are thresholds of the table pat_path names: they need pat_path")
     if pat_path is not None and (shard_rank is not None or not device_reader or host_prep or host_bcf):
@@ -158,8 +163,16 @@ def run(bam_path: str, reference: Dict[str, np.ndarray], bcf_path: str, sample: 
     want_regions = meth_regions is not None or meth_window is not None
     if meth_regions is not None and meth_window is not None:
         raise ValueError("meth_regions and meth_window exclude each other: the regions are the given ones or the fixed tiles")
-    if want_regions != (meth_regions_path is not None):
+    if (want_regions != (meth_regions_path is not None)) and not (want_regions and frag_path is not None):
         raise ValueError("meth_regions / meth_window and meth_regions_path go together: the regions to sum and the summary to write")
+    if frag_params is not None and frag_path is None:
+        raise ValueError("frag_params are thresholds of the summary frag_path names: they need frag_path")
+    if frag_path is not None and not want_regions:
+        raise ValueError("frag_path sums over the intervals of meth_regions or meth_window: it needs one of them")
+    if frag_path is not None:
+        from . import frag as _frag
+
+        _frag._params(frag_params)  # (refused before the run starts)
     if meth_window is not None and int(meth_window) < 1:
         raise ValueError("meth_window is a count of bases, 1 or more")
     if want_regions and (shard_rank is not None or not device_reader or host_prep or host_bcf):
@@ -230,6 +243,7 @@ def run(bam_path: str, reference: Dict[str, np.ndarray], bcf_path: str, sample: 
         meth_entries = []  # meth_index: (contig number, BED_ENTRY[], bytes of the block's table)
         bw_sites = cov_sites = 0
         region_out, region_cur = [], None  # the summary's lines, contig by contig; (name, regions, names) of the contig attached
+        frag_out, frag_totals = [], np.zeros(8, dtype=np.uint64)  # frag_path: the fragment summary's lines over the same regions
         c.reset_site_stats()
         sharded = shard_rank is not None
         if sharded:
@@ -280,11 +294,14 @@ def run(bam_path: str, reference: Dict[str, np.ndarray], bcf_path: str, sample: 
                 if region_cur is not None:
                     from . import methbed
 
-                    region_out.append(methbed.format_regions(region_cur[0], region_cur[1], region_cur[2], c.meth_regions_read()))
+                    if meth_regions_path is not None:
+                        region_out.append(methbed.format_regions(region_cur[0], region_cur[1], region_cur[2], c.meth_regions_read()))
+                    if frag_path is not None:
+                        frag_out.append(_frag.format_regions(region_cur[0], region_cur[1], region_cur[2], c.frag_read()))
                 region_cur = None
 
             def block_blobs():
-                nonlocal n_blocks, n_records, base_filter, passed, meth_lines, region_cur, bw_sites, cov_sites, bb_sites, var_totals, reads_lines, reads_totals, asm_lines, asm_totals, mbias_any, epi_lines, epi_totals, pat_lines, pat_totals
+                nonlocal n_blocks, n_records, base_filter, passed, meth_lines, region_cur, bw_sites, cov_sites, bb_sites, var_totals, reads_lines, reads_totals, asm_lines, asm_totals, mbias_any, epi_lines, epi_totals, pat_lines, pat_totals, frag_totals
                 before, cur_tid = c.site_totals(), -1
                 pat_base, pat_from = 0, 1  # the contig's CpGs in front of position pat_from
                 pat_room = 8.0  # the table's room in bytes a position: a quarter above the last block's need, so that a block is walked once
@@ -310,7 +327,12 @@ def run(bam_path: str, reference: Dict[str, np.ndarray], bcf_path: str, sample: 
                                 region_cur = (name, methbed.window_regions(refs[tid][1], int(meth_window)), None)
                             else:
                                 region_cur = (name, *region_sets[name]) if name in region_sets else None
-                            if c.meth_regions_attach(region_cur[1] if region_cur else []) == 0:
+                            n_att = 0
+                            if meth_regions_path is not None:
+                                n_att = c.meth_regions_attach(region_cur[1] if region_cur else [])
+                            if frag_path is not None:
+                                n_att = c.frag_attach(region_cur[1] if region_cur else [])
+                            if n_att == 0:
                                 region_cur = None
                         if dbsnp is not None:
                             dbsnp.load_contig(name)
@@ -341,8 +363,10 @@ def run(bam_path: str, reference: Dict[str, np.ndarray], bcf_path: str, sample: 
                         if mbias_path is not None:  # the block's raw templates, still in the reader's buffers, into the run's accumulator
                             c.block_mbias_rawdev(dblk.d_tpl, dblk.nr, dblk.d_seq, dblk.seq_bytes, dblk.d_misms, dblk.n_misms, mbias_cycles)
                             mbias_any = True
-                        if region_cur is not None:  # the block's cytosines into the attached regions' sums
+                        if region_cur is not None and meth_regions_path is not None:  # the block's cytosines into the attached regions' sums
                             c.block_meth_regions_kept(meth_params)
+                        if region_cur is not None and frag_path is not None and len(blob):  # ... and its templates into their fragment sums
+                            frag_totals += np.array(c.block_frag_kept(frag_params), dtype=np.uint64)
                         if want_cov:  # the coverage track, and the level track with it, from ONE sweep over the block's arrays
                             ns, lv, cv = c.block_bigwig_tracks_kept(tid, (_lib.BW_LEVEL if want_bw else 0) | _lib.BW_COVERAGE, meth_params, bw_par,
                                                                     read_stream=not bigwig_compress)
@@ -484,8 +508,12 @@ def run(bam_path: str, reference: Dict[str, np.ndarray], bcf_path: str, sample: 
                 bb_writer.finish()
             if want_regions:
                 regions_flush()
-                with open(meth_regions_path, "wb") as f:
-                    f.write(b"".join(region_out))
+                if meth_regions_path is not None:
+                    with open(meth_regions_path, "wb") as f:
+                        f.write(b"".join(region_out))
+                if frag_path is not None:
+                    with open(frag_path, "wb") as f:
+                        f.write(b"".join(frag_out))
             cts, bases = rd.filter_counts()
         cts[0] += int(passed[0])
         bases[0] += int(passed[1])
@@ -575,8 +603,11 @@ def run(bam_path: str, reference: Dict[str, np.ndarray], bcf_path: str, sample: 
             summary["cov_bigwig_sites"] = cov_sites
         if want_bb:
             summary["bigbed_items"] = bb_sites
-        if want_regions:
+        if meth_regions_path is not None:
             summary["meth_region_lines"] = sum(b.count(b"\n") for b in region_out)
+        if frag_path is not None:
+            summary["frag_lines"] = sum(b.count(b"\n") for b in frag_out)
+            summary["frag_totals"] = tuple(int(v) for v in frag_totals)
         return summary
     finally:
         if bw_writer is not None:
@@ -590,5 +621,7 @@ def run(bam_path: str, reference: Dict[str, np.ndarray], bcf_path: str, sample: 
         else:  # a supplied caller goes back as it came
             if on_device:
                 c.dbsnp_detach()
-            if want_regions:
+            if want_regions and meth_regions_path is not None:
                 c.meth_regions_attach([])
+            if frag_path is not None:
+                c.frag_attach([])

@@ -2174,6 +2174,94 @@ int bsc_pat_stream_read(bsc_context *ctx, uint64_t off, uint64_t n, void *dst);
 int bsc_pat_stream_detach(bsc_context *ctx, void **d_stream, uint64_t *n_bytes);
 
 /*
+ * The per-region fragment methylation summary (csrc/fragdev.hip: one walk behind the site pass and the scan of csrc/cpgreadsdev.hip;
+ * csrc/frag.c holds the host form, which is its checker; bs_call_amd/frag.py the Python rule).  Per region of a BED file — a marker, a CpG
+ * island, a DMR, a fixed tile — the number of templates (fragments) that are mostly unmethylated, mixed and mostly methylated within it: the
+ * U / X / M counts of fragment-level deconvolution and of `wgbstools homog`, with the region's discordant fragments and the sums from which
+ * the mean per-read level follows.  It is the product of the region summary above (which has forgotten the molecules) and the read-level
+ * tables (which know no regions): the walk adds straight into per-region accumulators and writes no table.  The reference has no such
+ * output: the rule is this project's own.
+ *
+ * COUNTS, SITE, BYTE(t, q) and STATE(t, s) are those of the read-level CpG table above, word for word; REGION is the region summary's; the
+ * inputs are those of bsc_cpg_reads_device.
+ * IN(s, R)  A site whose C is at the 1-based position p lies in the region R = {start, end} iff start < p <= end: REGION's containment,
+ *           applied to the C.  A CpG whose C is inside and whose G is outside belongs to R — for a G2A template too, whose byte is read
+ *           at p + 1; a CpG whose C is outside does not belong, wherever its G lies.
+ * Per (template t, region R)  k = the number of sites s with IN(s, R) and STATE(t, s) != none; m = the number of those with state M.
+ *           1 <= k < min_sites: t is SHORT in R.  k >= min_sites: t is a FRAGMENT of R, of exactly one class, tested in this order:
+ *             U iff 100 m <= u_max_pct k;  M iff 100 m >= m_min_pct k;  X otherwise
+ *           — in 64-bit integers.  A fragment is DISCORDANT iff 0 < m < k.  k == 0: t gives R nothing.
+ * SUMS      Eight u64 per region: {frags, U, X, M, K = sum of k, Mm = sum of m, disc, short}; K and Mm run over fragments only.  Regions may
+ *           overlap, nest, repeat and be empty: each is summed alone, and a template counts in every region where it qualifies.  Integer
+ *           adds alone: the result is a function of the input, whatever the order.
+ * Per block Only sites within x .. y count, as in the other read-level tables; the accumulators add over the block calls of a contig.
+ * TOTALS    of one call, eight u64: [0] templates with k_t >= 1 over the whole block (k_t as in the read-level table), [1 .. 7] the sums of
+ *           the seven columns frags .. disc over all attached regions.  short is per region only.
+ * LINE      Twelve tab-separated columns and '\n', plain decimals, no header, no float:
+ *             chrom  start  end  name  frags  U  X  M  K  Mm  disc  short
+ *           name: as bsc_meth_regions_format writes it (the BED's fourth column, or ".").  The lines come in the attached order and join
+ *           the region summary's lines on the first four columns.  The U / X / M shares, disc / frags and the mean level Mm / K are the
+ *           reader's (bs_call_amd/frag.py: fractions).
+ * Params    bsc_frag_params {min_sites, u_max_pct, m_min_pct, reserved}, default {3, 25, 75, 0}.  Refused with BSC_ERR_ARG: min_sites == 0, a
+ *           percentage above 100, u_max_pct >= m_min_pct, reserved != 0.
+ * LIMITS    No template spans two blocks: the reader ends a block only where the next forward-facing read begins more than one base behind
+ *           everything the block holds (csrc/bamio.c, csrc/bamdev.hip), and a mate joins its template in the block that holds it.  So a
+ *           fragment is counted once, in one block, and a region across a block border gets each template whole.  The one exception is the
+ *           reader's keep_unmatched: a mate that arrives after its partner's block has closed is a template of its own in the later block,
+ *           and the table then counts the molecule as two fragments (as every read-level table does).
+ *           A template's candidates are the attached regions of index [lo, hi): hi from the sorted starts, lo from the running maximum of
+ *           the ends.  A region longer than 65 536 bases is kept out of that running maximum and goes into a separate short list that every
+ *           template tests whole, 64 entries a round: a chromosome-long region listed first costs one round a template, not the whole
+ *           list.  A set of very many such regions costs (their number / 64) rounds a template.
+ *           A template whose span touches more than 64 tiles (4 096 positions: a long read) does not fit the walk's strip of masks: the
+ *           strip is then made again, read bytes and all, for every round of 64 candidates, the long list's rounds included, so such a
+ *           template costs (rounds x tiles) where a shorter one costs (rounds + tiles).
+ * Not gated by the called genotype, as the read-level table is not.
+ *
+ *   bsc_frag_params_default  {3, 25, 75, 0}
+ *   bsc_frag_regions_host    the host form: adds the block into acc[n_regions][8] (NOT zeroed here) and, where totals is not NULL, writes the
+ *                            call's eight totals.  regions need not be sorted.  A plain loop
+ *   bsc_frag_format          the lines of regions[0 .. n) of one contig -> buf, with bsc_meth_regions_format's return conventions and
+ *                            refusals: the length written; the length needed — and nothing written — when cap is too small; < 0 for a bad
+ *                            argument
+ *   bsc_frag_attach          regions[0 .. n) of ONE contig, sorted by (start, end), uploaded with the search's arrays; their accumulators
+ *                            zeroed.  n == 0 detaches.  bsc_meth_regions_attach's refusals, and the previous attachment stays.  The
+ *                            accumulators are this table's own: bsc_meth_regions_* neither see nor touch them.  Waits.
+ *   bsc_frag_device          adds one block from device-resident inputs (d_tpl 8-byte aligned, d_ref y - x + 3 codes) into the attached
+ *                            regions' accumulators; d_totals: eight device u64 (8-byte aligned), written.  Asynchronous on `stream`; calls
+ *                            may follow one another on any streams the caller orders (the adds are atomic).  Every workspace is reserved
+ *                            before anything is written; a refusal writes nothing.  BSC_ERR_ARG with nothing attached.  nr == 0 is legal
+ *                            and adds nothing (the totals are zeroed).
+ *   bsc_block_frag_kept      the twin of bsc_block_epi_kept, with its preconditions and refusals: walks the prepared templates, reads and
+ *                            reference codes the last *_keep call left in HBM.  totals (may be NULL): the call's eight.  Every other kept
+ *                            output is untouched, before or after.  Waits.
+ *   bsc_frag_read            the accumulators -> acc_host[n][8], n = the attached count; waits for the context's stream and the stream of
+ *                            the last accumulating call
+ *   bsc_frag_reset           zeroes them (waits likewise)
+ * Not built: sharded runs, the batched and host-buffer block entries, non-CpG contexts, classes other than the three, float columns.
+ */
+typedef struct {
+  uint32_t min_sites; /* FRAGMENT: k >= min_sites; 0 is refused */
+  uint32_t u_max_pct; /* U iff 100 m <= u_max_pct k */
+  uint32_t m_min_pct; /* M iff 100 m >= m_min_pct k; must exceed u_max_pct */
+  uint32_t reserved;  /* 0; anything else is refused */
+} bsc_frag_params;
+#define BSC_FRAG_N_SUMS 8
+#define BSC_FRAG_N_TOTALS 8
+void bsc_frag_params_default(bsc_frag_params *p);
+int bsc_frag_regions_host(const bsc_template *tpl, uint32_t nr, const uint8_t *seq, uint64_t seq_bytes, uint32_t x, uint32_t y, const uint8_t *ref,
+                          int32_t min_qual, const bsc_frag_params *p, const bsc_meth_region *regions, size_t n_regions, uint64_t *acc,
+                          uint64_t totals[8]);
+long bsc_frag_format(const char *contig, const bsc_meth_region *regions, const char *const *names, const uint64_t *acc, size_t n, char *buf,
+                     size_t cap);
+int bsc_frag_attach(bsc_context *ctx, const bsc_meth_region *regions, uint64_t n);
+int bsc_frag_device(bsc_context *ctx, const void *d_tpl, uint32_t nr, const void *d_seq, uint64_t seq_bytes, uint32_t x, uint32_t y, const void *d_ref,
+                    const bsc_frag_params *p, void *d_totals, void *stream);
+int bsc_block_frag_kept(bsc_context *ctx, const bsc_frag_params *p, uint64_t totals[8]);
+int bsc_frag_read(bsc_context *ctx, uint64_t *acc_host, uint64_t n);
+int bsc_frag_reset(bsc_context *ctx);
+
+/*
  * dbSNP index (host C + zlib; csrc/dbsnp.c): the reader of the compressed index bin/dbSNP_idx writes.  In the reference
  * the index never touches the likelihoods: an entry names the record (VCF ID), forces the AA / TT homozygous-reference
  * record of a site flagged in its `fq_mask` to be written (rs_found & 2, src/print_vcf.c:139) and feeds the dbSNP

@@ -135,6 +135,14 @@
  * --meth-pat-min-sites n (default 1): the states a template needs.  Refused where --meth-epialleles is.  Without the switch the program makes
  * the calls it made before the switch existed.
  *
+ * --meth-frags out.tsv: the per-region fragment methylation summary (include/bscall_amd.h has the rule) over the intervals of --meth-regions
+ * or --meth-window — per interval the templates that are mostly unmethylated, mixed and mostly methylated within it, twelve columns: chrom
+ * start end name frags U X M K Mm disc short, whose first four join the --meth-regions-out lines.  bsc_frag_attach at the contig change, where
+ * the region summary attaches; bsc_block_frag_kept behind every block; bsc_frag_read and bsc_frag_format at the next contig change and at the
+ * end.  --meth-frags-min-sites n (default 3), --meth-frags-u-max pct (25), --meth-frags-m-min pct (75).  With --meth-frags,
+ * --meth-regions-out may be left out.  Refused where --meth-regions is.  Without the switch the program makes the calls it made before the
+ * switch existed.
+ *
  * --mbias out.tsv: the M-bias table (include/bscall_amd.h has the rule) — methylated and unmethylated calls per sequencing cycle, by read 1 /
  * read 2, bisulfite strand and CpG / CHG / CHH, from the RAW templates as sequenced (no trim, clip or overlap edit): what -L / -R and the
  * under-conversion rate are chosen from.  Behind every block bsc_block_mbias_rawdev walks the block's raw arrays, still in the reader's
@@ -567,6 +575,24 @@ static uint64_t regions_flush(bsc_context *ctx, FILE *f, const char *contig, con
   return n;
 }
 
+/* --meth-frags: the attached contig's fragment accumulators read and its lines appended */
+static uint64_t frags_flush(bsc_context *ctx, FILE *f, const char *contig, const bsc_meth_region *regs, const char *const *names, uint64_t n) {
+  if (!n) return 0;
+  uint64_t *acc = xrealloc(NULL, (size_t)n * BSC_FRAG_N_SUMS * sizeof *acc);
+  CHECK(bsc_frag_read(ctx, acc, n));
+  const long need = bsc_frag_format(contig, regs, names, acc, (size_t)n, NULL, 0);
+  CHECK(need);
+  char *buf = xrealloc(NULL, (size_t)(need ? need : 1));
+  CHECK(bsc_frag_format(contig, regs, names, acc, (size_t)n, buf, (size_t)need));
+  if (fwrite(buf, 1, (size_t)need, f) != (size_t)need) {
+    perror("--meth-frags");
+    exit(1);
+  }
+  free(buf);
+  free(acc);
+  return n;
+}
+
 int main(int argc, char **argv) {
   int rank = -1, world = 1, merge = 0, bgzf = 0, text = 0, index = 0, meth_merge = 0;
   const char *dbsnp_path = NULL, *meth_path = NULL, *regions_path = NULL, *regions_out_path = NULL, *bigwig_path = NULL, *cov_path = NULL;
@@ -608,6 +634,14 @@ int main(int argc, char **argv) {
   int pat_opts = 0;
   if (argc >= 2 && !strcmp(argv[argc - 1], "--meth-pat") && (argc == 2 || strcmp(argv[argc - 2], "--meth-pat"))) {
     fprintf(stderr, "%s: --meth-pat takes the path of the pattern table to write\n", argv[0]);
+    return 2;
+  }
+  const char *frags_path = NULL; /* --meth-frags out.tsv: the per-region fragment methylation summary */
+  bsc_frag_params frpar;
+  bsc_frag_params_default(&frpar);
+  int frag_opts = 0;
+  if (argc >= 2 && !strcmp(argv[argc - 1], "--meth-frags") && (argc == 2 || strcmp(argv[argc - 2], "--meth-frags"))) {
+    fprintf(stderr, "%s: --meth-frags takes the path of the fragment summary to write\n", argv[0]);
     return 2;
   }
   const char *mbias_path = NULL; /* --mbias out.tsv: the M-bias table */
@@ -748,6 +782,19 @@ int main(int argc, char **argv) {
       ptpar.min_sites = (uint32_t)v;
       pat_opts = 1;
     }
+    else if (!strcmp(argv[1], "--meth-frags")) frags_path = argv[2];
+    else if (!strcmp(argv[1], "--meth-frags-min-sites") || !strcmp(argv[1], "--meth-frags-u-max") || !strcmp(argv[1], "--meth-frags-m-min")) {
+      char *end = NULL;
+      const unsigned long v = strtoul(argv[2], &end, 10);
+      if (!argv[2][0] || *end || argv[2][0] == '-' || v > 0xfffffffful) {
+        fprintf(stderr, "%s: %s takes a count, not '%s'\n", argv[0], argv[1], argv[2]);
+        return 2;
+      }
+      if (!strcmp(argv[1], "--meth-frags-min-sites")) frpar.min_sites = (uint32_t)v;
+      else if (!strcmp(argv[1], "--meth-frags-u-max")) frpar.u_max_pct = (uint32_t)v;
+      else frpar.m_min_pct = (uint32_t)v;
+      frag_opts = 1;
+    }
     else if (!strcmp(argv[1], "--meth-epialleles")) epi_path = argv[2];
     else if (!strcmp(argv[1], "--meth-epialleles-min-cov")) {
       char *end = NULL;
@@ -838,7 +885,7 @@ int main(int argc, char **argv) {
     argc -= 2;
   }
   if (argc < 5 || world < 1 || (rank >= 0 && rank >= world)) {
-    fprintf(stderr, "usage: %s [-O u|b] [--format bcf|vcf] [--index] [-D dbsnp.idx] [--meth out.bed [--meth-bgzf] [--meth-index tbi|csi] [--meth-merge | --meth-all] [--meth-min-cov n] [--meth-min-gq n] [--meth-pass]] [--meth-regions regions.bed | --meth-window n --meth-regions-out out.tsv] [--meth-bigwig out.bw [--meth-bigwig-section n] [--meth-bigwig-zoom n] [--meth-bigwig-compress: zlib sections, n <= 8157]: the methylation level as a bigWig track, per cytosine even with --meth-merge, under the --meth-* thresholds and --meth-all] [--cov-bigwig cov.bw: the depth of the same sites as a bigWig track, under the same --meth-bigwig-* switches] [--meth-bigbed out.bb [--meth-bigbed-items n] [--meth-bigbed-zoom n] [--meth-bigbed-compress: zlib blocks, n <= 652]] [--variants out: the records with an ALT allele, in the run's format and compression, with out.csi under --index [--variants-min-qual n] [--variants-pass] [--variants-known: dbSNP sites only, with -D]] [--meth-reads out.tsv: the read-level CpG concordance table, a line per reference CpG [--meth-reads-min-sites n] [--meth-reads-min-cov n]] [--mbias out.tsv: methylation by read cycle, from the reads as sequenced [--mbias-cycles n]] [--meth-asm out.tsv: the allele-specific methylation table, a line per heterozygous SNP and CpG near it [--meth-asm-window n] [--meth-asm-min-qual n] [--meth-asm-min-cov n] [--meth-asm-pass]] [--meth-epialleles out.tsv: the epiallele table, a line per window of four reference CpGs [--meth-epialleles-min-cov n]] [--meth-pat out.pat: the per-read CpG pattern table (PAT: chrom index pattern count, wgbstools-unpinned bytes, the index per contig, 64 CpGs a line at the most) [--meth-pat-min-sites n]] [--rank r --world n | --merge n] in.bam ref.fa out.bcf report.json [sample]\n", argv[0]);
+    fprintf(stderr, "usage: %s [-O u|b] [--format bcf|vcf] [--index] [-D dbsnp.idx] [--meth out.bed [--meth-bgzf] [--meth-index tbi|csi] [--meth-merge | --meth-all] [--meth-min-cov n] [--meth-min-gq n] [--meth-pass]] [--meth-regions regions.bed | --meth-window n --meth-regions-out out.tsv] [--meth-bigwig out.bw [--meth-bigwig-section n] [--meth-bigwig-zoom n] [--meth-bigwig-compress: zlib sections, n <= 8157]: the methylation level as a bigWig track, per cytosine even with --meth-merge, under the --meth-* thresholds and --meth-all] [--cov-bigwig cov.bw: the depth of the same sites as a bigWig track, under the same --meth-bigwig-* switches] [--meth-bigbed out.bb [--meth-bigbed-items n] [--meth-bigbed-zoom n] [--meth-bigbed-compress: zlib blocks, n <= 652]] [--variants out: the records with an ALT allele, in the run's format and compression, with out.csi under --index [--variants-min-qual n] [--variants-pass] [--variants-known: dbSNP sites only, with -D]] [--meth-reads out.tsv: the read-level CpG concordance table, a line per reference CpG [--meth-reads-min-sites n] [--meth-reads-min-cov n]] [--mbias out.tsv: methylation by read cycle, from the reads as sequenced [--mbias-cycles n]] [--meth-asm out.tsv: the allele-specific methylation table, a line per heterozygous SNP and CpG near it [--meth-asm-window n] [--meth-asm-min-qual n] [--meth-asm-min-cov n] [--meth-asm-pass]] [--meth-epialleles out.tsv: the epiallele table, a line per window of four reference CpGs [--meth-epialleles-min-cov n]] [--meth-frags out.tsv: fragments per interval of --meth-regions / --meth-window by class U / X / M [--meth-frags-min-sites n] [--meth-frags-u-max pct] [--meth-frags-m-min pct]] [--meth-pat out.pat: the per-read CpG pattern table (PAT: chrom index pattern count, wgbstools-unpinned bytes, the index per contig, 64 CpGs a line at the most) [--meth-pat-min-sites n]] [--rank r --world n | --merge n] in.bam ref.fa out.bcf report.json [sample]\n", argv[0]);
     return 2;
   }
   if (text && (rank >= 0 || merge > 0)) {
@@ -973,8 +1020,29 @@ int main(int argc, char **argv) {
     fprintf(stderr, "%s: --meth-regions and --meth-window exclude each other: the regions are the BED file's or the fixed tiles\n", argv[0]);
     return 2;
   }
-  if ((regions_path || meth_window) && !regions_out_path) {
+  if ((regions_path || meth_window) && !regions_out_path && !frags_path) {
     fprintf(stderr, "%s: --meth-regions / --meth-window need --meth-regions-out out.tsv, the summary to write\n", argv[0]);
+    return 2;
+  }
+  if (frag_opts && !frags_path) {
+    fprintf(stderr, "%s: --meth-frags-min-sites / -u-max / -m-min are thresholds of the summary --meth-frags writes: they need --meth-frags out.tsv\n", argv[0]);
+    return 2;
+  }
+  if (frags_path && !regions_path && !meth_window) {
+    fprintf(stderr, "%s: --meth-frags sums over the intervals of --meth-regions regions.bed or --meth-window n: it needs one of them\n", argv[0]);
+    return 2;
+  }
+  if (frags_path && (frpar.min_sites == 0 || frpar.u_max_pct > 100 || frpar.m_min_pct > 100 || frpar.u_max_pct >= frpar.m_min_pct)) {
+    fprintf(stderr, "%s: --meth-frags: min-sites is 1 at least, the percentages 100 at the most and u-max below m-min (got %u, %u, %u)\n", argv[0],
+            frpar.min_sites, frpar.u_max_pct, frpar.m_min_pct);
+    return 2;
+  }
+  if (frags_path && (rank >= 0 || world > 1 || merge > 0)) {
+    fprintf(stderr, "%s: --meth-frags sums a single run's blocks; a sharded run (--rank / --world / --merge) has none\n", argv[0]);
+    return 2;
+  }
+  if (frags_path && (getenv("BAM2BCF_HOST_PREP") || getenv("BAM2BCF_HOST_BCF") || getenv("BAM2BCF_HOST_READER"))) {
+    fprintf(stderr, "%s: --meth-frags walks the prepared reads the device reader's blocks leave on the device: not with BAM2BCF_HOST_READER / _HOST_BCF / _HOST_PREP\n", argv[0]);
     return 2;
   }
   if (regions_out_path && !regions_path && !meth_window) {
@@ -1112,11 +1180,22 @@ int main(int argc, char **argv) {
   uint64_t r_n = 0, region_lines = 0;
   const bsc_meth_region *r_regs = NULL;
   const char *const *r_names = NULL;
-  if (regions_out_path) {
-    rout = fopen(regions_out_path, "wb");
-    if (!rout) {
-      perror(regions_out_path);
+  FILE *fout = NULL; /* --meth-frags: the fragment summary over the same intervals, attached, read and appended where the region summary is */
+  uint64_t frag_lines = 0, frag_tot[BSC_FRAG_N_TOTALS] = {0};
+  if (frags_path) {
+    fout = fopen(frags_path, "wb");
+    if (!fout) {
+      perror(frags_path);
       return 1;
+    }
+  }
+  if (regions_out_path || frags_path) {
+    if (regions_out_path) {
+      rout = fopen(regions_out_path, "wb");
+      if (!rout) {
+        perror(regions_out_path);
+        return 1;
+      }
     }
     if (rbed) {
       rbed_of = xrealloc(NULL, ((size_t)n_ref + 1) * sizeof *rbed_of);
@@ -1383,6 +1462,7 @@ int main(int argc, char **argv) {
         memcpy(before, after, sizeof before);
       }
       if (rout && cur_tid >= 0) region_lines += regions_flush(ctx, rout, REF_NAME(cur_tid), r_regs, r_names, r_n);
+      if (fout && cur_tid >= 0) frag_lines += frags_flush(ctx, fout, REF_NAME(cur_tid), r_regs, r_names, r_n);
       cur_tid = blk.tid;
       pat_base = 0; /* --meth-pat: the index counts the contig's CpGs */
       pat_from = 1;
@@ -1427,7 +1507,7 @@ int main(int argc, char **argv) {
       codes_len = RJ.codes_len;
       CHECK(bsc_set_gc_bins_host(ctx, gc, (uint32_t)RJ.n_bins, RJ.gc_start));
       if (g_dbsnp) CHECK(bsc_dbsnp_attach(ctx, g_dbsnp, NULL)); /* what the job loaded behind the reference; the next job may load over it */
-      if (rout) { /* this contig's regions, their accumulators zeroed: the BED's, or the fixed tiles */
+      if (rout || fout) { /* this contig's regions, their accumulators zeroed: the BED's, or the fixed tiles */
         r_n = 0;
         r_regs = NULL;
         r_names = NULL;
@@ -1446,7 +1526,8 @@ int main(int argc, char **argv) {
           r_regs = rbed->regions + f0;
           r_names = (const char *const *)rbed->names + f0;
         }
-        CHECK(bsc_meth_regions_attach(ctx, r_regs, r_n));
+        if (rout) CHECK(bsc_meth_regions_attach(ctx, r_regs, r_n));
+        if (fout) CHECK(bsc_frag_attach(ctx, r_regs, r_n));
       }
       if (cur_tid + 1 < n_ref) ref_start(&RJ, argv[2], REF_NAME(cur_tid + 1), REF_LEN(cur_tid + 1), cur_tid + 1); /* the next one, meanwhile */
     }
@@ -1487,7 +1568,12 @@ int main(int argc, char **argv) {
         CHECK(bsc_block_csi_kept(ctx, 14, &ce, &cn, NULL));
         CHECK(bsc_csi_add(csi, dblk.tid, ce, cn, n_bytes));
       }
-      if (n_bytes && r_n) CHECK(bsc_block_meth_regions_kept(ctx, &mpar, NULL, NULL)); /* the block's cytosines into the attached regions' sums */
+      if (n_bytes && r_n && rout) CHECK(bsc_block_meth_regions_kept(ctx, &mpar, NULL, NULL)); /* the block's cytosines into the attached regions' sums */
+      if (n_bytes && r_n && fout) { /* the block's templates into the attached regions' fragment sums, from the prepared reads the call left on the device */
+        uint64_t ft[BSC_FRAG_N_TOTALS];
+        CHECK(bsc_block_frag_kept(ctx, &frpar, ft));
+        for (int k = 0; k < BSC_FRAG_N_TOTALS; k++) frag_tot[k] += ft[k];
+      }
       if (n_bytes && (bw || cw)) { /* the block's bigWig sections and summaries, from the same arrays: a host buffer and a job of its own per
                                     * track.  With --cov-bigwig ONE call reduces the block for every track asked for. */
         uint64_t b_raw = 0, b_sites = 0, b_sec = 0, b_zoom = 0;
@@ -2040,12 +2126,21 @@ int main(int argc, char **argv) {
       return 1;
     }
   }
+  if (fout) { /* the last contig's lines */
+    if (cur_tid >= 0) frag_lines += frags_flush(ctx, fout, REF_NAME(cur_tid), r_regs, r_names, r_n);
+    if (fclose(fout)) {
+      perror(frags_path);
+      return 1;
+    }
+  }
   if (rout) { /* the last contig's lines */
     if (cur_tid >= 0) region_lines += regions_flush(ctx, rout, REF_NAME(cur_tid), r_regs, r_names, r_n);
     if (fclose(rout)) {
       perror(regions_out_path);
       return 1;
     }
+  }
+  if (rout || fout) {
     free(rwin);
     free(rbed_of);
     bsc_meth_bed_free(rbed);
@@ -2157,6 +2252,10 @@ int main(int argc, char **argv) {
       printf("%llu records in the per-read CpG pattern table, %llu lines written (pieces %llu, templates %llu, C %llu T %llu)\n",
              (unsigned long long)pat_tot[0], (unsigned long long)pat_lines, (unsigned long long)pat_tot[1], (unsigned long long)pat_tot[2],
              (unsigned long long)pat_tot[3], (unsigned long long)pat_tot[4]);
+    if (frags_path)
+      printf("%llu fragment summary lines written (templates with a CpG state %llu; fragments in regions %llu: U %llu, X %llu, M %llu, discordant %llu)\n",
+             (unsigned long long)frag_lines, (unsigned long long)frag_tot[0], (unsigned long long)frag_tot[1], (unsigned long long)frag_tot[2],
+             (unsigned long long)frag_tot[3], (unsigned long long)frag_tot[4], (unsigned long long)frag_tot[7]);
     if (mbias_path)
       printf("M-bias table: %llu reads walked, %llu bytes mapped, %llu counted, %llu beyond the table, CpG %llu meth %llu unmeth, %llu reads skipped\n",
              (unsigned long long)mbias_tot[0], (unsigned long long)mbias_tot[1], (unsigned long long)mbias_tot[2], (unsigned long long)mbias_tot[3],
